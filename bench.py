@@ -2,10 +2,11 @@
 """bench.py — headline benchmark of the MI355X prover backend (BASELINE.json metric, configs[1]):
 standalone 2^20-point BLS12-377 G1 Pippenger MSM = one `aleo_mi355x_msm_g1_pinned` call per step — bases resident in
 HBM (the SRS of a proving key is pinned once), the 32 MB of canonical scalars in HOST memory and uploaded inside the timed
-region, result on the host.  The same line carries the variants beside it: scalars already resident, no fixed-base
-table, the table's build time and size.
+region, result on the host.  A plain run sets up, warms up, times the K steps and prints the line; with --full the same line
+also carries every secondary measurement and check (variants of the MSM, KZG chain, G2 MSM, proof proxies, the Varuna prover,
+the CPU baseline; at N > 1 the configs[4] split, proof replicas and the sharded NTT).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W [--config 4]
 
@@ -52,7 +53,13 @@ def main():
                     help="'gloo' is only for rehearsing the N>1 path with several ranks sharing one GPU")
     ap.add_argument('--launch-check', action='store_true',
                     help='N > 1 plumbing only (runs without a GPU): spawn / rendezvous / the 144-byte gather / the max-over-ranks reduction under --backend gloo; prints a line with value null')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the secondary measurements and checks the options above select; without it the run times the headline MSM only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last step\'s MSM result to DIR/msm_g1_result.npy (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.aux_sharded_ntt:
         raise SystemExit(aux_sharded_ntt(args))
     if args.in_process:
@@ -63,6 +70,10 @@ def main():
         raise SystemExit(spawn_ranks(args.gpus))
     if args.launch_check:
         raise SystemExit(launch_check(args))
+    if not args.full:
+        # a plain run is the headline alone: every secondary leg is switched off here, in one place
+        args.no_cpu_baseline = args.no_variants = args.no_kzg_chain = True
+        args.proof_proxy_lg = args.varuna_lg = args.concurrent_callers = args.sharded_ntt_lg = args.config4_lg = 0
 
     import torch
     import torch.distributed as dist
@@ -142,6 +153,8 @@ def main():
         k = sum(synth.limbs_to_int(row) for row in ks) % synth.FR_MODULUS
     if not result_is_multiple_of_generator(synth, res, k):       # big-integer double-and-add below: independent of the HIP path
         raise SystemExit('bench: MSM result does not equal k*G — refusing to report a number for a wrong result')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # variants of the same MSM, outside the timed region (every rank runs them so the ranks stay in step; rank 0 reports)
     variants = {}
@@ -445,6 +458,15 @@ def result_is_multiple_of_generator(synth, res, k) -> bool:
     return got == _g1_times(G, k % synth.FR_MODULUS, q)
 
 
+def dump_outputs(d, res):
+    """--dump-outputs: the MSM result a caller of the timed path receives — uint64[18], the Jacobian (X, Y, Z) with Z = 1 in Montgomery form, 6 limbs
+    each, or (1, 1, 0) for the identity — as DIR/msm_g1_result.npy: float64[3, 12], one row per coordinate, its 12 little-endian 32-bit words (exact in
+    float64).  The inputs are seeded, so two builds run with the same arguments can be compared word for word."""
+    os.makedirs(d, exist_ok=True)
+    words = np.asarray(res, dtype=np.uint64).reshape(18).view(np.uint32).reshape(3, 12)
+    np.save(os.path.join(d, 'msm_g1_result.npy'), words.astype(np.float64))
+
+
 def in_process_sharded(args):
     """bench.py --config 4 --in-process --gpus N: BASELINE configs[4] driven by ONE process over N device contexts of the C ABI
     (aleo_mi355x_bases_generate_sharded / aleo_mi355x_msm_g1_sharded: contiguous point shards, per-device Pippenger from one host thread per shard,
@@ -470,6 +492,8 @@ def in_process_sharded(args):
     elapsed = time.perf_counter() - t0
     if not result_is_multiple_of_generator(synth, res, synth.weighted_scalar_sum(scalars, 1)):
         raise SystemExit('bench: sharded MSM result does not equal k*G — refusing to report a number for a wrong result')
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
     print(json.dumps({
         'metric': 'MSM G1 scalar-muls/sec (2^%d bases total, BLS12-377, bit-exact)' % (total.bit_length() - 1), 'value': total * args.steps / elapsed, 'unit': 'scalar-muls/s',
         'n_gpus': len(set(devices)), 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'strong',

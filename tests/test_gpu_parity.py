@@ -1005,7 +1005,7 @@ def test_bench_spawns_two_ranks_on_one_card_without_a_launcher():
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--lg-n', '12', '--steps', '2', '--warmup', '1', '--no-variants',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--lg-n', '12', '--steps', '2', '--warmup', '1', '--full', '--no-variants',
                         '--no-cpu-baseline', '--varuna-lg', '0', '--sharded-ntt-lg', '0', '--config4-lg', '14'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -1020,6 +1020,28 @@ def test_bench_spawns_two_ranks_on_one_card_without_a_launcher():
     import torch
     g = torch.cuda.device_count()
     assert on.value + off.value == g * (g - 1)
+
+
+def test_bench_plain_run_times_the_asked_steps_and_dumps_the_result(tmp_path):
+    """A plain `bench.py --gpus 1` run times exactly --steps steps, carries no secondary leg (those need --full), and --dump-outputs writes the last
+    step's result: the uint64[18] a caller of aleo_mi355x_msm_g1_pinned receives for the same seeded inputs, as 32-bit words in float64."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--lg-n', '12', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out['steps'] == 3 and out['ms_per_step'] > 0 and out['value'] > 0 and out['higher_is_better'] is True and out['dtype'] == 'u32'
+    assert not {'cpu_baseline', 'proof_proxy', 'varuna_prove', 'kzg_chain_2^22', 'msm_g2', 'concurrent_callers', 'value_scalars_resident'} & set(out)
+    got = np.load(os.path.join(str(tmp_path), 'msm_g1_result.npy'))
+    assert got.dtype == np.float64 and got.shape == (3, 12)
+    n = 1 << 12
+    with aleo_amd.PinnedBases.generate_multiples(synth.generator_affine104(), 1, n) as pb:
+        want = M.VariableBase.msm(pb.precompute(), synth.uniform_scalars(n, 0xA1E00002))
+    assert (got.astype(np.uint64) == want.view(np.uint32).reshape(3, 12)).all()
 
 
 def test_rccl_runs_the_exchange_with_one_rank():
