@@ -93,26 +93,32 @@ def vk_points_of(vk_bytes: bytes):
 def fr_bytes(v): return int(v % R).to_bytes(32, 'little')
 
 
+def domain_sizes(n_constraints, n_public, n_private, nnz, domains='auto'):
+    """The circuit's domains: (|X|, |H|, {M: |K_M|}) for the non-zero counts nnz = {M: count} of A, B, C."""
+    n_x = 1
+    while n_x < n_public: n_x *= 2
+    n_h = 1
+    while n_h < max(n_constraints, n_x + n_private, 2 * n_x): n_h *= 2
+    n_k_m = {}
+    for name in 'abc':                                                          # one non-zero domain per matrix [UPSTREAM-RECALL: non_zero_{a,b,c}_domain]
+        n_k = 2
+        while n_k < nnz[name]: n_k *= 2
+        n_k_m[name] = n_k
+    # 'per_matrix': as above; 'shared': all three use the largest; 'auto' (the provers' default): shared below 2^18, where the rounds are
+    # latency-bound and one batched transform beats three short ones, per matrix from there on (fewer points to commit)
+    big = max(n_k_m.values())
+    if domains == 'shared' or (domains == 'auto' and big < (1 << 18)): n_k_m = {m: big for m in 'abc'}
+    else: assert domains in ('auto', 'per_matrix')
+    return n_x, n_h, n_k_m
+
+
 class Circuit:
     """R1CS in CSR-like python form: rows of (variable, value) for A, B, C; n_public counts the leading 1."""
     def __init__(self, n_constraints, n_public, n_private, a, b, c, domains='auto'):
         self.n_constraints, self.n_public, self.n_private = n_constraints, n_public, n_private
         self.m = {'a': a, 'b': b, 'c': c}
-        n_x = 1
-        while n_x < n_public: n_x *= 2
-        n_h = 1
-        while n_h < max(n_constraints, n_x + n_private, 2 * n_x): n_h *= 2
-        self.n_k_m = {}
-        for name, rows in (('a', a), ('b', b), ('c', c)):                        # one non-zero domain per matrix [UPSTREAM-RECALL: non_zero_{a,b,c}_domain]
-            nnz = sum(len(r) for r in rows); n_k = 2
-            while n_k < nnz: n_k *= 2
-            self.n_k_m[name] = n_k
-        # 'per_matrix': as above; 'shared': all three use the largest; 'auto' (the provers' default): shared below 2^18, where the rounds are
-        # latency-bound and one batched transform beats three short ones, per matrix from there on (fewer points to commit)
-        big = max(self.n_k_m.values())
-        if domains == 'shared' or (domains == 'auto' and big < (1 << 18)): self.n_k_m = {m: big for m in 'abc'}
-        else: assert domains in ('auto', 'per_matrix')
-        self.n_x, self.n_h, self.n_k = n_x, n_h, big
+        n_x, n_h, self.n_k_m = domain_sizes(n_constraints, n_public, n_private, {m: sum(len(r) for r in rows) for m, rows in self.m.items()}, domains)
+        self.n_x, self.n_h, self.n_k = n_x, n_h, max(self.n_k_m.values())
 
 
 class Setup:

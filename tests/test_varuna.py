@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import aleo_amd
 from aleo_amd import synth
-from oracle import varuna_ref as V, pyref
+from oracle import varuna_ref as V, index_ref as IR, pyref
 
 TAU, S_GAMMA = 0x1F3A9C0D5E7B24681357ACE02468BDF013579BDF02468ACE1234567, 0x0FEDCBA9876543210123456789ABCDEF55AA
 
@@ -564,7 +564,10 @@ def test_device_proofs_of_large_circuits_are_verified():
         with varuna.NativeCircuitIndex(csr1, n1, 4, len(z1) - 4, ck) as x1, varuna.NativeCircuitIndex(csr2, n2, 3, len(z2) - 3, ck) as x2:
             zz1, zz2 = lim(z1), lim(z2)
             data = varuna.prove_batch_native([x1, x2], [[zz1, zz1], [zz2]], 77)
-            vks = [V.VerifyingKey(x1.vk_bytes, 4), V.VerifyingKey(x2.vk_bytes, 3)]
+            # the exported keys are the circuits' own: equal to the index recomputed on the CPU (oracle/index_ref.py), whose bytes the verifier then holds
+            ref = [IR.IndexRef(csr1, n1, 4, len(z1) - 4, TAU, D).vk_bytes(), IR.IndexRef(csr2, n2, 3, len(z2) - 3, TAU, D).vk_bytes()]
+            assert [x1.vk_bytes, x2.vk_bytes] == ref
+            vks = [V.VerifyingKey(ref[0], 4), V.VerifyingKey(ref[1], 3)]
             assert (vks[0].circuit.n_h, vks[1].circuit.n_h) == (1 << 18, 1 << 15)
             single = x1.prove(zz1, 78)
         setup = V.Setup(TAU, S_GAMMA, D); pubs = [[z1[:4], z1[:4]], [z2[:3]]]
@@ -986,6 +989,7 @@ def test_a_2_18_constraint_proof_against_a_sharded_key(G):
     try:
         with varuna.NativeCircuitIndex(csr, n, 4, len(z) - 4, ck) as nx:
             vk0 = nx.vk_bytes; want = nx.prove([zz, zz], 4242)
+        assert vk0 == IR.IndexRef(csr, n, 4, len(z) - 4, TAU, D).vk_bytes()
         sb = aleo_amd.ShardedBases(ck.bases.download(), devices=[0] * G, precompute=True)
         try:
             # the entry point alone: three results, segments at offsets that cross shard boundaries (shard size 2^21 / G)
