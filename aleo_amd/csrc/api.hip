@@ -157,14 +157,11 @@ static int32_t get_device(Device** out) {
 //     queue each; with every context creating stream | side | hi at its first use they collided: a lockstep call of 8 proofs 31.8 -> 28.0 ms, of 16 58.5 -> 54.0;
 //   * more hardware queues than ~20 in all (GPU_MAX_HW_QUEUES >= 12, or a third priority level) and the same call takes 43-65 ms: the queues are oversubscribed;
 //   * EIGHT high-priority streams created in a row (one per context) made a 2^20-constraint proof — whose chains' sorts run on them — take 1.1-2.5 s instead of 80 ms; at normal
-//     priority the same arrangement is harmless.  So the device keeps a small POOL of high-priority streams (ALEO_MI355X_HI_POOL, default 4; chunked uploads need one per later
+//     priority the same arrangement is harmless.  So the device keeps a small POOL of high-priority streams (HI_POOL; chunked uploads need one per later
 //     chunk) that its contexts share round-robin, slot i and helper i + 1 on different ones.
-static bool hi_priority_on() { static const bool v = [] { const char* e = std::getenv("ALEO_MI355X_HI_PRIORITY"); return !(e && e[0] == '0'); }(); return v; }      // A/B: 0 = the `hi` streams at normal priority
-static int hi_pool_size() { static const int v = [] { const char* e = std::getenv("ALEO_MI355X_HI_POOL"); const int k = e ? std::atoi(e) : 4; return k >= 1 && k <= MAX_SLOTS ? k : 4; }(); return v; }
+static constexpr int HI_POOL = 4;
 static std::mutex g_stream_mu;
 static int32_t create_streams_in_order(Device* d) {
-  static const bool on = [] { const char* e = std::getenv("ALEO_MI355X_STREAM_ORDER"); return !(e && e[0] == '0'); }();      // A/B: 0 = every context creates its streams at its first use
-  if (!on) return ALEO_MI355X_OK;
   std::lock_guard<std::mutex> lk(g_stream_mu);
   if (d->slots[0].stream) return ALEO_MI355X_OK;
   for (int i = 0; i < d->n_slots; ++i) HIPCHK(hipStreamCreateWithFlags(&d->slots[i].stream, hipStreamNonBlocking));
@@ -173,12 +170,12 @@ static int32_t create_streams_in_order(Device* d) {
 }
 static int32_t hi_stream_for(Ctx* c, hipStream_t* out) {
   Device* d = c->dev;
-  if (!d) { int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi); if (!hi_priority_on()) hi = 0; HIPCHK(hipStreamCreateWithPriority(out, hipStreamNonBlocking, hi)); return ALEO_MI355X_OK; }
+  if (!d) { int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi); HIPCHK(hipStreamCreateWithPriority(out, hipStreamNonBlocking, hi)); return ALEO_MI355X_OK; }
   std::lock_guard<std::mutex> lk(g_stream_mu);
   const bool helper = c >= &d->helpers[0] && c < &d->helpers[MAX_SLOTS];
-  const int idx = helper ? (int)(c - &d->helpers[0]) + 1 : (int)(c - &d->slots[0]), k = idx % hi_pool_size();      // slot i and helpers i, i + 1 (a pipeline's ring, a chunked call's later chunks) on different ones
+  const int idx = helper ? (int)(c - &d->helpers[0]) + 1 : (int)(c - &d->slots[0]), k = idx % HI_POOL;      // slot i and helpers i, i + 1 (a pipeline's ring, a chunked call's later chunks) on different ones
   while (d->hi_made <= k) {
-    int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi); if (!hi_priority_on()) hi = 0;      // hi = the numerically lowest = highest priority
+    int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // hi = the numerically lowest = highest priority
     HIPCHK(hipStreamCreateWithPriority(&d->hi_pool[d->hi_made], hipStreamNonBlocking, hi)); ++d->hi_made;
   }
   *out = d->hi_pool[k]; return ALEO_MI355X_OK;
@@ -1086,12 +1083,10 @@ int32_t aleo_mi355x_varuna_prove_many(aleo_mi355x_prove_request* requests, size_
     // reductions and transcripts — a third of a lockstep round — run in their shadow.  Up to four proofs that is one proof per group; from five on the groups hold two or more
     // and batch their commitments.  Measured (2^15 constraints, same box; profiles/r05_lockstep_groups_ab.txt, r05_lockstep_retune*.txt, r05_group_min_ab.txt, r05_group_from_ab.txt):
     // 8 proofs 32.7 ms as one group, 27.3 as four; 2 proofs 10.4 ms in lockstep, 8.55 as two groups of one; 3: 13.5 -> 11.6; 4: 15.1 -> 14.5; 8 groups of one: 29.6.
-    // ALEO_MI355X_LOCKSTEP_GROUPS=1: one group; ALEO_MI355X_LOCKSTEP_GROUP_FROM / _GROUP_MIN: fewest proofs per call that is split / per group.  Proof bytes do not depend on any of it.
+    // Every call of two or more proofs is split, down to one proof per group.  ALEO_MI355X_LOCKSTEP_GROUPS=1: one group.  Proof bytes do not depend on any of it.
     static const int groups_env = [] { const char* e = std::getenv("ALEO_MI355X_LOCKSTEP_GROUPS"); const int k = e ? std::atoi(e) : 4; return k >= 1 && k <= 4 ? k : 4; }();
     int32_t rc = ALEO_MI355X_OK; bool split_done = false;
-    static const size_t group_min = [] { const char* e = std::getenv("ALEO_MI355X_LOCKSTEP_GROUP_MIN"); const int k = e ? std::atoi(e) : 1; return (size_t)(k >= 1 && k <= 64 ? k : 1); }();      // fewest proofs per group
-    static const size_t group_from = [] { const char* e = std::getenv("ALEO_MI355X_LOCKSTEP_GROUP_FROM"); const int k = e ? std::atoi(e) : 2; return (size_t)(k >= 2 && k <= 64 ? k : 2); }();      // fewest proofs per call that is split into groups
-    const size_t want_groups = live.size() >= group_from ? std::min<size_t>((size_t)groups_env, live.size() / group_min) : 1;
+    const size_t want_groups = live.size() >= 2 ? std::min<size_t>((size_t)groups_env, live.size()) : 1;
     if (want_groups >= 2) {
       // contexts for groups 1..: never waited for (whatever is free now); fewer groups if fewer are free
       std::vector<Ctx*> gc{c}; std::vector<std::unique_lock<std::mutex>> glk;
@@ -1105,8 +1100,8 @@ int32_t aleo_mi355x_varuna_prove_many(aleo_mi355x_prove_request* requests, size_
         std::vector<std::vector<ProveRequest>> grp(G); std::vector<std::vector<size_t>> at(G);
         for (size_t i = 0; i < live.size(); ++i) { const size_t g = i * G / live.size(); grp[g].push_back(live[i]); at[g].push_back(i); }      // contiguous, balanced
         std::vector<int32_t> rcs(G, ALEO_MI355X_OK); std::vector<std::string> errs(G); std::vector<std::thread> th; bool started = true;
-        // inside a group ONE thread runs the group's proofs (ALEO_MI355X_GROUP_WORKERS): the groups are the call's parallelism, and four busy streams beat eight (profiles/r05_lockstep_retune.txt: 29.4 / 28.5 / 27.5 ms per 8 proofs with 4 / 2 / 1 workers per group, 54.0 / 53.9 / 52.8 per 16)
-        static const int group_workers = [] { const char* e = std::getenv("ALEO_MI355X_GROUP_WORKERS"); const int k = e ? std::atoi(e) : 1; return k >= 1 && k <= MAX_SLOTS + 1 ? k : 1; }();
+        // inside a group ONE thread runs the group's proofs: the groups are the call's parallelism, and four busy streams beat eight (profiles/r05_lockstep_retune.txt: 29.4 / 28.5 / 27.5 ms per 8 proofs with 4 / 2 / 1 workers per group, 54.0 / 53.9 / 52.8 per 16)
+        constexpr int group_workers = 1;
         for (size_t g = 1; g < G && started; ++g) {
           try {
             th.emplace_back([&, g] {
@@ -1637,7 +1632,7 @@ int32_t aleo_mi355x_kzg_commit_batch_sharded_device(void* out104, uint64_t shard
 // every column transform has finished.  A device may be listed more than once (the tests: one card).
 }  // extern "C" (helpers of the sharded transform follow)
 namespace {
-struct NttShard { int dev = 0; hipStream_t st = nullptr; void *a = nullptr, *b = nullptr; ShardWs* w = nullptr; };      // two buffers of n / G elements each, ping-pong (owned by the device's ShardWs)
+struct NttShard { int dev = 0; hipStream_t st = nullptr; void *a = nullptr, *b = nullptr; };      // two buffers of n / G elements each, ping-pong (owned by the device's ShardWs)
 std::mutex g_ntt_sh_mu;                                     // one sharded transform at a time: it occupies every listed device anyway
 int32_t peer_copy(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t s) {
   if (dst_dev == src_dev) { HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s)); }
@@ -1655,45 +1650,7 @@ int32_t shard_ws(size_t ordinal, size_t bytes, NttShard* out) {
   }
   if (!w->st) HIPCHK(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking));
   { int32_t rc; if ((rc = w->a.reserve(bytes)) || (rc = w->b.reserve(bytes))) return rc; }
-  out->dev = d->device; out->st = w->st; out->a = w->a.p; out->b = w->b.p; out->w = w;
-  return ALEO_MI355X_OK;
-}
-// The strided moves between ONE pageable host buffer and a shard's device buffer through two pinned bounce buffers of the shard (A/B switch ALEO_MI355X_SHARD_BOUNCE=1;
-// default: hipMemcpy2DAsync on the pageable buffer, which the runtime stages itself).  The shard's own thread gathers / scatters the rows with memcpy while the previous
-// chunk is on the link, so G shards on G devices move their 1/G of the buffer in parallel without sharing the runtime's staging path.  rows x row_bytes, host pitch in bytes.
-static constexpr size_t BOUNCE_BYTES = (size_t)8 << 20;
-bool bounce_on() { static const bool v = [] { const char* e = std::getenv("ALEO_MI355X_SHARD_BOUNCE"); return e && e[0] == '1'; }(); return v; }
-int32_t bounce_reserve(ShardWs* w) {
-  if (w->pin_cap) return ALEO_MI355X_OK;
-  for (int b = 0; b < 2; ++b) { HIPCHK(hipHostMalloc(&w->pin[b], BOUNCE_BYTES, hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&w->pin_ev[b], hipEventDisableTiming)); }
-  w->pin_cap = BOUNCE_BYTES; return ALEO_MI355X_OK;
-}
-int32_t bounce_upload(ShardWs* w, char* d_dst, const char* h_src, size_t h_pitch, size_t row_bytes, size_t rows, hipStream_t st) {
-  int32_t rc = bounce_reserve(w); if (rc) return rc;
-  if (row_bytes > BOUNCE_BYTES) { HIPCHK(hipMemcpy2DAsync(d_dst, row_bytes, h_src, h_pitch, row_bytes, rows, hipMemcpyHostToDevice, st)); return ALEO_MI355X_OK; }
-  const size_t per = BOUNCE_BYTES / row_bytes;
-  for (size_t r0 = 0, i = 0; r0 < rows; r0 += per, ++i) {
-    const int b = (int)(i & 1); const size_t nr = rows - r0 < per ? rows - r0 : per;
-    if (i >= 2) HIPCHK(hipEventSynchronize(w->pin_ev[b]));
-    for (size_t r = 0; r < nr; ++r) std::memcpy((char*)w->pin[b] + r * row_bytes, h_src + (r0 + r) * h_pitch, row_bytes);
-    HIPCHK(hipMemcpyAsync(d_dst + r0 * row_bytes, w->pin[b], nr * row_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(w->pin_ev[b], st));
-  }
-  return ALEO_MI355X_OK;
-}
-int32_t bounce_download(ShardWs* w, char* h_dst, size_t h_pitch, const char* d_src, size_t row_bytes, size_t rows, hipStream_t st) {
-  int32_t rc = bounce_reserve(w); if (rc) return rc;
-  if (row_bytes > BOUNCE_BYTES) { HIPCHK(hipMemcpy2DAsync(h_dst, h_pitch, d_src, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost, st)); return ALEO_MI355X_OK; }
-  const size_t per = BOUNCE_BYTES / row_bytes; size_t prev_r0 = 0, prev_nr = 0; int prev_b = -1;
-  auto scatter = [&](int b, size_t r0, size_t nr) { for (size_t r = 0; r < nr; ++r) std::memcpy(h_dst + (r0 + r) * h_pitch, (const char*)w->pin[b] + r * row_bytes, row_bytes); };
-  for (size_t r0 = 0, i = 0; r0 < rows; r0 += per, ++i) {
-    const int b = (int)(i & 1); const size_t nr = rows - r0 < per ? rows - r0 : per;
-    HIPCHK(hipMemcpyAsync(w->pin[b], d_src + r0 * row_bytes, nr * row_bytes, hipMemcpyDeviceToHost, st));      // (buffer b was scattered out two chunks ago)
-    HIPCHK(hipEventRecord(w->pin_ev[b], st));
-    if (prev_b >= 0) { HIPCHK(hipEventSynchronize(w->pin_ev[prev_b])); scatter(prev_b, prev_r0, prev_nr); }
-    prev_b = b; prev_r0 = r0; prev_nr = nr;
-  }
-  if (prev_b >= 0) { HIPCHK(hipEventSynchronize(w->pin_ev[prev_b])); scatter(prev_b, prev_r0, prev_nr); }
+  out->dev = d->device; out->st = w->st; out->a = w->a.p; out->b = w->b.p;
   return ALEO_MI355X_OK;
 }
 }  // namespace
@@ -1729,8 +1686,7 @@ int32_t aleo_mi355x_ntt_fr_sharded(void* inout, uint32_t lg_n, int32_t direction
       // phase 1: columns in, column transforms, twiddle, blocks by destination
       phase([&]() -> int32_t {
         int32_t q = shard_ws(ordinal[g], per * 32, &d); if (q) return q;
-        if (bounce_on()) { if ((q = bounce_upload(d.w, (char*)d.a, host + g * Cg * 32, C * 32, Cg * 32, R, d.st))) return q; }
-        else HIPCHK(hipMemcpy2DAsync(d.a, Cg * 32, host + g * Cg * 32, C * 32, Cg * 32, R, hipMemcpyHostToDevice, d.st));          // a = [R][Cg]
+        HIPCHK(hipMemcpy2DAsync(d.a, Cg * 32, host + g * Cg * 32, C * 32, Cg * 32, R, hipMemcpyHostToDevice, d.st));          // a = [R][Cg] (the runtime stages the pageable buffer itself)
         if (type == ALEO_NTT_COSET && direction == ALEO_NTT_FORWARD && (q = aleo_mi355x_fr_grid_scale_device(d.a, lg_n, R, Cg, 0, g * Cg, C, 1, 0, d.st))) return q;
         if ((q = aleo_mi355x_fr_transpose_device(d.b, d.a, R, Cg, d.st))) return q;                                                   // b = [Cg][R]
         if ((q = aleo_mi355x_ntt_fr_batch_device(d.b, lg_r, Cg, ALEO_NTT_ORDER_NN, direction, ALEO_NTT_STANDARD, d.st))) return q;     // [c][k_r] (inverse: x R^-1)
@@ -1754,8 +1710,7 @@ int32_t aleo_mi355x_ntt_fr_sharded(void* inout, uint32_t lg_n, int32_t direction
         if ((q = aleo_mi355x_ntt_fr_batch_device(d.a, lg_c, Rg, ALEO_NTT_ORDER_NN, direction, ALEO_NTT_STANDARD, d.st))) return q;     // [k_r][k_c] (inverse: x C^-1)
         if ((q = aleo_mi355x_fr_transpose_device(d.b, d.a, Rg, C, d.st))) return q;                                                   // b = [k_c][k_r local]: X[k_c R + k_r]
         if (type == ALEO_NTT_COSET && direction == ALEO_NTT_INVERSE && (q = aleo_mi355x_fr_grid_scale_device(d.b, lg_n, C, Rg, 0, g * Rg, R, 1, 1, d.st))) return q;
-        if (bounce_on()) { if ((q = bounce_download(d.w, host + g * Rg * 32, R * 32, (const char*)d.b, Rg * 32, C, d.st))) return q; }
-        else HIPCHK(hipMemcpy2DAsync(host + g * Rg * 32, R * 32, d.b, Rg * 32, Rg * 32, C, hipMemcpyDeviceToHost, d.st));
+        HIPCHK(hipMemcpy2DAsync(host + g * Rg * 32, R * 32, d.b, Rg * 32, Rg * 32, C, hipMemcpyDeviceToHost, d.st));
         HIPCHK(hipStreamSynchronize(d.st));
         return ALEO_MI355X_OK;
       });

@@ -136,7 +136,7 @@ struct Ctx {                           // one concurrency slot
   hipEvent_t scratch_ev = nullptr; bool scratch_busy = false; hipStream_t scratch_stream = nullptr;
   hipStream_t side = nullptr;          // second stream of the slot: small read-backs that must not wait for the kernels queued behind them
   hipStream_t hi = nullptr;            // a high-priority stream: the sort of a later chunk / the next launch chain must get its workgroups in while an accumulation fills the chip (msm_run_chunked, run_chains)
-  hipStream_t aux = nullptr;           // a third normal-priority stream: run_chains_pipelined's sorts and reductions (ALEO_MI355X_PIPELINE_HI=1 puts them on `hi`)
+  hipStream_t aux = nullptr;           // a third normal-priority stream: run_chains_pipelined's sorts and reductions
   hipEvent_t ev_hop = nullptr;         // run_chains: a chain's sort (on hi) -> its accumulation (on the normal-priority stream)
 };
 
@@ -162,7 +162,7 @@ struct Barrier {                                           // reusable; C++17 ha
 
 // What one shard of a transform sharded over devices (aleo_mi355x_ntt_fr_sharded) keeps on its device between calls: a stream and two grow-only
 // buffers of n / G elements.  A device listed k times in a call uses its first k entries.
-struct ShardWs { hipStream_t st = nullptr; DevBuf a, b; void* pin[2] = {nullptr, nullptr}; size_t pin_cap = 0; hipEvent_t pin_ev[2] = {nullptr, nullptr}; };      // pin: two pinned bounce buffers for the strided host <-> device moves of the host-buffer transform (ALEO_MI355X_SHARD_BOUNCE=1)
+struct ShardWs { hipStream_t st = nullptr; DevBuf a, b; };
 
 struct Device {
   int device = -1;
@@ -177,7 +177,7 @@ struct Device {
   Ctx slots[MAX_SLOTS];
   std::vector<std::unique_ptr<ShardWs>> shard_ws;     // grown under mu; used only by the one sharded transform in flight (api.hip g_ntt_sh_mu)
   DevBuf shard_home;                   // ntt_sharded_device: the home device's transposed copy of the data (n elements), same lock
-  hipStream_t hi_pool[MAX_SLOTS] = {}; int hi_made = 0;      // the high-priority streams of the device, dealt to the contexts round-robin (api.hip first_use): at most ALEO_MI355X_HI_POOL of them exist
+  hipStream_t hi_pool[MAX_SLOTS] = {}; int hi_made = 0;      // the high-priority streams of the device, dealt to the contexts round-robin (api.hip first_use): at most four of them exist
   Ctx helpers[MAX_SLOTS];              // extra streams + scratch a lockstep call borrows for its worker threads (never handed out as API slots)
 };
 // Borrows up to `want` idle helper contexts of the device (try-lock: none is waited for); they are released when `hs` goes out of scope.

@@ -10,7 +10,7 @@
 //
 // Layouts at the boundary (snarkVM in-memory): G2Affine {x: Fq2 (c0, c1), y: Fq2, infinity: bool} = 4 x 48 bytes Montgomery +
 // flag byte at 192, stride 200 (or 192 without the flag); result G2Projective (Jacobian) {x, y, z: Fq2} = 288 bytes,
-// returned affine-normalised (x, y, 1) or (1, 1, 0) for the identity.  HBM: bases n x 192 B; partial sums 384 B per slice.
+// returned affine-normalised (x, y, 1) or (1, 1, 0) for the identity.  HBM: bases n x 192 B (+ 224 B 28-bit rows); partial sums 448 B per slice.
 #include "ctx.h"
 #include "ec.h"
 #include "fp28.h"
@@ -296,31 +296,7 @@ int32_t g2_unpack200(Ctx* c, const void* d_rows200, void* d_xy192, void* d_flags
   HIPCHK(hipGetLastError());
   return ALEO_MI355X_OK;
 }
-struct G2Affine;
-__device__ __noinline__ void g2_madd_ni(struct XYZZ2* pa, const G2Affine* pp);
-__device__ __noinline__ void g2_slice_slow_path(const char* bases192, const uint32_t* run, uint32_t j, uint32_t j1, char* slot);
 
-// ---- kernels (same bookkeeping as msm.hip, one lane per group operation) ----------------------------------------------------
-__global__ void __launch_bounds__(256) k_g2_accum(const char* __restrict__ bases, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ hist,
-                                                  const uint2* __restrict__ scan_local, const uint2* __restrict__ scan_blk, const uint32_t* __restrict__ total_pairs, uint32_t M,
-                                                  const uint32_t* __restrict__ meta, const uint32_t* __restrict__ order, const uint32_t* __restrict__ task_g, char* __restrict__ partial) {
-  uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= meta[0]) return;
-  const uint32_t sid = order[t], g = task_g[sid];
-  uint2 st = scan_at(scan_local, scan_blk, g);
-  uint32_t cnt = hist[g], m = slices_of(cnt, pick_rule(total_pairs, M)), k = sid - st.y;
-  uint32_t j0 = (uint32_t)(((uint64_t)k * cnt) / m), j1 = (uint32_t)(((uint64_t)(k + 1) * cnt) / m);
-  const uint32_t* run = sorted + st.x;
-  XYZZ2 acc = g2_infinity();
-  for (uint32_t j = j0; j < j1; ++j) {
-    const uint32_t e = run[j];
-    G2Affine p; const char* row = bases + (size_t)(e & 0x7fffffffu) * 192;
-    p.x = load_fq2(row); p.y = load_fq2(row + 96);
-    if (e >> 31) { p.y.a = Fq::sub<1>(Fq::zero(), p.y.a); p.y.b = Fq::sub<1>(Fq::zero(), p.y.b); }      // q - y per component (canonical inputs)
-    g2_madd_ni(&acc, &p);
-  }
-  store_xyzz2(partial + (size_t)sid * 384, acc);
-}
 // the rest of a slice whose fast loop met P == +-acc: the general 32-bit code, continuing from the sum the pair stored in the slice's slot
 __device__ __noinline__ void g2_slice_slow_path(const char* bases192, const uint32_t* run, uint32_t j, uint32_t j1, char* slot) {
   XYZZ2 acc; g2_p2_to_xyzz2(slot, &acc);
@@ -373,60 +349,7 @@ __global__ void __launch_bounds__(256, 2) k_g2_accum28(const char* __restrict__ 
     if (!odd) g2_slice_slow_path(bases192, run, j, j1, slot);
   }
 }
-// partial[ft + i] += partial[ft + i + half] inside every multi-slice bucket of the list
-__global__ void __launch_bounds__(256) k_g2_tree_pass(char* __restrict__ partial, const uint32_t* __restrict__ list, const uint2* __restrict__ scan_local,
-                                                      const uint2* __restrict__ scan_blk, uint32_t M, const uint32_t* __restrict__ meta, uint32_t pass, uint32_t max_pairs,
-                                                      uint32_t list_len) {
-  const uint32_t op = blockIdx.x * 256 + threadIdx.x;
-  uint32_t h = op / max_pairs, i = op % max_pairs;
-  if (h >= list_len) return;
-  uint32_t g = list[h];
-  uint32_t ft = scan_at(scan_local, scan_blk, g).y;
-  uint32_t fn = (g + 1 < M) ? scan_at(scan_local, scan_blk, g + 1).y : meta[0];
-  uint32_t L = fn - ft;
-  for (uint32_t p = 0; p < pass; ++p) L = (L + 1) >> 1;
-  if (L <= 1) return;
-  uint32_t half = (L + 1) >> 1;
-  if (i >= L - half) return;
-  char* pa = partial + (size_t)(ft + i) * 384;
-  XYZZ2 a = load_xyzz2(pa), b = load_xyzz2(pa + (size_t)half * 384);
-  g2_add_ni(&a, &b);
-  store_xyzz2(pa, a);
-}
-// one lane per chunk of S consecutive buckets of one window: V = sum_{b in chunk} (b + 1) * S_b (running sums, then the chunk base by double-and-add)
-__global__ void __launch_bounds__(256) k_g2_bucket_chunks(const char* __restrict__ partial, const uint32_t* __restrict__ hist, const uint2* __restrict__ scan_local,
-                                                          const uint2* __restrict__ scan_blk, uint32_t B, uint32_t S, uint32_t nchunks_total, char* __restrict__ V) {
-  uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= nchunks_total) return;
-  uint32_t cpw = B / S, w = t / cpw, j = t % cpw, g0 = w * B + j * S;
-  XYZZ2 run = g2_infinity(), acc = g2_infinity();
-  for (uint32_t k = 0; k < S; ++k) {
-    const uint32_t g = g0 + (S - 1 - k);
-    if (hist[g]) { XYZZ2 y = load_xyzz2(partial + (size_t)scan_at(scan_local, scan_blk, g).y * 384); g2_add_ni(&run, &y); }
-    g2_add_ni(&acc, &run);
-  }
-  const uint32_t base = j * S;
-  if (base) {
-    XYZZ2 r = g2_infinity();
-    for (int bit = 31 - __clz(base); bit >= 0; --bit) { g2_double_ni(&r); if ((base >> bit) & 1) g2_add_ni(&r, &run); }
-    g2_add_ni(&acc, &r);
-  }
-  store_xyzz2(V + (size_t)t * 384, acc);
-}
-// (debug / A-B aid, ALEO_MI355X_G2_PAIR28=2: the pair-form accumulation followed by the one-lane reduction) slice sums 448 B pair form -> 384 B XYZZ2
-__global__ void __launch_bounds__(256) k_g2_p2_to_32(const char* __restrict__ src, char* __restrict__ dst, const uint32_t* __restrict__ meta) {
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x; if (t >= meta[0]) return;
-  XYZZ2 v; g2_p2_to_xyzz2(src + (size_t)t * P2B, &v); store_xyzz2(dst + (size_t)t * 384, v);
-}
-// (debug, ALEO_MI355X_G2_PAIR28=3) slice sums of the two accumulation kernels compared as group elements: out[0] = slices that differ, out[1] = the first such slice
-__global__ void __launch_bounds__(256) k_g2_compare(const char* __restrict__ a384, const char* __restrict__ b384, const uint32_t* __restrict__ meta, uint32_t* __restrict__ out) {
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x; if (t >= meta[0]) return;
-  XYZZ2 a = load_xyzz2(a384 + (size_t)t * 384), b = load_xyzz2(b384 + (size_t)t * 384);
-  b.Y.a = lt2q(Fq::sub<2>(Fq::zero(), b.Y.a)); b.Y.b = lt2q(Fq::sub<2>(Fq::zero(), b.Y.b));
-  g2_add_ni(&a, &b);
-  if (!(g2_is_inf(a) || fq2_is_zero(a.ZZ))) { atomicAdd(out, 1u); atomicMin(out + 1, t); }
-}
-// ---- the reduction in the pair form (round 4): the same bookkeeping as the one-lane kernels above, one lane pair per operation, points of 448 bytes ------
+// ---- the reduction in the pair form (round 4): the bookkeeping of msm.hip, one lane pair per operation, points of 448 bytes ------
 __global__ void __launch_bounds__(256) k_g2p_tree_pass(char* __restrict__ partial, const uint32_t* __restrict__ list, const uint2* __restrict__ scan_local,
                                                        const uint2* __restrict__ scan_blk, uint32_t M, const uint32_t* __restrict__ meta, uint32_t pass, uint32_t max_pairs,
                                                        uint32_t list_len) {
@@ -478,24 +401,6 @@ __global__ void k_g2p_gather_windows(const char* __restrict__ V, uint32_t seg_le
   if (t >= W * 28) return;
   uint32_t w = t / 28, q = t % 28;
   ((uint4*)out)[t] = ((const uint4*)(V + (size_t)w * seg_len * P2B))[q];
-}
-
-// V[seg*seg_len + i] += V[seg*seg_len + i + half] for i < L - half
-__global__ void __launch_bounds__(256) k_g2_seg_tree_pass(char* __restrict__ V, uint32_t seg_len, uint32_t nseg, uint32_t L) {
-  const uint32_t half = (L + 1) >> 1, pairs = L - half;
-  const uint32_t op = blockIdx.x * 256 + threadIdx.x;
-  if (op >= pairs * nseg) return;
-  const uint32_t seg = op / pairs, i = op % pairs;
-  char* pa = V + ((size_t)seg * seg_len + i) * 384;
-  XYZZ2 a = load_xyzz2(pa), b = load_xyzz2(pa + (size_t)half * 384);
-  g2_add_ni(&a, &b);
-  store_xyzz2(pa, a);
-}
-__global__ void k_g2_gather_windows(const char* __restrict__ V, uint32_t seg_len, uint32_t W, char* __restrict__ out) {
-  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= W * 24) return;
-  uint32_t w = t / 24, q = t % 24;
-  ((uint4*)out)[t] = ((const uint4*)(V + (size_t)w * seg_len * 384))[q];
 }
 
 // Test hook: the pair-form addition / doubling against the one-lane 32-bit code on chains of real curve points (aleo_mi355x_selftest_g2pair).
@@ -637,33 +542,12 @@ int32_t msm_g2_run(Ctx* c, uint64_t* out_jac36, const void* d_xy, const uint8_t*
   const uint32_t M = sp.M, cpw = P.B / P.S, nchunks = cpw * P.W;
   if ((rc = c->partial.reserve(sp.slices_max * 448))) return rc;
   if ((rc = c->vbuf.reserve(((size_t)nchunks * 4 + P.W) * 448))) return rc;      // chunk sums | window sums | three working points per chunk (pair form)
-  static const int pair_mode = [] { const char* e = std::getenv("ALEO_MI355X_G2_PAIR28"); return e ? std::atoi(e) : 1; }();      // A/B switch: 0 = the round-2 kernels (32-bit limbs, one lane per operation, out-of-line field calls); 2 = pair-form accumulation + one-lane reduction
-  const bool pair_accum = pair_mode != 0; const bool pair28 = pair_mode == 1;      // (3: mode 2 + a comparison of the two accumulation kernels' slice sums on stderr)
-  const size_t PBY = pair28 ? 448 : 384;                    // bytes per stored point of the reduction
-  char* partial = c->partial.as<char>(); char* V = c->vbuf.as<char>(); char* Vout = V + (size_t)nchunks * PBY;
-  if (pair_accum) {
-    const bool resident = d_rows28 != nullptr && pair28;    // a pinned set (aleo_mi355x_bases_g2_pin) keeps its 28-bit rows
-    if ((rc = c->out_stage.reserve((resident ? 0 : n * 224) + (pair28 ? 0 : sp.slices_max * 384) + 256))) return rc;      // the bases in the 28-bit form (per call for the one-shot entry point)
-    if (!resident) hipLaunchKernelGGL(k_g2_rows_to28, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const char*)d_xy, c->out_stage.as<char>(), (uint32_t)n);
-    hipLaunchKernelGGL(k_g2_accum28, dim3(2 * sp.slice_blocks), dim3(256), 0, s, resident ? (const char*)d_rows28 : c->out_stage.as<const char>(), (const char*)d_xy, sp.sorted, sp.hist, sp.scan_local, sp.scan_blk,
-                       sp.total_pairs, M, sp.meta, sp.order, sp.task_g, partial);
-    if (!pair28) {                                         // mode 2: hand the slice sums to the one-lane kernels
-      char* p32 = c->out_stage.as<char>() + n * 224;
-      hipLaunchKernelGGL(k_g2_p2_to_32, dim3(sp.slice_blocks), dim3(256), 0, s, partial, p32, sp.meta);
-      if (pair_mode == 3) {                                // debug: the round-2 kernel's slice sums beside them
-        DevTmp ref, cnt; if ((rc = ref.alloc(sp.slices_max * 384)) || (rc = cnt.alloc(8))) return rc;
-        uint32_t init[2] = {0u, 0xffffffffu}; HIPCHK(hipMemcpyAsync(cnt.p, init, 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_g2_accum, dim3(sp.slice_blocks), dim3(256), 0, s, (const char*)d_xy, sp.sorted, sp.hist, sp.scan_local, sp.scan_blk, sp.total_pairs, M, sp.meta, sp.order, sp.task_g, (char*)ref.p);
-        hipLaunchKernelGGL(k_g2_compare, dim3(sp.slice_blocks), dim3(256), 0, s, (const char*)ref.p, (const char*)p32, sp.meta, (uint32_t*)cnt.p);
-        uint32_t res[2], hm[8]; HIPCHK(hipMemcpyAsync(res, cnt.p, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(hm, sp.meta, 32, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-        fprintf(stderr, "g2 debug: n = %zu, slices = %u, differing = %u, first = %u\n", n, hm[0], res[0], res[1]);
-        uint32_t ra[96], rb[96], rp[112]; HIPCHK(hipMemcpy(ra, ref.p, 384, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(rb, p32, 384, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(rp, c->partial.p, 448, hipMemcpyDeviceToHost));
-      }
-      partial = p32;
-    }
-  } else
-  hipLaunchKernelGGL(k_g2_accum, dim3(sp.slice_blocks), dim3(256), 0, s, (const char*)d_xy, sp.sorted, sp.hist, sp.scan_local, sp.scan_blk, sp.total_pairs, M, sp.meta,
-                     sp.order, sp.task_g, partial);
+  char* partial = c->partial.as<char>(); char* V = c->vbuf.as<char>(); char* Vout = V + (size_t)nchunks * 448;
+  const bool resident = d_rows28 != nullptr;                // a pinned set (aleo_mi355x_bases_g2_pin) keeps its 28-bit rows
+  if ((rc = c->out_stage.reserve((resident ? 0 : n * 224) + 256))) return rc;      // the bases in the 28-bit form (per call for the one-shot entry point)
+  if (!resident) hipLaunchKernelGGL(k_g2_rows_to28, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const char*)d_xy, c->out_stage.as<char>(), (uint32_t)n);
+  hipLaunchKernelGGL(k_g2_accum28, dim3(2 * sp.slice_blocks), dim3(256), 0, s, resident ? (const char*)d_rows28 : c->out_stage.as<const char>(), (const char*)d_xy, sp.sorted, sp.hist, sp.scan_local, sp.scan_blk,
+                     sp.total_pairs, M, sp.meta, sp.order, sp.task_g, partial);
   HIPCHK(hipGetLastError());
   SliceMeta sm;
   if ((rc = msm_wait_meta(c, sp, s, &sm))) return rc;
@@ -671,30 +555,24 @@ int32_t msm_g2_run(Ctx* c, uint64_t* out_jac36, const void* d_xy, const uint8_t*
     const uint32_t Lc = sm.super_overflow ? L : (L < 16u ? L : (16u >> (pass < 4 ? pass : 4)));
     if (sm.n_heavy && Lc > 1) {
       uint32_t mp = Lc >> 1; uint64_t threads = (uint64_t)sm.n_heavy * mp;
-      if (pair28) hipLaunchKernelGGL(k_g2p_tree_pass, dim3((uint32_t)((2 * threads + 255) / 256)), dim3(256), 0, s, partial, sp.heavy, sp.scan_local, sp.scan_blk, M, sp.meta, pass, mp, sm.n_heavy);
-      else hipLaunchKernelGGL(k_g2_tree_pass, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, partial, sp.heavy, sp.scan_local, sp.scan_blk, M, sp.meta, pass, mp, sm.n_heavy);
+      hipLaunchKernelGGL(k_g2p_tree_pass, dim3((uint32_t)((2 * threads + 255) / 256)), dim3(256), 0, s, partial, sp.heavy, sp.scan_local, sp.scan_blk, M, sp.meta, pass, mp, sm.n_heavy);
     }
     if (sm.n_super) {
       uint32_t mp = L >> 1; uint64_t threads = (uint64_t)sm.n_super * mp;
-      if (pair28) hipLaunchKernelGGL(k_g2p_tree_pass, dim3((uint32_t)((2 * threads + 255) / 256)), dim3(256), 0, s, partial, sp.super_list, sp.scan_local, sp.scan_blk, M, sp.meta, pass, mp, sm.n_super);
-      else hipLaunchKernelGGL(k_g2_tree_pass, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, partial, sp.super_list, sp.scan_local, sp.scan_blk, M, sp.meta, pass, mp, sm.n_super);
+      hipLaunchKernelGGL(k_g2p_tree_pass, dim3((uint32_t)((2 * threads + 255) / 256)), dim3(256), 0, s, partial, sp.super_list, sp.scan_local, sp.scan_blk, M, sp.meta, pass, mp, sm.n_super);
     }
   }
-  if (pair28) hipLaunchKernelGGL(k_g2p_bucket_chunks, dim3((nchunks + 63) / 64), dim3(128), 0, s, partial, sp.hist, sp.scan_local, sp.scan_blk, P.B, P.S, nchunks, V, Vout + (size_t)P.W * 448);
-  else hipLaunchKernelGGL(k_g2_bucket_chunks, dim3((nchunks + 255) / 256), dim3(256), 0, s, partial, sp.hist, sp.scan_local, sp.scan_blk, P.B, P.S, nchunks, V);
+  hipLaunchKernelGGL(k_g2p_bucket_chunks, dim3((nchunks + 63) / 64), dim3(128), 0, s, partial, sp.hist, sp.scan_local, sp.scan_blk, P.B, P.S, nchunks, V, Vout + (size_t)P.W * 448);
   for (uint32_t L = cpw; L > 1; L = (L + 1) >> 1) {
     uint32_t pairs = (L - ((L + 1) >> 1)) * P.W;
-    if (pair28) hipLaunchKernelGGL(k_g2p_seg_tree_pass, dim3((2 * pairs + 255) / 256), dim3(256), 0, s, V, cpw, P.W, L);
-    else hipLaunchKernelGGL(k_g2_seg_tree_pass, dim3((pairs + 255) / 256), dim3(256), 0, s, V, cpw, P.W, L);
+    hipLaunchKernelGGL(k_g2p_seg_tree_pass, dim3((2 * pairs + 255) / 256), dim3(256), 0, s, V, cpw, P.W, L);
   }
-  if (pair28) hipLaunchKernelGGL(k_g2p_gather_windows, dim3((P.W * 28 + 255) / 256), dim3(256), 0, s, V, cpw, P.W, Vout);
-  else hipLaunchKernelGGL(k_g2_gather_windows, dim3((P.W * 24 + 255) / 256), dim3(256), 0, s, V, cpw, P.W, Vout);
+  hipLaunchKernelGGL(k_g2p_gather_windows, dim3((P.W * 28 + 255) / 256), dim3(256), 0, s, V, cpw, P.W, Vout);
   char* h_win = (char*)c->h_pinned + 64;
-  HIPCHK(hipMemcpyAsync(h_win, Vout, (size_t)P.W * PBY, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h_win, Vout, (size_t)P.W * 448, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
-  // host tail: total = sum_w 2^(c w) * S_w (Horner from the top window); device coordinates are lazily reduced (< 2q)
-  auto lazy2 = [](const uint64_t* p) { HFq2 r; r.a = HFq::reduce_lazy(p); r.b = HFq::reduce_lazy(p + 6); return r; };
+  // host tail: total = sum_w 2^(c w) * S_w (Horner from the top window)
   // a 56-byte component of the pair form: value * 2^392 (+ a few q) as 14 x 28-bit limbs; * 2^376 under the 2^-384 of the host Montgomery product gives the HFq form
   auto comp28 = [](const char* p) {
     const uint32_t* w = (const uint32_t*)p; uint64_t big[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -718,10 +596,7 @@ int32_t msm_g2_run(Ctx* c, uint64_t* out_jac36, const void* d_xy, const uint8_t*
   HXYZZ2 total = HXYZZ2::infinity();
   for (int w = (int)P.W - 1; w >= 0; --w) {
     for (int d = 0; d < plan_win_width((int)P.c, w); ++d) total = h2double(total);
-    HXYZZ2 v;
-    if (pair28) v = point28(h_win + (size_t)w * 448);
-    else { const uint64_t* src = (const uint64_t*)(h_win + (size_t)w * 384); v.X = lazy2(src); v.Y = lazy2(src + 12); v.ZZ = lazy2(src + 24); v.ZZZ = lazy2(src + 36); }
-    total = h2add(total, v);
+    total = h2add(total, point28(h_win + (size_t)w * 448));
   }
   h2store_jacobian_normalized(out_jac36, total);
   return ALEO_MI355X_OK;

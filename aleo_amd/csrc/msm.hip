@@ -51,8 +51,6 @@ MsmPlan make_plan(size_t n, int pre_c) {
     // running-sum chunk: 2S dependent additions per lane pair vs. one more level of masked sums per halving; measured
     // best at 16 for 2^19 buckets (enough chunks to fill the chip) and 4 for 2^15..2^16 buckets (latency only)
     p.c = (uint32_t)pre_c; p.W = 1; p.B = 1u << (pre_c - 1); p.M = p.B; p.S = pre_c >= 20 ? 16 : 4;
-    static const int s_env = [] { const char* e = std::getenv("ALEO_MI355X_CHUNK_S"); return e ? std::atoi(e) : 0; }();      // experiment knob (wide tables only)
-    if (pre_c >= 20 && (s_env == 4 || s_env == 8 || s_env == 16 || s_env == 32)) p.S = (uint32_t)s_env;
     return p;
   }
   uint32_t lg = 0; while (((size_t)1 << (lg + 1)) <= n) ++lg;
@@ -679,12 +677,9 @@ constexpr uint32_t lg_lanes(uint32_t lanes) { return lanes == 4 ? 2u : 1u; }
 // lanes per addition for a launch of `ops` independent additions: quads up to two waves per SIMD (2^17 lanes), pairs beyond.  Measured: k_seg_fold 90 -> 57 us,
 // k_tree_pass 15 -> 11 us, a 2^15-constraint proof 6.9 -> 6.6 ms; with the cut at 2^16 lanes the proof is at 6.8 ms.  (The 2^15-chunk kernel of the
 // widest window is the exception: 2^17 quad lanes take what 2^16 pair lanes take, 330 against 321 us — it keeps the pair form.)
-static inline bool quads_on() { static const bool v = [] { const char* e = std::getenv("ALEO_MI355X_QUAD_ADD"); return !(e && e[0] == '0'); }(); return v; }      // A/B switch: 0 = lane pairs everywhere
+static constexpr uint32_t QUAD_MAX_LG = 17;  // lg of the most quad lanes a launch may have
 static constexpr uint32_t ASIDE_MAX = 8;  // super-heavy buckets whose slice trees may run beside the reduction (msm_run)
-static inline bool aside_on() { static const bool v = [] { const char* e = std::getenv("ALEO_MI355X_ASIDE"); return !(e && e[0] == '0'); }(); return v; }      // A/B switch
-static inline bool prog_on() { static const bool v = [] { const char* e = std::getenv("ALEO_MI355X_SUM_TREE"); return !(e && e[0] == '0'); }(); return v; }      // A/B switch: 0 = masked trees on the wide tables too
-static inline uint32_t quad_max_lg() { static const uint32_t v = [] { const char* e = std::getenv("ALEO_MI355X_QUAD_MAX_LG"); const int k = e ? std::atoi(e) : 17; return (uint32_t)(k >= 10 && k <= 24 ? k : 17); }(); return v; }      // A/B: lg of the most quad lanes a launch may have
-static inline uint32_t grp_lanes(uint64_t ops) { return quads_on() && ops * 4 <= ((uint64_t)1 << quad_max_lg()) ? 4u : 2u; }
+static inline uint32_t grp_lanes(uint64_t ops) { return ops * 4 <= ((uint64_t)1 << QUAD_MAX_LG) ? 4u : 2u; }
 // partial[ft + i] += partial[ft + i + half] inside every multi-slice bucket: one launch per level serves both lists of the scan —
 // the common one (buckets of <= 16 slices, `pairs_a` lane pairs each) and the super-heavy one (`pairs_b` each; skewed scalars).
 template <bool F28, uint32_t LANES = 2>
@@ -738,35 +733,6 @@ __global__ void k_gather_super(const char* __restrict__ partial, const uint32_t*
 }
 
 // ---- bucket reduction -----------------------------------------------------------------------------
-// One lane PAIR per chunk of S consecutive buckets of one window: running sums run += S_b, acc += run (b descending)
-// kept in LDS between the cooperative additions, so acc = sum_{b in chunk} (b - base + 1) * S_b and run = chunk total.
-// Both go to HBM (V, Vrun); the chunk weights are applied by masked sums (fixed-base path).
-static constexpr uint32_t CHUNK_PAIRS = 128;        // chunks per 256-thread block (LANES = 2; 64 with quads)
-template <bool F28, uint32_t LANES = 2>
-__global__ void __launch_bounds__(256) k_bucket_chunks_pair(const char* __restrict__ partial, const uint32_t* __restrict__ hist, const uint2* __restrict__ scan_local,
-                                                       const uint2* __restrict__ scan_blk, uint32_t B, uint32_t S, uint32_t nchunks_total, char* __restrict__ V,
-                                                       uint32_t v_set_stride, char* __restrict__ Vrun, FrontChain older) {
-  constexpr uint32_t PB = PtFmt<F28>::BYTES, PW = PtFmt<F28>::WORDS;
-  constexpr uint32_t CPB = 256 / LANES;                   // chunks per block
-  __shared__ __attribute__((aligned(16))) uint32_t lds[2 * CPB * PW];
-  const uint32_t pr = threadIdx.x >> lg_lanes(LANES), t = blockIdx.x * CPB + pr;
-  if (t >= nchunks_total) return;
-  char* run = (char*)(lds + pr * PW); char* acc = (char*)(lds + (CPB + pr) * PW);
-  grp_zero<LANES, PB>(run); grp_zero<LANES, PB>(acc);
-  pair_fence();
-  const uint32_t cpw = B / S, w = t / cpw, j = t % cpw, g0 = w * B + j * S;
-  // the address of bucket k + 1's sum (two dependent loads: histogram, scan) is fetched while bucket k's two additions run
-  auto sum_of = [&](uint32_t g) -> const char* { return hist[g] ? partial + (size_t)scan_at(scan_local, scan_blk, g).y * PB : chain_sum(older, g); };      // older: buckets only earlier chunks of the request touched
-  const char* nxt = sum_of(g0 + S - 1);
-  for (uint32_t k = 0; k < S; ++k) {
-    const char* cur = nxt;
-    if (k + 1 < S) nxt = sum_of(g0 + S - 2 - k);
-    if (cur) { pt_add_grp<LANES, F28>(run, cur, run); pair_fence(); }
-    pt_add_grp<LANES, F28>(acc, run, acc); pair_fence();
-  }
-  grp_copy<LANES, PB>(run, Vrun + (size_t)t * PB); grp_copy<LANES, PB>(acc, V + ((size_t)w * v_set_stride + j) * PB);
-}
-
 // One lane QUAD per chunk of S consecutive buckets: running sums run_k = run_{k-1} + S_b (b descending) and acc += run_{k-1}
 // are independent once run_{k-1} exists, so two lane pairs work one step apart (S + 1 dependent additions instead of 2S):
 // sub-pair 0 extends the running sum (double-buffered in LDS), sub-pair 1 folds the previous one into acc.  Both make the
@@ -1031,21 +997,17 @@ template <bool MONT> static void launch_sort(int c, bool pre, const SortArgs& a,
 }
 
 
-// lg of the slice count pick_rule() aims for when it cuts buckets to fill the chip (2^17 = 2 waves per SIMD: measured equal to 2^18 on uniform input, 4 % better on witness-like scalars); ALEO_MI355X_FILL_SHIFT
-// overrides it for experiments
-static uint32_t fill_shift() {
-  static const uint32_t v = [] { const char* e = std::getenv("ALEO_MI355X_FILL_SHIFT"); int k = e ? std::atoi(e) : 17; return (uint32_t)(k >= 14 && k <= 22 ? k : 17); }();
-  return v;
-}
+// lg of the slice count pick_rule() aims for when it cuts buckets to fill the chip (2^17 = 2 waves per SIMD: measured equal to 2^18 on uniform input, 4 % better on witness-like scalars)
+static constexpr uint32_t FILL_SHIFT = 17;
 
 // Upper bound of the slice count the device will compute (k_scan_tiles / pick_rule), from what the host knows: `pairs_max`
 // (>= the real pair count) and the bucket count M.  Every non-empty bucket is at least one slice; a bucket cut at `split`
-// adds cnt / split more.  pick_rule's split is >= 8 (4 below 2^18 pairs) always; it is >= pairs / 2^fill_shift / 1.125 while the fill rule decides and
+// adds cnt / split more.  pick_rule's split is >= 8 (4 below 2^18 pairs) always; it is >= pairs / 2^FILL_SHIFT / 1.125 while the fill rule decides and
 // >= the mean bucket size while the mean rule decides, until the 256-point cap takes over.  The grids of the slice kernels
 // and of the accumulation are sized by this bound, so no launch waits for the device's own count to reach the host.
 static size_t slice_bound(size_t pairs_max, size_t M) {
   const size_t nonempty = M < pairs_max ? M : pairs_max;
-  const size_t fill_cap = ((size_t)9 << fill_shift()) >> 3;          // pairs / fill < 1.125 * 2^fill_shift while the fill rule decides
+  const size_t fill_cap = ((size_t)9 << FILL_SHIFT) >> 3;          // pairs / fill < 1.125 * 2^FILL_SHIFT while the fill rule decides
   const size_t by_rule = M + fill_cap + pairs_max / 256;
   const size_t by_min = pairs_max / 4;          // pick_rule's shortest split (the device decides 4 or 8 from its own pair count, which may be far below pairs_max)
   return nonempty + (by_min < by_rule ? by_min : by_rule) + 1;
@@ -1068,9 +1030,7 @@ int32_t msm_sort_phase(Ctx* c, SegArgs& segs, size_t pts, bool mont, const uint8
   SortPhase& sp = *out; sp.P = P;
   // columns of the level-1 count matrix: the blocks of a set's segments side by side; every row is as wide as the widest set
   uint32_t width[MAX_SETS] = {}, nblk_x = 0;
-  static const uint32_t tile_max = [] { const char* e = std::getenv("ALEO_MI355X_PART_TILE_MAX"); const int k = e ? std::atoi(e) : 8192; return (uint32_t)(k == 2048 || k == 4096 || k == 8192 ? k : 8192); }();      // A/B switch
-  uint32_t tile = pts >= ((size_t)1 << 22) ? 8192u : (pts >= ((size_t)1 << 21) ? 4096u : PART_TILE);
-  segs.tile = tile < tile_max ? tile : tile_max;
+  segs.tile = pts >= ((size_t)1 << 22) ? 8192u : (pts >= ((size_t)1 << 21) ? 4096u : PART_TILE);
   for (uint32_t q = 0; q < segs.nseg; ++q) {
     const uint32_t nb = (segs.n[q] + segs.tile - 1) / segs.tile, st = pre ? segs.set[q] : 0;
     segs.col0[q] = width[st]; width[st] += nb; nblk_x = nb > nblk_x ? nb : nblk_x;
@@ -1122,7 +1082,7 @@ int32_t msm_sort_phase(Ctx* c, SegArgs& segs, size_t pts, bool mont, const uint8
   const uint32_t nparts_max = ncb + (uint32_t)(pairs_max / BIN_PART) + 1;
   if (mont) launch_sort<true>(P.c, pre, sa, 0, s); else launch_sort<false>(P.c, pre, sa, 0, s);
   hipLaunchKernelGGL(k_scan32_tiles, dim3(cnt_tiles), dim3(256), 0, s, sa.cnt, (uint32_t)cnt_len, sa.off_local, cnt_tile_tot);
-  hipLaunchKernelGGL(k_scan32_top, dim3(1), dim3(256), 0, s, cnt_tile_tot, cnt_tiles, sa.off_blk, fill_shift());
+  hipLaunchKernelGGL(k_scan32_top, dim3(1), dim3(256), 0, s, cnt_tile_tot, cnt_tiles, sa.off_blk, FILL_SHIFT);
   if (mont) launch_sort<true>(P.c, pre, sa, 1, s); else launch_sort<false>(P.c, pre, sa, 1, s);
   hipLaunchKernelGGL(k_bin_parts, dim3(1), dim3(256), 0, s, sa.off_local, sa.off_blk, nblk, ncb, cnt_tiles, part_start);
   hipLaunchKernelGGL(k_bin_hist, dim3(nparts_max), dim3(256), 0, s, sa.items, sa.off_local, sa.off_blk, nblk, ncb, cnt_tiles, LB, part_start, hist);
@@ -1135,8 +1095,7 @@ int32_t msm_sort_phase(Ctx* c, SegArgs& segs, size_t pts, bool mont, const uint8
   uint32_t* host_meta = nullptr;
   HIPCHK(hipHostGetDevicePointer((void**)&host_meta, c->h_pinned, 0));
   sp.meta_seq = ++c->meta_seq;
-  static const bool fuse_top_env = [] { const char* e = std::getenv("ALEO_MI355X_FUSE_SCAN_TOP"); return !(e && e[0] == '0'); }();      // A/B switch
-  const bool fuse_top = fuse_top_env && lean && ntiles <= FUSED_TILES;      // (calls that time their phases keep the sort / slice-order boundary at ev[1])
+  const bool fuse_top = lean && ntiles <= FUSED_TILES;      // (calls that time their phases keep the sort / slice-order boundary at ev[1])
   if (!fuse_top) hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, tile_tot, ntiles, scan_blk, meta, (volatile uint32_t*)host_meta, sp.meta_seq);
   HIPCHK(hipGetLastError());
   if (!lean) HIPCHK(hipEventRecord(c->ev[1], s));
@@ -1271,7 +1230,7 @@ static int32_t msm_front_finish(Ctx* c, hipStream_t s, Front& f, bool allow_asid
   // A handful of super-heavy buckets (witness-like scalars: the digit-1 bucket of the lowest window holds a fifth of the points) have a slice tree of
   // 10+ dependent levels while the common list is done after 4.  Then the long trees run ASIDE, on the slot's side stream, over slices 1.. of their
   // buckets; the reduction below goes ahead with slice 0 as those buckets' sums, and the host adds (b + 1) * (sum of slices 1..) to the result.
-  const bool aside = f.aside = allow_aside && f.masked && aside_on() && sm.n_super >= 1 && sm.n_super <= ASIDE_MAX && !sm.super_overflow && sm.max_m >= 64;
+  const bool aside = f.aside = allow_aside && f.masked && sm.n_super >= 1 && sm.n_super <= ASIDE_MAX && !sm.super_overflow && sm.max_m >= 64;
   uint32_t* h_aside = (uint32_t*)((char*)c->h_pinned + 64 + (size_t)f.nseg * 224);
   if (aside) {
     if (f.lean) HIPCHK(hipEventRecord(c->ev[5], s));          // (nothing has been queued behind the accumulation yet: the same position)
@@ -1286,9 +1245,8 @@ static int32_t msm_front_finish(Ctx* c, hipStream_t s, Front& f, bool allow_asid
     hipLaunchKernelGGL(k_gather_super, dim3((sm.n_super * 57 + 255) / 256), dim3(256), 0, c->side, partial, sp.super_list, sm.n_super, scan_local, scan_blk, dst);
     HIPCHK(hipEventRecord(c->ev[4], c->side));
   }
-  // the levels behind the first in one launch (k_tree_rest) when only the common list is left and no bucket has more than 8 slices (ALEO_MI355X_TREE_REST=0: one launch per level)
-  static const bool tree_rest = [] { const char* e = std::getenv("ALEO_MI355X_TREE_REST"); return !(e && e[0] == '0'); }();
-  const bool rest_ok = tree_rest && pre && quads_on() && !sm.super_overflow && (aside || sm.n_super == 0) && sm.n_heavy && sm.max_common > 2 && sm.max_common <= 8;
+  // the levels behind the first in one launch (k_tree_rest) when only the common list is left and no bucket has more than 8 slices
+  const bool rest_ok = pre && !sm.super_overflow && (aside || sm.n_super == 0) && sm.n_heavy && sm.max_common > 2 && sm.max_common <= 8;
   if (sm.NT) {
     for (uint32_t pass = 0, L = sm.max_m, Lcm = sm.max_common; L > 1; ++pass, L = (L + 1) >> 1, Lcm = (Lcm + 1) >> 1) {
       if (rest_ok && pass == 1) {
@@ -1361,31 +1319,23 @@ static int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bo
     // (masked => pre: the partial sums are 28-bit points)
     // every launch below picks lanes per addition by its own width (grp_lanes): four while it is latency-bound, two once the additions fill the chip
     // wide tables (2^19 buckets, S = 16): one lane pair per chunk (32 dependent additions) against two pairs one step apart (17): reduce phase 0.487 -> 0.460 ms
-    // at 2^20; S = 8 / 32 / 4 with either form: 0.51-0.54 / 0.48-0.55 / 0.66-0.72 ms (ALEO_MI355X_CHUNK_S, ALEO_MI355X_CHUNK_FORM=1: A/B switches)
-    static const uint32_t prog_min_c = [] { const char* e = std::getenv("ALEO_MI355X_SUM_TREE_MIN_C"); const int k = e ? std::atoi(e) : 13; return (uint32_t)(k >= 13 && k <= 24 ? k : 13); }();
-    const bool prog = P.c >= prog_min_c && prog_on() && cpw > FOLD;      // (a set of <= 256 chunks would go straight to the final fold: the masked form keeps those)
+    // at 2^20; S = 8 / 32 / 4 with either form: 0.51-0.54 / 0.48-0.55 / 0.66-0.72 ms
+    // Sum trees (k_prog_*) against masked trees: reduce phase of the 2^20 MSM 0.464 -> 0.412 ms at S = 16 (S = 8: 0.537 -> 0.451, S = 4: 0.720 -> 0.508: the
+    // chunk kernel is bound by its 2 additions per bucket, not by their order, so smaller chunks still lose); on the small tables too: 2^15-constraint proof
+    // 6.47 -> 6.35 ms, eight instances at 2^13 7.19 -> 6.88 ms.  Below c = 13 the masked trees stay.
+    constexpr uint32_t SUM_TREE_MIN_C = 13;
+    const bool prog = P.c >= SUM_TREE_MIN_C && cpw > FOLD;      // (a set of <= 256 chunks would go straight to the final fold: the masked form keeps those)
     uint32_t out_pts = fseg;                               // result points per set the host tail reads
     if (!enqueued) {
-    static const bool wide_two_groups = [] { const char* e = std::getenv("ALEO_MI355X_CHUNK_FORM"); return !(e && e[0] == '1'); }();
-    if (P.c >= 20 && !wide_two_groups) {
-      if (grp_lanes(2 * (uint64_t)nchunks) == 4) hipLaunchKernelGGL((k_bucket_chunks_pair<true, 4>), dim3((nchunks + 63) / 64), dim3(256), 0, s, partial, hist, scan_local, scan_blk, P.B, P.S, nchunks, V, setw, Vrun, older);
-      else hipLaunchKernelGGL(k_bucket_chunks_pair<true>, dim3((nchunks + CHUNK_PAIRS - 1) / CHUNK_PAIRS), dim3(256), 0, s, partial, hist, scan_local, scan_blk, P.B, P.S, nchunks, V, setw, Vrun, older);
-    } else {
-      if (grp_lanes(2 * (uint64_t)nchunks) == 4) hipLaunchKernelGGL((k_bucket_chunks<true, 4>), dim3((nchunks + 31) / 32), dim3(256), 0, s, partial, hist, scan_local, scan_blk, P.B, P.S, nchunks, V, setw, Vrun, older);
-      else hipLaunchKernelGGL(k_bucket_chunks<true>, dim3((nchunks + CHUNK_QUADS - 1) / CHUNK_QUADS), dim3(256), 0, s, partial, hist, scan_local, scan_blk, P.B, P.S, nchunks, V, setw, Vrun, older);
-    }
-    // Measured (ALEO_MI355X_SUM_TREE=0 is the A/B switch; ALEO_MI355X_SUM_TREE_MIN_C limits it to the wider tables): reduce phase of the 2^20 MSM 0.464 -> 0.412 ms at
-    // S = 16 (S = 8: 0.537 -> 0.451, S = 4: 0.720 -> 0.508: the chunk kernel is bound by its 2 additions per bucket, not by their order, so smaller chunks still lose);
-    // on the small tables too: 2^15-constraint proof 6.47 -> 6.35 ms, eight instances at 2^13 7.19 -> 6.88 ms.
+    if (grp_lanes(2 * (uint64_t)nchunks) == 4) hipLaunchKernelGGL((k_bucket_chunks<true, 4>), dim3((nchunks + 31) / 32), dim3(256), 0, s, partial, hist, scan_local, scan_blk, P.B, P.S, nchunks, V, setw, Vrun, older);
+    else hipLaunchKernelGGL(k_bucket_chunks<true>, dim3((nchunks + CHUNK_QUADS - 1) / CHUNK_QUADS), dim3(256), 0, s, partial, hist, scan_local, scan_blk, P.B, P.S, nchunks, V, setw, Vrun, older);
     if (prog) {
       char* G0 = Tout; char* G1 = G0 + (size_t)K * (3 * (cpw / 2)) * PB28;      // ping-pong: a set is at most 3 segments of cpw / 2 points after the first pass
       const char* node = Vrun; uint32_t node_ss = cpw; const char* A = V; uint32_t a_ss = setw; const char* T = Vrun; uint32_t t_ss = 0, nT = 0, L = cpw;
       char* dstbuf = G0;
-      // ALEO_MI355X_PROG_PASS2=0: one level per launch throughout (A/B switch)
-      static const bool pass2_on = [] { const char* e = std::getenv("ALEO_MI355X_PROG_PASS2"); return !(e && e[0] == '0'); }();
       while (L > FOLD) {
         const uint32_t half = L >> 1, out_ss = (3 + nT) * half; const uint64_t ops = (uint64_t)(2 + nT) * half * K;
-        if (pass2_on && (L >> 2) >= FOLD && grp_lanes(ops) == 4) {      // two levels at once: L -> L / 4
+        if ((L >> 2) >= FOLD && grp_lanes(ops) == 4) {      // two levels at once: L -> L / 4
           const uint32_t quarter = L >> 2, out2 = (4 + nT) * quarter; const uint64_t octs = (uint64_t)(2 + nT) * quarter * K;
           hipLaunchKernelGGL(k_prog_pass2, dim3((uint32_t)((octs + 31) / 32)), dim3(256), 0, s, node, node_ss, A, a_ss, T, t_ss, nT, L, K, dstbuf, out2);
           node = dstbuf; node_ss = out2; A = dstbuf + (size_t)quarter * PB28; a_ss = out2; T = dstbuf + (size_t)2 * quarter * PB28; t_ss = out2; nT += 2; L = quarter;
@@ -1402,8 +1352,7 @@ static int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bo
       out_pts = 1 + nT + lgL;                              // = 1 + lgN
       char* dst = nullptr;
       HIPCHK(hipHostGetDevicePointer((void**)&dst, h_win, 0));
-      if (quads_on()) hipLaunchKernelGGL(k_prog_final<4>, dim3(K * out_pts), dim3(512), 0, s, fin, fin_ss, L, nT, lgL, K, dst);
-      else hipLaunchKernelGGL(k_prog_final<2>, dim3(K * out_pts), dim3(256), 0, s, fin, fin_ss, L, nT, lgL, K, dst);
+      hipLaunchKernelGGL(k_prog_final<4>, dim3(K * out_pts), dim3(512), 0, s, fin, fin_ss, L, nT, lgL, K, dst);
     } else {
     {
       const uint64_t ops = (uint64_t)tseg * lgN * K;
@@ -1426,8 +1375,7 @@ static int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bo
       // mapped), so the result needs neither a gather launch nor a copy — the stream synchronisation below is all that is left
       char* dst = nullptr;
       HIPCHK(hipHostGetDevicePointer((void**)&dst, h_win, 0));
-      if (quads_on()) hipLaunchKernelGGL(k_seg_fold<4>, dim3(nseg), dim3(512), 0, s, cur, stride, L, nseg, dst, 1u);
-      else hipLaunchKernelGGL(k_seg_fold<2>, dim3(nseg), dim3(256), 0, s, cur, stride, L, nseg, dst, 1u);
+      hipLaunchKernelGGL(k_seg_fold<4>, dim3(nseg), dim3(512), 0, s, cur, stride, L, nseg, dst, 1u);
     } else {
       hipLaunchKernelGGL(k_gather_strided, dim3((nseg * 14 + 255) / 256), dim3(256), 0, s, cur, stride, nseg, Tout);
       HIPCHK(hipMemcpyAsync(h_win, Tout, (size_t)nseg * PB28, hipMemcpyDeviceToHost, s));
@@ -1435,13 +1383,10 @@ static int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bo
     }
     HIPCHK(hipEventRecord(c->ev[3], s));
     if (f.lean && older.n == 0 && !aside) {                  // single-chain prover commitments: clear the sort's block for the next chain now, under the host tail (ev[3] sits in front of it; not with trees still running aside: they read the lists in that block)
-      static const bool clear_ahead = [] { const char* e = std::getenv("ALEO_MI355X_CLEAR_AHEAD"); return !(e && e[0] == '0'); }();      // A/B switch
       // (as much as the largest chain seen on this context needs, within the allocation: a proof's chains differ in size, and a chain larger than its predecessor would fill again)
-      if (clear_ahead) {
-        if (sp.zero_bytes > c->hist_zero_max) c->hist_zero_max = sp.zero_bytes;
-        const size_t z = c->hist_zero_max <= c->hist.cap && (void*)sp.hist == c->hist.p ? c->hist_zero_max : sp.zero_bytes;
-        HIPCHK(hipMemsetAsync(sp.hist, 0, z, s)); c->hist_clean = z; c->hist_clean_stream = s; c->hist_clean_ptr = (void*)sp.hist;
-      }
+      if (sp.zero_bytes > c->hist_zero_max) c->hist_zero_max = sp.zero_bytes;
+      const size_t z = c->hist_zero_max <= c->hist.cap && (void*)sp.hist == c->hist.p ? c->hist_zero_max : sp.zero_bytes;
+      HIPCHK(hipMemsetAsync(sp.hist, 0, z, s)); c->hist_clean = z; c->hist_clean_stream = s; c->hist_clean_ptr = (void*)sp.hist;
     }
     } else if (prog) { uint32_t L = cpw, nT = 0; while (L > FOLD) { ++nT; L >>= 1; } uint32_t lgL = 0; while ((1u << lgL) < L) ++lgL; out_pts = 1 + nT + lgL; }
     if (!collect) return ALEO_MI355X_OK;
@@ -1470,8 +1415,8 @@ static int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bo
       for (uint32_t r = 0; r < na; ++r) total = hadd(total, lazy_point28(hw + (size_t)r * PB28));
       totals[q] = total;
     };
-    static const uint32_t tail_pool_min = [] { const char* e = std::getenv("ALEO_MI355X_TAIL_POOL"); const int k = e ? std::atoi(e) : 3; return (uint32_t)(k <= 0 ? 0x7fffffff : k); }();      // A/B switch: results from which the pool is used (0 = never; 2^15 proof: 5.68 / 5.65 / 5.74 ms with 8 / 3 / 2, profiles/r05_tailpool_min_ab.txt)
-    if (K >= tail_pool_min) host_parallel_for(K, horner); else for (uint32_t q = 0; q < K; ++q) horner(q);
+    constexpr uint32_t TAIL_POOL = 3;                      // results from which the pool is used (2^15 proof: 5.68 / 5.65 / 5.74 ms with 8 / 3 / 2, profiles/r05_tailpool_min_ab.txt)
+    if (K >= TAIL_POOL) host_parallel_for(K, horner); else for (uint32_t q = 0; q < K; ++q) horner(q);
     for (uint32_t h = 0; aside && h < sm.n_super; ++h) {             // (b + 1) * (slices 1.. of super-heavy bucket b), by double-and-add
       const uint32_t* rec = h_aside + (size_t)h * 57; const uint32_t g = rec[56], q = g / P.B, wgt = g % P.B + 1;
       if (q >= K) { g_last_error = "msm: internal: super-heavy bucket outside the sets"; return ALEO_MI355X_ERR_HIP; }
@@ -1517,45 +1462,16 @@ static int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bo
   return ALEO_MI355X_OK;
 }
 
-static int32_t msm_run_chunked(Ctx* c, HelperSet& hs, uint64_t* out_jac18, const PinnedBases& pb, size_t n, bool mont, hipStream_t s, const void* host_src, const MsmJob* dev_job = nullptr);
-static uint32_t chunks3_min_lg();
-// Requests with the scalars already on the device CAN go in chunks too (msm_run_chunked with dev_job): the sort of the later chunks then runs beside the
-// accumulation of the earlier ones instead of in front of everything.  Measured and OFF by default (round 4, resident uniform scalars, whole / chunked):
-// 2^20 2.82 / 3.03 ms, 2^21 5.12 / 5.24, 2^22 9.41 / 9.51 — without an upload to hide, the seeded launches (+5 % accumulation time: shorter slices, a seed
-// read and a product per bucket) and the sort that crawls beside an accumulation holding every wave slot cost more than the 0.3-1.0 ms of sort they
-// move out of the way; holding a later chunk's sort until the previous accumulation starts (as run_chains does for whole chains) makes it worse
-// (2^20 3.07, 2^21 5.91, 2^22 9.83 ms against 2.83 / 5.04 / 9.32 whole: tools/resident_ab.py).  ALEO_MI355X_CHUNK_DEV_MIN_LG: lg of the smallest such
-// request (default 0 = never; the GPU suite passes with 20).
-// the cut of a device-scalar request: segment of `len` scalars up to `pc` percent, on a multiple of 256 scalars (msm_run_chunked)
-static inline size_t chunk_cut(size_t len, uint32_t pc) { const size_t v = pc >= 100u ? len : ((size_t)((double)len * pc / 100.0)) & ~(size_t)255; return v < len ? v : len; }
-static const uint32_t CHUNK_SHARE_DEV[4][3] = {{0, 0, 0}, {0, 0, 0}, {28, 72, 0}, {12, 28, 60}};
-// every chunk of a Q-chunk device-scalar request must hold at least one scalar (a request of many short segments can leave the first chunk empty: then the
-// whole-request chain runs instead)
-static bool chunks_all_nonempty(const MsmJob& job, uint32_t Q) {
-  uint32_t cum = 0;
-  for (uint32_t k = 0; k < Q; ++k) {
-    const uint32_t lo = cum, hi = k + 1 == Q ? 100u : cum + CHUNK_SHARE_DEV[Q][k]; cum = hi; bool any = false;
-    for (uint32_t q = 0; q < job.nseg && !any; ++q) any = chunk_cut(job.segs[q].len, hi) > chunk_cut(job.segs[q].len, lo);
-    if (!any) return false;
-  }
-  return true;
-}
-static uint32_t chunk_dev_min_lg() { static const uint32_t v = [] { const char* e = std::getenv("ALEO_MI355X_CHUNK_DEV_MIN_LG"); const int k = e ? std::atoi(e) : 0; return (uint32_t)(k >= 0 && k <= 40 ? k : 0); }(); return v; }
+// Requests with the scalars already on the device run whole.  In chunks (the sort of the later chunks beside the accumulation of the earlier ones instead of
+// in front of everything) they measured slower (round 4, resident uniform scalars, whole / chunked): 2^20 2.82 / 3.03 ms, 2^21 5.12 / 5.24, 2^22 9.41 / 9.51 —
+// without an upload to hide, the seeded launches (+5 % accumulation time: shorter slices, a seed read and a product per bucket) and the sort that crawls
+// beside an accumulation holding every wave slot cost more than the 0.3-1.0 ms of sort they move out of the way; holding a later chunk's sort until the
+// previous accumulation starts (as run_chains does for whole chains) makes it worse (2^20 3.07, 2^21 5.91, 2^22 9.83 ms against 2.83 / 5.04 / 9.32 whole:
+// tools/resident_ab.py).
 int32_t msm_run(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s) {
   if (job.k == 0) return ALEO_MI355X_OK;
-  if (chunk_dev_min_lg() && !job.sparse && c->dev && job.k <= MAX_SETS && job.nseg <= MAX_SEGS) {
-    size_t pts = 0, reach = 0; bool in_range = true;
-    for (uint32_t q = 0; q < job.nseg; ++q) { const MsmSeg& g = job.segs[q]; if (!g.len) continue; pts += g.len; reach = g.off + g.len > reach ? g.off + g.len : reach; in_range = in_range && g.out < job.k; }
-    if (job.tier_n > reach && job.tier_n <= pb.n) reach = job.tier_n;
-    bool tiered = false; for (const auto& t : pb.tab) if (t.d && reach >= t.min_n && reach <= t.cover) { tiered = job.k <= 1 || job.k <= msm_max_sets(pb, reach); break; }
-    if (in_range && tiered && pts >= ((size_t)1 << chunk_dev_min_lg())) {
-      HelperSet hs; { const int32_t rc = acquire_helpers(c->dev, pts >= ((size_t)1 << chunks3_min_lg()) ? 2 : 1, hs); if (rc) return rc; }
-      if (!hs.ctx.empty() && chunks_all_nonempty(job, 1 + (uint32_t)hs.ctx.size())) return msm_run_chunked(c, hs, out_jac18, pb, reach, job.mont, s, nullptr, &job);
-    }
-  }
   Front f; int32_t rc;
-  static const bool lean_off = [] { const char* e = std::getenv("ALEO_MI355X_LEAN"); return e && e[0] == '0'; }();      // A/B switch: 0 = phase-timing events in the prover's chains too (round 4)
-  f.lean = job.lean && !lean_off;
+  f.lean = job.lean;
   if ((rc = msm_front_sort(c, pb, job, s, f))) return rc;
   if (f.empty) { for (uint32_t q = 0; q < job.k; ++q) host::hstore_jacobian_normalized(out_jac18 + 18 * q, host::HXYZZ::infinity()); return ALEO_MI355X_OK; }
   if ((rc = msm_front_accum(c, s, f, nullptr, nullptr))) return rc;
@@ -1580,44 +1496,24 @@ int32_t msm_run(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob
 // profiles/r04_chunk_cumask_ab.jsonl): sorts confined to 16-64 reserved CUs are 4-8x slower (2^20: 4.5 / 3.8 / 3.4 ms with 16 / 32 / 64 CUs against 3.26), and
 // keeping the accumulations off 8-32 CUs while the sorts run anywhere changes nothing at 2^20 and costs 5-8 % beyond.
 // (Round 3 ran two halves as two complete MSMs on two host threads: that paid the 0.4 ms bucket reduction twice and lost below 2^21 points.)
-// dev_job != nullptr: the scalars are already on the device (any number of sets and segments: every segment is cut at the same fractions; n = the request's
-// reach, its tier) — nothing is uploaded, and what the later chunks hide under the earlier chunks' accumulation is their sort alone, so the first chunk is
-// smaller (28 / 72 %, 12 / 28 / 60 %); the helper streams first wait for an event on `s`, where the caller's scalars may still be in flight.
-static int32_t msm_run_chunked(Ctx* c, HelperSet& hs, uint64_t* out_jac18, const PinnedBases& pb, size_t n, bool mont, hipStream_t s, const void* host_src, const MsmJob* dev_job) {
+static int32_t msm_run_chunked(Ctx* c, HelperSet& hs, uint64_t* out_jac18, const PinnedBases& pb, size_t n, bool mont, hipStream_t s, const void* host_src) {
   const uint32_t Q = 1 + (uint32_t)hs.ctx.size();           // 2 or 3
-  static const uint32_t share_host[4][3] = {{0, 0, 0}, {0, 0, 0}, {37, 63, 0}, {18, 30, 52}}; const uint32_t (*share_dev)[3] = CHUNK_SHARE_DEV;
-  static const uint32_t share0_env = [] { const char* e = std::getenv("ALEO_MI355X_CHUNK_SHARE0"); const int k = e ? std::atoi(e) : 0; return (uint32_t)(k >= 5 && k <= 95 ? k : 0); }();      // experiment knob: first chunk's percentage of a two-chunk host-scalar request
-  uint32_t share_env[4][3] = {{0, 0, 0}, {0, 0, 0}, {share0_env, 100 - share0_env, 0}, {18, 30, 52}};
-  const uint32_t (*share)[3] = dev_job ? share_dev : (share0_env ? share_env : share_host);
-  const uint32_t K = dev_job ? dev_job->k : 1u;
+  static const uint32_t share[4][3] = {{0, 0, 0}, {0, 0, 0}, {37, 63, 0}, {18, 30, 52}};
   Ctx* cx[3] = {c, Q > 1 ? hs.ctx[0] : nullptr, Q > 2 ? hs.ctx[1] : nullptr}; hipStream_t st[3] = {s, Q > 1 ? hs.ctx[0]->hi : nullptr, Q > 2 ? hs.ctx[1]->hi : nullptr};
   StreamDrainGuard guard; for (uint32_t k = 0; k < Q; ++k) { guard.add(st[k]); guard.add(cx[k]->side); }
   size_t lo[4] = {0, 0, 0, 0};
   for (uint32_t k = 0, acc = 0; k < Q; ++k) { acc += share[Q][k]; lo[k + 1] = k + 1 == Q ? n : (((size_t)((double)n * acc / 100.0)) + 255) & ~(size_t)255; if (lo[k + 1] > n) lo[k + 1] = n; }
-  Front f[3]; MsmSeg seg[3]; std::vector<MsmSeg> dsegs[3]; int32_t rc; uint32_t cum[4] = {0, 0, 0, 0};
-  for (uint32_t k = 0; k < Q; ++k) cum[k + 1] = k + 1 == Q ? 100u : cum[k] + share[Q][k];
-  if (dev_job) {
-    HIPCHK(hipEventRecord(c->ev[4], s));                     // ev[4]: free here (no slice trees aside in a chunked request)
-    for (uint32_t k = 1; k < Q; ++k) HIPCHK(hipStreamWaitEvent(st[k], c->ev[4], 0));
-  }
+  Front f[3]; MsmSeg seg[3]; int32_t rc;
   auto drain = [&](int32_t code) { const std::string keep = g_last_error; for (uint32_t k = 0; k < Q; ++k) (void)hipStreamSynchronize(st[k]); g_last_error = keep; return code; };
   auto view = [&](uint32_t k) { return FrontView{cx[k]->partial.as<char>(), f[k].sp.hist, f[k].sp.scan_local, f[k].sp.scan_blk}; };
   auto chain_before = [&](uint32_t k) { FrontChain ch; for (uint32_t i = k; i-- > 0;) ch.v[ch.n++] = view(i); return ch; };      // newest first
   for (uint32_t k = 0; k < Q; ++k) {
-    MsmJob j; j.mont = mont; j.tier_n = n; j.k = K;
-    if (dev_job) {                                           // every segment cut at the same fractions (boundaries on multiples of 256 scalars)
-      for (uint32_t q = 0; q < dev_job->nseg; ++q) {
-        const MsmSeg& g = dev_job->segs[q]; const size_t a0 = chunk_cut(g.len, cum[k]), a1 = chunk_cut(g.len, cum[k + 1]);
-        if (a1 > a0) { MsmSeg h = g; h.d_ptr = (const char*)g.d_ptr + a0 * 32; h.len = a1 - a0; h.off = g.off + a0; dsegs[k].push_back(h); }
-      }
-      j.segs = dsegs[k].data(); j.nseg = (uint32_t)dsegs[k].size();
-    } else {
-      const size_t len = lo[k + 1] - lo[k];
-      if ((rc = cx[k]->scalars_stage.reserve((len ? len : 1) * 32))) return drain(rc);
-      if (hipMemcpyAsync(cx[k]->scalars_stage.p, (const char*)host_src + lo[k] * 32, len * 32, hipMemcpyHostToDevice, st[k]) != hipSuccess) { g_last_error = "msm: upload of a chunk failed"; return drain(ALEO_MI355X_ERR_HIP); }
-      seg[k].d_ptr = cx[k]->scalars_stage.p; seg[k].len = len; seg[k].off = lo[k];
-      j.segs = &seg[k]; j.nseg = 1;
-    }
+    MsmJob j; j.mont = mont; j.tier_n = n; j.k = 1;
+    const size_t len = lo[k + 1] - lo[k];
+    if ((rc = cx[k]->scalars_stage.reserve((len ? len : 1) * 32))) return drain(rc);
+    if (hipMemcpyAsync(cx[k]->scalars_stage.p, (const char*)host_src + lo[k] * 32, len * 32, hipMemcpyHostToDevice, st[k]) != hipSuccess) { g_last_error = "msm: upload of a chunk failed"; return drain(ALEO_MI355X_ERR_HIP); }
+    seg[k].d_ptr = cx[k]->scalars_stage.p; seg[k].len = len; seg[k].off = lo[k];
+    j.segs = &seg[k]; j.nseg = 1;
     if ((rc = msm_front_sort(cx[k], pb, j, st[k], f[k]))) return drain(rc);
     if (f[k].empty || !f[k].masked || f[k].P.c != f[0].P.c || f[k].sp.M != f[0].sp.M) { g_last_error = "msm: internal: chunks without a shared table window"; return drain(ALEO_MI355X_ERR_HIP); }
     if (k) { if ((rc = msm_front_finish(cx[k - 1], st[k - 1], f[k - 1], false))) return drain(rc); }      // chunk k - 1's slice trees: its bucket sums are final at its ev[2]
@@ -1626,12 +1522,8 @@ static int32_t msm_run_chunked(Ctx* c, HelperSet& hs, uint64_t* out_jac18, const
   }
   if ((rc = msm_front_finish(cx[Q - 1], st[Q - 1], f[Q - 1], false))) return drain(rc);
   // the reduction runs where the newest sums are; it synchronises that stream, behind which (event by event) every earlier chunk has finished
-  const bool fire = dev_job && dev_job->fire_tail && c->tail_hook;
-  if (fire) cx[Q - 1]->tail_hook = std::move(c->tail_hook);      // the caller's next kernels (queued on ITS stream by the hook) go out when the reduction has been queued
-  c->tail_hook = fire ? nullptr : c->tail_hook;
-  if ((rc = msm_back(cx[Q - 1], out_jac18, f[Q - 1], st[Q - 1], fire, chain_before(Q - 1)))) { cx[Q - 1]->tail_hook = nullptr; return drain(rc); }
-  cx[Q - 1]->tail_hook = nullptr;
-  if (!fire) HIPCHK(hipStreamSynchronize(s));                // (with a hook the caller's stream carries the hook's kernels: the caller orders its own work behind them)
+  if ((rc = msm_back(cx[Q - 1], out_jac18, f[Q - 1], st[Q - 1], false, chain_before(Q - 1)))) return drain(rc);
+  HIPCHK(hipStreamSynchronize(s));
   MsmTiming tm = cx[Q - 1]->last_msm; float ms = 0, kern = 0;
   for (uint32_t k = 0; k < Q; ++k) { HIPCHK(hipEventElapsedTime(&ms, cx[k]->ev[6], cx[k]->ev[5])); kern += ms; }
   tm.accum_kernel = kern / Q; tm.accum_launches = (int)Q;
@@ -1654,9 +1546,8 @@ static int32_t msm_run_chunked(Ctx* c, HelperSet& hs, uint64_t* out_jac18, const
 // with their streams drained, so the caller sees the usual synchronous call.
 namespace {
 struct Chain { std::vector<MsmSeg> segs; std::vector<uint32_t> results; size_t points = 0; bool sparse = false, fire_tail = false; };
-inline bool chains_overlap_on() { static const bool v = [] { const char* e = std::getenv("ALEO_MI355X_CHAIN_OVERLAP"); return !(e && e[0] == '0'); }(); return v; }      // A/B switch
 }
-// The pipelined form (round 4; ALEO_MI355X_CHAIN_PIPELINE=0 restores the two host threads).  A 2^20-constraint proof showed what the two threads leave on
+// The pipelined form (round 4; the two host threads above remain for requests with a chain off the table tiers).  A 2^20-constraint proof showed what the two threads leave on
 // the table (profiles/r04_varuna_2^20_timeline_two_threads.txt): both chains of a round sort first (2.6 ms with no accumulation running), then their accumulations
 // share the chip, then both reductions trail — 28 of 80 ms per proof with no accumulation kernel on the card.  Here ONE host thread queues the chains so that
 // the accumulations run back to back and everything else runs beside them:
@@ -1667,10 +1558,8 @@ inline bool chains_overlap_on() { static const bool v = [] { const char* e = std
 //   host would wait for reduction i - 1, which crawls beside accumulation i (an accumulation holds every wave slot: a 512-thread k_prog_final block waits
 //   milliseconds for a whole CU to drain), and sort i + 1 would run exposed after it — measured: 1.3 ms gaps between the accumulations of an
 //   8-instance round.
-static bool chain_pipeline_on() { static const bool v = [] { const char* e = std::getenv("ALEO_MI355X_CHAIN_PIPELINE"); return !(e && e[0] == '0'); }(); return v; }
 static int32_t run_chains_pipelined(Ctx* c, const std::vector<Ctx*>& helpers, uint64_t* out_jac18, const PinnedBases& pb, std::vector<Chain>& chains, bool mont, hipStream_t s) {
-  static const bool on_hi = [] { const char* e = std::getenv("ALEO_MI355X_PIPELINE_HI"); return e && e[0] == '1'; }();      // A/B: the chains' sorts and reductions on the high-priority streams (rounds 3-4) instead of normal-priority ones
-  auto SS = [&](Ctx* x) { return on_hi ? x->hi : x->aux; };
+  auto SS = [&](Ctx* x) { return x->aux; };                 // the chains' sorts and reductions: normal priority (rounds 3-4 put them on the high-priority streams)
   const size_t n = chains.size(), R = 1 + helpers.size();   // a ring of R contexts: chain i on context i mod R
   std::vector<Ctx*> cx(R); std::vector<hipStream_t> acc_st(R);
   cx[0] = c; acc_st[0] = s; for (size_t k = 1; k < R; ++k) { cx[k] = helpers[k - 1]; acc_st[k] = helpers[k - 1]->stream; }
@@ -1736,19 +1625,17 @@ static int32_t run_chains(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, st
   };
   size_t total = 0; for (auto& ch : chains) total += ch.points;
   HelperSet hs;
-  if (chains.size() >= 2 && total >= ((size_t)1 << 20) && chains_overlap_on() && c->dev) { const int32_t rc = acquire_helpers(c->dev, chain_pipeline_on() && chains.size() >= 3 ? 2 : 1, hs); if (rc) return rc; }
+  if (chains.size() >= 2 && total >= ((size_t)1 << 20) && c->dev) { const int32_t rc = acquire_helpers(c->dev, chains.size() >= 3 ? 2 : 1, hs); if (rc) return rc; }
   if (hs.ctx.empty()) { lean_now = lean; for (auto& ch : chains) { const int32_t rc = run_one(c, ch, s); if (rc) return rc; } return ALEO_MI355X_OK; }
   Ctx* h = hs.ctx[0];
-  if (chain_pipeline_on()) {
-    bool all_tiered = true;                                   // every chain on a table tier (the grouping of msm_batch makes them so, except the tier-less singles)
-    for (auto& ch : chains) {
-      size_t reach = 0; for (auto& g : ch.segs) if (g.len) reach = g.off + g.len > reach ? g.off + g.len : reach;
-      bool t_ok = reach == 0;                                 // (an empty chain: its results are the identity)
-      if (reach) for (const auto& t : pb.tab) if (t.d && reach >= t.min_n && reach <= t.cover) { t_ok = ch.results.size() <= 1 || ch.results.size() <= msm_max_sets(pb, reach); break; }
-      all_tiered = all_tiered && t_ok && ch.results.size() <= MAX_SETS;
-    }
-    if (all_tiered) return run_chains_pipelined(c, hs.ctx, out_jac18, pb, chains, mont, s);
+  bool all_tiered = true;                                   // every chain on a table tier (the grouping of msm_batch makes them so, except the tier-less singles)
+  for (auto& ch : chains) {
+    size_t reach = 0; for (auto& g : ch.segs) if (g.len) reach = g.off + g.len > reach ? g.off + g.len : reach;
+    bool t_ok = reach == 0;                                 // (an empty chain: its results are the identity)
+    if (reach) for (const auto& t : pb.tab) if (t.d && reach >= t.min_n && reach <= t.cover) { t_ok = ch.results.size() <= 1 || ch.results.size() <= msm_max_sets(pb, reach); break; }
+    all_tiered = all_tiered && t_ok && ch.results.size() <= MAX_SETS;
   }
+  if (all_tiered) return run_chains_pipelined(c, hs.ctx, out_jac18, pb, chains, mont, s);
   HIPCHK(hipEventRecord(c->ev[4], s));                     // ev[4] is free until this chain's own msm_run (which may use it for its aside trees) starts
   HIPCHK(hipStreamWaitEvent(h->stream, c->ev[4], 0));
   std::atomic<size_t> next{0}; int32_t rc_h = ALEO_MI355X_OK; std::string err_h; MsmTiming tm_h{};
@@ -1769,16 +1656,15 @@ static int32_t run_chains(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, st
   return ALEO_MI355X_OK;
 }
 
-// One result over n points.  Scalars already on the device: one launch chain.  HOST scalars against a table tier, from 2^ALEO_MI355X_MERGE_MIN_LG points
-// (default 19; 0 = never): two or three chunks on as many contexts that share the buckets and one bucket reduction (msm_run_chunked) — most of the upload
-// disappears under the earlier chunks' kernels.  Smaller or table-less requests upload whole.
-static uint32_t chunks3_min_lg() { static const uint32_t v = [] { const char* e = std::getenv("ALEO_MI355X_CHUNKS3_MIN_LG"); const int k = e ? std::atoi(e) : 21; return (uint32_t)(k >= 0 && k <= 40 ? k : 21); }(); return v; }      // three chunks from here on (40 = never)
-static uint32_t merge_min_lg() { static const uint32_t v = [] { const char* e = std::getenv("ALEO_MI355X_MERGE_MIN_LG"); const int k = e ? std::atoi(e) : 19; return (uint32_t)(k >= 0 && k <= 30 ? k : 19); }(); return v; }
+// One result over n points.  Scalars already on the device: one launch chain.  HOST scalars against a table tier, from 2^MERGE_MIN_LG points: two (three
+// from 2^CHUNKS3_MIN_LG) chunks on as many contexts that share the buckets and one bucket reduction (msm_run_chunked) — most of the upload disappears under
+// the earlier chunks' kernels (measurements at msm_run_chunked).  Smaller or table-less requests upload whole.
+static constexpr uint32_t MERGE_MIN_LG = 19, CHUNKS3_MIN_LG = 21;
 int32_t msm_run1_split(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const void* d_scalars, size_t n, bool mont, hipStream_t s, bool sparse, const void* host_src, bool may_merge) {
   bool tiered = false;
   for (const auto& t : pb.tab) if (t.d && n >= t.min_n && n <= t.cover) tiered = true;
   HelperSet hs;
-  if (host_src && may_merge && !sparse && tiered && merge_min_lg() && n >= ((size_t)1 << merge_min_lg()) && c->dev) { const int32_t rc = acquire_helpers(c->dev, n >= ((size_t)1 << chunks3_min_lg()) ? 2 : 1, hs); if (rc) return rc; }
+  if (host_src && may_merge && !sparse && tiered && n >= ((size_t)1 << MERGE_MIN_LG) && c->dev) { const int32_t rc = acquire_helpers(c->dev, n >= ((size_t)1 << CHUNKS3_MIN_LG) ? 2 : 1, hs); if (rc) return rc; }
   if (!hs.ctx.empty()) return msm_run_chunked(c, hs, out_jac18, pb, n, mont, s, host_src);
   if (host_src) {
     const int32_t rc = c->scalars_stage.reserve((n ? n : 1) * 32); if (rc) return rc;

@@ -485,17 +485,11 @@ static int32_t build_tables(NttTables* t, uint32_t lg_n, int direction) {
   return ALEO_MI355X_OK;
 }
 
-template <uint32_t TE, uint32_t NT, int GM = 3>
+// The 32-bit-limb kernels run the latency form of small transforms (ntt_run_chunk): 512-element tiles (16 KiB of LDS), one butterfly stage per group.
 static int32_t run_passes(Ctx* c, char* buf, char* tmp, uint32_t lg_n, uint32_t batch, const NttTables* t, int pre_coset, int post_coset, int do_scale, FrArg sc, hipStream_t s, NttSrc ext = NttSrc{}) {
-  constexpr uint32_t lgTE = TE == 4096 ? 12 : (TE == 2048 ? 11 : 9);
-  static_assert(TE == 4096 || TE == 2048 || TE == 512, "tile sizes with a kernel instance");
+  constexpr uint32_t TE = 512, NT = 256, lgTE = 9;
+  constexpr int GM = 1;
   constexpr size_t lds_bytes = (size_t)TE * 32;
-  constexpr int attr_bit = TE == 4096 ? 2 : 1;          // the LDS limit is a property of (kernel, device): remembered per device
-  if (lds_bytes > 65536 && !(c->dev->ntt_attr_mask.load() & attr_bit)) {
-    HIPCHK(hipFuncSetAttribute((const void*)k_ntt_strided<TE, NT, GM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    HIPCHK(hipFuncSetAttribute((const void*)k_ntt_final<TE, NT, GM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    c->dev->ntt_attr_mask.fetch_or(attr_bit);
-  }
   const char* inner = (const char*)t->d_inner; const char* twh = (const char*)t->d_tw_hi; const char* twl = (const char*)t->d_tw_lo;
   const char* csh = (const char*)t->d_cs_hi; const char* csl = (const char*)t->d_cs_lo;
   const uint32_t maxL = lgTE < INNER_MAX_LG ? lgTE : INNER_MAX_LG;            // longest in-LDS transform with this tile
@@ -537,12 +531,13 @@ static int32_t run_passes(Ctx* c, char* buf, char* tmp, uint32_t lg_n, uint32_t 
 
 
 // run_passes on the 29-bit-limb kernels (tiles of 9 planes: 144 KiB / 72 KiB); same pass splits, same launch geometry
-template <uint32_t TE, uint32_t NT, int GM = 3>
+template <uint32_t TE, uint32_t NT>
 static int32_t run_passes29(Ctx* c, char* buf, char* tmp, uint32_t lg_n, uint32_t batch, const NttTables* t, int pre_coset, int post_coset, int do_scale, hipStream_t s, NttSrc ext = NttSrc{}) {
   constexpr uint32_t lgTE = TE == 4096 ? 12 : 11;
   static_assert(TE == 4096 || TE == 2048, "tile sizes with a kernel instance");
+  constexpr int GM = 3;
   constexpr size_t lds_bytes = (size_t)TE * 36;
-  constexpr int attr_bit = (TE == 4096 ? 8 : 4) << (GM == 2 ? 2 : 0);
+  constexpr int attr_bit = TE == 4096 ? 8 : 4;          // the LDS limit is a property of (kernel, device): remembered per device
   if (!(c->dev->ntt_attr_mask.load() & attr_bit)) {
     HIPCHK(hipFuncSetAttribute((const void*)k_ntt29_strided<TE, NT, GM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     HIPCHK(hipFuncSetAttribute((const void*)k_ntt29_final<TE, NT, GM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -563,7 +558,7 @@ static int32_t run_passes29(Ctx* c, char* buf, char* tmp, uint32_t lg_n, uint32_
   } else if (npass == 2) {
     uint32_t lgBn = s3, lgT = lgT_for(s1, lgBn);
     const char* direct = nullptr;
-    static const uint32_t direct_max = [] { const char* e = std::getenv("ALEO_MI355X_NTT_DIRECT_MAX"); const int k = e ? std::atoi(e) : 21; return (uint32_t)(k >= 0 && k <= 22 ? k : 21); }();      // 2^21: 0.286 -> 0.271 ms with the table, 2^22: 0.549 -> 0.564 ms (the extra 32 B per element of HBM reads cost more than the product; round 4: fetching a lane's eight table entries in one go ahead of the products changes nothing — 2^22 0.581 / 0.588 ms without / with the table, 2^21 0.277 / 0.283 ms with the entries fetched late / ahead)
+    constexpr uint32_t direct_max = 21;      // 2^21: 0.286 -> 0.271 ms with the table, 2^22: 0.549 -> 0.564 ms (the extra 32 B per element of HBM reads cost more than the product; round 4: fetching a lane's eight table entries in one go ahead of the products changes nothing — 2^22 0.581 / 0.588 ms without / with the table, 2^21 0.277 / 0.283 ms with the entries fetched late / ahead)
     if (lg_n >= 12 && lg_n <= direct_max) {
       std::lock_guard<std::mutex> lk(c->dev->mu);
       NttTables* tm = const_cast<NttTables*>(t);
@@ -693,10 +688,6 @@ int32_t ntt_run_from(Ctx* c, void* d_out, const void* d_src, size_t src_stride, 
   return ALEO_MI355X_OK;
 }
 
-// Calls of at most 2^wide_lg() elements in all (transforms of 2^10 … 2^18 points) take the one-butterfly-per-lane tiles: 2^12 52 -> 22 us, 2^15 64 -> 27 us,
-// 3 x 2^15 67 -> 30 us, 8 x 2^16 85 -> 72 us; from 2^20 elements on the three-stage register groups win again (8 x 2^17: 138 against 142 us)
-// (tools/ntt_small_probe.py, profiles/r02_ntt_small_probe.jsonl).  ALEO_MI355X_NTT_WIDE_LG overrides the cut, 0 = never.
-static uint32_t wide_lg() { static const uint32_t v = [] { const char* e = std::getenv("ALEO_MI355X_NTT_WIDE_LG"); int k = e ? std::atoi(e) : 19; return (uint32_t)(k >= 0 && k <= 24 ? k : 19); }(); return v; }
 static int32_t ntt_run_chunk(Ctx* c, void* d_inout, uint32_t lg_n, uint32_t batch, int32_t order, int32_t direction, int32_t type, hipStream_t s, NttSrc ext) {
   const size_t n = (size_t)1 << lg_n, bytes = n * 32 * batch;
   int32_t rc;
@@ -713,27 +704,16 @@ static int32_t ntt_run_chunk(Ctx* c, void* d_inout, uint32_t lg_n, uint32_t batc
   const int coset = (type == ALEO_NTT_COSET), inv = (direction == ALEO_NTT_INVERSE);
   const int pre_coset = coset && !inv, post_coset = coset && inv, do_scale = inv && !coset;   // cs_lo carries n^-1 for coset_ifft
   FrArg sc; std::memcpy(sc.v, t->scale, 32);
-  // 128 KiB tiles: 2^20..2^22 (at 2^19 they are only 128 blocks for 256 CUs: 242 against 343 GB/s with 64 KiB tiles); beyond 2^22 three
-  // passes are needed either way and two 64 KiB blocks per CU overlap their HBM phases better (2^24: 3.5 vs 4.0 ms)
-  // small transforms are latency-bound on the few blocks a 2048-element tile leaves them (2^16: 32 blocks on 256 CUs): 512-element
-  // tiles of one wave each spread them over the chip (2^16: 0.085 -> see profiles/); batches already have the blocks
-  static const int force_tile = [] { const char* e = std::getenv("ALEO_MI355X_NTT_TILE"); return e ? std::atoi(e) : 0; }();      // experiments only
-  static const bool limbs29 = [] { const char* e = std::getenv("ALEO_MI355X_NTT29"); return !(e && e[0] == '0'); }();      // A/B switch: 0 = the 32-bit-limb kernels everywhere
-  const bool big_tile_default = !(lg_n >= 10 && lg_n <= 18 && ((size_t)batch << lg_n) <= ((size_t)1 << 18)) &&
-                                !(lg_n >= 10 && lg_n <= 18 && ((size_t)batch << lg_n) <= ((size_t)1 << wide_lg()));
-  if (limbs29 && (force_tile == 2048 || force_tile == 4096 || (force_tile == 0 && big_tile_default))) {
-    static const int gm = [] { const char* e = std::getenv("ALEO_MI355X_NTT29_GM"); return e ? std::atoi(e) : 3; }();      // experiment knob
-    if ((force_tile == 4096 || (force_tile == 0 && lg_n >= 20 && lg_n <= 22)) && gm == 2) rc = run_passes29<4096, 1024, 2>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext);
-    else if (force_tile == 4096 || (force_tile == 0 && lg_n >= 20 && lg_n <= 22)) rc = run_passes29<4096, 512>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext);
-    else rc = run_passes29<2048, 256>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext);
-  }
-  else if (force_tile == 2048) rc = run_passes<2048, 256>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, sc, s, ext);
-  else if (force_tile == 4096) rc = run_passes<4096, 512>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, sc, s, ext);
-  else if (force_tile == 512 && lg_n <= 18) rc = run_passes<512, 64>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, sc, s, ext);
-  else if (lg_n >= 20 && lg_n <= 22) rc = run_passes<4096, 512>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, sc, s, ext);
-  else if (lg_n >= 10 && lg_n <= 18 && ((size_t)batch << lg_n) <= ((size_t)1 << wide_lg())) rc = run_passes<512, 256, 1>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, sc, s, ext);      // latency form
-  else if (lg_n >= 10 && lg_n <= 18 && ((size_t)batch << lg_n) <= ((size_t)1 << 18)) rc = run_passes<512, 64>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, sc, s, ext);
-  else rc = run_passes<2048, 256>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, sc, s, ext);
+  // Small transforms are latency-bound on the few blocks a 2048-element tile leaves them (2^16: 32 blocks on 256 CUs); 512-element tiles spread them
+  // over the chip.  Calls of at most 2^19 elements in all (transforms of 2^10 … 2^18 points) take the one-butterfly-per-lane tiles of the 32-bit kernels:
+  // 2^12 52 -> 22 us, 2^15 64 -> 27 us, 3 x 2^15 67 -> 30 us, 8 x 2^16 85 -> 72 us; from 2^20 elements on the three-stage register groups win again
+  // (8 x 2^17: 138 against 142 us) (tools/ntt_small_probe.py, profiles/r02_ntt_small_probe.jsonl).
+  // Everything else runs on the 29-bit-limb kernels.  128 KiB-class tiles for 2^20..2^22 (at 2^19 they are only 128 blocks for 256 CUs: 242 against
+  // 343 GB/s with 64 KiB tiles); beyond 2^22 three passes are needed either way and two 64 KiB-class blocks per CU overlap their HBM phases better
+  // (2^24: 3.5 vs 4.0 ms).
+  if (lg_n >= 10 && lg_n <= 18 && ((size_t)batch << lg_n) <= ((size_t)1 << 19)) rc = run_passes(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, sc, s, ext);      // latency form
+  else if (lg_n >= 20 && lg_n <= 22) rc = run_passes29<4096, 512>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext);
+  else rc = run_passes29<2048, 256>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext);
   if (rc) return rc;
   if (out_rev) {
     hipLaunchKernelGGL(k_bitrev_copy, gperm, dim3(256), 0, s, buf, tmp, lg_n);

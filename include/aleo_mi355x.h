@@ -95,7 +95,9 @@ int32_t aleo_mi355x_peer_info(int32_t* enabled_pairs, int32_t* refused_pairs);
  * opts in to a cache for callers that cannot hold a bases_pin handle: arrays of >= 1024 points stay in HBM keyed by host
  * pointer + stride and are re-validated on each call by hashing 256 sampled points (32 at the front, the rest spread);
  * the third use builds the fixed-base table (~0.15 s, inside that call).  Contract when opted in: a base array must not
- * be rewritten in place (nor its address reused for different points) between calls — unsampled changes are not seen. */
+ * be rewritten in place (nor its address reused for different points) between calls — unsampled changes are not seen.
+ * Without the cache the call's copy of the bases lives in the serving slot's grow-only buffers, kept like its other workspaces;
+ * ALEO_MI355X_COLD_POOL=0 (read once) allocates and frees them in every call instead. */
 int32_t aleo_mi355x_msm_g1(void* out_jacobian, const void* bases, size_t base_stride, const void* scalars, size_t n);
 
 /* SRS residency: upload + convert a base set once per proving key (SURVEY.md §5 "device-resident SRS").
@@ -129,8 +131,8 @@ int32_t aleo_mi355x_bases_info(uint64_t handle, uint64_t* out, int32_t cap);
 /* Copies pinned bases [offset, offset+n) back to the host as snarkVM Affine (stride 104). */
 int32_t aleo_mi355x_bases_download(uint64_t handle, size_t offset, size_t n, void* out_affine104);
 /* MSM over the first n pinned bases; scalars: host pointer (pageable memory is fine: the upload runs at the link's rate either way).  Against a set with
- * window tables, from 2^19 points on (ALEO_MI355X_MERGE_MIN_LG), the scalars go up and through in 2 chunks of 37 / 63 % (3 of 18 / 30 / 52 % from 2^21
- * points, ALEO_MI355X_CHUNKS3_MIN_LG) on contexts of their own: a later chunk's upload and sort run under the previous chunk's accumulation, each
+ * window tables, from 2^19 points on, the scalars go up and through in 2 chunks of 37 / 63 % (3 of 18 / 30 / 52 % from 2^21
+ * points) on contexts of their own: a later chunk's upload and sort run under the previous chunk's accumulation, each
  * accumulation is SEEDED with the bucket sums of the chunk before it (no merge kernel), and ONE bucket reduction follows the last chunk; the result
  * does not depend on it. */
 int32_t aleo_mi355x_msm_g1_pinned(void* out_jacobian, uint64_t handle, const void* scalars, size_t n);

@@ -79,7 +79,7 @@ def test_ntt_golden_vectors():
             assert got == _ints(case[name]), (case['n'], name)
 
 
-@pytest.mark.parametrize('lg', [1, 2, 3, 7, 10, 11, 12, 15, 18, 19, 20])
+@pytest.mark.parametrize('lg', [1, 2, 3, 7, 10, 11, 12, 14, 15, 18, 19, 20])
 def test_ntt_matches_oracle_all_variants(lg):
     x = c.fr_to_mont(util.uniform_scalars(1 << lg, 100 + lg))
     d = aleo_amd.EvaluationDomain(1 << lg)
@@ -421,13 +421,13 @@ def test_bad_arguments_are_rejected():
 
 def test_msm_fixed_base_table_path():
     """bases_precompute(): the 13-window fixed-base table must give the same group element as the plain path."""
-    for n in (1000, 1 << 14, 1 << 16, 1 << 18):
+    for n in (1000, 5000, 1 << 14, 1 << 16, 1 << 18):
         with M.PinnedBases.generate_multiples(synth.generator_affine104(), 1, n) as pb:
             S = util.uniform_scalars(n, 8800 + n); Wt = util.witness_like_scalars(n, 8900 + n)
             plain_u, plain_w = M.VariableBase.msm(pb, S), M.VariableBase.msm(pb, Wt)
             pb.precompute()
             assert (M.VariableBase.msm(pb, S) == plain_u).all() and (M.VariableBase.msm(pb, Wt) == plain_w).all()
-            assert c.jac_to_int_point(plain_u) == util.expected_multiples_msm(S, n)
+            assert c.jac_to_int_point(plain_u) == util.expected_multiples_msm(S, n) and c.jac_to_int_point(plain_w) == util.expected_multiples_msm(Wt, n)
             rm1 = np.tile(c.ints_to_limbs([p.FR_MODULUS - 1], 4), (n, 1))                  # top-window carry
             assert c.jac_to_int_point(M.VariableBase.msm(pb, rm1)) == util.expected_multiples_msm(rm1, n)
             assert c.jac_to_int_point(M.VariableBase.msm(pb, S[: n // 2])) == util.expected_multiples_msm(S, n // 2)   # prefix: plain path

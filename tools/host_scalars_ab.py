@@ -1,6 +1,6 @@
 """Host-scalar MSMs against a pinned set with tables (the headline call: aleo_mi355x_msm_g1_pinned), for the sizes given: wall ms per call, the
-library's phase record, and the result checked against k G in big integers (bench.py's gate).  The merged-halves path is switched by the environment
-(ALEO_MI355X_MERGE_MIN_LG: 0 = off) — run the script once per setting for an A/B.  Not a test."""
+library's phase record, and the result checked against k G in big integers (bench.py's gate).  Host-scalar requests of 2^19 points and more against a
+table run in chunks (msm_run_chunked) — run the script once per build (ALEO_MI355X_LIB selects another one) for an A/B.  Not a test."""
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -17,5 +17,5 @@ for lg in [int(a) for a in sys.argv[1:]] or [18, 19, 20, 21, 22]:
         torch.cuda.synchronize(); t0 = time.perf_counter(); reps = 10
         for _ in range(reps): M.VariableBase.msm(pb, sc)
         dt = (time.perf_counter() - t0) / reps * 1e3
-        print(json.dumps({'lg_n': lg, 'scalars': kind, 'merge_min_lg': os.environ.get('ALEO_MI355X_MERGE_MIN_LG', 'default'), 'ms': round(dt, 4), 'ok': ok, 'phases': {k: round(v, 4) for k, v in M.last_msm_timing().items()}}), flush=True)
+        print(json.dumps({'lg_n': lg, 'scalars': kind, 'ms': round(dt, 4), 'ok': ok, 'phases': {k: round(v, 4) for k, v in M.last_msm_timing().items()}}), flush=True)
     pb.close()

@@ -1,5 +1,5 @@
-"""Resident forward NTTs of the sizes given, timed by events on the launch stream (ms per transform, algorithmic GB/s at 64 B per element); the environment
-selects the variant under test (ALEO_MI355X_NTT_DIRECT_MAX, ALEO_MI355X_NTT29, ALEO_MI355X_NTT_TILE, ...): run once per setting.  Checks fft -> ifft = id."""
+"""Resident forward NTTs of the sizes given, timed by events on the launch stream (ms per transform, algorithmic GB/s at 64 B per element); run once per
+build (ALEO_MI355X_LIB selects another one) for an A/B.  Checks fft -> ifft = id."""
 import os, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -21,4 +21,4 @@ for lg in [int(a) for a in sys.argv[1:]] or [20, 21, 22, 24]:
         d.ntt_device(y.data_ptr(), 0, 0, 0, st.cuda_stream); d.ntt_device(y.data_ptr(), 0, 1, 0, st.cuda_stream); st.synchronize()
     ok = bool((y.cpu().numpy().view(np.uint64).reshape(-1, 4) == h).all())
     print(json.dumps({'lg_n': lg, 'ms': round(ms, 4), 'alg_GBps': round(64.0 * n / ms / 1e6, 1), 'round_trip_ok': ok,
-                      'env': {k: v for k, v in os.environ.items() if k.startswith('ALEO_MI355X_NTT')}}), flush=True)
+                      'lib': os.environ.get('ALEO_MI355X_LIB', 'default')}), flush=True)

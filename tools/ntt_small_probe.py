@@ -1,5 +1,5 @@
-"""Device time of small transforms (not a test): single and batched, 2^10 … 2^18, HIP events on the launch stream.  Compare ALEO_MI355X_NTT_WIDE_LG=0
-(three-stage register groups, one wave per 512-element tile) with the default (one butterfly per lane for transforms of <= 2^18 elements in all)."""
+"""Device time of small transforms (not a test): single and batched, 2^10 … 2^18, HIP events on the launch stream (one butterfly per lane for calls of
+<= 2^19 elements in all; compare a build with its parent)."""
 import os, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -12,7 +12,7 @@ def ntt_fr_batch_device(ptr, lg, batch, order, direction, type_, stream):
 dev = torch.device('cuda', 0); torch.cuda.set_device(0)
 aleo_amd._lib.check(aleo_amd.lib().aleo_mi355x_init_device(0), 'init')
 ts = torch.cuda.Stream(); torch.cuda.set_stream(ts); st = ts.cuda_stream
-out = {'wide_lg': os.environ.get('ALEO_MI355X_NTT_WIDE_LG', 'default')}
+out = {}
 for lg in (10, 12, 13, 14, 15, 16, 17, 18):
     for batch in (1, 3, 8):
         if (batch << lg) > (1 << 20): continue

@@ -1,5 +1,5 @@
-"""Resident-scalar MSMs (aleo_mi355x_msm_g1_device against a pinned set with tables), wall ms per call over 10 calls, for the sizes given; the environment
-selects the variant (ALEO_MI355X_CHUNK_DEV_MIN_LG: chunked launch chains for device scalars).  Result checked against k G in big integers.  Not a test."""
+"""Resident-scalar MSMs (aleo_mi355x_msm_g1_device against a pinned set with tables), wall ms per call over 10 calls, for the sizes given; run once per
+build (ALEO_MI355X_LIB selects another one) for an A/B.  Result checked against k G in big integers.  Not a test."""
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -16,5 +16,5 @@ for lg in [int(a) for a in sys.argv[1:]] or [20, 21, 22]:
         t0 = time.perf_counter(); reps = 10
         for _ in range(reps): M.VariableBase.msm_device(pb, d.data_ptr(), n)
         dt = (time.perf_counter() - t0) / reps * 1e3
-        print(json.dumps({'lg_n': lg, 'scalars': kind, 'chunk_dev_min_lg': os.environ.get('ALEO_MI355X_CHUNK_DEV_MIN_LG', 'off'), 'ms': round(dt, 4), 'ok': ok, 'phases': {k: round(v, 4) for k, v in M.last_msm_timing().items()}}), flush=True)
+        print(json.dumps({'lg_n': lg, 'scalars': kind, 'ms': round(dt, 4), 'ok': ok, 'phases': {k: round(v, 4) for k, v in M.last_msm_timing().items()}}), flush=True)
     pb.close()

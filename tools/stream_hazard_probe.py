@@ -1,12 +1,12 @@
 """One process that first touches EVERY context of the device — a lockstep call of 16 proofs (four groups and their workers), four threads of chunked host-scalar MSMs
 (helpers' high-priority streams) — and then times what depends on how the streams landed on hardware queues: the lockstep call again, the chunked MSM, a 2^20-constraint
-proof (pipelined chains).  Not a test; run once per ALEO_MI355X_STREAM_ORDER / ALEO_MI355X_HI_POOL / ALEO_MI355X_PIPELINE_HI setting."""
+proof (pipelined chains).  Not a test; run once per build (or GPU_MAX_HW_QUEUES setting) to compare."""
 import os, sys, json, time, threading
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 import bench
 from aleo_amd import synth, varuna, msm as M
-out = {k: os.environ.get(k, 'default') for k in ('ALEO_MI355X_STREAM_ORDER', 'ALEO_MI355X_HI_POOL', 'ALEO_MI355X_PIPELINE_HI', 'ALEO_MI355X_HI_PRIORITY')}
+out = {'GPU_MAX_HW_QUEUES': os.environ.get('GPU_MAX_HW_QUEUES', 'default')}
 n, csr, z, zz, ck, D = bench._varuna_instance(synth, 15, 55)
 def med(fn, reps):
     fn(); ts = []
