@@ -9,7 +9,7 @@ python3 "$here/../../tools/gen_fr29_asm.py" "$here/fr29_mont_gen.h"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Xarch_host -mbmi2 -Xarch_host -madx -Wall -Wno-unused-function -Wno-unused-variable ${ALEO_MI355X_CXXFLAGS:-}"
 objs=(); pids=()
-for f in api msm ntt frops wire g2 varuna sponge; do
+for f in $(cat "$here/units.txt"); do      # the translation units, one object each (tools/ntt_phase_probe.sh links the same list)
   rm -f "$out/$f.o"                      # a failed compile must not link a stale object
   "$HIPCC" $FLAGS -c "$here/$f.hip" -o "$out/$f.o" &
   pids+=("$!"); objs+=("$out/$f.o")

@@ -75,7 +75,7 @@ struct PinnedBases {
   PreTable range; size_t range_off = 0;
   bool tabled = false;         // msm_precompute has run (a set below 2^10 points gets no table)
   // a sharded copy of the same points on several devices (aleo_mi355x_bases_attach_shards): commitments of >= shard_min points made against this set by the
-  // prover / the segment entry points go to the shards (api.hip commit_sharded) — 0 = none
+  // prover / the segment entry points go to the shards (sharded.hip commit_sharded) — 0 = none
   uint64_t shards = 0; size_t shard_min = 0;
   size_t shard_ntt_min = (size_t)1 << 24;      // transforms of at least this many elements take the shards' devices too (aleo_mi355x_bases_shard_transforms; default 2^24: below it the 4-step split costs more in barriers and copies than a 0.1-2 ms single-device transform does)
   size_t n = 0;
@@ -125,7 +125,7 @@ struct Ctx {                           // one concurrency slot
   std::function<int32_t()> tail_hook;
   DevBuf prover_ws; void* prover_pin = nullptr; size_t prover_pin_cap = 0;      // varuna.hip: one proof's device workspace, pinned staging of the assignments
   MsmTiming last_msm;
-  DevBuf cold_raw, cold_xy, cold_xy28, cold_flags;      // the cold one-shot MSM (api.hip cold_bases): the call's copy of the caller's bases, grow-only like every other workspace of the slot
+  DevBuf cold_raw, cold_xy, cold_xy28, cold_flags;      // the cold one-shot MSM (bases.hip cold_bases): the call's copy of the caller's bases, grow-only like every other workspace of the slot
   DevBuf ntt_tmp, ntt_stage;
   // ntt_tmp is scratch of the *_device entry points, which enqueue on the CALLER's stream and return without synchronising;
   // the slot is then handed to the next call, possibly on another stream.  scratch_ev is recorded after the last kernel that
@@ -175,9 +175,9 @@ struct Device {
   std::map<uint64_t, std::shared_ptr<struct VarunaIndexOwner>> varuna; uint64_t next_varuna = 1;      // circuit indices (varuna.hip)
   std::atomic<int> ntt_attr_mask{0};   // which NTT kernel instances had their LDS limit raised on THIS device
   Ctx slots[MAX_SLOTS];
-  std::vector<std::unique_ptr<ShardWs>> shard_ws;     // grown under mu; used only by the one sharded transform in flight (api.hip g_ntt_sh_mu)
+  std::vector<std::unique_ptr<ShardWs>> shard_ws;     // grown under mu; used only by the one sharded transform in flight (sharded.hip g_ntt_sh_mu)
   DevBuf shard_home;                   // ntt_sharded_device: the home device's transposed copy of the data (n elements), same lock
-  hipStream_t hi_pool[MAX_SLOTS] = {}; int hi_made = 0;      // the high-priority streams of the device, dealt to the contexts round-robin (api.hip first_use): at most four of them exist
+  hipStream_t hi_pool[MAX_SLOTS] = {}; int hi_made = 0;      // the high-priority streams of the device, dealt to the contexts round-robin (device.hip first_use): at most four of them exist
   Ctx helpers[MAX_SLOTS];              // extra streams + scratch a lockstep call borrows for its worker threads (never handed out as API slots)
 };
 // Borrows up to `want` idle helper contexts of the device (try-lock: none is waited for); they are released when `hs` goes out of scope.
@@ -208,12 +208,12 @@ inline int32_t msm_run1(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, cons
   MsmJob j; j.segs = &g; j.nseg = 1; j.k = 1; j.mont = mont; j.sparse = sparse; return msm_run(c, out_jac18, pb, j, s);
 }
 int32_t msm_batch(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s);
-// api.hip: the same request against a SHARDED copy of the base set (handle of aleo_mi355x_bases_pin_sharded): every segment is cut at the shard boundaries,
+// sharded.hip: the same request against a SHARDED copy of the base set (handle of aleo_mi355x_bases_pin_sharded): every segment is cut at the shard boundaries,
 // device g pulls its pieces of the scalar vectors from the calling thread's device (peer copies; same device: none) and runs msm_batch against its shard,
 // the G x k partial results are added on the host in shard order.  `s` (the stream the scalars were produced on) is synchronised first when s_drain; the results are
 // normalised exactly like msm_batch's, so the bytes equal the single-device call's.  `c` is the caller's slot: shard work never waits for it.
 int32_t commit_sharded(Ctx* c, uint64_t sharded_handle, const MsmSeg* segs, uint32_t nseg, uint32_t k, bool mont, uint64_t* out_jac18, hipStream_t s, bool s_drain);
-// api.hip: one transform of 2^lg_n elements resident at d_inout on the caller's device, computed over the listed devices (4-step, peer copies, no host buffer); blocking
+// sharded.hip: one transform of 2^lg_n elements resident at d_inout on the caller's device, computed over the listed devices (4-step, peer copies, no host buffer); blocking
 int32_t ntt_sharded_device(Ctx* c, void* d_inout, uint32_t lg_n, int32_t direction, int32_t type, const int* devices, size_t n_devices, hipStream_t s);
 int32_t sharded_devices(uint64_t sharded_handle, std::vector<int>* out);      // the device list of a sharded base set
 // One result over n points, scalars on the device (host_src == nullptr) or still on the host (then d_scalars is ignored and the scalars are uploaded into the
@@ -264,7 +264,7 @@ int32_t fr_scale_rows(Ctx* c, void* d_dst, const void* d_src, size_t n, size_t r
 int32_t fr_split_quotient(Ctx* c, void* d_hq, void* d_rq, const void* d_q, const void* d_mask, size_t n, void* host_sum_devptr, hipStream_t s);
 int32_t fr_sub_mul(Ctx* c, void* d_dst, const void* d_a, const void* d_b, const void* d_m, size_t n, hipStream_t s);
 int32_t fr_pick(Ctx* c, void* dst_devptr, const void* const* d_src, size_t count, hipStream_t s);
-// varuna.hip / api.hip
+// varuna.hip (jacobian_rows_to_affine104: api.hip)
 int32_t varuna_prove(Ctx* c, const PinnedBases& pb, const aleo_mi355x_varuna_index& ix, const void* const* assignments, size_t k, const uint8_t* seed32, uint8_t* out, size_t* out_len);
 // one request of a lockstep call (varuna_prove_many): the circuits of ONE proof, its assignments, seed and output; status / error come back per request
 struct ProveRequest { std::vector<const aleo_mi355x_varuna_index*> ixs; const void* const* assignments = nullptr; const size_t* ks = nullptr; const uint8_t* seed32 = nullptr;

@@ -606,7 +606,7 @@ int32_t msm_g2_run(Ctx* c, uint64_t* out_jac36, const void* d_xy, const uint8_t*
 
 using namespace aleo_mi355x;
 
-// Slot acquisition lives in api.hip; these two entry points are defined there around msm_g2_run / the host group law:
+// Slot acquisition lives in device.hip; the two entry points are defined in api.hip around msm_g2_run / the host group law:
 namespace aleo_mi355x {
 int32_t g2_sum_host(uint64_t* out36, const uint64_t* pts36, size_t count) {
   host::HXYZZ2 t = host::HXYZZ2::infinity();

@@ -1,7 +1,7 @@
 """Run by tests/test_gpu_parity.py in a child process with ALEO_MI355X_SLOTS=1: the FIRST call this process makes into the library is a batched
 transform through a *_device entry point — once with stream == NULL (the slot's own stream; torch's default stream has handle 0), once, in a second
 child, on a created stream — i.e. the first-use path of a slot's stream, events and stream-ordered scratch (scratch_acquire / scratch_release,
-api.hip), which round 2 crashed in once while it was being introduced ("The host segfault of round 2").  Prints FIRST CALL OK."""
+device.hip), which round 2 crashed in once while it was being introduced ("The host segfault of round 2").  Prints FIRST CALL OK."""
 import os, sys, ctypes
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
 import numpy as np, torch

@@ -543,7 +543,7 @@ def test_concurrent_callers_share_the_device_safely():
 
 def test_chunked_host_scalar_calls_from_six_threads_share_the_high_priority_streams():
     """Chunked host-scalar MSMs (the headline call's path: the later chunks run on a borrowed helper's high-priority stream) from six threads at once.  The device
-    keeps a POOL of four high-priority streams (api.hip first_use: eight in a row made pipelined proofs crawl), so helpers 0 and 4, 1 and 5 share one: the calls
+    keeps a POOL of four high-priority streams (device.hip first_use: eight in a row made pipelined proofs crawl), so helpers 0 and 4, 1 and 5 share one: the calls
     must still return their own results, and mixed with three-chunk requests (2^21 points: two helpers each)."""
     import threading
     n = 1 << 21

@@ -11,7 +11,8 @@ if [ "$1" = build ]; then
   mkdir -p $ab
   for v in 1 2 3; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Xarch_host -mbmi2 -Xarch_host -madx -Wno-unused-function -Wno-unused-variable -DALEO_NTT_PROBE=$v -c $src/ntt.hip -o $ab/ntt_p$v.o
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ab/libprobe$v.so $lib/api.o $lib/msm.o $ab/ntt_p$v.o $lib/frops.o $lib/wire.o $lib/g2.o $lib/varuna.o $lib/sponge.o
+    objs=(); for f in $(cat $src/units.txt); do if [ $f = ntt ]; then objs+=($ab/ntt_p$v.o); else objs+=($lib/$f.o); fi; done      # the library's units (build.sh), the transform swapped
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ab/libprobe$v.so "${objs[@]}"
   done
   exit 0
 fi
