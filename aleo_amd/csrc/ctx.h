@@ -196,10 +196,10 @@ void host_trace_mark(const char* label);
 extern bool g_host_trace_on;
 int32_t ensure_host_pinned(Ctx* c, size_t bytes);
 
-// msm.hip
+// msm_request.hip (one launch chain: msm.hip, through msm_chain.h; the scalar sort and the table tiers: msm_sort.hip, msm_common.h)
 // One launch chain computes job.k results ("sets"); result q is the sum over the segments with out == q of
 //   sum_i scalar[i] * base[off + i],  i < len    (scalars at the DEVICE pointer d_ptr; the segment array itself is host memory).
-// k > 1 needs a table tier that covers every base reached and k <= msm_max_sets(); msm_batch() groups arbitrary requests accordingly.
+// k > 1 needs a table tier that covers every base reached and k <= msm_max_sets(); msm_batch() groups arbitrary requests accordingly.  The sets share every launch — one sort over k * 2^(c-1) buckets, one accumulation, one reduction: what the commitments of one prover round need (2^14..2^17 points each: alone they are latency-bound).
 struct MsmSeg { const void* d_ptr = nullptr; size_t len = 0, off = 0; uint32_t out = 0; };
 struct MsmJob { const MsmSeg* segs = nullptr; uint32_t nseg = 0, k = 0; bool mont = false; bool sparse = false; bool fire_tail = false; size_t tier_n = 0; bool lean = false; };      // lean: no phase-timing events on the stream (the prover's commitments: MsmTiming then only carries the host tail)      // tier_n: pick the table tier as for a reach of tier_n (a part of a split request keeps the whole request's window)      // fire_tail: this launch chain is the whole request — run Ctx::tail_hook behind its last kernel      // sparse: hint — use the set's range table when every segment lies inside it
 int32_t msm_run(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s);
@@ -208,6 +208,20 @@ inline int32_t msm_run1(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, cons
   MsmJob j; j.segs = &g; j.nseg = 1; j.k = 1; j.mont = mont; j.sparse = sparse; return msm_run(c, out_jac18, pb, j, s);
 }
 int32_t msm_batch(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s);
+// One result over n points, scalars on the device (host_src == nullptr) or still on the host (then d_scalars is ignored and the scalars are uploaded into the
+// contexts' staging buffers): host scalars from 2^19 points on go in two halves on two contexts that share one bucket reduction — msm_run1_split
+int32_t msm_run1_split(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const void* d_scalars, size_t n, bool mont, hipStream_t s, bool sparse, const void* host_src, bool may_merge = true);
+// msm.hip: self-tests of the device group law
+int32_t selftest_madd28(Ctx* c, uint32_t lanes, uint32_t steps, uint64_t seed, uint32_t* failures);
+int32_t selftest_addquad(Ctx* c, uint32_t ops, uint64_t seed, uint32_t* failures);
+// g1_setup.hip: synthetic base sets, the fixed-base tables, row formats
+int32_t generate_multiples(Ctx* c, const void* base104, uint64_t first, size_t n, PinnedBases* out);
+int32_t generate_from_scalars(Ctx* c, const void* base104, const void* scalars32, size_t n, PinnedBases* out);
+int32_t msm_precompute(Ctx* c, PinnedBases* pb);
+int32_t msm_precompute_range(Ctx* c, PinnedBases* pb, size_t off, size_t n, int window_bits);
+int32_t unpack_affine104(Ctx* c, const void* d_rows104, void* d_xy96, void* d_flags, size_t n, hipStream_t s);      // d_flags: n bytes + a uint32 count at the next multiple of 4
+int32_t rows_to28_into(const void* d_xy96, void* d_dst, size_t n, hipStream_t s);
+int32_t make_rows28(Ctx* c, PinnedBases* pb);          // fills pb->d_xy28 from pb->d_xy
 // sharded.hip: the same request against a SHARDED copy of the base set (handle of aleo_mi355x_bases_pin_sharded): every segment is cut at the shard boundaries,
 // device g pulls its pieces of the scalar vectors from the calling thread's device (peer copies; same device: none) and runs msm_batch against its shard,
 // the G x k partial results are added on the host in shard order.  `s` (the stream the scalars were produced on) is synchronised first when s_drain; the results are
@@ -216,21 +230,6 @@ int32_t commit_sharded(Ctx* c, uint64_t sharded_handle, const MsmSeg* segs, uint
 // sharded.hip: one transform of 2^lg_n elements resident at d_inout on the caller's device, computed over the listed devices (4-step, peer copies, no host buffer); blocking
 int32_t ntt_sharded_device(Ctx* c, void* d_inout, uint32_t lg_n, int32_t direction, int32_t type, const int* devices, size_t n_devices, hipStream_t s);
 int32_t sharded_devices(uint64_t sharded_handle, std::vector<int>* out);      // the device list of a sharded base set
-// One result over n points, scalars on the device (host_src == nullptr) or still on the host (then d_scalars is ignored and the scalars are uploaded into the
-// contexts' staging buffers): host scalars from 2^19 points on go in two halves on two contexts that share one bucket reduction — msm.hip msm_run1_split
-int32_t msm_run1_split(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const void* d_scalars, size_t n, bool mont, hipStream_t s, bool sparse, const void* host_src, bool may_merge = true);
-uint32_t msm_max_sets(const PinnedBases& pb, size_t n);
-int32_t launch_fq_mul(Ctx* c, void* r, const void* a, const void* b, size_t n);
-int32_t launch_fr_mul(Ctx* c, void* r, const void* a, const void* b, size_t n);
-int32_t generate_multiples(Ctx* c, const void* base104, uint64_t first, size_t n, PinnedBases* out);
-int32_t generate_from_scalars(Ctx* c, const void* base104, const void* scalars32, size_t n, PinnedBases* out);
-int32_t msm_precompute(Ctx* c, PinnedBases* pb);
-int32_t msm_precompute_range(Ctx* c, PinnedBases* pb, size_t off, size_t n, int window_bits);
-int32_t unpack_affine104(Ctx* c, const void* d_rows104, void* d_xy96, void* d_flags, size_t n, hipStream_t s);      // d_flags: n bytes + a uint32 count at the next multiple of 4
-int32_t rows_to28_into(const void* d_xy96, void* d_dst, size_t n, hipStream_t s);
-int32_t make_rows28(Ctx* c, PinnedBases* pb);          // fills pb->d_xy28 from pb->d_xy
-int32_t selftest_madd28(Ctx* c, uint32_t lanes, uint32_t steps, uint64_t seed, uint32_t* failures);
-int32_t selftest_addquad(Ctx* c, uint32_t ops, uint64_t seed, uint32_t* failures);
 // g2.hip
 int32_t msm_g2_run(Ctx* c, uint64_t* out_jac36, const void* d_xy, const uint8_t* d_inf, const void* d_scalars, size_t n, hipStream_t s, const void* d_rows28 = nullptr);      // d_rows28: the set's resident 28-bit rows (a pinned G2 set), else built per call
 int32_t g2_rows_to28(const void* d_xy192, void* d_dst224, size_t n, hipStream_t s);
@@ -238,6 +237,8 @@ int32_t g2_sum_host(uint64_t* out36, const uint64_t* pts36, size_t count);
 int32_t selftest_g2pair(Ctx* c, const void* aff192_host, uint32_t n, uint32_t npairs, uint32_t* failures2);      // [0] pairs that disagreed, [1] OR of the failing steps
 int32_t g2_unpack200(Ctx* c, const void* d_rows200, void* d_xy192, void* d_flags, uint32_t* d_count, size_t n, hipStream_t s);      // 200-byte G2Affine rows -> 192-byte rows + flag bytes + their count
 // frops.hip
+int32_t launch_fq_mul(Ctx* c, void* r, const void* a, const void* b, size_t n);
+int32_t launch_fr_mul(Ctx* c, void* r, const void* a, const void* b, size_t n);
 int32_t fr_lin(Ctx* c, void* d_dst, size_t n, const void* c0, const void* c1, const void* d_a, const void* c2, const void* d_b, hipStream_t s);
 int32_t fr_powers(Ctx* c, void* d_dst, size_t n, const void* first, const void* ratio, hipStream_t s);
 int32_t fr_gather_mul(Ctx* c, void* d_dst, size_t n, const void* d_scale, const void* d_t1, const void* d_idx1, const void* d_t2, const void* d_idx2, hipStream_t s);

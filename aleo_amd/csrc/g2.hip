@@ -4,7 +4,7 @@
 // every curve but BLS12-377 G1 to the standard Pippenger] over snarkvm-curves bls12_377/{fq2,g2}.rs (pin: /root/reference/Cargo.lock:2637).
 // The prover never runs a G2 MSM (G2 appears in the verifying key and in SRS setup), so this path is built for
 // parity and reach, not for the last percent: it shares the whole scalar side with G1 — signed-digit windows, the two-level
-// counting sort, slice sizing and ordering (msm_sort_phase: none of it depends on the group) — and swaps the group law:
+// counting sort, slice sizing and ordering (msm_sort.hip msm_sort_phase: none of it depends on the group) — and swaps the group law:
 // extended Jacobian (XYZZ) over Fq2 on the 32-bit-limb Montgomery blocks of fp.h, one lane per addition, out-of-line field
 // calls (a 2 x 12-limb product inlined ten times per addition would not fit the register file).
 //
@@ -573,29 +573,16 @@ int32_t msm_g2_run(Ctx* c, uint64_t* out_jac36, const void* d_xy, const uint8_t*
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
   // host tail: total = sum_w 2^(c w) * S_w (Horner from the top window)
-  // a 56-byte component of the pair form: value * 2^392 (+ a few q) as 14 x 28-bit limbs; * 2^376 under the 2^-384 of the host Montgomery product gives the HFq form
-  auto comp28 = [](const char* p) {
-    const uint32_t* w = (const uint32_t*)p; uint64_t big[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 14; ++i) {
-      const int pos = 28 * i, j = pos >> 6, sh = pos & 63;
-      const unsigned __int128 add = (unsigned __int128)w[i] << sh;
-      unsigned __int128 t = (unsigned __int128)big[j] + (uint64_t)add; big[j] = (uint64_t)t;
-      t = (unsigned __int128)big[j + 1] + (uint64_t)(add >> 64) + (uint64_t)(t >> 64); big[j + 1] = (uint64_t)t;
-      uint64_t cr = (uint64_t)(t >> 64);
-      for (int q = j + 2; q < 8 && cr; ++q) { t = (unsigned __int128)big[q] + cr; big[q] = (uint64_t)t; cr = (uint64_t)(t >> 64); }
-    }
-    HFq c376 = HFq::zero(); c376.l[5] = 1ull << 56;
-    return HFq::mul(HFq::reduce_lazy(big), c376);
-  };
+  // (a 56-byte component of the pair form: host_field.hpp hfq_from28)
   auto point28 = [&](const char* p) {
     HXYZZ2 v; HFq2* f[4] = {&v.X, &v.Y, &v.ZZ, &v.ZZZ};
-    for (int i = 0; i < 4; ++i) { f[i]->a = comp28(p + 112 * i); f[i]->b = comp28(p + 112 * i + 56); }
+    for (int i = 0; i < 4; ++i) { f[i]->a = hfq_from28((const uint32_t*)(p + 112 * i)); f[i]->b = hfq_from28((const uint32_t*)(p + 112 * i + 56)); }
     if (v.ZZ.is_zero()) return HXYZZ2::infinity();
     return v;
   };
   HXYZZ2 total = HXYZZ2::infinity();
   for (int w = (int)P.W - 1; w >= 0; --w) {
-    for (int d = 0; d < plan_win_width((int)P.c, w); ++d) total = h2double(total);
+    for (int d = 0; d < win_width((int)P.c, w); ++d) total = h2double(total);
     total = h2add(total, point28(h_win + (size_t)w * 448));
   }
   h2store_jacobian_normalized(out_jac36, total);

@@ -249,6 +249,35 @@ inline HXYZZ hfrom_jacobian(const uint64_t* j18) {
   r.ZZ = HFq::sqr(Z); r.ZZZ = HFq::mul(r.ZZ, Z);
   return r;
 }
+// Points as the device leaves them.  A 192-byte point of the plain path: four coordinates of 12 x 32-bit Montgomery limbs, < 2q or looser.
+static inline HXYZZ lazy_point(const char* p) {
+  const uint64_t* src = (const uint64_t*)p;
+  HXYZZ v; v.X = HFq::reduce_lazy(src); v.Y = HFq::reduce_lazy(src + 6); v.ZZ = HFq::reduce_lazy(src + 12); v.ZZZ = HFq::reduce_lazy(src + 18);
+  return v;
+}
+// A 56-byte coordinate of the 28-bit forms (fp28.h; G1's table path, G2's pair form): value * 2^392 mod q (+ a few q) as 14 x 28-bit limbs (possibly
+// loose); * 2^376 under the 2^-384 of the host Montgomery product gives value * 2^384, the HFq form.
+static inline HFq hfq_from28(const uint32_t* w) {
+  uint64_t big[8] = {0, 0, 0, 0, 0, 0, 0, 0};           // sum_i w_i * 2^(28 i), limbs may exceed 28 bits
+  for (int i = 0; i < 14; ++i) {
+    const int pos = 28 * i, j = pos >> 6, sh = pos & 63;
+    const unsigned __int128 add = (unsigned __int128)w[i] << sh;
+    unsigned __int128 t = (unsigned __int128)big[j] + (uint64_t)add; big[j] = (uint64_t)t;
+    t = (unsigned __int128)big[j + 1] + (uint64_t)(add >> 64) + (uint64_t)(t >> 64); big[j + 1] = (uint64_t)t;
+    uint64_t cr = (uint64_t)(t >> 64);
+    for (int q = j + 2; q < 8 && cr; ++q) { t = (unsigned __int128)big[q] + cr; big[q] = (uint64_t)t; cr = (uint64_t)(t >> 64); }
+  }
+  HFq c376 = HFq::zero(); c376.l[5] = 1ull << 56;
+  return HFq::mul(HFq::reduce_lazy(big), c376);        // value < 64q < 2^384: six limbs hold it
+}
+// a 224-byte point of G1's table path (X | Y | ZZ | ZZZ); ZZ = 0 is the identity
+static inline HXYZZ lazy_point28(const char* p) {
+  const uint32_t* w = (const uint32_t*)p;
+  HXYZZ v; v.X = hfq_from28(w); v.Y = hfq_from28(w + 14); v.ZZ = hfq_from28(w + 28); v.ZZZ = hfq_from28(w + 42);
+  if (v.ZZ.is_zero()) return HXYZZ::infinity();
+  return v;
+}
+
 // Writes the affine-normalised point as Jacobian (x, y, 1); infinity as snarkVM's Projective::zero() = (1, 1, 0).
 inline void hstore_jacobian_normalized(uint64_t* j18, const HXYZZ& p) {
   HFq x, y;

@@ -1,5 +1,6 @@
-// msm_common.h — what the G1 and G2 multi-scalar multiplications share (msm.hip, g2.hip): the plan, the results of the sort /
-// slice phase (which depends on the scalars only, not on the group) and the device helpers that read them.
+// msm_common.h — what the G1 and G2 multi-scalar multiplications share (msm_sort.hip defines it; msm.hip, msm_request.hip, g1_setup.hip and g2.hip
+// use it): the plan, the window geometry, the table tiers' lookup and set capacities, the results of the sort / slice phase (which depends on
+// the scalars only, not on the group) and the device helpers that read them.
 #pragma once
 #include "ctx.h"
 
@@ -13,9 +14,20 @@ static constexpr uint32_t SUPER_CAP = 4096;     // buckets with > 16 slices kept
 static constexpr uint32_t MAX_SLICE = 512;      // longest slice pick_rule() can produce
 
 struct MsmPlan { uint32_t c, W, B, M, S; };
-// Balanced windows (msm.hip): the top W*c - 254 windows are c-1 bits wide.
-inline int plan_win_width(int c, int w) { const int W = ((int)SCALAR_BITS + c - 1) / c, full = W - (W * c - (int)SCALAR_BITS); return w < full ? c : c - 1; }
+// Balanced windows.  W = ceil(254 / C) windows cover exactly 254 bits: the top D = W*C - 254 windows are C-1 bits wide, so no
+// window is short.  (With W uniform C-bit windows the last one keeps 254 - (W-1)*C bits — 14 of 20 at C = 20, 7 of 13 at C = 13 — and
+// its few buckets receive n / 2^13 .. n / 2^6 points each: on the table path, where all windows share one bucket set, those
+// buckets had to be cut into slices and folded by 3-10 extra tree launches.)  Window w starts at bit win_offset(C, w).
+__host__ __device__ constexpr int win_count(int c) { return ((int)SCALAR_BITS + c - 1) / c; }
+__host__ __device__ constexpr int win_full(int c) { return win_count(c) - (win_count(c) * c - (int)SCALAR_BITS); }      // windows of the full width c
+__host__ __device__ constexpr int win_width(int c, int w) { return w < win_full(c) ? c : c - 1; }
+__host__ __device__ constexpr int win_offset(int c, int w) { return w <= win_full(c) ? w * c : win_full(c) * c + (w - win_full(c)) * (c - 1); }
 MsmPlan make_plan(size_t n, int pre_c);
+// The table tier of a pinned set that serves a reach of n points (first match in pb.tab order), or null: the plain path.  Results ("sets") one launch
+// chain may hold: a set is 2^(c-9) coarse bins of the sort, a chain has MAX_COARSE_ALL (and <= MAX_SETS sets) — on the tier that serves n / on the range table.
+__attribute__((visibility("hidden"))) const PinnedBases::PreTable* msm_tier(const PinnedBases& pb, size_t n);
+__attribute__((visibility("hidden"))) uint32_t msm_range_sets(const PinnedBases& pb);
+uint32_t msm_max_sets(const PinnedBases& pb, size_t n);
 // A segment = one scalar vector: n scalars at ptr multiply the bases [off, off + n) of the pinned set and add into result `set`.
 // Several segments may feed one set (KZG10::commit with hiding: the polynomial against the powers and the blinding polynomial against
 // the gamma powers behind them; a degree-bounded polynomial is one segment at the shifted powers' offset).  col0: first column of the
