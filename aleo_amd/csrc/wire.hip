@@ -188,6 +188,52 @@ int32_t aleo_mi355x_bech32m_decode(void* out, size_t* len, char* hrp_out, size_t
   } catch (...) { return ALEO_MI355X_ERR_HIP; }
 }
 
+// A record ciphertext string ("record1…", bech32m): what the ownership scan (records.hip) needs of it.  Layout, read off the reference's own vector
+// (wasm/src/record/record_ciphertext.rs:96 of the reference, 118 payload bytes; snarkVM 0.14.5 console/program/src/data/record/bytes.rs [UPSTREAM-RECALL]):
+//   u8 owner variant (0 public: 32 B address x | 1 private: u16 field count = 1, 32 B c0) | u8 entry count | per entry: u8 name length, name, u16 byte
+//   length, that many bytes | 32 B nonce x | end.  Fields little-endian canonical.  owner_kind: 0 / 1; owner32: the address x or c0; nonce32: the nonce x.
+int32_t aleo_mi355x_record_parse(const char* record1, int32_t* owner_kind, void* owner32, void* nonce32) {
+  try {
+    if (!record1 || !owner_kind || !owner32 || !nonce32) return ALEO_MI355X_ERR_BAD_ARG;
+    const size_t slen = std::strlen(record1);
+    if (slen > (1u << 20)) { g_last_error = "record_parse: string too long"; return ALEO_MI355X_ERR_BAD_ARG; }
+    std::vector<uint8_t> b(slen + 1); size_t len = b.size(); char hrp[16];
+    const int32_t rc = aleo_mi355x_bech32m_decode(b.data(), &len, hrp, sizeof hrp, record1);
+    if (rc) return rc;
+    if (std::strcmp(hrp, "record")) { g_last_error = "record_parse: the prefix is not 'record'"; return ALEO_MI355X_ERR_BAD_ARG; }
+    size_t at = 0;
+    auto need = [&](size_t k) { return at + k <= len; };
+    auto refuse = [&](const char* why) { g_last_error = why; return ALEO_MI355X_ERR_BAD_ARG; };
+    auto field = [&](void* out) { HFr v; std::memcpy(v.l, b.data() + at, 32); at += 32; if (HFr::geq_p(v.l)) return false; std::memcpy(out, v.l, 32); return true; };
+    if (!need(1)) return refuse("record_parse: truncated");
+    const uint8_t kind = b[at++];
+    if (kind > 1) return refuse("record_parse: unknown owner variant");
+    if (kind == 1) {
+      if (!need(2)) return refuse("record_parse: truncated");
+      const unsigned cnt = b[at] | (b[at + 1] << 8); at += 2;
+      if (cnt != 1) return refuse("record_parse: a private owner is a ciphertext of one field");
+    }
+    if (!need(32)) return refuse("record_parse: truncated");
+    if (!field(owner32)) return refuse("record_parse: the owner field is not canonical");
+    if (!need(1)) return refuse("record_parse: truncated");
+    const unsigned entries = b[at++];
+    for (unsigned e = 0; e < entries; ++e) {
+      if (!need(1)) return refuse("record_parse: truncated");
+      const size_t nl = b[at++];
+      if (!need(nl + 2)) return refuse("record_parse: truncated");
+      at += nl;
+      const size_t el = b[at] | (b[at + 1] << 8); at += 2;
+      if (!need(el)) return refuse("record_parse: an entry runs past the end of the payload");
+      at += el;
+    }
+    if (!need(32)) return refuse("record_parse: truncated");
+    if (!field(nonce32)) return refuse("record_parse: the nonce is not canonical");
+    if (at != len) return refuse("record_parse: trailing bytes");
+    *owner_kind = kind;
+    return ALEO_MI355X_OK;
+  } catch (...) { return ALEO_MI355X_ERR_HIP; }
+}
+
 // Byte layout of a Varuna proof (see the file header; field order read off the reference's own proof string, batch of one
 // circuit with one instance; the multi-circuit order is [UPSTREAM-RECALL]).  *len: in = capacity, out = bytes written.
 int32_t aleo_mi355x_proof_to_bytes(void* out, size_t* len, const aleo_mi355x_proof_parts* p) {

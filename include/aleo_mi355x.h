@@ -506,6 +506,24 @@ int32_t aleo_mi355x_last_msm_timing(double* out_ms, int32_t cap);
  * the GPU box's host cores (bench.py cpu_baseline.crossover; profiles/r04_crossover.json); ALEO_MI355X_MIN_MSM / ALEO_MI355X_MIN_NTT override them. */
 size_t aleo_mi355x_min_msm(void);
 size_t aleo_mi355x_min_ntt(void);
+
+/* The ownership scan of record ciphertexts: for every record of a batch, does the account own it?  What the reference asks record by record with
+ * `record.is_owner_with_address_x_coordinate(&view_key, &address_x_coordinate)` (rust/src/api/blocking.rs:213-218, :274-276; RecordCiphertext.isOwner).
+ *   record_parse   host: a "record1..." string -> owner variant (0 public, 1 private), the owner field (address x, or the one field c0 of the owner
+ *                  ciphertext) and the nonce x, 32 canonical little-endian bytes each.  Refuses a wrong prefix or checksum, a private owner whose field count
+ *                  is not 1, an entry that overruns the payload, trailing bytes and non-canonical fields.  Public owners are compared by the caller.
+ *   records_scan   n private-owner records, all buffers on the host: owner_c0 and nonce_x n x 32 B canonical, view_key32 a canonical scalar below the
+ *                  subgroup order, address_x32 the address's x.  flags[i] = 1 owner, 0 not owner, 2 malformed (c0 or the nonce not below r, or the nonce x not
+ *                  on the curve); a malformed record never fails the batch.  rvk_out (optional, n x 32 B): the x of view_key * nonce — the record view key the
+ *                  host decrypts an owned record with — zeros where the flag is 2.  Defined for EVERY on-curve x: where upstream would have refused the record
+ *                  on parsing (no prime-order point with that x) the scan answers by the same formula; full validation stays with decryption.  Batches
+ *                  below min_records run on the host inside the call.  Thread-safe (one slot per call); n = 0 is fine; large n goes through in chunks.
+ *   records_scan_host   the same bytes out, computed on the CPU by the calling thread; touches no device.
+ *   min_records    the batch size from which records_scan takes the GPU: 64, the measured crossover against the host path on one thread (profiles/records_scan.txt: 0.88x at 2^5, 2.0x at 2^6); ALEO_MI355X_MIN_RECORDS overrides it, read per call. */
+int32_t aleo_mi355x_record_parse(const char* record1, int32_t* owner_kind, void* owner32, void* nonce32);
+int32_t aleo_mi355x_records_scan(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_key32, const void* address_x32);
+int32_t aleo_mi355x_records_scan_host(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_key32, const void* address_x32);
+size_t aleo_mi355x_min_records(void);
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */
 const char* aleo_mi355x_version(void);

@@ -11,6 +11,7 @@
 //   snarkvm_synthesizer_snark::ProvingKey::prove_batch / snarkvm_algorithms::snark::varuna::{CircuitProvingKey, Proof}: a proving key bound
 //       to one circuit, `prove_batch(&[assignment])` -> Proof, Proof Display as bech32m `proof1…`; `prove_batch(keys -> assignments)` over several
 //       keys and `Trace::prove_execution / prove_fee` above it (rows a6 / a7 of SURVEY.md §8)
+//   snarkvm_console_program::Record<N, Ciphertext<N>>::{from_str, is_owner} and the record search around it (RecordCiphertext, find_owned)
 // Layouts are snarkVM's: Fr = 4 x u64 Montgomery, scalar = 4 x u64 canonical, G1Affine = 104 bytes, Projective = 144 bytes.
 #pragma once
 #include <chrono>
@@ -437,5 +438,77 @@ class Trace {
  private:
   KeyedAssignments keyed_;
 };
+
+// ---- record ownership (the SDK's record search) ------------------------------------------------------------------------------------
+// snarkvm_console_account::{ViewKey, Address} as the scan takes them: the scalar of "AViewKey1…" (base58) and the x-coordinate of "aleo1…" (bech32m),
+// 32 little-endian bytes each.  The address of a view key is not derived here (upstream's generator is a hash to the curve): callers hold both.
+struct ViewKey {
+  uint8_t scalar[32];
+  static Result<ViewKey> from_string(const std::string& s) {
+    static const char* B58 = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
+    static const uint8_t prefix[7] = {14, 138, 223, 204, 247, 224, 122};
+    uint8_t raw[39] = {};                                         // big-endian base-256 digits of the base-58 number
+    for (char ch : s) {
+      const char* q = ch ? std::strchr(B58, ch) : nullptr;
+      if (!q) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+      uint32_t carry = (uint32_t)(q - B58);
+      for (int i = 38; i >= 0; --i) { carry += 58u * raw[i]; raw[i] = (uint8_t)carry; carry >>= 8; }
+      if (carry) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+    }
+    if (std::memcmp(raw, prefix, 7)) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+    ViewKey v; std::memcpy(v.scalar, raw + 7, 32); return {v, Error{0}};
+  }
+};
+struct Address {
+  uint8_t x[32];
+  static Result<Address> from_string(const std::string& s) {
+    uint8_t raw[64]; size_t len = sizeof raw; char hrp[16];
+    int32_t rc = aleo_mi355x_bech32m_decode(raw, &len, hrp, sizeof hrp, s.c_str());
+    if (rc) return {std::nullopt, Error{rc}};
+    if (std::strcmp(hrp, "aleo") || len != 32) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+    Address a; std::memcpy(a.x, raw, 32); return {a, Error{0}};
+  }
+};
+
+// Record<N, Ciphertext<N>> as far as ownership goes: FromStr, is_owner (RecordCiphertext.isOwner of the reference's wasm), and the batch form.
+class RecordCiphertext {
+ public:
+  static Result<RecordCiphertext> from_string(const std::string& s) {
+    RecordCiphertext r; int32_t kind = -1;
+    int32_t rc = aleo_mi355x_record_parse(s.c_str(), &kind, r.owner_, r.nonce_);
+    if (rc) return {std::nullopt, Error{rc}};
+    r.private_owner_ = kind == 1; r.string_ = s; return {std::move(r), Error{0}};
+  }
+  const std::string& to_string() const { return string_; }
+  bool owner_is_private() const { return private_owner_; }
+  const uint8_t* owner_field() const { return owner_; }           // the address x (public owner) or the one field of the owner ciphertext
+  const uint8_t* nonce_x() const { return nonce_; }
+  Result<bool> is_owner(const ViewKey& vk, const Address& address) const {
+    if (!private_owner_) return {std::memcmp(owner_, address.x, 32) == 0, Error{0}};
+    uint8_t flag = 0; int32_t rc = aleo_mi355x_records_scan(&flag, nullptr, owner_, nonce_, 1, vk.scalar, address.x);
+    if (rc) return {std::nullopt, Error{rc}};
+    return {flag == 1, Error{0}};
+  }
+ private:
+  std::string string_; bool private_owner_ = false; uint8_t owner_[32] = {}, nonce_[32] = {};
+};
+
+struct OwnedRecord { size_t index; bool has_view_key; uint8_t record_view_key_x[32]; };      // has_view_key: false for a public owner (nothing is encrypted)
+// The records of `batch` the account owns, in order, with the x of view_key * nonce of each (what decrypts it): one scan for the whole batch.  An Err means
+// "test them on the CPU one by one", as for every other operator.
+inline Result<std::vector<OwnedRecord>> find_owned(const std::vector<RecordCiphertext>& batch, const ViewKey& vk, const Address& address) {
+  std::vector<uint8_t> c0, nx; std::vector<size_t> at;
+  for (size_t i = 0; i < batch.size(); ++i)
+    if (batch[i].owner_is_private()) { c0.insert(c0.end(), batch[i].owner_field(), batch[i].owner_field() + 32); nx.insert(nx.end(), batch[i].nonce_x(), batch[i].nonce_x() + 32); at.push_back(i); }
+  std::vector<uint8_t> flags(at.size()), rvk(32 * at.size());
+  if (!at.empty()) { int32_t rc = aleo_mi355x_records_scan(flags.data(), rvk.data(), c0.data(), nx.data(), at.size(), vk.scalar, address.x); if (rc) return {std::nullopt, Error{rc}}; }
+  std::vector<OwnedRecord> out; size_t j = 0;
+  for (size_t i = 0; i < batch.size(); ++i) {
+    if (!batch[i].owner_is_private()) { if (!std::memcmp(batch[i].owner_field(), address.x, 32)) out.push_back(OwnedRecord{i, false, {}}); continue; }
+    if (flags[j] == 1) { OwnedRecord o{i, true, {}}; std::memcpy(o.record_view_key_x, rvk.data() + 32 * j, 32); out.push_back(o); }
+    ++j;
+  }
+  return {std::move(out), Error{0}};
+}
 
 }  // namespace aleo_mi355x
