@@ -215,6 +215,8 @@ int32_t msm_run1_split(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const
 // msm.hip: self-tests of the device group law
 int32_t selftest_madd28(Ctx* c, uint32_t lanes, uint32_t steps, uint64_t seed, uint32_t* failures);
 int32_t selftest_addquad(Ctx* c, uint32_t ops, uint64_t seed, uint32_t* failures);
+// msm_sort.hip: the slice stage (bucket scan, top scan, slice ordering) on a host histogram, checked against a host recount
+int32_t selftest_slice_order(Ctx* c, const uint32_t* h_hist, uint32_t M, uint32_t pairs, bool fused, uint32_t* violations);
 // g1_setup.hip: synthetic base sets, the fixed-base tables, row formats
 int32_t generate_multiples(Ctx* c, const void* base104, uint64_t first, size_t n, PinnedBases* out);
 int32_t generate_from_scalars(Ctx* c, const void* base104, const void* scalars32, size_t n, PinnedBases* out);

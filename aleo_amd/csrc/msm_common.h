@@ -36,7 +36,7 @@ struct SegArgs { const char* ptr[MAX_SEGS]; uint32_t n[MAX_SEGS], off[MAX_SEGS],
 
 // Slice sizing.  A bucket of <= single points is one slice (one lane); larger buckets are cut into slices of <= split.
 struct SliceRule { uint32_t single, split; };
-__device__ __forceinline__ SliceRule pick_rule(const uint32_t* total_pairs, uint32_t M) {
+__host__ __device__ __forceinline__ SliceRule pick_rule(const uint32_t* total_pairs, uint32_t M) {
   // Two pulls.  Keep buckets whole where possible (every extra slice is a 14-product tree addition): single = 2 x the
   // mean bucket size.  But fill the chip: the launch wants >= 2^18 slices (2 waves per SIMD), and a lane needs ~11 us per
   // addition, so when there are few pairs (small n, sparse scalars) slices are cut down to pairs / 2^18 points even if
@@ -57,11 +57,11 @@ __device__ __forceinline__ SliceRule pick_rule(const uint32_t* total_pairs, uint
   if (by_mean >= 2u * fill) { r.single = fill; r.split = fill; }
   return r;
 }
-__device__ __forceinline__ uint32_t slices_of(uint32_t cnt, SliceRule r) { return cnt <= r.single ? (cnt ? 1u : 0u) : (cnt + r.split - 1) / r.split; }
+__host__ __device__ __forceinline__ uint32_t slices_of(uint32_t cnt, SliceRule r) { return cnt <= r.single ? (cnt ? 1u : 0u) : (cnt + r.split - 1) / r.split; }
 __device__ __forceinline__ uint2 scan_at(const uint2* local, const uint2* blk, uint32_t g) {
   uint2 a = local[g], b = blk[g / SCAN_TILE]; return make_uint2(a.x + b.x, a.y + b.y);
 }
-__device__ __forceinline__ uint32_t slice_len(uint32_t cnt, uint32_t m, uint32_t k) {
+__host__ __device__ __forceinline__ uint32_t slice_len(uint32_t cnt, uint32_t m, uint32_t k) {
   return (uint32_t)(((uint64_t)(k + 1) * cnt) / m) - (uint32_t)(((uint64_t)k * cnt) / m);
 }
 
@@ -70,7 +70,7 @@ __device__ __forceinline__ uint32_t slice_len(uint32_t cnt, uint32_t m, uint32_t
 //   stream (bit 31 = negate), bucket runs contiguous | task_g[sid] bucket of slice sid | order[t] slice ids, longest first |
 //   meta[0] slices, [1] most slices in one bucket, [2] pairs, [3] multi-slice buckets (listed in heavy[]), [5] super-heavy ones, [6] most slices of a bucket in heavy[] (<= 16)
 struct SortPhase {
-  MsmPlan P; uint32_t M = 0, digitsW = 0, slice_blocks = 0; size_t slices_max = 0, pairs_max = 0;
+  MsmPlan P; uint32_t M = 0, digitsW = 0, slice_blocks = 0; size_t slices_max = 0, pairs_max = 0;      // slice_blocks = ceil(slices_max / 256): the ACCUMULATION's grid, a lane per slice (k_slice_order sizes its own: 2048 slices per block)
   uint32_t *hist = nullptr, *heavy = nullptr, *meta = nullptr; uint2 *scan_local = nullptr, *scan_blk = nullptr;
   uint32_t *sorted = nullptr, *task_g = nullptr, *order = nullptr; const uint32_t* total_pairs = nullptr; const uint32_t* super_list = nullptr;
   uint32_t meta_seq = 0;      // the sequence number k_scan_top stores behind the slice metadata in the slot's pinned buffer (msm_wait_meta polls for it)

@@ -45,6 +45,10 @@ int32_t msm_run(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob
 // profiles/r04_chunk_cumask_ab.jsonl): sorts confined to 16-64 reserved CUs are 4-8x slower (2^20: 4.5 / 3.8 / 3.4 ms with 16 / 32 / 64 CUs against 3.26), and
 // keeping the accumulations off 8-32 CUs while the sorts run anywhere changes nothing at 2^20 and costs 5-8 % beyond.
 // (Round 3 ran two halves as two complete MSMs on two host threads: that paid the 0.4 ms bucket reduction twice and lost below 2^21 points.)
+// First-chunk share re-measured on the one-launch slice ordering (msm_sort.hip k_slice_order; wall ms per call, bench steps of 20, the three builds alternated, two boxes;
+// profiles/r06_sort_chain_ab.txt):   2^20, 7 runs each:  30 % 2.857-2.928 (median 2.884) | 33 % 2.807-2.983 (2.868) | 37 % 2.820-2.966 (2.917)
+//                                    2^19, 3 runs each:  30 % 1.790-1.853 (1.790)       | 33 % 1.800-1.825 (1.809) | 37 % 1.785-1.868 (1.790)
+// The medians differ by <= 0.05 ms where one share's own runs spread over 0.07-0.18: inside the noise, 37 / 63 stays.  The three-chunk split at 2^21 was not re-measured.
 static int32_t msm_run_chunked(Ctx* c, HelperSet& hs, uint64_t* out_jac18, const PinnedBases& pb, size_t n, bool mont, hipStream_t s, const void* host_src) {
   const uint32_t Q = 1 + (uint32_t)hs.ctx.size();           // 2 or 3
   static const uint32_t share[4][3] = {{0, 0, 0}, {0, 0, 0}, {37, 63, 0}, {18, 30, 52}};

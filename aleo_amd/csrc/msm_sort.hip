@@ -1,6 +1,7 @@
 // msm_sort.hip — the scalar side of the Pippenger multi-scalar multiplications, shared by G1 (msm.hip) and G2 (g2.hip): everything msm_common.h
 // declares — the plan and the table tiers' set capacities, signed balanced digits, the two-level counting sort into contiguous bucket runs of 4-byte
 // point indices (bit 31 = negate), slices (whole buckets up to 2x the mean size, longer ones cut at the mean; sorted by length so a wave's lanes run equal trips), the slice metadata's way to the host.  None of it depends on the group.
+#include <algorithm>
 #include "ec.h"
 #include "msm_common.h"
 
@@ -322,41 +323,62 @@ __global__ void __launch_bounds__(256) k_bin_scatter(const uint2* __restrict__ i
 // slices (tried) put a 2.7 ms floor under a 2.4 ms kernel, because the top window of a 253-bit scalar only has 13 bits
 // and its 4779 buckets hold ~300 points each.  64/32 keeps the floor at about half the kernel time.
 // Sparse inputs (witness-like scalars, small n) use 32/32 so that the accumulation still fills every SIMD.
+// The same pass counts the slice LENGTHS (len_count, the histogram k_slice_order sorts by): a bucket of cnt points cut into m slices has cnt mod m slices of
+// ceil(cnt / m) points and the rest of floor(cnt / m) — slice_len() telescopes to cnt and every term is one of the two — so a bucket is two LDS increments and a
+// block one global add per length it met.  Multi-slice buckets are ranked by the block's scan as well: a block claims its stretch of either list with ONE global
+// atomic (one atomic per bucket before: the 4779 top-window buckets of a 2^20-point call sit in three tiles and drew theirs from one address).
 __global__ void __launch_bounds__(256) k_scan_tiles(const uint32_t* hist, uint32_t M, const uint32_t* total_pairs, uint2* scan_local, uint2* tile_tot, uint32_t* meta,
-                                                    uint32_t* __restrict__ heavy) {
-  __shared__ uint2 wsum[4];
+                                                    uint32_t* __restrict__ heavy, uint32_t* __restrict__ len_count) {
+  __shared__ uint2 wsum[4]; __shared__ uint32_t wlist[4], claim[2], lh[MAX_SLICE + 1];
+  for (uint32_t i = threadIdx.x; i <= MAX_SLICE; i += 256) lh[i] = 0;
+  __syncthreads();
   uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * 8;
   const SliceRule rule = pick_rule(total_pairs, M);
-  uint32_t c[8]; uint32_t mx = 0, mxc = 0;
+  uint32_t c[8], ms[8]; uint32_t mx = 0, mxc = 0, lists = 0;      // lists: this lane's common-list buckets | super-list buckets << 16 (a tile has <= 2048 of either)
 #pragma unroll
   for (int k = 0; k < 8; ++k) c[k] = (base + k < M) ? hist[base + k] : 0u;
   uint2 pre[8]; uint2 run = make_uint2(0, 0);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    pre[k] = run; uint32_t m = slices_of(c[k], rule); run.x += c[k]; run.y += m; mx = mx > m ? mx : m;
+    pre[k] = run; const uint32_t m = ms[k] = slices_of(c[k], rule); run.x += c[k]; run.y += m; mx = mx > m ? mx : m;
+    if (m) { const uint32_t q = c[k] / m, r = c[k] - q * m; if (r) atomicAdd(&lh[q + 1], r); atomicAdd(&lh[q], m - r); }
     // multi-slice buckets are the only work of the slice tree; the few with > 16 slices (skewed scalars) get their own
     // list so that the launch width of the common list stays at 8 pairs per bucket
-    if (m > 16) { uint32_t q = atomicAdd(&meta[5], 1u); if (q < SUPER_CAP) heavy[M + 2048 + q] = base + k; else heavy[atomicAdd(&meta[3], 1u)] = base + k; }
-    else if (m > 1) { heavy[atomicAdd(&meta[3], 1u)] = base + k; mxc = mxc > m ? mxc : m; }
+    if (m > 16) lists += 1u << 16;
+    else if (m > 1) { lists += 1u; mxc = mxc > m ? mxc : m; }
   }
-  if (mxc > 1) atomicMax(&meta[6], mxc);                   // most slices of a common-list bucket: the depth of ITS tree (msm_run)
   // wave inclusive scan of the per-thread totals
-  uint2 inc = run; int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint2 inc = run; uint32_t linc = lists; int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
-    uint32_t ox = __shfl_up(inc.x, d), oy = __shfl_up(inc.y, d);
-    if (lane >= d) { inc.x += ox; inc.y += oy; }
+    uint32_t ox = __shfl_up(inc.x, d), oy = __shfl_up(inc.y, d), ol = __shfl_up(linc, d);
+    if (lane >= d) { inc.x += ox; inc.y += oy; linc += ol; }
   }
-  if (lane == 63) wsum[wv] = inc;
+  if (lane == 63) { wsum[wv] = inc; wlist[wv] = linc; }
   __syncthreads();
-  uint2 woff = make_uint2(0, 0);
-  for (int k = 0; k < wv; ++k) { woff.x += wsum[k].x; woff.y += wsum[k].y; }
+  uint2 woff = make_uint2(0, 0); uint32_t loff = 0;
+  for (int k = 0; k < wv; ++k) { woff.x += wsum[k].x; woff.y += wsum[k].y; loff += wlist[k]; }
   uint2 excl = make_uint2(woff.x + inc.x - run.x, woff.y + inc.y - run.y);
 #pragma unroll
   for (int k = 0; k < 8; ++k) if (base + k < M) scan_local[base + k] = make_uint2(excl.x + pre[k].x, excl.y + pre[k].y);
-  if (threadIdx.x == 255) tile_tot[blockIdx.x] = make_uint2(woff.x + inc.x, woff.y + inc.y);
-  for (int d = 32; d >= 1; d >>= 1) { uint32_t o = __shfl_xor(mx, d); mx = mx > o ? mx : o; }
+  if (threadIdx.x == 255) {
+    tile_tot[blockIdx.x] = make_uint2(woff.x + inc.x, woff.y + inc.y);
+    const uint32_t tot = loff + linc, nc = tot & 0xffffu, ns = tot >> 16;
+    claim[0] = nc ? atomicAdd(&meta[3], nc) : 0u; claim[1] = ns ? atomicAdd(&meta[5], ns) : 0u;
+  }
+  __syncthreads();
+  if (lists) {
+    const uint32_t lexcl = loff + linc - lists; uint32_t qc = claim[0] + (lexcl & 0xffffu), qs = claim[1] + (lexcl >> 16);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (ms[k] > 16) { const uint32_t q = qs++; if (q < SUPER_CAP) heavy[M + 2048 + q] = base + k; else heavy[atomicAdd(&meta[3], 1u)] = base + k; }      // list full: over to the common one
+      else if (ms[k] > 1) heavy[qc++] = base + k;
+    }
+  }
+  for (uint32_t i = threadIdx.x; i <= MAX_SLICE; i += 256) if (lh[i]) atomicAdd(&len_count[i], lh[i]);
+  for (int d = 32; d >= 1; d >>= 1) { uint32_t o = __shfl_xor(mx, d), oc = __shfl_xor(mxc, d); mx = mx > o ? mx : o; mxc = mxc > oc ? mxc : oc; }
   if (lane == 0 && mx) atomicMax(&meta[1], mx);
+  if (lane == 0 && mxc > 1) atomicMax(&meta[6], mxc);       // most slices of a common-list bucket: the depth of ITS tree (msm_run)
 }
 
 // host_meta (device pointer of the slot's mapped pinned buffer): meta[0..7] go there followed by the call's sequence number at word 8, so the host reads the
@@ -395,37 +417,50 @@ __global__ void __launch_bounds__(256) k_scan_top(const uint2* tile_tot, uint32_
 // ---- slice ordering: lanes of one wave should run the same trip count --------------------------------
 // Slices are at most 512 points long; bucket sizes are Poisson, so slice lengths vary 2:1 inside a wave if
 // taken in bucket order (measured: 31 % of the accumulation's lanes idle).  A counting sort by length (longest
-// first) costs two tiny launches: block-local LDS histograms + a handful of global atomics per block.
-// sid -> bucket (binary search over first_slice), stores task_g[sid], counts slice lengths
-// FUSED (round 5, <= 512 scan tiles — every chain of a prover round): the exclusive scan of the tile totals, a single-block launch of its own until now (k_scan_top,
-// ~5-8 us per chain at real-circuit sizes), runs in every block's prologue over LDS; block 0 also leaves scan_blk, the totals and the host's copy of the slice
-// metadata behind for the kernels that follow (k_slice_order, the accumulation, the trees and the reduction read them from memory as before).
+// first) costs ONE launch behind the bucket scan, which has left the length counts (len_count) behind:
+//   a block takes ORDER_BATCH consecutive slice ids, 8 per lane.  It finds the buckets of its first and its last slice with two rounds of loads (every lane
+//   looks at tile prefixes, then at 8 buckets of the one tile), marks the first slice of every non-empty bucket in between in LDS and spreads the marks with
+//   a running maximum: sid -> bucket (task_g) without a search per slice (a binary search over all M buckets was 19 dependent rounds of two global loads
+//   per lane), and a bucket of thousands of slices (witness-like scalars) is spread over the lanes of as many blocks as it has batches.  Where the stretch of
+//   buckets is longer than STRETCH_CAP (sparse input: mostly empty buckets, few slices, few blocks) the lanes binary-search that stretch instead (>= 13 dependent rounds).
+//   Lengths are ranked in an LDS histogram with wave-aggregated atomics (lds_rank) and a block draws one global atomic per length it holds.
+// (len_start[l] = number of slices longer than l is recomputed by every block from the ~513 length counts — a single-block launch of its own, k_len_starts,
+//  cost ~6 us per chain at the sizes of real circuits)
+// FUSED (<= 512 scan tiles — every chain of a prover round): the exclusive scan of the tile totals, otherwise the single-block launch k_scan_top
+// (~5-8 us per chain at real-circuit sizes), runs in every block's prologue over LDS; block 0 also leaves scan_blk, the totals and the host's copy of the slice
+// metadata behind for the kernels that follow (the accumulation, the trees and the reduction read them from memory as before).
+// The grid comes from slice_bound(), about twice the real slice count: a block beyond it leaves as soon as it knows the count, before the set-up of the ordering
+// (length offsets, histogram, marks) — at once where k_scan_top has left the count in meta[0]; FUSED blocks must take the prologue's scan (two loads, an LDS scan
+// over <= 512 tile totals, two barriers) to learn it.
 static constexpr uint32_t FUSED_TILES = 512;
+static constexpr uint32_t ORDER_BATCH = 2048;     // slices per block: 8 per lane
+static constexpr uint32_t STRETCH_CAP = 8192;     // buckets a block walks to mark its slices' owners (32 per lane)
 template <bool FUSED>
-__global__ void __launch_bounds__(256) k_slice_count(const uint32_t* __restrict__ hist, const uint2* __restrict__ scan_local, const uint2* scan_blk_in,
-                                                     uint32_t M, const uint32_t* __restrict__ total_pairs, uint32_t* meta, uint32_t* __restrict__ task_g,
-                                                     uint32_t* __restrict__ len_count, const uint2* __restrict__ tile_tot, uint32_t ntiles, uint2* scan_blk_out,
+__global__ void __launch_bounds__(256) k_slice_order(const uint32_t* __restrict__ hist, const uint2* __restrict__ scan_local, uint2* scan_blk, const uint2* __restrict__ tile_tot,
+                                                     uint32_t ntiles, const uint32_t* __restrict__ total_pairs, uint32_t M, uint32_t* meta, uint32_t* __restrict__ task_g,
+                                                     const uint32_t* __restrict__ len_count, uint32_t* __restrict__ len_cursor, uint32_t* __restrict__ order,
                                                      volatile uint32_t* host_meta, uint32_t seq) {
-  __shared__ uint32_t h[MAX_SLICE + 1];
-  __shared__ uint2 sblk[FUSED ? FUSED_TILES : 1]; __shared__ uint2 wtot[4]; __shared__ uint32_t s_total;
-  for (uint32_t i = threadIdx.x; i <= MAX_SLICE; i += 256) h[i] = 0;
-  uint32_t total_slices;
+  __shared__ uint2 sblk[FUSED ? FUSED_TILES : 1]; __shared__ uint2 wtot2[4];
+  __shared__ uint32_t s_total, s_tile[2], s_loc[2], wtot[4];
+  __shared__ __attribute__((aligned(16))) uint32_t mark[ORDER_BATCH];
+  __shared__ uint32_t h[MAX_SLICE + 1], base[MAX_SLICE + 1], len_start[MAX_SLICE + 2];
+  const uint32_t tid = threadIdx.x; const int lane = tid & 63, wv = tid >> 6;
+  uint32_t total;
   if constexpr (FUSED) {
-    const uint32_t tid = threadIdx.x; const int lane = tid & 63, wv = tid >> 6;
     const uint2 v0 = 2 * tid < ntiles ? tile_tot[2 * tid] : make_uint2(0u, 0u), v1 = 2 * tid + 1 < ntiles ? tile_tot[2 * tid + 1] : make_uint2(0u, 0u);
     uint2 inc = make_uint2(v0.x + v1.x, v0.y + v1.y);
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const uint32_t ox = __shfl_up(inc.x, d), oy = __shfl_up(inc.y, d); if (lane >= d) { inc.x += ox; inc.y += oy; } }
-    if (lane == 63) wtot[wv] = inc;
+    if (lane == 63) wtot2[wv] = inc;
     __syncthreads();
-    uint2 off = make_uint2(0u, 0u); for (int k = 0; k < wv; ++k) { off.x += wtot[k].x; off.y += wtot[k].y; }
+    uint2 off = make_uint2(0u, 0u); for (int k = 0; k < wv; ++k) { off.x += wtot2[k].x; off.y += wtot2[k].y; }
     const uint2 excl = make_uint2(off.x + inc.x - v0.x - v1.x, off.y + inc.y - v0.y - v1.y);
     if (2 * tid < FUSED_TILES) sblk[2 * tid] = excl;
     if (2 * tid + 1 < FUSED_TILES) sblk[2 * tid + 1] = make_uint2(excl.x + v0.x, excl.y + v0.y);
     if (tid == 255) s_total = off.y + inc.y;
     if (blockIdx.x == 0) {
-      if (2 * tid < ntiles) scan_blk_out[2 * tid] = excl;
-      if (2 * tid + 1 < ntiles) scan_blk_out[2 * tid + 1] = make_uint2(excl.x + v0.x, excl.y + v0.y);
+      if (2 * tid < ntiles) scan_blk[2 * tid] = excl;
+      if (2 * tid + 1 < ntiles) scan_blk[2 * tid + 1] = make_uint2(excl.x + v0.x, excl.y + v0.y);
       if (tid == 255) {
         const uint32_t slices = off.y + inc.y, pairs = off.x + inc.x;
         meta[0] = slices; meta[2] = pairs;
@@ -438,66 +473,102 @@ __global__ void __launch_bounds__(256) k_slice_count(const uint32_t* __restrict_
       }
     }
     __syncthreads();
-    total_slices = s_total;
+    total = s_total;
   } else {
-    __syncthreads();
-    total_slices = meta[0];
+    total = meta[0];
   }
-  auto at = [&](uint32_t g) -> uint2 {
-    const uint2 a = scan_local[g]; uint2 b;
-    if constexpr (FUSED) b = sblk[g / SCAN_TILE]; else b = scan_blk_in[g / SCAN_TILE];
-    return make_uint2(a.x + b.x, a.y + b.y);
-  };
-  uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (t < total_slices) {
-    uint32_t lo = 0, hi = M - 1;        // largest g with first_slice(g) <= t
-    while (lo < hi) {
-      uint32_t mid = (lo + hi + 1) >> 1;
-      if (at(mid).y <= t) lo = mid; else hi = mid - 1;
-    }
-    uint32_t g = lo, cnt = hist[g], m = slices_of(cnt, pick_rule(total_pairs, M)), k = t - at(g).y;
-    task_g[t] = g;
-    atomicAdd(&h[slice_len(cnt, m, k)], 1u);
-  }
-  __syncthreads();
-  for (uint32_t i = threadIdx.x; i <= MAX_SLICE; i += 256) if (h[i]) atomicAdd(&len_count[i], h[i]);
-}
+  const uint32_t s0 = blockIdx.x * ORDER_BATCH;
+  if (s0 >= total) return;
+  const uint32_t s1 = (total - s0 < ORDER_BATCH ? total : s0 + ORDER_BATCH) - 1;      // this block's slices: s0 .. s1
+  auto blk_y = [&](uint32_t T) -> uint32_t { if constexpr (FUSED) return sblk[T].y; else return scan_blk[T].y; };
+  auto first_slice = [&](uint32_t g) -> uint32_t { return scan_local[g].y + blk_y(g / SCAN_TILE); };
 
-// order[pos] = sid, longest slices first
-// (len_start[l] = number of slices longer than l is recomputed by every block from the ~257 length counts — a single-block launch of its own, k_len_starts,
-//  cost ~6 us per chain at the sizes of real circuits)
-__global__ void __launch_bounds__(256) k_slice_order(const uint32_t* __restrict__ hist, const uint2* __restrict__ scan_local, const uint2* __restrict__ scan_blk,
-                                                     const uint32_t* __restrict__ total_pairs, uint32_t M, const uint32_t* __restrict__ meta, const uint32_t* __restrict__ task_g,
-                                                     const uint32_t* __restrict__ len_count, uint32_t* __restrict__ len_cursor, uint32_t* __restrict__ order) {
-  __shared__ uint32_t h[MAX_SLICE + 1], base[MAX_SLICE + 1], len_start[MAX_SLICE + 2], wtot[4];
   {                                                        // suffix sums of len_count: lane t owns the lengths PER t .. PER t + PER - 1
     constexpr uint32_t PER = (MAX_SLICE + 1 + 255) / 256;
-    const uint32_t t = threadIdx.x; uint32_t cnt[PER], tot = 0;
+    uint32_t cnt[PER], tot = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < PER; ++k) { const uint32_t l = PER * t + k; cnt[k] = l <= MAX_SLICE ? len_count[l] : 0u; tot += cnt[k]; }
-    uint32_t inc = tot; const int lane = t & 63, wv = t >> 6;
+    for (uint32_t k = 0; k < PER; ++k) { const uint32_t l = PER * tid + k; cnt[k] = l <= MAX_SLICE ? len_count[l] : 0u; tot += cnt[k]; }
+    uint32_t inc = tot;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_down(inc, d); if (lane + d < 64) inc += o; }      // inclusive suffix sum inside the wave
     if (lane == 0) wtot[wv] = inc;
     __syncthreads();
     uint32_t run = inc - tot; for (int k = wv + 1; k < 4; ++k) run += wtot[k];      // slices longer than this lane's last length
 #pragma unroll
-    for (uint32_t k = PER; k-- > 0;) { const uint32_t l = PER * t + k; if (l <= MAX_SLICE) len_start[l] = run; run += cnt[k]; }
+    for (uint32_t k = PER; k-- > 0;) { const uint32_t l = PER * tid + k; if (l <= MAX_SLICE) len_start[l] = run; run += cnt[k]; }
   }
-  for (uint32_t i = threadIdx.x; i <= MAX_SLICE; i += 256) h[i] = 0;
-  __syncthreads();
-  uint32_t t = blockIdx.x * 256 + threadIdx.x, len = 0, rank = 0;
-  bool live = t < meta[0];
-  if (live) {
-    uint32_t g = task_g[t], cnt = hist[g], m = slices_of(cnt, pick_rule(total_pairs, M)), k = t - scan_at(scan_local, scan_blk, g).y;
-    len = slice_len(cnt, m, k);
-    rank = atomicAdd(&h[len], 1u);
+  for (uint32_t i = tid; i <= MAX_SLICE; i += 256) h[i] = 0;
+  for (uint32_t i = tid; i < ORDER_BATCH; i += 256) mark[i] = 0;
+
+  // the buckets of slices s0 and s1: the largest g with first_slice(g) <= s (empty buckets share their successor's first slice) — first its tile, then its place in the tile
+  for (uint32_t T = tid; T < ntiles; T += 256) {
+    const uint32_t y = blk_y(T), yn = T + 1 < ntiles ? blk_y(T + 1) : 0xffffffffu;
+    if (y <= s0 && yn > s0) s_tile[0] = T;
+    if (y <= s1 && yn > s1) s_tile[1] = T;
   }
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i <= MAX_SLICE; i += 256)
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const uint32_t s = j ? s1 : s0, T = s_tile[j], by = blk_y(T), e0 = T * SCAN_TILE + tid * 8;
+    uint32_t v[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = (e0 + k < M && tid * 8 + k < SCAN_TILE) ? scan_local[e0 + k].y + by : 0xffffffffu;      // (the next tile starts beyond s)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (v[k] <= s && v[k + 1] > s) s_loc[j] = e0 + k;
+  }
+  __syncthreads();
+  const uint32_t g_lo = s_loc[0], g_hi = s_loc[1];
+  const bool walk = g_hi - g_lo < STRETCH_CAP;
+  uint32_t gq[8];
+  if (walk) {
+#pragma unroll 4
+    for (uint32_t g = g_lo + tid; g <= g_hi; g += 256)
+      if (hist[g]) { const uint32_t slot = g == g_lo ? 0u : first_slice(g) - s0; if (slot < ORDER_BATCH) mark[slot] = g + 1u; }      // first slices of distinct non-empty buckets differ; those behind g_lo's lie in (s0, s1]
+    __syncthreads();
+    const uint4 m0 = ((const uint4*)mark)[2 * tid], m1 = ((const uint4*)mark)[2 * tid + 1];
+    gq[0] = m0.x; gq[1] = m0.y; gq[2] = m0.z; gq[3] = m0.w; gq[4] = m1.x; gq[5] = m1.y; gq[6] = m1.z; gq[7] = m1.w;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) gq[k] = gq[k] > gq[k - 1] ? gq[k] : gq[k - 1];
+    uint32_t inc = gq[7];                                  // running maximum over the lanes before this one
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d); if (lane >= d && o > inc) inc = o; }
+    if (lane == 63) wtot[wv] = inc;
+    uint32_t before = __shfl_up(inc, 1); if (lane == 0) before = 0;
+    __syncthreads();
+    for (int k = 0; k < wv; ++k) before = wtot[k] > before ? wtot[k] : before;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) gq[k] = (gq[k] > before ? gq[k] : before) - 1u;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const uint32_t sid = s0 + tid * 8 + k;
+      uint32_t lo = g_lo, hi = g_hi;
+      if (sid <= s1) while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (first_slice(mid) <= sid) lo = mid; else hi = mid - 1; }
+      gq[k] = lo;
+    }
+  }
+  const SliceRule rule = pick_rule(total_pairs, M);
+  uint32_t len[8], rank[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const uint32_t sid = s0 + tid * 8 + k; len[k] = 0;
+    if (sid <= s1) { const uint32_t g = gq[k], cnt = hist[g]; len[k] = slice_len(cnt, slices_of(cnt, rule), sid - first_slice(g)); }
+  }
+  if (s0 + tid * 8 + 7 <= s1) {
+    uint4* dst = (uint4*)(task_g + s0 + tid * 8);
+    dst[0] = make_uint4(gq[0], gq[1], gq[2], gq[3]); dst[1] = make_uint4(gq[4], gq[5], gq[6], gq[7]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (s0 + tid * 8 + k <= s1) task_g[s0 + tid * 8 + k] = gq[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) rank[k] = lds_rank(h, len[k], s0 + tid * 8 + k <= s1, lane);
+  __syncthreads();
+  for (uint32_t i = tid; i <= MAX_SLICE; i += 256)
     if (h[i]) base[i] = len_start[i] + atomicAdd(&len_cursor[i], h[i]);
   __syncthreads();
-  if (live) order[base[len] + rank] = t;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) if (s0 + tid * 8 + k <= s1) order[base[len[k]] + rank[k]] = s0 + tid * 8 + k;
 }
 
 // ---- dispatch on the window width ---------------------------------------------------------------
@@ -539,6 +610,22 @@ static uint32_t sets_of_window(int c) {
 }
 uint32_t msm_max_sets(const PinnedBases& pb, size_t n) { const PinnedBases::PreTable* t = msm_tier(pb, n); return t ? sets_of_window(t->c) : 1; }
 uint32_t msm_range_sets(const PinnedBases& pb) { return sets_of_window(pb.range.c); }
+
+// Everything behind the bucket histogram: bucket scan (+ slice lengths, multi-slice lists), top scan (a launch of its own, or fused into the next one), slice ordering.
+// ev (optional) is recorded behind the scan, in front of the slice ordering.
+static int32_t launch_slice_stage(const SortPhase& sp, uint2* tile_tot, const uint32_t* total_pairs, uint32_t* host_meta, bool fuse_top, hipEvent_t ev, hipStream_t s) {
+  const uint32_t M = sp.M, ntiles = (M + SCAN_TILE - 1) / SCAN_TILE;
+  uint32_t* len_count = sp.meta + 16; uint32_t* len_cursor = len_count + MAX_SLICE + 1;   // zeroed with hist/meta
+  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, s, sp.hist, M, total_pairs, sp.scan_local, tile_tot, sp.meta, sp.heavy, len_count);
+  if (!fuse_top) hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, tile_tot, ntiles, sp.scan_blk, sp.meta, (volatile uint32_t*)host_meta, sp.meta_seq);
+  HIPCHK(hipGetLastError());
+  if (ev) HIPCHK(hipEventRecord(ev, s));
+  const uint32_t blocks = (uint32_t)((sp.slices_max + ORDER_BATCH - 1) / ORDER_BATCH);
+  hipLaunchKernelGGL(fuse_top ? k_slice_order<true> : k_slice_order<false>, dim3(blocks), dim3(256), 0, s, sp.hist, sp.scan_local, sp.scan_blk, (const uint2*)tile_tot, ntiles,
+                     total_pairs, M, sp.meta, sp.task_g, len_count, len_cursor, sp.order, fuse_top ? (volatile uint32_t*)host_meta : nullptr, fuse_top ? sp.meta_seq : 0u);
+  HIPCHK(hipGetLastError());
+  return ALEO_MI355X_OK;
+}
 
 int32_t msm_sort_phase(Ctx* c, SegArgs& segs, size_t pts, bool mont, const uint8_t* d_inf, uint32_t row_stride,
                        const MsmPlan& P, bool pre, hipStream_t s, SortPhase* out, bool lean) {
@@ -602,22 +689,15 @@ int32_t msm_sort_phase(Ctx* c, SegArgs& segs, size_t pts, bool mont, const uint8
   hipLaunchKernelGGL(k_bin_parts, dim3(1), dim3(256), 0, s, sa.off_local, sa.off_blk, nblk, ncb, cnt_tiles, part_start);
   hipLaunchKernelGGL(k_bin_hist, dim3(nparts_max), dim3(256), 0, s, sa.items, sa.off_local, sa.off_blk, nblk, ncb, cnt_tiles, LB, part_start, hist);
   hipLaunchKernelGGL(k_bin_scatter, dim3(nparts_max), dim3(256), 0, s, sa.items, sa.off_local, sa.off_blk, nblk, ncb, cnt_tiles, LB, part_start, hist, bin_cursor, sorted);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, s, hist, M, total_pairs, scan_local, tile_tot, meta, heavy);
-  // The slice count, the longest bucket and the list lengths size the slice-tree launches.  k_scan_top stores them (and this call's sequence number behind them)
-  // into the slot's pinned, device-mapped buffer; the slice kernels and the accumulation — launched with grids from slice_bound() — follow on `s` at once, and
-  // the host polls the sequence number long before the accumulation ends (msm_wait_meta): the GPU never waits for the round trip, and nothing but kernels
-  // sits on the stream (rounds 1-4 copied the words back on the side stream behind an event of `s`: a copy launch and ~6 us of idle GPU per chain).
+  // The slice count, the longest bucket and the list lengths size the slice-tree launches.  k_scan_top (or block 0 of the fused k_slice_order) stores them (and this
+  // call's sequence number behind them) into the slot's pinned, device-mapped buffer; the slice ordering and the accumulation — launched with grids from slice_bound() —
+  // follow on `s` at once, and the host polls the sequence number long before the accumulation ends (msm_wait_meta): the GPU never waits for the round trip, and nothing
+  // but kernels sits on the stream (rounds 1-4 copied the words back on the side stream behind an event of `s`: a copy launch and ~6 us of idle GPU per chain).
   uint32_t* host_meta = nullptr;
   HIPCHK(hipHostGetDevicePointer((void**)&host_meta, c->h_pinned, 0));
   sp.meta_seq = ++c->meta_seq;
   const bool fuse_top = lean && ntiles <= FUSED_TILES;      // (calls that time their phases keep the sort / slice-order boundary at ev[1])
-  if (!fuse_top) hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, tile_tot, ntiles, scan_blk, meta, (volatile uint32_t*)host_meta, sp.meta_seq);
-  HIPCHK(hipGetLastError());
-  if (!lean) HIPCHK(hipEventRecord(c->ev[1], s));
-  uint32_t* len_count = meta + 16; uint32_t* len_cursor = len_count + MAX_SLICE + 1;   // zeroed with hist/meta
-  auto* const count = fuse_top ? k_slice_count<true> : k_slice_count<false>;
-  hipLaunchKernelGGL(count, dim3(sp.slice_blocks), dim3(256), 0, s, hist, scan_local, (const uint2*)scan_blk, M, total_pairs, meta, task_g, len_count, (const uint2*)tile_tot, ntiles, scan_blk, fuse_top ? (volatile uint32_t*)host_meta : nullptr, fuse_top ? sp.meta_seq : 0u);
-  hipLaunchKernelGGL(k_slice_order, dim3(sp.slice_blocks), dim3(256), 0, s, hist, scan_local, scan_blk, total_pairs, M, meta, task_g, len_count, len_cursor, order);
+  if ((rc = launch_slice_stage(sp, tile_tot, total_pairs, host_meta, fuse_top, lean ? nullptr : c->ev[1], s))) return rc;
   HIPCHK(hipGetLastError());
   return ALEO_MI355X_OK;
 }
@@ -645,5 +725,87 @@ int32_t msm_wait_meta(Ctx* c, const SortPhase& sp, hipStream_t s, SliceMeta* m) 
   }
   return ALEO_MI355X_OK;
 }
+
+// Test hook (aleo_mi355x_selftest_slice_order): the slice stage alone — bucket scan, top scan (fused or not), slice ordering — on a histogram from the host, and
+// what it left behind checked against a host recount.  A mis-sorted `order` leaves every sum right and only costs time: no result test can see it.
+int32_t selftest_slice_order(Ctx* c, const uint32_t* h_hist, uint32_t M, uint32_t pairs, bool fused, uint32_t* violations) {
+  const uint32_t ntiles = (M + SCAN_TILE - 1) / SCAN_TILE;
+  uint64_t sum = 0; for (uint32_t g = 0; g < M; ++g) sum += h_hist[g];
+  if (!M || M > (1u << 20) || sum >= (1ull << 31) || (fused && ntiles > FUSED_TILES)) { g_last_error = "selftest_slice_order: bad argument"; return ALEO_MI355X_ERR_BAD_ARG; }
+  SortPhase sp; sp.M = M; sp.pairs_max = sum > pairs ? (size_t)sum : pairs; sp.slices_max = slice_bound(sp.pairs_max, M);
+  const size_t hist_words = 3 * (size_t)M + 2048 + SUPER_CAP;
+  int32_t rc;
+  if ((rc = c->hist.reserve(hist_words * 4))) return rc;
+  if ((rc = c->scan_local.reserve((size_t)M * 8))) return rc;
+  if ((rc = c->scan_blk.reserve(2 * (size_t)ntiles * 8 + 64))) return rc;
+  if ((rc = c->task_g.reserve(2 * sp.slices_max * 4))) return rc;
+  if ((rc = c->part_cnt.reserve(16))) return rc;
+  if ((rc = ensure_host_pinned(c, 64))) return rc;
+  // the host's recount — first, so that a histogram the reservations (slice_bound) do not cover is refused and never launched
+  const uint32_t tp[2] = {pairs, FILL_SHIFT};
+  const SliceRule rule = pick_rule(tp, M);
+  std::vector<uint32_t> first(M + 1), len_want(MAX_SLICE + 1, 0);
+  uint32_t NT = 0, max_m = 0, max_common = 0, n_common = 0, n_super = 0;
+  for (uint32_t g = 0; g < M; ++g) {
+    const uint32_t cnt = h_hist[g], m = slices_of(cnt, rule);
+    first[g] = NT; NT += m; max_m = m > max_m ? m : max_m;
+    if (m > 16) ++n_super; else if (m > 1) { ++n_common; max_common = m > max_common ? m : max_common; }
+    for (uint32_t k = 0; k < m; ++k) { const uint32_t l = slice_len(cnt, m, k); if (l <= MAX_SLICE) ++len_want[l]; }
+  }
+  first[M] = NT;
+  if (pairs < sum || NT > sp.slices_max) { g_last_error = "selftest_slice_order: total_pairs below the histogram's sum"; return ALEO_MI355X_ERR_BAD_ARG; }      // (the rule would cut finer than slice_bound() allows for)
+  hipStream_t s = c->stream;
+  sp.hist = c->hist.as<uint32_t>(); sp.heavy = sp.hist + M; sp.meta = sp.heavy + M; sp.super_list = sp.heavy + M + 2048;
+  sp.scan_local = c->scan_local.as<uint2>(); uint2* tile_tot = c->scan_blk.as<uint2>(); sp.scan_blk = tile_tot + ntiles;
+  sp.task_g = c->task_g.as<uint32_t>(); sp.order = sp.task_g + sp.slices_max;
+  uint32_t* total_pairs = c->part_cnt.as<uint32_t>();
+  c->hist_clean = 0;
+  HIPCHK(hipMemsetAsync(sp.hist, 0, hist_words * 4, s));
+  HIPCHK(hipMemcpyAsync(sp.hist, h_hist, (size_t)M * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(total_pairs, tp, 8, hipMemcpyHostToDevice, s));
+  uint32_t* host_meta = nullptr;
+  HIPCHK(hipHostGetDevicePointer((void**)&host_meta, c->h_pinned, 0));
+  sp.meta_seq = ++c->meta_seq;
+  if ((rc = launch_slice_stage(sp, tile_tot, total_pairs, host_meta, fused, nullptr, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+
+  uint32_t bad = 0;
+  uint32_t meta[8 + 8 + MAX_SLICE + 1];
+  HIPCHK(hipMemcpy(meta, sp.meta, sizeof meta, hipMemcpyDeviceToHost));
+  const uint32_t over = n_super > SUPER_CAP ? n_super - SUPER_CAP : 0;
+  const uint32_t want[7] = {NT, max_m, (uint32_t)sum, n_common + over, 0u, n_super, max_common};
+  const volatile uint32_t* hm = (const volatile uint32_t*)c->h_pinned;
+  for (int i = 0; i < 7; ++i) { bad += meta[i] != want[i]; bad += hm[i] != want[i]; }
+  bad += hm[8] != sp.meta_seq;
+  for (uint32_t l = 0; l <= MAX_SLICE; ++l) bad += meta[16 + l] != len_want[l];
+  // both lists as sets: every multi-slice bucket once; the super list holds buckets of > 16 slices only, the common list such buckets only past SUPER_CAP
+  if (meta[3] == want[3] && meta[5] == want[5]) {
+    const uint32_t ns = n_super < SUPER_CAP ? n_super : SUPER_CAP;
+    std::vector<uint32_t> lc(want[3]), ls(ns), seen(M, 0);
+    if (!lc.empty()) HIPCHK(hipMemcpy(lc.data(), sp.heavy, lc.size() * 4, hipMemcpyDeviceToHost));
+    if (!ls.empty()) HIPCHK(hipMemcpy(ls.data(), sp.super_list, ls.size() * 4, hipMemcpyDeviceToHost));
+    uint32_t long_in_common = 0;
+    for (uint32_t g : lc) { if (g >= M) { ++bad; continue; } const uint32_t m = slices_of(h_hist[g], rule); bad += m <= 1; long_in_common += m > 16; bad += seen[g]++ != 0; }
+    for (uint32_t g : ls) { if (g >= M) { ++bad; continue; } bad += slices_of(h_hist[g], rule) <= 16; bad += seen[g]++ != 0; }
+    bad += long_in_common != over;
+  }
+  if (meta[0] == NT && NT) {
+    std::vector<uint32_t> task(NT), ord(NT), hit(NT, 0);
+    HIPCHK(hipMemcpy(task.data(), sp.task_g, (size_t)NT * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ord.data(), sp.order, (size_t)NT * 4, hipMemcpyDeviceToHost));
+    for (uint32_t sid = 0; sid < NT; ++sid) { const uint32_t g = task[sid]; bad += !(g < M && first[g] <= sid && sid < first[g + 1]); }
+    uint32_t prev = 0xffffffffu;
+    for (uint32_t t = 0; t < NT; ++t) {
+      const uint32_t sid = ord[t];
+      if (sid >= NT || hit[sid]++) { ++bad; continue; }      // not a permutation of [0, NT)
+      uint32_t g = (uint32_t)(std::upper_bound(first.begin(), first.begin() + M, sid) - first.begin()) - 1;
+      const uint32_t cnt = h_hist[g], l = slice_len(cnt, slices_of(cnt, rule), sid - first[g]);
+      bad += l > prev; prev = l;                            // longest first
+    }
+  }
+  *violations = bad;
+  return ALEO_MI355X_OK;
+}
+
 
 }  // namespace aleo_mi355x

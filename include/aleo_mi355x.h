@@ -484,6 +484,13 @@ int32_t aleo_mi355x_selftest_madd28(uint32_t lanes, uint32_t steps, uint64_t see
  * (identity operands, equal points, opposite points): *failures = number of disagreements (mod q, all four coordinates). */
 int32_t aleo_mi355x_selftest_addquad(uint32_t ops, uint64_t seed, uint32_t* failures);
 
+/* The slice stage of the MSM sort alone (bucket scan, top scan, slice ordering) on a histogram from the host: hist[g] = points of bucket g, n_buckets <= 2^20,
+ * total_pairs = the pair count the slice rule is picked from (the sum of hist or more: less is refused); fused != 0 runs the top scan inside the ordering kernel, as the
+ * chains of a proof do.  *violations = how often what the device left behind breaks one of: `order` is a permutation of the slice ids; slice lengths never increase along
+ * it; task_g[sid] is the bucket whose slice range holds sid; the length counts, the slice metadata (device and host copy) and both multi-slice bucket lists (as
+ * sets) equal a host recount. */
+int32_t aleo_mi355x_selftest_slice_order(const uint32_t* hist, uint32_t n_buckets, uint32_t total_pairs, int32_t fused, uint32_t* violations);
+
 /* The lane-pair Fq2 arithmetic of the G2 path (g2.hip: components of an Fq2 value across two lanes, 28-bit limbs) against the one-lane 32-bit code on
  * chains over n_points affine G2 points (192-byte rows, host memory, >= 3 of them, all on the curve): sums, a sum with a shared operand, a doubling, the
  * same-point case of the addition.  failures2[0] = pairs that disagreed, failures2[1] = OR of the failing steps (1 a, 2 s, 4 u, 8 2u, 16 u + u). */
