@@ -24,6 +24,7 @@ EXPORTS = [
     'aleo_mi355x_init_device', 'aleo_mi355x_device_count', 'aleo_mi355x_peer_info', 'aleo_mi355x_min_msm', 'aleo_mi355x_min_ntt', 'aleo_mi355x_kzg_commit_segments_sharded_device', 'aleo_mi355x_kzg_commit_batch_sharded_device', 'aleo_mi355x_bases_attach_shards', 'aleo_mi355x_bases_shard_transforms', 'aleo_mi355x_bases_pin_sharded', 'aleo_mi355x_bases_generate_sharded', 'aleo_mi355x_bases_unpin_sharded',
     'aleo_mi355x_bases_sharded_info', 'aleo_mi355x_msm_g1_sharded', 'aleo_mi355x_fr_transpose_device', 'aleo_mi355x_ntt_fr_sharded', 'aleo_mi355x_ntt_fr_sharded_device', 'aleo_mi355x_selftest_host_inverse', 'aleo_mi355x_varuna_prove_many',
     'aleo_mi355x_record_parse', 'aleo_mi355x_records_scan', 'aleo_mi355x_records_scan_host', 'aleo_mi355x_min_records',
+    'aleo_mi355x_records_scan_many', 'aleo_mi355x_records_scan_many_host',
 ]
 
 
@@ -161,6 +162,8 @@ def lib():
         'aleo_mi355x_records_scan': ([vp, vp, vp, vp, sz, vp, vp], i32),
         'aleo_mi355x_records_scan_host': ([vp, vp, vp, vp, sz, vp, vp], i32),
         'aleo_mi355x_min_records': ([], sz),
+        'aleo_mi355x_records_scan_many': ([vp, vp, vp, vp, sz, vp, vp, sz], i32),
+        'aleo_mi355x_records_scan_many_host': ([vp, vp, vp, vp, sz, vp, vp, sz], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name); f.argtypes = args; f.restype = res

@@ -668,6 +668,6 @@ int32_t aleo_mi355x_selftest_host_inverse(uint32_t count, uint64_t seed, uint32_
   });
 }
 const char* aleo_mi355x_last_error(void) { return g_last_error.c_str(); }
-const char* aleo_mi355x_version(void) { return "aleo_mi355x 0.3.0 (gfx950)"; }
+const char* aleo_mi355x_version(void) { return "aleo_mi355x 0.4.0 (gfx950)"; }
 
 }  // the entry points

@@ -2,7 +2,8 @@
 loop around `record.is_owner_with_address_x_coordinate` in rust/src/api/blocking.rs:213-218, :274-276 — for a whole batch at a time, through the C ABI
 (aleo_mi355x_record_parse, aleo_mi355x_records_scan: csrc/wire.hip, csrc/records.hip).  View keys (base58, "AViewKey1…") and addresses (bech32m,
 "aleo1…") are decoded here; the address of a view key is NOT derived (that needs upstream's hash-to-curve generator), so callers pass both, as the
-reference's call sites do."""
+reference's call sites do.  scan_many / find_owned_many ask for several accounts over the same records in one call (aleo_mi355x_records_scan_many:
+csrc/records_many.hip), as a front end does that runs the search for several callers (rust/develop/src/routes.rs:112, :143, :194-220 of the reference)."""
 from __future__ import annotations
 import ctypes
 import numpy as np
@@ -53,6 +54,20 @@ def scan(owner_c0: np.ndarray, nonce_x: np.ndarray, view_key, address, want_rvk:
     return flags, rvk
 
 
+def scan_many(owner_c0: np.ndarray, nonce_x: np.ndarray, view_keys, addresses, want_rvk: bool = True, host: bool = False):
+    """scan for several accounts over the same n records in one call (aleo_mi355x_records_scan_many / _many_host): flags (uint8[K, n]) and, when want_rvk,
+    the record view keys' x (uint8[K, n, 32]); row j is what scan returns for (view_keys[j], addresses[j]) alone.  1 <= K <= 64; keys may repeat."""
+    c0 = np.ascontiguousarray(owner_c0, dtype=np.uint8).reshape(-1, 32); nx = np.ascontiguousarray(nonce_x, dtype=np.uint8).reshape(-1, 32)
+    if c0.shape != nx.shape: raise ValueError('owner_c0 and nonce_x differ in length')
+    if len(view_keys) != len(addresses): raise ValueError('view_keys and addresses differ in length')
+    n, k = c0.shape[0], len(view_keys)
+    flags = np.zeros((k, n), dtype=np.uint8); rvk = np.zeros((k, n, 32), dtype=np.uint8) if want_rvk else None
+    vk = np.frombuffer(b''.join(view_key_bytes(v) for v in view_keys), dtype=np.uint8); ax = np.frombuffer(b''.join(address_x_bytes(a) for a in addresses), dtype=np.uint8)
+    f = lib().aleo_mi355x_records_scan_many_host if host else lib().aleo_mi355x_records_scan_many
+    check(f(_p(flags), _p(rvk) if want_rvk else None, _p(c0), _p(nx), n, _p(vk), _p(ax), k), 'records_scan_many')
+    return flags, rvk
+
+
 class RecordCiphertext:
     """A parsed "record1…" string: the owner variant, the owner field (address x, or the one field of the owner ciphertext) and the nonce x."""
 
@@ -90,3 +105,19 @@ def find_owned(ciphertexts, view_key, address):
             if flags[j] == 1: owned[i] = rvk[j].tobytes()
     idx = sorted(owned)
     return idx, [owned[i] for i in idx]
+
+
+def find_owned_many(ciphertexts, accounts):
+    """find_owned for several accounts over the same records: `accounts` is a sequence of (view_key, address) pairs, the result a list with, for each of
+    them, what find_owned returns.  Every string is parsed once and the private owners of all accounts go through one scan_many call."""
+    recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
+    accounts = [(vk, address_x_bytes(a)) for vk, a in accounts]
+    priv = [i for i, r in enumerate(recs) if r.owner_kind == OWNER_PRIVATE]
+    owned = [{i: None for i, r in enumerate(recs) if r.owner_kind == OWNER_PUBLIC and r.owner == ax} for _, ax in accounts]
+    if priv and accounts:
+        c0 = np.frombuffer(b''.join(recs[i].owner for i in priv), dtype=np.uint8).reshape(-1, 32)
+        nx = np.frombuffer(b''.join(recs[i].nonce for i in priv), dtype=np.uint8).reshape(-1, 32)
+        flags, rvk = scan_many(c0, nx, [vk for vk, _ in accounts], [ax for _, ax in accounts])
+        for a, mine in enumerate(owned):
+            for j in np.nonzero(flags[a] == 1)[0]: mine[priv[j]] = rvk[a, j].tobytes()
+    return [(sorted(mine), [mine[i] for i in sorted(mine)]) for mine in owned]

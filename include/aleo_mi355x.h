@@ -531,6 +531,20 @@ int32_t aleo_mi355x_record_parse(const char* record1, int32_t* owner_kind, void*
 int32_t aleo_mi355x_records_scan(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_key32, const void* address_x32);
 int32_t aleo_mi355x_records_scan_host(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_key32, const void* address_x32);
 size_t aleo_mi355x_min_records(void);
+
+/* The same scan for SEVERAL accounts over one set of records in one call: what a front end asks that runs the record search for several callers over the same
+ * blocks (the reference's dev server: rust/develop/src/routes.rs:112, :143, :194-220 -> rust/src/api/blocking.rs:229-292).
+ *   records_scan_many   owner_c0, nonce_x: n x 32 B as for records_scan; view_keys32, address_xs32: n_keys x 32 B, key j's scalar and address x; 1 <= n_keys <= 64,
+ *                  repeated keys allowed, n = 0 is fine.  flags (n_keys x n bytes, [key][record]) and rvk_out (optional, n_keys x n x 32 B): row j is byte for
+ *                  byte what records_scan_host returns for key j alone.  A view key not below the subgroup order or an address x not canonical refuses the
+ *                  call before any launch; last_error names the key's index.  The records go to the device once per chunk (a launch covers at most 2^22
+ *                  pairs and 2^20 records); from 65 536 lanes per launch on, one lane answers a group of 2, 4 or 8 keys and shares among them what depends on
+ *                  the record alone (csrc/records_many_lane.h; the widest group W that leaves the launch 65 536 lanes, with W / 2 < n_keys), below that one key per lane.
+ *                  ALEO_MI355X_SCAN_KEYS_PER_LANE (1, 2, 4, 8; unset, 0 or anything else = that rule), read per call, forces the group's width; the bytes do not
+ *                  depend on it.  A call with n * n_keys below min_records runs on the host.  Thread-safe (one slot per call).
+ *   records_scan_many_host   the same bytes out from n_keys passes of the host path; touches no device. */
+int32_t aleo_mi355x_records_scan_many(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys);
+int32_t aleo_mi355x_records_scan_many_host(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys);
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */
 const char* aleo_mi355x_version(void);

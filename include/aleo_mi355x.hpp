@@ -11,7 +11,7 @@
 //   snarkvm_synthesizer_snark::ProvingKey::prove_batch / snarkvm_algorithms::snark::varuna::{CircuitProvingKey, Proof}: a proving key bound
 //       to one circuit, `prove_batch(&[assignment])` -> Proof, Proof Display as bech32m `proof1…`; `prove_batch(keys -> assignments)` over several
 //       keys and `Trace::prove_execution / prove_fee` above it (rows a6 / a7 of SURVEY.md §8)
-//   snarkvm_console_program::Record<N, Ciphertext<N>>::{from_str, is_owner} and the record search around it (RecordCiphertext, find_owned)
+//   snarkvm_console_program::Record<N, Ciphertext<N>>::{from_str, is_owner} and the record search around it (RecordCiphertext, find_owned, find_owned_many)
 // Layouts are snarkVM's: Fr = 4 x u64 Montgomery, scalar = 4 x u64 canonical, G1Affine = 104 bytes, Projective = 144 bytes.
 #pragma once
 #include <chrono>
@@ -507,6 +507,29 @@ inline Result<std::vector<OwnedRecord>> find_owned(const std::vector<RecordCiphe
     if (!batch[i].owner_is_private()) { if (!std::memcmp(batch[i].owner_field(), address.x, 32)) out.push_back(OwnedRecord{i, false, {}}); continue; }
     if (flags[j] == 1) { OwnedRecord o{i, true, {}}; std::memcpy(o.record_view_key_x, rvk.data() + 32 * j, 32); out.push_back(o); }
     ++j;
+  }
+  return {std::move(out), Error{0}};
+}
+
+// find_owned for several accounts over the same batch: one aleo_mi355x_records_scan_many call (at most 64 accounts) instead of one scan per account.
+// (*result)[a] is what find_owned returns for accounts[a].
+struct Account { ViewKey view_key; Address address; };
+inline Result<std::vector<std::vector<OwnedRecord>>> find_owned_many(const std::vector<RecordCiphertext>& batch, const std::vector<Account>& accounts) {
+  std::vector<uint8_t> c0, nx, vks, axs; std::vector<size_t> at;
+  for (size_t i = 0; i < batch.size(); ++i)
+    if (batch[i].owner_is_private()) { c0.insert(c0.end(), batch[i].owner_field(), batch[i].owner_field() + 32); nx.insert(nx.end(), batch[i].nonce_x(), batch[i].nonce_x() + 32); at.push_back(i); }
+  for (const auto& a : accounts) { vks.insert(vks.end(), a.view_key.scalar, a.view_key.scalar + 32); axs.insert(axs.end(), a.address.x, a.address.x + 32); }
+  const size_t n = at.size(), k = accounts.size();
+  std::vector<uint8_t> flags(k * n), rvk(32 * k * n);
+  if (n && k) { int32_t rc = aleo_mi355x_records_scan_many(flags.data(), rvk.data(), c0.data(), nx.data(), n, vks.data(), axs.data(), k); if (rc) return {std::nullopt, Error{rc}}; }
+  std::vector<std::vector<OwnedRecord>> out(k);
+  for (size_t a = 0; a < k; ++a) {
+    size_t j = 0;
+    for (size_t i = 0; i < batch.size(); ++i) {
+      if (!batch[i].owner_is_private()) { if (!std::memcmp(batch[i].owner_field(), accounts[a].address.x, 32)) out[a].push_back(OwnedRecord{i, false, {}}); continue; }
+      if (flags[a * n + j] == 1) { OwnedRecord o{i, true, {}}; std::memcpy(o.record_view_key_x, rvk.data() + 32 * (a * n + j), 32); out[a].push_back(o); }
+      ++j;
+    }
   }
   return {std::move(out), Error{0}};
 }

@@ -11,8 +11,16 @@ every shape is warmed up once; a figure is the median of at least three calls an
 Up to 2^--host-lg records the one-thread host path is TIMED at every size (so a call's fixed costs — ctypes, the recoding of the key — are in the crossover);
 above it, and for 16 threads everywhere, the host time is the measured rate times n, and the table says so.
 
-  python tools/records_scan_bench.py [--max-lg 22] [--out profiles/records_scan.txt]"""
-import argparse, os, statistics, sys, time
+  python tools/records_scan_bench.py [--max-lg 22] [--out profiles/records_scan.txt]
+
+With --keys the tool measures the grouped scan instead (aleo_mi355x_records_scan_many: K accounts over the same records in one call) against what it replaces,
+K calls of aleo_mi355x_records_scan over those records — made through --baseline-lib when given (another build of the library, for instance the parent
+commit's), else through this build, whose single-key kernel is the same code.  Shapes are lg n:K pairs; at each shape the baseline, the library's own rule and
+every forced width (ALEO_MI355X_SCAN_KEYS_PER_LANE = 1, 2, 4, 8) are warmed up once and then timed in turn, round after round, so that whatever else the
+machine does falls on all of them alike; output buffers are allocated once, outside the timed calls.  A figure is the median over the rounds, with min..max.
+
+  python tools/records_scan_bench.py --keys [--shapes 20:8,20:3,18:8,16:16,12:8] [--rounds 7] [--baseline-lib PATH] [--out profiles/records_scan_many.txt]"""
+import argparse, ctypes, os, statistics, sys, time
 from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
@@ -53,12 +61,77 @@ def timed(f, min_time=0.5, min_reps=3):
     return statistics.median(ts), min(ts), max(ts), len(ts)
 
 
+def many_keys(k, seed=23):
+    """k different accounts: view keys below the subgroup order, any canonical field element as address x (the scan's time does not depend on it)"""
+    rng = np.random.default_rng(seed)
+    vks = [int.from_bytes(rng.bytes(31), 'little') % ps.ED_SUBGROUP_ORDER for _ in range(k)]
+    to_rows = lambda vals: np.frombuffer(b''.join(int(v).to_bytes(32, 'little') for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+    return to_rows(vks), to_rows([int.from_bytes(rng.bytes(31), 'little') for _ in range(k)])
+
+
+def bench_many(a):
+    L = aleo_amd.lib(); aleo_amd._lib.check(L.aleo_mi355x_init_device(-1), 'init')      # no GPU, no numbers
+    base = L
+    if a.baseline_lib:
+        base = ctypes.CDLL(os.path.abspath(a.baseline_lib))
+        for name in ('aleo_mi355x_records_scan', 'aleo_mi355x_init_device'): getattr(base, name).restype = ctypes.c_int32
+        base.aleo_mi355x_records_scan.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2
+        base.aleo_mi355x_init_device.argtypes = [ctypes.c_int32]
+        base.aleo_mi355x_version.restype = ctypes.c_char_p
+        assert base.aleo_mi355x_init_device(-1) == 0
+    shapes = [tuple(int(v) for v in s.split(':')) for s in a.shapes.split(',')]
+    c0, nx, _, _ = make_records(1 << max(lg for lg, _ in shapes))
+    p = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    configs = ['K single scans', 'rule', 'W=1', 'W=2', 'W=4', 'W=8']
+    lines = ['records_scan_bench --keys: aleo_mi355x_records_scan_many (K accounts, n records, one call; host buffers, upload and download inside the timed call) against',
+             'K calls of aleo_mi355x_records_scan over the same records (%s).  ms per call: median (min..max) over %d rounds, the configurations timed in turn within a round;'
+             % ('baseline library: %s' % base.aleo_mi355x_version().decode() if a.baseline_lib else 'this build', a.rounds),
+             'x = the baseline\'s median over the configuration\'s.  W = keys per lane forced by ALEO_MI355X_SCAN_KEYS_PER_LANE; rule = unset.', '%s' % L.aleo_mi355x_version().decode(), '']
+    for lg, k in shapes:
+        n = 1 << lg
+        vk, ax = many_keys(k)
+        C0, NX = c0[:n], nx[:n]
+        flags = np.zeros((k, n), dtype=np.uint8); rvk = np.zeros((k, n, 32), dtype=np.uint8)
+        bflags = np.ones((k, n), dtype=np.uint8); brvk = np.ones((k, n, 32), dtype=np.uint8)
+        def run(cfg):
+            if cfg == 'K single scans':
+                for j in range(k): assert base.aleo_mi355x_records_scan(p(bflags[j]), p(brvk[j]), p(C0), p(NX), n, p(vk[j]), p(ax[j])) == 0
+                return
+            if cfg == 'rule': os.environ.pop('ALEO_MI355X_SCAN_KEYS_PER_LANE', None)
+            else: os.environ['ALEO_MI355X_SCAN_KEYS_PER_LANE'] = cfg[2:]
+            aleo_amd._lib.check(L.aleo_mi355x_records_scan_many(p(flags), p(rvk), p(C0), p(NX), n, p(vk), p(ax), k), 'records_scan_many')
+        run(configs[0])
+        for cfg in configs[1:]:                              # warm-up of every shape and width, and the parity of what is about to be timed
+            flags[:] = 7; run(cfg)
+            assert flags.tobytes() == bflags.tobytes() and rvk.tobytes() == brvk.tobytes(), 'records_scan_many (%s) and K single scans disagree at n = 2^%d, K = %d' % (cfg, lg, k)
+        ts = {cfg: [] for cfg in configs}
+        for _ in range(a.rounds):
+            for cfg in configs:
+                t0 = time.perf_counter(); run(cfg); ts[cfg].append(time.perf_counter() - t0)
+        os.environ.pop('ALEO_MI355X_SCAN_KEYS_PER_LANE', None)
+        b = statistics.median(ts[configs[0]])
+        lines.append('n = 2^%d, K = %d  (%d pairs)' % (lg, k, n * k))
+        for cfg in configs:
+            m = statistics.median(ts[cfg])
+            lines.append('  %-15s %10.3f  (%.3f..%.3f)  %6.2fx  %8.2f M pairs/s' % (cfg, m * 1e3, min(ts[cfg]) * 1e3, max(ts[cfg]) * 1e3, b / m, n * k / m / 1e6))
+        lines.append('  spread of the baseline: %.1f %% of its median' % ((max(ts[configs[0]]) - min(ts[configs[0]])) / b * 100))
+        print('\n'.join(lines[-len(configs) - 2:]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    open(a.out, 'w').write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--keys', action='store_true', help='measure the grouped scan (records_scan_many) against K single scans')
+    ap.add_argument('--shapes', default='20:8,20:3,18:8,16:16,12:8', help='with --keys: lg n:K pairs')
+    ap.add_argument('--rounds', type=int, default=7); ap.add_argument('--baseline-lib', default=None, help='with --keys: the library that makes the K single scans')
     ap.add_argument('--min-lg', type=int, default=2); ap.add_argument('--max-lg', type=int, default=22)
     ap.add_argument('--host-lg', type=int, default=12, help='size of the one-thread host measurement (its rate does not depend on the size)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'records_scan.txt'))
     a = ap.parse_args()
+    if a.keys:
+        if a.out == ap.get_default('out'): a.out = os.path.join(ROOT, 'profiles', 'records_scan_many.txt')
+        return bench_many(a)
     L = aleo_amd.lib(); aleo_amd._lib.check(L.aleo_mi355x_init_device(-1), 'init')      # no GPU, no numbers
     c0, nx, vk, ax = make_records(1 << a.max_lg)
     lines = ['records_scan_bench: records/s of the ownership scan; gpu = aleo_mi355x_records_scan on host buffers (upload and download inside the call), '
