@@ -25,11 +25,18 @@ EXPORTS = [
     'aleo_mi355x_bases_sharded_info', 'aleo_mi355x_msm_g1_sharded', 'aleo_mi355x_fr_transpose_device', 'aleo_mi355x_ntt_fr_sharded', 'aleo_mi355x_ntt_fr_sharded_device', 'aleo_mi355x_selftest_host_inverse', 'aleo_mi355x_varuna_prove_many',
     'aleo_mi355x_record_parse', 'aleo_mi355x_records_scan', 'aleo_mi355x_records_scan_host', 'aleo_mi355x_min_records',
     'aleo_mi355x_records_scan_many', 'aleo_mi355x_records_scan_many_host',
+    'aleo_mi355x_records_decrypt_fields', 'aleo_mi355x_records_decrypt_fields_host', 'aleo_mi355x_min_decrypt',
+    'aleo_mi355x_record_fields', 'aleo_mi355x_record_plaintext', 'aleo_mi355x_record_decrypt',
 ]
 
 
 class AleoMi355xError(RuntimeError):
     status = None
+
+
+class NotOwner(AleoMi355xError):
+    """ALEO_MI355X_ERR_NOT_OWNER: a record's decrypted (or public) owner is not the given address."""
+    status = 7
 
 
 class UnsatisfiedAssignment(AleoMi355xError):
@@ -164,6 +171,12 @@ def lib():
         'aleo_mi355x_min_records': ([], sz),
         'aleo_mi355x_records_scan_many': ([vp, vp, vp, vp, sz, vp, vp, sz], i32),
         'aleo_mi355x_records_scan_many_host': ([vp, vp, vp, vp, sz, vp, vp, sz], i32),
+        'aleo_mi355x_records_decrypt_fields': ([vp, vp, vp, vp, vp, sz], i32),
+        'aleo_mi355x_records_decrypt_fields_host': ([vp, vp, vp, vp, vp, sz], i32),
+        'aleo_mi355x_min_decrypt': ([], sz),
+        'aleo_mi355x_record_fields': ([ctypes.c_char_p, vp, sz, ctypes.POINTER(sz)], i32),
+        'aleo_mi355x_record_plaintext': ([ctypes.c_char_p, vp, sz, vp, ctypes.c_char_p, ctypes.POINTER(sz)], i32),
+        'aleo_mi355x_record_decrypt': ([ctypes.c_char_p, vp, vp, ctypes.c_char_p, ctypes.POINTER(sz)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name); f.argtypes = args; f.restype = res
@@ -174,7 +187,7 @@ def lib():
 def check(status: int, what: str):
     if status != 0:
         L = lib()
-        e = (UnsatisfiedAssignment if status == UnsatisfiedAssignment.status else AleoMi355xError)(
+        e = {UnsatisfiedAssignment.status: UnsatisfiedAssignment, NotOwner.status: NotOwner}.get(status, AleoMi355xError)(
             f'{what}: {L.aleo_mi355x_strerror(status).decode()} [{L.aleo_mi355x_last_error().decode()}]')
         e.status = status
         raise e

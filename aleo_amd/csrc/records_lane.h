@@ -108,10 +108,11 @@ template <bool LAST> __device__ __forceinline__ void psd_full(F29 (&s)[9], const
 #pragma unroll
   for (int i = 0; i < 9; ++i) s[i] = o[i];
 }
-// The permutation of poseidon.hpp (poseidon_permute<4, 8>), of which only element 1 of the result is kept
-__device__ __forceinline__ F29 psd_permute_take1(F29 (&s)[9], const uint32_t* __restrict__ K) {
+// The permutation of poseidon.hpp (poseidon_permute<4, 8>).  ALL: every element of the result is kept, tidied — the state a sponge goes on from — and the last
+// round is one more turn of the second half's loop; otherwise it is written out and computes element 1 alone
+template <bool ALL> __device__ __forceinline__ void psd_permute_rounds(F29 (&s)[9], const uint32_t* __restrict__ K) {
   for (int half = 0; half < 2; ++half) {
-    const int rounds = half == 0 ? 4 : 3;
+    const int rounds = half == 0 || ALL ? 4 : 3;
     for (int r = 0; r < rounds; ++r) {
       const uint32_t ark = half == 0 ? RK_ARK_HEAD + 9 * r : (r == 0 ? (uint32_t)RK_ARK_AFTER : RK_ARK_TAIL + 9 * (r - 1));
       psd_full<false>(s, K, ark, half == 0 && r == 3 ? (uint32_t)RK_PRE : (uint32_t)RK_MDS);
@@ -129,9 +130,12 @@ __device__ __forceinline__ F29 psd_permute_take1(F29 (&s)[9], const uint32_t* __
         s[0] = s0;
       }
   }
-  psd_full<true>(s, K, RK_ARK_TAIL + 18, RK_MDS);
-  return s[1];
+  if constexpr (!ALL) psd_full<true>(s, K, RK_ARK_TAIL + 18, RK_MDS);
 }
+// ... of which only element 1 of the result is kept (the scan: one randomizer)
+__device__ __forceinline__ F29 psd_permute_take1(F29 (&s)[9], const uint32_t* __restrict__ K) { psd_permute_rounds<false>(s, K); return s[1]; }
+// ... and the whole of it (records_decrypt_lane.h: eight randomizers per permutation)
+__device__ __forceinline__ void psd_permute(F29 (&s)[9], const uint32_t* __restrict__ K) { psd_permute_rounds<true>(s, K); }
 
 // One record.  c0w / nxw: the canonical little-endian words of the owner ciphertext's field and of the nonce x.  Returns the flag (0 not owner, 1 owner,
 // 2 malformed).  `emit` is handed the canonical limbs of the record view key's x (zeros with flag 2) between the scalar multiplication and the hash,

@@ -3,11 +3,14 @@ loop around `record.is_owner_with_address_x_coordinate` in rust/src/api/blocking
 (aleo_mi355x_record_parse, aleo_mi355x_records_scan: csrc/wire.hip, csrc/records.hip).  View keys (base58, "AViewKey1…") and addresses (bech32m,
 "aleo1…") are decoded here; the address of a view key is NOT derived (that needs upstream's hash-to-curve generator), so callers pass both, as the
 reference's call sites do.  scan_many / find_owned_many ask for several accounts over the same records in one call (aleo_mi355x_records_scan_many:
-csrc/records_many.hip), as a front end does that runs the search for several callers (rust/develop/src/routes.rs:112, :143, :194-220 of the reference)."""
+csrc/records_many.hip), as a front end does that runs the search for several callers (rust/develop/src/routes.rs:112, :143, :194-220 of the reference).
+What the reference does with an owned record next — `record.decrypt(&view_key)`, `microcredits()` (rust/src/api/blocking.rs:274-283; RecordCiphertext.decrypt
+of the wasm) — is RecordCiphertext.decrypt, decrypt_fields and decrypt_owned here (aleo_mi355x_record_decrypt, aleo_mi355x_records_decrypt_fields,
+aleo_mi355x_record_fields, aleo_mi355x_record_plaintext: csrc/records_decrypt.hip), down to RecordPlaintext strings."""
 from __future__ import annotations
 import ctypes
 import numpy as np
-from ._lib import lib, check, AleoMi355xError
+from ._lib import lib, check, AleoMi355xError, NotOwner      # noqa: F401
 from . import wire
 
 _B58 = '123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz'
@@ -87,6 +90,126 @@ class RecordCiphertext:
         if self.owner_kind == OWNER_PUBLIC: return self.owner == address_x_bytes(address)
         flags, _ = scan(np.frombuffer(self.owner, dtype=np.uint8), np.frombuffer(self.nonce, dtype=np.uint8), view_key, address, want_rvk=False)
         return int(flags[0]) == 1
+
+    def fields(self) -> np.ndarray:
+        """The record's private fields in randomizer order (uint8[m, 32]): the owner's if it is private, then every private entry's."""
+        n = ctypes.c_size_t(0)
+        check(lib().aleo_mi355x_record_fields(self.string.encode(), None, 0, ctypes.byref(n)), 'record_fields')
+        out = np.zeros((n.value, 32), dtype=np.uint8)
+        if n.value: check(lib().aleo_mi355x_record_fields(self.string.encode(), _p(out), n.value, ctypes.byref(n)), 'record_fields')
+        return out
+
+    def plaintext(self, plain_fields: np.ndarray, address=None) -> 'RecordPlaintext':
+        """The RecordPlaintext of this record from its decrypted fields (aleo_mi355x_record_plaintext); with an address, NotOwner unless the owner is it."""
+        f = np.ascontiguousarray(plain_fields, dtype=np.uint8).reshape(-1, 32)
+        ax = np.frombuffer(address_x_bytes(address), dtype=np.uint8) if address is not None else None
+        return RecordPlaintext(_string_out(lambda buf, ln: lib().aleo_mi355x_record_plaintext(self.string.encode(), _p(f), f.shape[0], _p(ax) if ax is not None else None, buf, ln), 'record_plaintext'))
+
+    def decrypt(self, view_key, address) -> 'RecordPlaintext':
+        """RecordCiphertext.decrypt(viewKey), on the host (aleo_mi355x_record_decrypt): NotOwner when the view key does not decrypt the owner to the address."""
+        vk = np.frombuffer(view_key_bytes(view_key), dtype=np.uint8); ax = np.frombuffer(address_x_bytes(address), dtype=np.uint8)
+        return RecordPlaintext(_string_out(lambda buf, ln: lib().aleo_mi355x_record_decrypt(self.string.encode(), _p(vk), _p(ax), buf, ln), 'record_decrypt'))
+
+
+def _string_out(call, what: str) -> str:
+    """A string through the (out, in/out length) convention of the C ABI: a first try with room for most records, a second with the length the first returned."""
+    cap = 4096
+    for _ in range(2):
+        buf = ctypes.create_string_buffer(cap); ln = ctypes.c_size_t(cap)
+        rc = call(buf, ctypes.byref(ln))
+        if rc == 0: return buf.value.decode()
+        if rc != 2 or ln.value < cap: break
+        cap = ln.value + 1
+    check(rc, what)
+
+
+class RecordPlaintext:
+    """A decrypted record: its string as the reference prints it, the owner's address, the nonce's x, and the entries by name — a literal as its text with the
+    visibility ("1500000000000000u64.private"), a struct as a dict of the same."""
+
+    def __init__(self, string: str):
+        self.string = string
+        body, at = _parse_plaintext(string, 0)
+        if not isinstance(body, dict) or string[at:].strip() or 'owner' not in body or '_nonce' not in body: raise ValueError('not a record plaintext')
+        self.owner, self.owner_visibility = body.pop('owner').rsplit('.', 1)
+        nonce = body.pop('_nonce')
+        if not nonce.endswith('group.public'): raise ValueError('not a record plaintext')
+        self.nonce = int(nonce[:-len('group.public')])
+        self.entries = body
+
+    def __str__(self): return self.string
+    def __repr__(self): return 'RecordPlaintext(%r)' % self.string
+    def __eq__(self, other): return isinstance(other, RecordPlaintext) and other.string == self.string
+    def __hash__(self): return hash(self.string)
+
+    def microcredits(self) -> int:
+        """The value of a u64 entry named microcredits, else 0 (RecordPlaintext.microcredits of the wasm)."""
+        v = self.entries.get('microcredits')
+        if not isinstance(v, str): return 0
+        lit = v.rsplit('.', 1)[0]
+        return int(lit[:-3]) if lit.endswith('u64') and lit[:-3].isdigit() else 0
+
+
+def _parse_plaintext(s: str, at: int):
+    """One value of a plaintext string from position `at`: ('{' name: value, ... '}') -> dict, anything else -> the literal's text.  Returns (value, next position)."""
+    while s[at] in ' \n': at += 1
+    if s[at] != '{':
+        start = at; quoted = False
+        while at < len(s) and (quoted or s[at] not in ',\n}'):
+            if s[at] == '"': quoted = not quoted
+            at += 1
+        return s[start:at].strip(), at
+    out = {}; at += 1
+    while True:
+        while s[at] in ' \n,': at += 1
+        if s[at] == '}': return out, at + 1
+        colon = s.index(':', at)
+        name = s[at:colon].strip()
+        out[name], at = _parse_plaintext(s, colon + 1)
+
+
+def decrypt_fields(rvk: np.ndarray, offsets, fields: np.ndarray, host: bool = False):
+    """The plain fields (uint8[total, 32]) and the flags (uint8[n]: 0 decrypted, 2 malformed, its rows zeros) of n records: record i has the record view key x
+    rvk[i] and the private fields fields[offsets[i]:offsets[i + 1]] in randomizer order.  host=True computes on the CPU (aleo_mi355x_records_decrypt_fields_host),
+    else the library routes; the bytes are the same."""
+    rv = np.ascontiguousarray(rvk, dtype=np.uint8).reshape(-1, 32); f = np.ascontiguousarray(fields, dtype=np.uint8).reshape(-1, 32)
+    off = np.ascontiguousarray(offsets, dtype=np.uint32)
+    n = rv.shape[0]
+    if off.shape != (n + 1,): raise ValueError('offsets must hold one entry more than there are records')
+    if n and int(off.max()) > f.shape[0]: raise ValueError('offsets reach past the fields')
+    plain = np.zeros_like(f); flags = np.zeros(n, dtype=np.uint8)
+    fn = lib().aleo_mi355x_records_decrypt_fields_host if host else lib().aleo_mi355x_records_decrypt_fields
+    check(fn(_p(plain), _p(flags), _p(rv), _p(off), _p(f), n), 'records_decrypt_fields')
+    return plain, flags
+
+
+def decrypt_owned(ciphertexts, view_key, address):
+    """[(index, RecordPlaintext)] of the records the account owns: the batch form of the reference's `if record.is_owner(..) { record.decrypt(..) }` loop.
+    Every string is parsed once; one scan says which private owners are the account and hands back their record view keys, one decrypt_fields call decrypts the
+    fields of all owned records, and the strings are put together on the host.  A record with a public owner equal to the address is included (its owner needs
+    no hash; its private entries, if any, do).  An owned record whose decrypted entries do not parse raises."""
+    recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
+    ax = address_x_bytes(address)
+    fields = {i: r.fields() for i, r in enumerate(recs) if r.owner_kind == OWNER_PUBLIC and r.owner == ax}      # public owners that match: usually no private field
+    scanned = [i for i, r in enumerate(recs) if r.owner_kind == OWNER_PRIVATE or (i in fields and len(fields[i]))]
+    rvks = {}
+    if scanned:
+        c0 = np.frombuffer(b''.join(recs[i].owner for i in scanned), dtype=np.uint8).reshape(-1, 32)
+        nx = np.frombuffer(b''.join(recs[i].nonce for i in scanned), dtype=np.uint8).reshape(-1, 32)
+        flags, rvk = scan(c0, nx, view_key, ax)
+        for j, i in enumerate(scanned):
+            if i in fields:
+                if flags[j] == 2: raise AleoMi355xError('decrypt_owned: record %d has a nonce that is not on the curve' % i)
+                rvks[i] = rvk[j]
+            elif flags[j] == 1: rvks[i] = rvk[j]; fields[i] = recs[i].fields()
+    idx = sorted(fields)
+    offsets = np.zeros(len(idx) + 1, dtype=np.uint32)
+    if idx: offsets[1:] = np.cumsum([len(fields[i]) for i in idx])
+    flat = np.concatenate([fields[i] for i in idx]) if idx else np.zeros((0, 32), dtype=np.uint8)
+    zero = np.zeros(32, dtype=np.uint8)
+    plain, flags = decrypt_fields(np.stack([rvks.get(i, zero) for i in idx]) if idx else np.zeros((0, 32), dtype=np.uint8), offsets, flat)
+    if (flags != 0).any(): raise AleoMi355xError('decrypt_owned: record %d is malformed' % idx[int(np.nonzero(flags)[0][0])])
+    return [(i, recs[i].plaintext(plain[offsets[k]:offsets[k + 1]], ax)) for k, i in enumerate(idx)]
 
 
 def find_owned(ciphertexts, view_key, address):

@@ -57,6 +57,7 @@ extern "C" {
 #define ALEO_MI355X_ERR_BAD_HANDLE 4
 #define ALEO_MI355X_ERR_OOM 5
 #define ALEO_MI355X_ERR_UNSATISFIED 6  /* varuna_prove*: an assignment does not satisfy its circuit (upstream: the synthesiser's is_satisfied check) */
+#define ALEO_MI355X_ERR_NOT_OWNER 7    /* record_plaintext, record_decrypt: the decrypted (or public) owner is not the given address (upstream: "Decryption failed - view key did not match record") */
 
 /* NTT enums: mirror snarkvm_algorithms_cuda::{NTTInputOutputOrder, NTTDirection, NTTType} */
 #define ALEO_NTT_ORDER_NN 0   /* natural in, natural out (what fft_in_place exposes) */
@@ -545,6 +546,48 @@ size_t aleo_mi355x_min_records(void);
  *   records_scan_many_host   the same bytes out from n_keys passes of the host path; touches no device. */
 int32_t aleo_mi355x_records_scan_many(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys);
 int32_t aleo_mi355x_records_scan_many_host(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys);
+/* Decrypting the records an account owns: what the reference does next with every record the search finds — `record.decrypt(&view_key)` and the sum of
+ * `microcredits()` (rust/src/api/blocking.rs:274-283), RecordCiphertext.decrypt(viewKey) -> RecordPlaintext (wasm/src/record/record_ciphertext.rs:48-57).
+ * snarkVM 0.14.5 console/program/src/data/record/decrypt.rs, ciphertext/decrypt.rs [UPSTREAM-RECALL], pinned by the reference's own ciphertext and plaintext
+ * strings (tests/golden/reference_records.json) as far as they reach: a private owner, a private u64 entry, a public group nonce.
+ *   The private fields of a record, in randomizer order: the owner's one field if the owner is private, then the fields of every private entry in entry order
+ *   (m in all); randomizers = hash_many_psd8([domain "AleoSymmetricEncryption0", rvk], m), plain_i = c_i - randomizers_i, rvk the record view key's x that
+ *   records_scan returns.  The owner's plain field is the address x; an entry's plain fields are one Plaintext in bits (252 per field).
+ *   records_decrypt_fields   n records, all buffers on the host: rvk n x 32 B canonical; offsets n + 1 entries, offsets[0] = 0, nondecreasing (record i has the
+ *                  fields offsets[i] .. offsets[i + 1], at most 65 535 of them); fields offsets[n] x 32 B canonical.  plain_out (offsets[n] x 32 B, not the
+ *                  `fields` buffer): the plain fields, canonical; flags[i] = 0 decrypted, 2 malformed (rvk or one of the record's fields not below r: its rows
+ *                  are zeros, its neighbours are not affected).  Offsets that decrease or do not start at 0, or a record of more than 65 535 fields, refuse
+ *                  the call before any launch.  Returns byte for byte what records_decrypt_fields_host returns.  One record per lane; a launch covers at most
+ *                  2^20 records and 2^22 fields, cut at record boundaries (ALEO_MI355X_DECRYPT_CHUNK_FIELDS, read per call, lowers the field cap: for tests;
+ *                  the bytes do not depend on it).  Thread-safe (one slot per call); n = 0 and records without fields are fine.
+ *   records_decrypt_fields_host   the same bytes, computed on the CPU by the calling thread; touches no device.
+ *   min_decrypt    the size, counted in permutations (the sum of ceil(m / 8) over the records), from which records_decrypt_fields takes the GPU; a call
+ *                  below it runs on the calling thread.  The default, 64, is NOT a measured crossover: no GPU run could be made when this was written (profiles/records_decrypt.txt says what is missing); it is the
+ *                  crossover measured for the scan (min_records), whose small calls have the same shape, one wave running one dependent chain. ALEO_MI355X_MIN_DECRYPT overrides it, read per call.
+ *   record_fields  host: the private fields of a "record1..." string in randomizer order, 32 B each, into fields_out (room for `cap` fields); *n_fields_out = their
+ *                  number.  fields_out = NULL only counts.  Refuses whatever record_parse refuses, an entry without a known visibility, a private entry
+ *                  whose length is not that of its field count or whose fields are not canonical.
+ *   record_plaintext   host: puts n_fields decrypted fields (the record's own count) back into the record's structure and writes the RecordPlaintext string
+ *                  "{\n  owner: aleo1....private,\n  <name>: <value>.<visibility>,\n  ...  _nonce: <decimal>group.public\n}".  address_x32 (may be NULL): the
+ *                  owner, decrypted or public, must be it, else ERR_NOT_OWNER.  *out_len: in = the capacity of out, out = the string's length (without the
+ *                  terminating 0, which is written as well): a buffer that is too short returns BAD_ARG with the length in place.  An entry that does not
+ *                  parse is BAD_ARG, and last_error names it.  Literals by type number: 0 address (253 bits, bech32m), 1 boolean, 2 field, 3 group (253 bits,
+ *                  decimal x), 4-8 i8..i128 (two's complement), 9-13 u8..u128, 14 scalar (251 bits), 15 string (quoted), each followed by its type's suffix
+ *                  and the entry's visibility; a size that does not fit the type, a value not below the modulus and an unknown type are refused.  Types 0, 2
+ *                  and 12 are pinned by reference-held vectors, the others are [UPSTREAM-RECALL].  Struct entries (one member per line, two spaces deeper per
+ *                  level, the closing brace at the entry's own indentation) and the byte layout of public and constant entries (u8 variant; literal: u16 type,
+ *                  little-endian value bytes, a string with a u16 length; struct: u8 member count, per member u8 name length, name, u16 length, plaintext)
+ *                  are [UPSTREAM-RECALL] too, and UNPINNED: nothing the reference holds shows one.
+ *   record_decrypt   the one-record mirror of RecordCiphertext.decrypt, entirely on the host: rvk from the host scan, the fields from the host path above, then
+ *                  record_plaintext.  The address is passed in, not derived from the view key; a public owner is compared with it; ERR_NOT_OWNER when the view
+ *                  key does not decrypt the owner to it.  A record with no private field needs no hash (and view_key32 may be NULL). */
+int32_t aleo_mi355x_records_decrypt_fields(void* plain_out, uint8_t* flags, const void* rvk, const uint32_t* offsets, const void* fields, size_t n);
+int32_t aleo_mi355x_records_decrypt_fields_host(void* plain_out, uint8_t* flags, const void* rvk, const uint32_t* offsets, const void* fields, size_t n);
+size_t aleo_mi355x_min_decrypt(void);
+int32_t aleo_mi355x_record_fields(const char* record1, void* fields_out, size_t cap, size_t* n_fields_out);
+int32_t aleo_mi355x_record_plaintext(const char* record1, const void* plain_fields, size_t n_fields, const void* address_x32, char* out, size_t* out_len);
+int32_t aleo_mi355x_record_decrypt(const char* record1, const void* view_key32, const void* address_x32, char* out, size_t* out_len);
+
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */
 const char* aleo_mi355x_version(void);

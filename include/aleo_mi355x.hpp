@@ -11,7 +11,8 @@
 //   snarkvm_synthesizer_snark::ProvingKey::prove_batch / snarkvm_algorithms::snark::varuna::{CircuitProvingKey, Proof}: a proving key bound
 //       to one circuit, `prove_batch(&[assignment])` -> Proof, Proof Display as bech32m `proof1…`; `prove_batch(keys -> assignments)` over several
 //       keys and `Trace::prove_execution / prove_fee` above it (rows a6 / a7 of SURVEY.md §8)
-//   snarkvm_console_program::Record<N, Ciphertext<N>>::{from_str, is_owner} and the record search around it (RecordCiphertext, find_owned, find_owned_many)
+//   snarkvm_console_program::Record<N, Ciphertext<N>>::{from_str, is_owner, decrypt} and the record search around it (RecordCiphertext, RecordPlaintext,
+//   find_owned, find_owned_many, decrypt_owned)
 // Layouts are snarkVM's: Fr = 4 x u64 Montgomery, scalar = 4 x u64 canonical, G1Affine = 104 bytes, Projective = 144 bytes.
 #pragma once
 #include <chrono>
@@ -43,6 +44,7 @@ struct Error {
   int32_t code;
   std::string message() const { return std::string(aleo_mi355x_strerror(code)) + " [" + aleo_mi355x_last_error() + "]"; }
   bool unsatisfied() const { return code == ALEO_MI355X_ERR_UNSATISFIED; }      // a prover refused an assignment that violates its circuit
+  bool not_owner() const { return code == ALEO_MI355X_ERR_NOT_OWNER; }          // a record's owner is not the given address (upstream: "view key did not match record")
 };
 template <class T> struct Result {       // Ok(value) or Err(Error), like the Rust side sees it
   std::optional<T> value; Error error{0};
@@ -470,7 +472,32 @@ struct Address {
   }
 };
 
-// Record<N, Ciphertext<N>> as far as ownership goes: FromStr, is_owner (RecordCiphertext.isOwner of the reference's wasm), and the batch form.
+// Record<N, Plaintext<N>> as its string, the way the reference prints it ("{\n  owner: aleo1….private,\n  microcredits: 1500000000000000u64.private,\n  _nonce: …group.public\n}").
+class RecordPlaintext {
+ public:
+  explicit RecordPlaintext(std::string s) : string_(std::move(s)) {}
+  const std::string& to_string() const { return string_; }
+  // RecordPlaintext.microcredits of the reference's wasm: the value of a u64 entry of that name at the record's top level, else 0
+  uint64_t microcredits() const {
+    const std::string key = "\n  microcredits: ";
+    const size_t at = string_.find(key); if (at == std::string::npos) return 0;
+    size_t p = at + key.size(); uint64_t v = 0; bool digits = false;
+    while (p < string_.size() && string_[p] >= '0' && string_[p] <= '9') { v = v * 10 + (uint64_t)(string_[p++] - '0'); digits = true; }
+    return digits && string_.compare(p, 4, "u64.") == 0 ? v : 0;
+  }
+ private:
+  std::string string_;
+};
+// a string through the (out, in/out length) convention of the C ABI: a first try with room for most records, a second with the length the first returned
+template <class Call> inline Result<RecordPlaintext> record_string_out(Call&& call) {
+  std::string buf(4096, '\0'); size_t len = buf.size();
+  int32_t rc = call(&buf[0], &len);
+  if (rc == ALEO_MI355X_ERR_BAD_ARG && len >= buf.size()) { buf.assign(len + 1, '\0'); len = buf.size(); rc = call(&buf[0], &len); }
+  if (rc) return {std::nullopt, Error{rc}};
+  buf.resize(len); return {RecordPlaintext(std::move(buf)), Error{0}};
+}
+
+// Record<N, Ciphertext<N>>: FromStr, is_owner and decrypt (RecordCiphertext.isOwner / .decrypt of the reference's wasm), and the batch forms below.
 class RecordCiphertext {
  public:
   static Result<RecordCiphertext> from_string(const std::string& s) {
@@ -488,6 +515,22 @@ class RecordCiphertext {
     uint8_t flag = 0; int32_t rc = aleo_mi355x_records_scan(&flag, nullptr, owner_, nonce_, 1, vk.scalar, address.x);
     if (rc) return {std::nullopt, Error{rc}};
     return {flag == 1, Error{0}};
+  }
+  // RecordCiphertext.decrypt(viewKey), on the host; ALEO_MI355X_ERR_NOT_OWNER when the view key does not decrypt the owner to the address
+  Result<RecordPlaintext> decrypt(const ViewKey& vk, const Address& address) const {
+    return record_string_out([&](char* out, size_t* len) { return aleo_mi355x_record_decrypt(string_.c_str(), vk.scalar, address.x, out, len); });
+  }
+  // the private fields in randomizer order, 32 bytes each: the owner's if it is private, then every private entry's
+  Result<std::vector<uint8_t>> fields() const {
+    size_t n = 0; int32_t rc = aleo_mi355x_record_fields(string_.c_str(), nullptr, 0, &n);
+    if (rc) return {std::nullopt, Error{rc}};
+    std::vector<uint8_t> f(32 * n);
+    if (n && (rc = aleo_mi355x_record_fields(string_.c_str(), f.data(), n, &n))) return {std::nullopt, Error{rc}};
+    return {std::move(f), Error{0}};
+  }
+  // the plaintext from this record's decrypted fields (records_decrypt_fields); the owner must be `address`
+  Result<RecordPlaintext> plaintext(const uint8_t* plain_fields, size_t n_fields, const Address& address) const {
+    return record_string_out([&](char* out, size_t* len) { return aleo_mi355x_record_plaintext(string_.c_str(), plain_fields, n_fields, address.x, out, len); });
   }
  private:
   std::string string_; bool private_owner_ = false; uint8_t owner_[32] = {}, nonce_[32] = {};
@@ -509,6 +552,50 @@ inline Result<std::vector<OwnedRecord>> find_owned(const std::vector<RecordCiphe
     ++j;
   }
   return {std::move(out), Error{0}};
+}
+
+// The records of `batch` the account owns, decrypted: the batch form of the reference's `if record.is_owner(..) { record.decrypt(..) }` loop
+// (rust/src/api/blocking.rs:274-283).  One scan for the private owners (and for the record view keys of matching public owners that hold private entries), one
+// aleo_mi355x_records_decrypt_fields call for the fields of all owned records, the strings on the host.  An owned record whose entries do not parse fails the call.
+struct DecryptedRecord { size_t index; RecordPlaintext plaintext; };
+inline Result<std::vector<DecryptedRecord>> decrypt_owned(const std::vector<RecordCiphertext>& batch, const ViewKey& vk, const Address& address) {
+  using Out = Result<std::vector<DecryptedRecord>>;
+  std::vector<std::vector<uint8_t>> fields(batch.size());
+  std::vector<uint8_t> c0, nx; std::vector<size_t> at;                // what goes through the scan
+  for (size_t i = 0; i < batch.size(); ++i) {
+    bool scan = batch[i].owner_is_private();
+    if (!scan && !std::memcmp(batch[i].owner_field(), address.x, 32)) { auto f = batch[i].fields(); if (!f.is_ok()) return Out{std::nullopt, f.error}; fields[i] = std::move(*f.value); scan = !fields[i].empty(); }
+    if (scan) { c0.insert(c0.end(), batch[i].owner_field(), batch[i].owner_field() + 32); nx.insert(nx.end(), batch[i].nonce_x(), batch[i].nonce_x() + 32); at.push_back(i); }
+  }
+  std::vector<uint8_t> flags(at.size()), rvk(32 * at.size());
+  if (!at.empty()) { int32_t rc = aleo_mi355x_records_scan(flags.data(), rvk.data(), c0.data(), nx.data(), at.size(), vk.scalar, address.x); if (rc) return Out{std::nullopt, Error{rc}}; }
+  std::vector<size_t> owned; std::vector<uint8_t> keys, flat; std::vector<uint32_t> offsets{0};
+  size_t j = 0;
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const bool scanned = j < at.size() && at[j] == i;
+    const bool is_public = !batch[i].owner_is_private();
+    bool mine = is_public && !std::memcmp(batch[i].owner_field(), address.x, 32);
+    uint8_t key[32] = {};
+    if (scanned) {
+      if (is_public && flags[j] == 2) return Out{std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+      if (is_public || flags[j] == 1) { std::memcpy(key, rvk.data() + 32 * j, 32); mine = true; }
+      if (!is_public && flags[j] == 1) { auto f = batch[i].fields(); if (!f.is_ok()) return Out{std::nullopt, f.error}; fields[i] = std::move(*f.value); }
+      ++j;
+    }
+    if (!mine) continue;
+    owned.push_back(i); keys.insert(keys.end(), key, key + 32); flat.insert(flat.end(), fields[i].begin(), fields[i].end());
+    offsets.push_back((uint32_t)(flat.size() / 32));
+  }
+  std::vector<uint8_t> plain(flat.size()), dflags(owned.size());
+  if (!owned.empty()) { int32_t rc = aleo_mi355x_records_decrypt_fields(plain.data(), dflags.data(), keys.data(), offsets.data(), flat.data(), owned.size()); if (rc) return Out{std::nullopt, Error{rc}}; }
+  std::vector<DecryptedRecord> out;
+  for (size_t k = 0; k < owned.size(); ++k) {
+    if (dflags[k]) return Out{std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+    auto p = batch[owned[k]].plaintext(plain.data() + 32 * (size_t)offsets[k], offsets[k + 1] - offsets[k], address);
+    if (!p.is_ok()) return Out{std::nullopt, p.error};
+    out.push_back(DecryptedRecord{owned[k], std::move(*p.value)});
+  }
+  return Out{std::move(out), Error{0}};
 }
 
 // find_owned for several accounts over the same batch: one aleo_mi355x_records_scan_many call (at most 64 accounts) instead of one scan per account.
