@@ -25,6 +25,7 @@ EXPORTS = [
     'aleo_mi355x_bases_sharded_info', 'aleo_mi355x_msm_g1_sharded', 'aleo_mi355x_fr_transpose_device', 'aleo_mi355x_ntt_fr_sharded', 'aleo_mi355x_ntt_fr_sharded_device', 'aleo_mi355x_selftest_host_inverse', 'aleo_mi355x_varuna_prove_many',
     'aleo_mi355x_record_parse', 'aleo_mi355x_records_scan', 'aleo_mi355x_records_scan_host', 'aleo_mi355x_min_records',
     'aleo_mi355x_records_scan_many', 'aleo_mi355x_records_scan_many_host',
+    'aleo_mi355x_records_parse_many', 'aleo_mi355x_records_parse_many_host', 'aleo_mi355x_records_scan_strings', 'aleo_mi355x_records_scan_strings_host',
     'aleo_mi355x_records_decrypt_fields', 'aleo_mi355x_records_decrypt_fields_host', 'aleo_mi355x_min_decrypt',
     'aleo_mi355x_record_fields', 'aleo_mi355x_record_plaintext', 'aleo_mi355x_record_decrypt',
 ]
@@ -171,6 +172,10 @@ def lib():
         'aleo_mi355x_min_records': ([], sz),
         'aleo_mi355x_records_scan_many': ([vp, vp, vp, vp, sz, vp, vp, sz], i32),
         'aleo_mi355x_records_scan_many_host': ([vp, vp, vp, vp, sz, vp, vp, sz], i32),
+        'aleo_mi355x_records_parse_many': ([vp, vp, vp, vp, vp, sz], i32),
+        'aleo_mi355x_records_parse_many_host': ([vp, vp, vp, vp, vp, sz], i32),
+        'aleo_mi355x_records_scan_strings': ([vp, vp, vp, vp, vp, sz, vp, vp, sz], i32),
+        'aleo_mi355x_records_scan_strings_host': ([vp, vp, vp, vp, vp, sz, vp, vp, sz], i32),
         'aleo_mi355x_records_decrypt_fields': ([vp, vp, vp, vp, vp, sz], i32),
         'aleo_mi355x_records_decrypt_fields_host': ([vp, vp, vp, vp, vp, sz], i32),
         'aleo_mi355x_min_decrypt': ([], sz),

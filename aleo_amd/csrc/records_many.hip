@@ -10,8 +10,7 @@
 // multiple of W) lies in device memory and is read through uniform loads.  W = 1 is records_scan_lane itself over the same grid.  Results are written
 // [key][record of the chunk] and copied to the caller's [key][record] rows.
 // A launch covers at most SCAN_MANY_PAIRS = 2^22 pairs and 2^20 records: 64 B per record and 33 B per pair keep the slot's grow-only scratch near 200 MB.
-#include "entry.h"
-#include "records_host.hpp"
+#include "records_strings.h"
 #include "records_many_lane.h"
 #include <cstdlib>
 #include <string>
@@ -24,10 +23,8 @@ static constexpr uint32_t SCAN_BLOCK = 256;
 static constexpr size_t SCAN_MANY_PAIRS = (size_t)1 << 22, SCAN_MANY_RECORDS = (size_t)1 << 20;
 static constexpr size_t SCAN_FULL_LANES = 65536;            // 256 CUs x 4 SIMDs x 64 lanes at one wave per SIMD: below it a call's time is one lane's chain, which a group makes ~W times longer
 
-struct ManyKeys { std::vector<ScanArgs> args; std::vector<HFr> addr; };
-
 // the per-call arguments of every key; a refused key is named by its index
-static int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32, size_t n_keys) {
+int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32, size_t n_keys) {
   if (n_keys < 1 || n_keys > SCAN_MANY_KEYS) return bad_arg("records_scan_many: n_keys must be 1..64");
   if (!view_keys32 || !address_xs32) return bad_arg("records_scan_many: null buffer");
   k.args.resize(n_keys); k.addr.resize(n_keys);
@@ -99,10 +96,13 @@ static uint32_t scan_many_width(size_t records_per_launch, size_t n_keys) {
   return 1;
 }
 
-static int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k) {
+// The records of a chunk reach dc0 / dnx either as the caller's rows, by two copies, or from `strings` (records_strings.h): its text goes up and k_records_parse
+// writes the rows; its chunks are cut at the character cap as well, and k_records_resolve follows the scan kernel.
+int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings) {
   const RecordsConsts& C = records_consts();
   const size_t n_keys = k.args.size();
   size_t chunk = SCAN_MANY_PAIRS / n_keys; if (chunk > SCAN_MANY_RECORDS) chunk = SCAN_MANY_RECORDS; if (chunk > n) chunk = n;
+  if (strings) strings->cut_chunks(n, chunk);
   const uint32_t W = scan_many_width(chunk, n_keys);
   std::vector<ScanArgs> table((n_keys + W - 1) / W * W, ScanArgs{});      // the padding: no digits at all
   std::copy(k.args.begin(), k.args.end(), table.begin());
@@ -113,14 +113,19 @@ static int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const 
     HIPCHK(hipMemcpyAsync(c->records_k.p, C.words.data(), RK_WORDS * 4, hipMemcpyHostToDevice, s));
   }
   const size_t keys_bytes = (table.size() * sizeof(ScanArgs) + 31) & ~(size_t)31;
-  if ((rc = c->scalars_stage.reserve(keys_bytes + chunk * 64 + chunk * n_keys * 33))) return rc;
+  const size_t rows_bytes = (keys_bytes + chunk * 64 + chunk * n_keys * 33 + 31) & ~(size_t)31;
+  if ((rc = c->scalars_stage.reserve(rows_bytes + (strings ? strings->scratch_bytes() : 0)))) return rc;
   char* dkeys = c->scalars_stage.as<char>(); char* dc0 = dkeys + keys_bytes; char* dnx = dc0 + chunk * 32; char* drvk = dnx + chunk * 32; uint8_t* dfl = (uint8_t*)(drvk + chunk * n_keys * 32);
+  char* dstr = dkeys + rows_bytes;
   HIPCHK(hipMemcpyAsync(dkeys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, s));
   const uint32_t* dK = c->records_k.as<uint32_t>();
-  for (size_t at = 0; at < n; at += chunk) {
-    const size_t m = n - at < chunk ? n - at : chunk;
-    HIPCHK(hipMemcpyAsync(dc0, (const char*)owner_c0 + at * 32, m * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dnx, (const char*)nonce_x + at * 32, m * 32, hipMemcpyHostToDevice, s));
+  for (size_t at = 0, ck = 0, m; at < n; at += m, ++ck) {
+    m = strings ? strings->cut[ck + 1] - at : (n - at < chunk ? n - at : chunk);
+    if (strings) { if ((rc = strings->fill(s, ck, dstr, dc0, dnx))) return rc; }
+    else {
+      HIPCHK(hipMemcpyAsync(dc0, (const char*)owner_c0 + at * 32, m * 32, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(dnx, (const char*)nonce_x + at * 32, m * 32, hipMemcpyHostToDevice, s));
+    }
     switch (W) {
       case 8: launch_many<8>(s, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys); break;
       case 4: launch_many<4>(s, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys); break;
@@ -128,6 +133,7 @@ static int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const 
       default: launch_many<1>(s, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys);
     }
     HIPCHK(hipGetLastError());
+    if (strings && (rc = strings->resolve(s, ck, dstr, dfl, drvk, dc0, (const ScanArgs*)dkeys, n_keys))) return rc;
     // rows of m on the device, rows of n at the caller
     HIPCHK(hipMemcpy2DAsync(flags + at, n, dfl, m, m, n_keys, hipMemcpyDeviceToHost, s));
     if (rvk_out) HIPCHK(hipMemcpy2DAsync((char*)rvk_out + at * 32, n * 32, drvk, m * 32, m * 32, n_keys, hipMemcpyDeviceToHost, s));

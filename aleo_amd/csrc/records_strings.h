@@ -1,0 +1,34 @@
+// records_strings.h — what records_many.hip and records_strings.hip share: the keys of a multi-account scan, its device flow, and the source of strings that
+// flow can be given in place of the caller's 32-byte rows (records_strings.hip: the chunk's text goes up, k_records_parse writes the rows where the scan kernels
+// read them, k_records_resolve settles the refused strings and the public owners behind the scan).
+#pragma once
+#include "entry.h"
+#include "records_host.hpp"
+#include <vector>
+
+namespace aleo_mi355x {
+
+struct ManyKeys { std::vector<ScanArgs> args; std::vector<HFr> addr; };
+
+// n strings one after another in `text`, string i at text[offsets[i] .. offsets[i + 1]), cut into chunks of whole records: chunk k holds the records
+// cut[k] .. cut[k + 1], at most `record_cap` of them and, unless it is one record, at most the character cap (ALEO_MI355X_SCAN_CHUNK_CHARS, read per call; 256 MiB)
+// of uploaded characters.  A string longer than RS_MAX_CHARS is refused without being uploaded: it counts, and travels, as the empty string, which is refused too.
+struct StringSource {
+  const char* text; const uint64_t* offsets; int8_t* kinds;   // kinds: the caller's, or null
+  std::vector<size_t> cut;
+  size_t max_records = 0, max_chars = 0;                      // of one chunk
+  std::vector<uint32_t> rel;                                  // the chunk-relative offsets on their way to the device: kept until the stream has taken them
+  void cut_chunks(size_t n, size_t record_cap);
+  size_t scratch_bytes() const;                               // of device memory behind the rows, 32-byte aligned
+  // chunk k: uploads text and offsets into `scratch` and launches k_records_parse, which fills dc0 / dnx (32 B per record) and the kinds kept in scratch
+  int32_t fill(hipStream_t s, size_t k, char* scratch, char* dc0, char* dnx);
+  // behind the scan kernel: k_records_resolve over flags / rvk ([key][record of the chunk]), then the copy of the kinds to the caller
+  int32_t resolve(hipStream_t s, size_t k, char* scratch, uint8_t* dflags, char* drvk, const char* dc0, const ScanArgs* dkeys, size_t n_keys);
+};
+
+// records_many.hip
+int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32, size_t n_keys);
+// the records come as rows (owner_c0, nonce_x) or, when `strings` is given, from it
+int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings = nullptr);
+
+}  // namespace aleo_mi355x

@@ -6,7 +6,10 @@ reference's call sites do.  scan_many / find_owned_many ask for several accounts
 csrc/records_many.hip), as a front end does that runs the search for several callers (rust/develop/src/routes.rs:112, :143, :194-220 of the reference).
 What the reference does with an owned record next — `record.decrypt(&view_key)`, `microcredits()` (rust/src/api/blocking.rs:274-283; RecordCiphertext.decrypt
 of the wasm) — is RecordCiphertext.decrypt, decrypt_fields and decrypt_owned here (aleo_mi355x_record_decrypt, aleo_mi355x_records_decrypt_fields,
-aleo_mi355x_record_fields, aleo_mi355x_record_plaintext: csrc/records_decrypt.hip), down to RecordPlaintext strings."""
+aleo_mi355x_record_fields, aleo_mi355x_record_plaintext: csrc/records_decrypt.hip), down to RecordPlaintext strings.
+Callers that hold "record1…" strings — what the chain hands out — pass them as they are: RecordBatch puts them into one blob, parse_many / scan_strings
+(aleo_mi355x_records_parse_many, aleo_mi355x_records_scan_strings: csrc/records_strings.hip) decode them on the device, and find_owned, find_owned_many and
+decrypt_owned take that road for a RecordBatch or a sequence of strings, building RecordCiphertext objects only for the records they return or decrypt."""
 from __future__ import annotations
 import ctypes
 import numpy as np
@@ -111,6 +114,81 @@ class RecordCiphertext:
         return RecordPlaintext(_string_out(lambda buf, ln: lib().aleo_mi355x_record_decrypt(self.string.encode(), _p(vk), _p(ax), buf, ln), 'record_decrypt'))
 
 
+class RecordBatch:
+    """n "record1…" strings as the C ABI takes them: the text of all of them one after another (bytes) and n + 1 uint64 offsets."""
+
+    def __init__(self, text: bytes, offsets: np.ndarray):
+        self.text = bytes(text); self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if self.offsets.ndim != 1 or len(self.offsets) < 1 or self.offsets[0] != 0 or int(self.offsets[-1]) != len(self.text) or (np.diff(self.offsets.astype(np.int64)) < 0).any():
+            raise ValueError('offsets must start at 0, not decrease and end at the length of the text')
+
+    @classmethod
+    def from_strings(cls, strings) -> 'RecordBatch':
+        """One join of all strings; the lengths by numpy (encoded one by one only when a string is not ASCII, which no record is)."""
+        strings = list(strings)
+        text = ''.join(strings).encode()
+        lens = np.fromiter(map(len, strings), dtype=np.uint64, count=len(strings))
+        if int(lens.sum()) != len(text): lens = np.fromiter((len(s.encode()) for s in strings), dtype=np.uint64, count=len(strings))
+        offsets = np.zeros(len(strings) + 1, dtype=np.uint64); np.cumsum(lens, out=offsets[1:])
+        return cls(text, offsets)
+
+    @classmethod
+    def from_text(cls, text: bytes, sep: bytes = b'\n') -> 'RecordBatch':
+        """The strings of a text that holds one per line (or between any other one-byte separator): the separators are dropped, a trailing one is ignored."""
+        if len(sep) != 1: raise ValueError('the separator is one byte')
+        a = np.frombuffer(bytes(text), dtype=np.uint8)
+        is_sep = a == sep[0]
+        ends = np.flatnonzero(is_sep)
+        if len(a) and not is_sep[-1]: ends = np.append(ends, len(a))
+        starts = np.concatenate([[0], ends[:-1] + 1]) if len(ends) else ends
+        offsets = np.zeros(len(ends) + 1, dtype=np.uint64); np.cumsum(ends - starts, out=offsets[1:])
+        return cls(a[~is_sep].tobytes(), offsets)
+
+    def __len__(self): return len(self.offsets) - 1
+
+    def string(self, i: int) -> str:
+        if not 0 <= i < len(self): raise IndexError(i)
+        return self.text[int(self.offsets[i]):int(self.offsets[i + 1])].decode(errors='replace')
+
+
+def _text_p(batch): return ctypes.cast(ctypes.c_char_p(batch.text), ctypes.c_void_p)
+
+
+def parse_many(batch: RecordBatch, host: bool = False):
+    """kinds (int8[n]: 0 public owner, 1 private owner, -1 a string that does not parse), the owner fields and the nonces' x (uint8[n, 32] each, zeros where the
+    kind is -1) of a batch of strings: what RecordCiphertext.from_string reads out of each, in one call (aleo_mi355x_records_parse_many / _many_host)."""
+    n = len(batch)
+    kinds = np.zeros(n, dtype=np.int8); owner = np.zeros((n, 32), dtype=np.uint8); nonce = np.zeros((n, 32), dtype=np.uint8)
+    f = lib().aleo_mi355x_records_parse_many_host if host else lib().aleo_mi355x_records_parse_many
+    check(f(_p(kinds), _p(owner), _p(nonce), _text_p(batch), _p(batch.offsets), n), 'records_parse_many')
+    return kinds, owner, nonce
+
+
+def scan_strings(batch: RecordBatch, view_keys, addresses, want_rvk: bool = True, host: bool = False):
+    """scan_many straight from strings (aleo_mi355x_records_scan_strings / _strings_host): flags (uint8[K, n]: 0 not owner, 1 owner, 2 malformed, 3 the string does
+    not parse), kinds (int8[n], as parse_many) and, when want_rvk, the record view keys' x (uint8[K, n, 32]).  A public owner is compared with the address."""
+    if len(view_keys) != len(addresses): raise ValueError('view_keys and addresses differ in length')
+    n, k = len(batch), len(view_keys)
+    flags = np.zeros((k, n), dtype=np.uint8); kinds = np.zeros(n, dtype=np.int8); rvk = np.zeros((k, n, 32), dtype=np.uint8) if want_rvk else None
+    vk = np.frombuffer(b''.join(view_key_bytes(v) for v in view_keys), dtype=np.uint8); ax = np.frombuffer(b''.join(address_x_bytes(a) for a in addresses), dtype=np.uint8)
+    f = lib().aleo_mi355x_records_scan_strings_host if host else lib().aleo_mi355x_records_scan_strings
+    check(f(_p(flags), _p(kinds), _p(rvk) if want_rvk else None, _text_p(batch), _p(batch.offsets), n, _p(vk), _p(ax), k), 'records_scan_strings')
+    return flags, kinds, rvk
+
+
+def _as_batch(ciphertexts):
+    """The RecordBatch of a RecordBatch or of a sequence that holds only strings, else None (RecordCiphertext objects take the road they always took)."""
+    if isinstance(ciphertexts, RecordBatch): return ciphertexts
+    if isinstance(ciphertexts, (list, tuple)) and all(isinstance(c, str) for c in ciphertexts): return RecordBatch.from_strings(ciphertexts)
+    return None
+
+
+def _raise_unparsed(batch: RecordBatch, unparsed: np.ndarray):
+    """What RecordCiphertext.from_string raises for the first string that does not parse."""
+    bad = np.flatnonzero(unparsed)
+    if len(bad): RecordCiphertext.from_string(batch.string(int(bad[0])))
+
+
 def _string_out(call, what: str) -> str:
     """A string through the (out, in/out length) convention of the C ABI: a first try with room for most records, a second with the length the first returned."""
     cap = 4096
@@ -188,8 +266,10 @@ def decrypt_owned(ciphertexts, view_key, address):
     Every string is parsed once; one scan says which private owners are the account and hands back their record view keys, one decrypt_fields call decrypts the
     fields of all owned records, and the strings are put together on the host.  A record with a public owner equal to the address is included (its owner needs
     no hash; its private entries, if any, do).  An owned record whose decrypted entries do not parse raises."""
-    recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
     ax = address_x_bytes(address)
+    batch = _as_batch(ciphertexts)
+    if batch is not None: return _decrypt_owned_strings(batch, view_key, ax)
+    recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
     fields = {i: r.fields() for i, r in enumerate(recs) if r.owner_kind == OWNER_PUBLIC and r.owner == ax}      # public owners that match: usually no private field
     scanned = [i for i, r in enumerate(recs) if r.owner_kind == OWNER_PRIVATE or (i in fields and len(fields[i]))]
     rvks = {}
@@ -202,6 +282,27 @@ def decrypt_owned(ciphertexts, view_key, address):
                 if flags[j] == 2: raise AleoMi355xError('decrypt_owned: record %d has a nonce that is not on the curve' % i)
                 rvks[i] = rvk[j]
             elif flags[j] == 1: rvks[i] = rvk[j]; fields[i] = recs[i].fields()
+    return _decrypt_found(recs, fields, rvks, ax)
+
+
+def _decrypt_owned_strings(batch: RecordBatch, view_key, ax: bytes):
+    """decrypt_owned from strings: one scan_strings call says who owns what; only the owned records become RecordCiphertext objects."""
+    flags, kinds, rvk = scan_strings(batch, [view_key], [ax])
+    _raise_unparsed(batch, flags[0] == 3)
+    recs, fields, rvks = {}, {}, {}
+    for i in np.flatnonzero(flags[0] == 1).tolist():
+        recs[i] = RecordCiphertext.from_string(batch.string(i)); fields[i] = recs[i].fields()
+        if kinds[i] == OWNER_PRIVATE: rvks[i] = rvk[0, i]
+        elif len(fields[i]):
+            # a zero row is the key of a nonce x = 0, or stands for a nonce that is not on the curve: the one-record scan says which
+            if not rvk[0, i].any() and scan(np.frombuffer(recs[i].owner, dtype=np.uint8), np.frombuffer(recs[i].nonce, dtype=np.uint8), view_key, ax, want_rvk=False)[0][0] == 2:
+                raise AleoMi355xError('decrypt_owned: record %d has a nonce that is not on the curve' % i)
+            rvks[i] = rvk[0, i]
+    return _decrypt_found(recs, fields, rvks, ax)
+
+
+def _decrypt_found(recs, fields, rvks, ax: bytes):
+    """The tail of decrypt_owned: fields[i] the private fields of every owned record i, rvks[i] its record view key x (absent where there is no private field)."""
     idx = sorted(fields)
     offsets = np.zeros(len(idx) + 1, dtype=np.uint32)
     if idx: offsets[1:] = np.cumsum([len(fields[i]) for i in idx])
@@ -216,8 +317,10 @@ def find_owned(ciphertexts, view_key, address):
     """The indices of the records the account owns, and their record view keys' x (32 little-endian bytes each; None for a public owner, whose record is
     not encrypted to anyone): the batch form of the reference's record search.  `ciphertexts`: strings or RecordCiphertext objects; a string that does
     not parse raises."""
-    recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
     ax = address_x_bytes(address)
+    batch = _as_batch(ciphertexts)
+    if batch is not None: return _find_owned_strings(batch, [(view_key, ax)])[0]
+    recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
     priv = [i for i, r in enumerate(recs) if r.owner_kind == OWNER_PRIVATE]
     owned = {i: None for i, r in enumerate(recs) if r.owner_kind == OWNER_PUBLIC and r.owner == ax}
     if priv:
@@ -233,8 +336,10 @@ def find_owned(ciphertexts, view_key, address):
 def find_owned_many(ciphertexts, accounts):
     """find_owned for several accounts over the same records: `accounts` is a sequence of (view_key, address) pairs, the result a list with, for each of
     them, what find_owned returns.  Every string is parsed once and the private owners of all accounts go through one scan_many call."""
-    recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
     accounts = [(vk, address_x_bytes(a)) for vk, a in accounts]
+    batch = _as_batch(ciphertexts)
+    if batch is not None: return _find_owned_strings(batch, accounts)
+    recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
     priv = [i for i, r in enumerate(recs) if r.owner_kind == OWNER_PRIVATE]
     owned = [{i: None for i, r in enumerate(recs) if r.owner_kind == OWNER_PUBLIC and r.owner == ax} for _, ax in accounts]
     if priv and accounts:
@@ -244,3 +349,17 @@ def find_owned_many(ciphertexts, accounts):
         for a, mine in enumerate(owned):
             for j in np.nonzero(flags[a] == 1)[0]: mine[priv[j]] = rvk[a, j].tobytes()
     return [(sorted(mine), [mine[i] for i in sorted(mine)]) for mine in owned]
+
+
+def _find_owned_strings(batch: RecordBatch, accounts):
+    """find_owned_many from strings: one scan_strings call; a public owner's record has no record view key (None)."""
+    if not accounts:
+        _raise_unparsed(batch, parse_many(batch)[0] < 0)
+        return []
+    flags, kinds, rvk = scan_strings(batch, [vk for vk, _ in accounts], [ax for _, ax in accounts])
+    _raise_unparsed(batch, flags[0] == 3)
+    out = []
+    for a in range(len(accounts)):
+        idx = np.flatnonzero(flags[a] == 1).tolist()
+        out.append((idx, [rvk[a, i].tobytes() if kinds[i] == OWNER_PRIVATE else None for i in idx]))
+    return out

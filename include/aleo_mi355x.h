@@ -546,6 +546,29 @@ size_t aleo_mi355x_min_records(void);
  *   records_scan_many_host   the same bytes out from n_keys passes of the host path; touches no device. */
 int32_t aleo_mi355x_records_scan_many(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys);
 int32_t aleo_mi355x_records_scan_many_host(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys);
+/* The record search straight from "record1..." strings: what a caller holds who reads records out of block JSON, as the reference does
+ * (rust/src/api/blocking.rs:209-218, :264-276; RecordCiphertext.fromString).  The strings come in one blob and are decoded on the device: bech32m, checksum and
+ * the layout walk of record_parse, one string per lane (csrc/records_strings_lane.h), writing the scan's inputs where the scan kernels read them.
+ *   text, offsets  the strings one after another, no separators; offsets: n + 1 entries, offsets[0] = 0, nondecreasing; string i is text[offsets[i] .. offsets[i + 1]).
+ *   records_parse_many   kinds[i] = 0 public owner, 1 private owner, -1 for a string record_parse refuses (a NUL inside a span, the empty span and a span of more
+ *                  than 2^20 characters are refused); owner32 / nonce32 (n x 32 B): what record_parse writes, zeros where kinds[i] = -1.  A refused string is a
+ *                  per-record answer, not a failed call.  Below min_records strings the call runs on the calling thread.
+ *   records_parse_many_host   the same bytes out, computed on the CPU by the calling thread, with no allocation per string; touches no device.
+ *   records_scan_strings   the scan of records_scan_many over the strings, 1 <= n_keys <= 64 (n_keys = 1 is the single scan; the width rule of records_scan_many
+ *                  applies unchanged).  flags (n_keys x n bytes, [key][record]): 0 not owner, 1 owner, 2 malformed (as records_scan), 3 the string does not
+ *                  parse.  A public owner is compared with the key's address x (flag 0 or 1; the nonce plays no part); a private owner goes through the scan.
+ *                  rvk_out (optional, n_keys x n x 32 B): the x of view key * nonce for every string that parses, public owners included, zeros where the nonce
+ *                  is malformed or the string does not parse.  kinds (optional, n): as records_parse_many.  The call fails only for null buffers, offsets that
+ *                  decrease or do not start at 0, a key records_scan_many refuses, or a HIP error.  Chunks hold whole records, within the record and pair caps
+ *                  of records_scan_many and 256 MiB of characters (ALEO_MI355X_SCAN_CHUNK_CHARS, read per call, lowers that cap: for tests; the bytes out do not
+ *                  depend on it); an over-long string is not uploaded.  A call with n * n_keys below min_records runs on the host.  Thread-safe (one slot per call).
+ *   records_scan_strings_host   the same bytes out, computed on the CPU by the calling thread; touches no device. */
+int32_t aleo_mi355x_records_parse_many(int8_t* kinds, void* owner32, void* nonce32, const char* text, const uint64_t* offsets, size_t n);
+int32_t aleo_mi355x_records_parse_many_host(int8_t* kinds, void* owner32, void* nonce32, const char* text, const uint64_t* offsets, size_t n);
+int32_t aleo_mi355x_records_scan_strings(uint8_t* flags, int8_t* kinds, void* rvk_out, const char* text, const uint64_t* offsets, size_t n,
+                                         const void* view_keys32, const void* address_xs32, size_t n_keys);
+int32_t aleo_mi355x_records_scan_strings_host(uint8_t* flags, int8_t* kinds, void* rvk_out, const char* text, const uint64_t* offsets, size_t n,
+                                              const void* view_keys32, const void* address_xs32, size_t n_keys);
 /* Decrypting the records an account owns: what the reference does next with every record the search finds — `record.decrypt(&view_key)` and the sum of
  * `microcredits()` (rust/src/api/blocking.rs:274-283), RecordCiphertext.decrypt(viewKey) -> RecordPlaintext (wasm/src/record/record_ciphertext.rs:48-57).
  * snarkVM 0.14.5 console/program/src/data/record/decrypt.rs, ciphertext/decrypt.rs [UPSTREAM-RECALL], pinned by the reference's own ciphertext and plaintext

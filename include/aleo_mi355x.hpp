@@ -12,7 +12,7 @@
 //       to one circuit, `prove_batch(&[assignment])` -> Proof, Proof Display as bech32m `proof1…`; `prove_batch(keys -> assignments)` over several
 //       keys and `Trace::prove_execution / prove_fee` above it (rows a6 / a7 of SURVEY.md §8)
 //   snarkvm_console_program::Record<N, Ciphertext<N>>::{from_str, is_owner, decrypt} and the record search around it (RecordCiphertext, RecordPlaintext,
-//   find_owned, find_owned_many, decrypt_owned)
+//   find_owned, find_owned_many, decrypt_owned; RecordBatch: the same three straight from "record1…" strings)
 // Layouts are snarkVM's: Fr = 4 x u64 Montgomery, scalar = 4 x u64 canonical, G1Affine = 104 bytes, Projective = 144 bytes.
 #pragma once
 #include <chrono>
@@ -619,6 +619,68 @@ inline Result<std::vector<std::vector<OwnedRecord>>> find_owned_many(const std::
     }
   }
   return {std::move(out), Error{0}};
+}
+
+// n "record1…" strings as the C ABI takes them — the text of all of them one after another and n + 1 offsets — for callers that hold what the chain hands out:
+// the overloads below send the strings to the device as they are (aleo_mi355x_records_scan_strings) and parse on the host only the records they decrypt.
+class RecordBatch {
+ public:
+  // (no default constructor: `{}` where a batch is expected goes on meaning an empty vector of RecordCiphertext)
+  explicit RecordBatch(const std::vector<std::string>& strings) : offsets_{0} { for (const auto& s : strings) push_back(s); }
+  // the strings of a text that holds one per line (or between any other separator character): the separators are dropped, a trailing one is ignored
+  static RecordBatch from_text(const std::string& text, char sep = '\n') {
+    RecordBatch b(std::vector<std::string>{});
+    for (size_t at = 0; at < text.size();) {
+      size_t end = text.find(sep, at); if (end == std::string::npos) end = text.size();
+      b.text_.append(text, at, end - at); b.offsets_.push_back(b.text_.size());
+      at = end + 1;
+    }
+    return b;
+  }
+  void push_back(const std::string& s) { text_ += s; offsets_.push_back(text_.size()); }
+  size_t size() const { return offsets_.size() - 1; }
+  std::string string(size_t i) const { return text_.substr((size_t)offsets_[i], (size_t)(offsets_[i + 1] - offsets_[i])); }
+  const char* text() const { return text_.data(); }
+  const uint64_t* offsets() const { return offsets_.data(); }
+ private:
+  std::string text_; std::vector<uint64_t> offsets_;
+};
+
+// find_owned_many from strings: one aleo_mi355x_records_scan_strings call.  A string that does not parse fails the call with what RecordCiphertext::from_string
+// returns for the first of them (the batch of objects could not have been built).
+inline Result<std::vector<std::vector<OwnedRecord>>> find_owned_many(const RecordBatch& batch, const std::vector<Account>& accounts) {
+  const size_t n = batch.size(), k = accounts.size();
+  std::vector<uint8_t> vks, axs;
+  for (const auto& a : accounts) { vks.insert(vks.end(), a.view_key.scalar, a.view_key.scalar + 32); axs.insert(axs.end(), a.address.x, a.address.x + 32); }
+  std::vector<uint8_t> flags(k * n), rvk(32 * k * n), rows; std::vector<int8_t> kinds(n);
+  if (k) { int32_t rc = aleo_mi355x_records_scan_strings(flags.data(), kinds.data(), rvk.data(), batch.text(), batch.offsets(), n, vks.data(), axs.data(), k); if (rc) return {std::nullopt, Error{rc}}; }
+  else { rows.resize(64 * n); int32_t rc = aleo_mi355x_records_parse_many(kinds.data(), rows.data(), rows.data() + 32 * n, batch.text(), batch.offsets(), n); if (rc) return {std::nullopt, Error{rc}}; }
+  for (size_t i = 0; i < n; ++i)
+    if (kinds[i] < 0) { auto r = RecordCiphertext::from_string(batch.string(i)); return {std::nullopt, r.is_ok() ? Error{ALEO_MI355X_ERR_BAD_ARG} : r.error}; }
+  std::vector<std::vector<OwnedRecord>> out(k);
+  for (size_t a = 0; a < k; ++a)
+    for (size_t i = 0; i < n; ++i)
+      if (flags[a * n + i] == 1) { OwnedRecord o{i, kinds[i] == 1, {}}; if (o.has_view_key) std::memcpy(o.record_view_key_x, rvk.data() + 32 * (a * n + i), 32); out[a].push_back(o); }
+  return {std::move(out), Error{0}};
+}
+inline Result<std::vector<OwnedRecord>> find_owned(const RecordBatch& batch, const ViewKey& vk, const Address& address) {
+  auto r = find_owned_many(batch, std::vector<Account>{Account{vk, address}});
+  if (!r.is_ok()) return {std::nullopt, r.error};
+  return {std::move((*r.value)[0]), Error{0}};
+}
+// decrypt_owned from strings: the scan over the strings says which records are the account's; those alone become RecordCiphertext objects and go through the
+// batch above (which scans these few once more for their record view keys and keeps every error it has).
+inline Result<std::vector<DecryptedRecord>> decrypt_owned(const RecordBatch& batch, const ViewKey& vk, const Address& address) {
+  using Out = Result<std::vector<DecryptedRecord>>;
+  auto found = find_owned(batch, vk, address);
+  if (!found.is_ok()) return Out{std::nullopt, found.error};
+  std::vector<RecordCiphertext> mine;
+  for (const auto& o : *found.value) { auto r = RecordCiphertext::from_string(batch.string(o.index)); if (!r.is_ok()) return Out{std::nullopt, r.error}; mine.push_back(std::move(*r.value)); }
+  auto dec = decrypt_owned(mine, vk, address);
+  if (!dec.is_ok()) return dec;
+  if (dec.value->size() != mine.size()) return Out{std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+  for (size_t j = 0; j < mine.size(); ++j) (*dec.value)[j].index = (*found.value)[j].index;
+  return dec;
 }
 
 }  // namespace aleo_mi355x
