@@ -14,6 +14,7 @@
 #include "records_host.hpp"
 #include "records_decrypt_lane.h"
 #include "records_plaintext.hpp"
+#include "records_strings.h"
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -42,21 +43,6 @@ static int32_t decrypt_args_ok(const void* plain_out, const uint8_t* flags, cons
   return ALEO_MI355X_OK;
 }
 
-// one record on the host: the flag, and its m plain rows (zeros with flag 2)
-static uint8_t decrypt_one_host(uint8_t* plain, const uint8_t* rvk32, const uint8_t* fields, size_t m) {
-  HFr rv; std::memcpy(rv.l, rvk32, 32);
-  bool bad = HFr::geq_p(rv.l);
-  std::vector<HFr> c(m), rnd(m);
-  for (size_t j = 0; j < m; ++j) { std::memcpy(c[j].l, fields + 32 * j, 32); bad = bad || HFr::geq_p(c[j].l); }
-  if (bad) { std::memset(plain, 0, 32 * m); return 2; }
-  if (!m) return 0;
-  static const HFr dom = host::fr_domain_separator("AleoSymmetricEncryption0");
-  const HFr in[2] = {dom, HFr::to_mont(rv)};
-  host::poseidon_hash_many_fr<8>(in, 2, rnd.data(), m);
-  for (size_t j = 0; j < m; ++j) { const HFr o = HFr::from_mont(HFr::sub(HFr::to_mont(c[j]), rnd[j])); std::memcpy(plain + 32 * j, o.l, 32); }
-  return 0;
-}
-
 static int32_t decrypt_on_host(uint8_t* plain, uint8_t* flags, const uint8_t* rvk, const uint32_t* offsets, const uint8_t* fields, size_t n) {
   for (size_t i = 0; i < n; ++i) flags[i] = decrypt_one_host(plain + (size_t)offsets[i] * 32, rvk + 32 * i, fields + (size_t)offsets[i] * 32, offsets[i + 1] - offsets[i]);
   return ALEO_MI355X_OK;
@@ -80,11 +66,17 @@ __global__ void __launch_bounds__(DECRYPT_BLOCK) k_records_decrypt(char* __restr
   flags[i] = (uint8_t)flag;
 }
 
+// the field cap of a launch, and the launch itself for records_found.hip, whose records are on the device already
+size_t decrypt_chunk_fields() { size_t cap = env_size("ALEO_MI355X_DECRYPT_CHUNK_FIELDS", DECRYPT_CHUNK_FIELDS); return cap < 1 || cap > DECRYPT_CHUNK_FIELDS ? DECRYPT_CHUNK_FIELDS : cap; }
+void launch_records_decrypt(hipStream_t s, char* io, uint8_t* dflags, const char* drvk, const uint32_t* doffsets, uint32_t base, size_t n, const uint32_t* dK) {
+  hipLaunchKernelGGL(k_records_decrypt, dim3((uint32_t)((n + DECRYPT_BLOCK - 1) / DECRYPT_BLOCK)), dim3(DECRYPT_BLOCK), 0, s, io, dflags, drvk, doffsets, base, (uint32_t)n, dK);
+}
+
 // Copies, launch and synchronisation as records_scan_on_device (records.hip).  A chunk: as many whole records as stay within DECRYPT_CHUNK_RECORDS and the field
 // cap, and one at least.  ALEO_MI355X_DECRYPT_CHUNK_FIELDS (read per call) lowers the field cap; the bytes do not depend on it.
 static int32_t decrypt_on_device(Ctx* c, uint8_t* plain, uint8_t* flags, const uint8_t* rvk, const uint32_t* offsets, const uint8_t* fields, size_t n) {
   const RecordsConsts& C = records_consts();
-  size_t cap = env_size("ALEO_MI355X_DECRYPT_CHUNK_FIELDS", DECRYPT_CHUNK_FIELDS); if (cap < 1 || cap > DECRYPT_CHUNK_FIELDS) cap = DECRYPT_CHUNK_FIELDS;
+  const size_t cap = decrypt_chunk_fields();
   std::vector<size_t> cut{0};                                 // chunk k: records cut[k] .. cut[k + 1]
   size_t max_records = 0, max_fields = 0;
   for (size_t at = 0; at < n;) {
@@ -152,8 +144,8 @@ using namespace aleo_mi355x;
 
 extern "C" {
 
-// The number of permutations from which records_decrypt_fields takes the GPU.  NOT measured yet (profiles/records_decrypt.txt): the scan's measured crossover
-// stands in, since a small call of either is one wave running one dependent chain against the host path on one thread.
+// The number of permutations from which records_decrypt_fields takes the GPU: the measured crossover against the host path on one thread (profiles/records_decrypt.txt:
+// records of two fields, 0.99x at 2^5, 2.68x at 2^6), which is the scan's as well — a small call of either is one wave running one dependent chain.
 size_t aleo_mi355x_min_decrypt(void) { return env_size("ALEO_MI355X_MIN_DECRYPT", (size_t)1 << 6); }
 
 int32_t aleo_mi355x_records_decrypt_fields_host(void* plain_out, uint8_t* flags, const void* rvk, const uint32_t* offsets, const void* fields, size_t n) {

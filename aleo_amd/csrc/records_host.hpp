@@ -163,4 +163,20 @@ static const char* scan_args(ScanArgs& a, HFr& addr_mont, const void* view_key32
   return nullptr;
 }
 
+// ---- the decryption of one record's private fields (records_decrypt.hip, records_found_host.hpp) ------------------------------------------------------------
+// one record on the host: the flag, and its m plain rows (zeros with flag 2)
+static uint8_t decrypt_one_host(uint8_t* plain, const uint8_t* rvk32, const uint8_t* fields, size_t m) {
+  HFr rv; std::memcpy(rv.l, rvk32, 32);
+  bool bad = HFr::geq_p(rv.l);
+  std::vector<HFr> c(m), rnd(m);
+  for (size_t j = 0; j < m; ++j) { std::memcpy(c[j].l, fields + 32 * j, 32); bad = bad || HFr::geq_p(c[j].l); }
+  if (bad) { std::memset(plain, 0, 32 * m); return 2; }
+  if (!m) return 0;
+  static const HFr dom = host::fr_domain_separator("AleoSymmetricEncryption0");
+  const HFr in[2] = {dom, HFr::to_mont(rv)};
+  host::poseidon_hash_many_fr<8>(in, 2, rnd.data(), m);
+  for (size_t j = 0; j < m; ++j) { const HFr o = HFr::from_mont(HFr::sub(HFr::to_mont(c[j]), rnd[j])); std::memcpy(plain + 32 * j, o.l, 32); }
+  return 0;
+}
+
 }  // namespace aleo_mi355x

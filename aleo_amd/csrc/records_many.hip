@@ -143,6 +143,11 @@ int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* o
   return ALEO_MI355X_OK;
 }
 
+// for records_found.hip, which runs the one-key scan between a parse and a walk of its own
+void launch_scan_one_key(hipStream_t s, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkey) {
+  launch_many<1>(s, dflags, drvk, dc0, dnx, m, dK, dkey, 1);
+}
+
 }  // namespace aleo_mi355x
 
 using namespace aleo_mi355x;

@@ -24,11 +24,23 @@ struct StringSource {
   int32_t fill(hipStream_t s, size_t k, char* scratch, char* dc0, char* dnx);
   // behind the scan kernel: k_records_resolve over flags / rvk ([key][record of the chunk]), then the copy of the kinds to the caller
   int32_t resolve(hipStream_t s, size_t k, char* scratch, uint8_t* dflags, char* drvk, const char* dc0, const ScanArgs* dkeys, size_t n_keys);
+  // where fill left the chunk's relative offsets, kinds and text inside `scratch` (records_found.hip walks the owned records from them)
+  void parts(char* scratch, const uint32_t** off, const int8_t** kinds, const char** text) const;
 };
+
+// records_strings.hip: what both paths of a call over strings refuse before they look at one
+int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offsets, size_t n);
 
 // records_many.hip
 int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32, size_t n_keys);
 // the records come as rows (owner_c0, nonce_x) or, when `strings` is given, from it
 int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings = nullptr);
+// the one-key launch of k_records_scan_many over m records already on the device (flags m B, rvk m x 32 B); the caller checks hipGetLastError
+void launch_scan_one_key(hipStream_t s, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkey);
+
+// records_decrypt.hip
+size_t decrypt_chunk_fields();                                // the field cap of one k_records_decrypt launch (ALEO_MI355X_DECRYPT_CHUNK_FIELDS, read per call)
+// k_records_decrypt over n records already on the device: io the fields from offsets[0] on, in place; the caller checks hipGetLastError
+void launch_records_decrypt(hipStream_t s, char* io, uint8_t* dflags, const char* drvk, const uint32_t* doffsets, uint32_t base, size_t n, const uint32_t* dK);
 
 }  // namespace aleo_mi355x

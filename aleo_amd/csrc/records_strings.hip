@@ -26,7 +26,7 @@ static constexpr size_t STRINGS_CHUNK_CHARS = (size_t)256 << 20;
 static size_t env_size(const char* name, size_t dflt) { const char* e = std::getenv(name); if (!e || !*e) return dflt; char* end = nullptr; const unsigned long long v = std::strtoull(e, &end, 10); return end && *end == 0 ? (size_t)v : dflt; }
 
 // what both paths refuse before they look at a string
-static int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offsets, size_t n) {
+int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offsets, size_t n) {
   if (!n) return ALEO_MI355X_OK;
   if (!offsets) { g_last_error = std::string(who) + ": null buffer"; return ALEO_MI355X_ERR_BAD_ARG; }
   if (offsets[0] != 0) { g_last_error = std::string(who) + ": offsets[0] is not 0"; return ALEO_MI355X_ERR_BAD_ARG; }
@@ -172,6 +172,10 @@ int32_t StringSource::resolve(hipStream_t s, size_t k, char* scratch, uint8_t* d
   HIPCHK(hipGetLastError());
   if (kinds) HIPCHK(hipMemcpyAsync(kinds + at, dkinds, m, hipMemcpyDeviceToHost, s));
   return ALEO_MI355X_OK;
+}
+
+void StringSource::parts(char* scratch, const uint32_t** off, const int8_t** kinds_, const char** text_) const {
+  *off = (const uint32_t*)scratch; *kinds_ = (const int8_t*)(scratch + up32((max_records + 1) * 4)); *text_ = (const char*)*kinds_ + up32(max_records);
 }
 
 // parse_many on the device: the chunks of a scan over strings, the parse kernel alone, the rows copied back

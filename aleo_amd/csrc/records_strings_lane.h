@@ -10,20 +10,16 @@
 //   length, that many bytes | 32 B nonce x, canonical | end.
 //
 // Two passes over the characters and no buffer.  The first folds every symbol into the checksum, starting from the state after the expanded prefix (a compile-time
-// constant), and notes a character outside the alphabet.  The second walks the layout through byte_at(j), which reads the two or three symbols that cover payload
-// byte j: the walk touches the count and length bytes and the two fields, a few dozen bytes of a record, whatever the entries hold.  A wave runs to its longest
+// constant), and notes a character outside the alphabet.  The second walks the layout through byte_at(j) (records_symbols_lane.h), which reads the two or three
+// symbols that cover payload byte j: the walk touches the count and length bytes and the two fields, a few dozen bytes of a record, whatever the entries hold.  A wave runs to its longest
 // string; strings are not sorted by length (a wave's cost is its longest lane's either way, and an order costs a pass and a gather).
 // Plain C++: no thread index, the characters come through a callable, so tests/cpp/records_strings_lane_emul.cpp runs it on the host.
 #pragma once
-#include <cstdint>
+#include "records_symbols_lane.h"
 
 namespace aleo_mi355x {
 
-static constexpr uint32_t RS_MAX_CHARS = 1u << 20;            // a longer string is refused (wire.hip: "record_parse: string too long")
-static constexpr uint32_t RS_PREFIX_CHARS = 7, RS_CHECKSUM_SYMBOLS = 6;
 static constexpr uint32_t RS_BECH32M = 0x2bc830a3u;
-// r, in little-endian words
-static constexpr uint32_t RS_FR_WORDS[8] = {0x00000001u, 0x0a118000u, 0xd0000001u, 0x59aa76feu, 0x5c37b001u, 0x60b44d1eu, 0x9a2ca556u, 0x12ab655eu};
 
 constexpr uint32_t rs_polymod_step(uint32_t chk, uint32_t v) {
   const uint32_t b = chk >> 25;
@@ -39,16 +35,6 @@ constexpr uint32_t rs_polymod_prefix(const char* hrp) {
   return chk;
 }
 static constexpr uint32_t RS_PREFIX_STATE = rs_polymod_prefix("record");
-
-// character -> symbol, -1 outside the alphabet
-struct RsSymbols { int8_t of[128]; };
-constexpr RsSymbols rs_symbols() {
-  RsSymbols t{};
-  for (int i = 0; i < 128; ++i) t.of[i] = -1;
-  const char* alphabet = "qpzry9x8gf2tvdw0s3jn54khce6mua7l";
-  for (int i = 0; i < 32; ++i) t.of[(unsigned char)alphabet[i]] = (int8_t)i;
-  return t;
-}
 
 // One string of `len` characters, character i through ch(i) (0 <= i < len, asked for in any order and more than once).  Returns the owner variant (0 public,
 // 1 private) with the canonical words of the owner field and of the nonce x, or -1 for a string aleo_mi355x_record_parse refuses, both rows zeros.
@@ -73,13 +59,7 @@ __host__ __device__ __forceinline__ int32_t records_parse_lane(LoadChar&& ch, ui
   if (!ok || chk != RS_BECH32M) return -1;
   const uint32_t left = (5u * D) & 7u, nb = (5u * D) >> 3;      // D <= 2^20: no overflow
   if (left >= 5 || (left && (sym(D - 1) & ((1u << left) - 1u)))) return -1;
-  // payload byte j lies in symbols k = floor(8 j / 5) .. k + 2; k + 2 may be a checksum symbol, whose bits the shift drops
-  auto byte_at = [&](uint32_t j) {
-    const uint32_t k = (8u * j) / 5u, o = 8u * j - 5u * k;
-    uint32_t v = (sym(k) << 10) | (sym(k + 1) << 5);
-    if (o >= 3) v |= sym(k + 2);
-    return (v >> (7u - o)) & 0xffu;
-  };
+  auto byte_at = [&](uint32_t j) { return rs_byte_at(sym, j); };                    // records_symbols_lane.h
   // 32 bytes from byte j on, as little-endian words: the symbols are read once each, in order; returns whether the value is below r
   auto field = [&](uint32_t j, uint32_t (&w)[8]) {
     uint32_t k = (8u * j) / 5u;

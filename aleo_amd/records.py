@@ -9,7 +9,9 @@ of the wasm) — is RecordCiphertext.decrypt, decrypt_fields and decrypt_owned h
 aleo_mi355x_record_fields, aleo_mi355x_record_plaintext: csrc/records_decrypt.hip), down to RecordPlaintext strings.
 Callers that hold "record1…" strings — what the chain hands out — pass them as they are: RecordBatch puts them into one blob, parse_many / scan_strings
 (aleo_mi355x_records_parse_many, aleo_mi355x_records_scan_strings: csrc/records_strings.hip) decode them on the device, and find_owned, find_owned_many and
-decrypt_owned take that road for a RecordBatch or a sequence of strings, building RecordCiphertext objects only for the records they return or decrypt."""
+decrypt_owned take that road for a RecordBatch or a sequence of strings, building RecordCiphertext objects only for the records they return or decrypt.
+decrypt_strings and balance (aleo_mi355x_records_decrypt_strings: csrc/records_found.hip) go from the strings of one account's search to the plain fields and
+microcredits of the records it owns in one call, and bring back only those; decrypt_owned on strings is that call and the rendering of the strings."""
 from __future__ import annotations
 import ctypes
 import numpy as np
@@ -261,10 +263,62 @@ def decrypt_fields(rvk: np.ndarray, offsets, fields: np.ndarray, host: bool = Fa
     return plain, flags
 
 
+class FoundRecords:
+    """What decrypt_strings returns, as numpy copies: for the c records the account owns, in ascending record index, index (uint32[c]), kind (int8[c]: 0 public
+    owner, 1 private), rvk (uint8[c, 32]), offsets (uint32[c + 1]) into plain (uint8[fields, 32]: the decrypted private fields in randomizer order), status
+    (uint8[c]: 0 decrypted, 2 malformed, 4 the structure is refused) and microcredits (uint64[c]); unparsed / first_unparsed: the strings that do not parse."""
+
+    def __init__(self, index, kind, rvk, offsets, plain, status, microcredits, unparsed: int, first_unparsed: int):
+        self.index, self.kind, self.rvk, self.offsets, self.plain, self.status, self.microcredits = index, kind, rvk, offsets, plain, status, microcredits
+        self.unparsed, self.first_unparsed = unparsed, first_unparsed
+
+    def __len__(self): return len(self.index)
+
+    def fields(self, k: int) -> np.ndarray:
+        """The plain fields of the k-th owned record."""
+        return self.plain[int(self.offsets[k]):int(self.offsets[k + 1])]
+
+    def arrays(self): return (self.index, self.kind, self.rvk, self.offsets, self.plain, self.status, self.microcredits)
+
+
+def decrypt_strings(batch, view_key, address, host: bool = False) -> FoundRecords:
+    """The records one account owns among a RecordBatch (or a sequence of strings), decrypted, in one call (aleo_mi355x_records_decrypt_strings / _strings_host):
+    the scan, the owned records' private fields, their decryption and their microcredits, all on the device; only the owned records come back.  A string that
+    does not parse is counted (unparsed, first_unparsed), not raised."""
+    b = _as_batch(batch)
+    if b is None: raise TypeError('decrypt_strings takes a RecordBatch or a sequence of strings')
+    vk = np.frombuffer(view_key_bytes(view_key), dtype=np.uint8); ax = np.frombuffer(address_x_bytes(address), dtype=np.uint8)
+    L = lib(); out = ctypes.c_void_p()
+    f = L.aleo_mi355x_records_decrypt_strings_host if host else L.aleo_mi355x_records_decrypt_strings
+    check(f(ctypes.byref(out), _text_p(b), _p(b.offsets), len(b), _p(vk), _p(ax)), 'records_decrypt_strings')
+    try:
+        c, nf = int(L.aleo_mi355x_found_count(out)), int(L.aleo_mi355x_found_fields(out))
+        def copy(name, dtype, count, shape):
+            size = count * np.dtype(dtype).itemsize
+            return np.frombuffer(ctypes.string_at(getattr(L, 'aleo_mi355x_found_' + name)(out), size) if size else b'', dtype=dtype).reshape(shape).copy()
+        return FoundRecords(copy('index', np.uint32, c, (c,)), copy('kind', np.int8, c, (c,)), copy('rvk', np.uint8, 32 * c, (c, 32)), copy('offsets', np.uint32, c + 1, (c + 1,)),
+                            copy('plain', np.uint8, 32 * nf, (nf, 32)), copy('status', np.uint8, c, (c,)), copy('microcredits', np.uint64, c, (c,)),
+                            int(L.aleo_mi355x_found_unparsed(out)), int(L.aleo_mi355x_found_first_unparsed(out)))
+    finally:
+        L.aleo_mi355x_found_free(out)
+
+
+def balance(ciphertexts, view_key, address):
+    """(the sum of the microcredits of the records the account owns, their indices) over a RecordBatch or a sequence of strings: the reference's
+    get_unspent_records sum (rust/src/api/blocking.rs:274-283) without the spent check, in one decrypt_strings call.  Only records with status 0 count; a
+    string that does not parse raises what RecordCiphertext.from_string raises."""
+    b = _as_batch(ciphertexts)
+    if b is None: b = RecordBatch.from_strings([str(c) for c in ciphertexts])
+    found = decrypt_strings(b, view_key, address)
+    if found.unparsed: RecordCiphertext.from_string(b.string(found.first_unparsed))
+    return sum(int(v) for v in found.microcredits[found.status == 0]), found.index.tolist()
+
+
 def decrypt_owned(ciphertexts, view_key, address):
     """[(index, RecordPlaintext)] of the records the account owns: the batch form of the reference's `if record.is_owner(..) { record.decrypt(..) }` loop.
-    Every string is parsed once; one scan says which private owners are the account and hands back their record view keys, one decrypt_fields call decrypts the
-    fields of all owned records, and the strings are put together on the host.  A record with a public owner equal to the address is included (its owner needs
+    From strings or a RecordBatch it is one decrypt_strings call and the rendering of the owned records; from RecordCiphertext objects every string is parsed once, one
+    scan says which private owners are the account and hands back their record view keys, one decrypt_fields call decrypts the fields of all owned records, and the
+    strings are put together on the host.  A record with a public owner equal to the address is included (its owner needs
     no hash; its private entries, if any, do).  An owned record whose decrypted entries do not parse raises."""
     ax = address_x_bytes(address)
     batch = _as_batch(ciphertexts)
@@ -286,19 +340,17 @@ def decrypt_owned(ciphertexts, view_key, address):
 
 
 def _decrypt_owned_strings(batch: RecordBatch, view_key, ax: bytes):
-    """decrypt_owned from strings: one scan_strings call says who owns what; only the owned records become RecordCiphertext objects."""
-    flags, kinds, rvk = scan_strings(batch, [view_key], [ax])
-    _raise_unparsed(batch, flags[0] == 3)
-    recs, fields, rvks = {}, {}, {}
-    for i in np.flatnonzero(flags[0] == 1).tolist():
-        recs[i] = RecordCiphertext.from_string(batch.string(i)); fields[i] = recs[i].fields()
-        if kinds[i] == OWNER_PRIVATE: rvks[i] = rvk[0, i]
-        elif len(fields[i]):
-            # a zero row is the key of a nonce x = 0, or stands for a nonce that is not on the curve: the one-record scan says which
-            if not rvk[0, i].any() and scan(np.frombuffer(recs[i].owner, dtype=np.uint8), np.frombuffer(recs[i].nonce, dtype=np.uint8), view_key, ax, want_rvk=False)[0][0] == 2:
-                raise AleoMi355xError('decrypt_owned: record %d has a nonce that is not on the curve' % i)
-            rvks[i] = rvk[0, i]
-    return _decrypt_found(recs, fields, rvks, ax)
+    """decrypt_owned from strings: one decrypt_strings call finds, gathers and decrypts; the host renders the owned records' strings and nothing else.  What the
+    road over scan_strings raised is raised still, in the same order: the first string that does not parse, then per owned record what record_fields refuses or
+    the nonce that is not on the curve, then a malformed record, then what record_plaintext refuses."""
+    found = decrypt_strings(batch, view_key, ax)
+    if found.unparsed: RecordCiphertext.from_string(batch.string(found.first_unparsed))
+    for k, i in enumerate(found.index.tolist()):
+        if found.status[k] == 4: RecordCiphertext.from_string(batch.string(i)).fields()
+        if found.status[k] == 2 and found.kind[k] == OWNER_PUBLIC: raise AleoMi355xError('decrypt_owned: record %d has a nonce that is not on the curve' % i)
+    bad = np.flatnonzero(found.status != 0)
+    if len(bad): raise AleoMi355xError('decrypt_owned: record %d is malformed' % int(found.index[bad[0]]))
+    return [(i, RecordCiphertext(batch.string(i), int(found.kind[k]), b'', b'').plaintext(found.fields(k), ax)) for k, i in enumerate(found.index.tolist())]
 
 
 def _decrypt_found(recs, fields, rvks, ax: bytes):

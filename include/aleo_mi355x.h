@@ -585,8 +585,8 @@ int32_t aleo_mi355x_records_scan_strings_host(uint8_t* flags, int8_t* kinds, voi
  *                  the bytes do not depend on it).  Thread-safe (one slot per call); n = 0 and records without fields are fine.
  *   records_decrypt_fields_host   the same bytes, computed on the CPU by the calling thread; touches no device.
  *   min_decrypt    the size, counted in permutations (the sum of ceil(m / 8) over the records), from which records_decrypt_fields takes the GPU; a call
- *                  below it runs on the calling thread.  The default, 64, is NOT a measured crossover: no GPU run could be made when this was written (profiles/records_decrypt.txt says what is missing); it is the
- *                  crossover measured for the scan (min_records), whose small calls have the same shape, one wave running one dependent chain. ALEO_MI355X_MIN_DECRYPT overrides it, read per call.
+ *                  below it runs on the calling thread.  The default, 64, is the measured crossover against the host path on one thread (profiles/records_decrypt.txt:
+ *                  records of two fields, 0.99x at 2^5, 2.68x at 2^6, and the GPU ahead at every larger size); ALEO_MI355X_MIN_DECRYPT overrides it, read per call.
  *   record_fields  host: the private fields of a "record1..." string in randomizer order, 32 B each, into fields_out (room for `cap` fields); *n_fields_out = their
  *                  number.  fields_out = NULL only counts.  Refuses whatever record_parse refuses, an entry without a known visibility, a private entry
  *                  whose length is not that of its field count or whose fields are not canonical.
@@ -610,6 +610,46 @@ size_t aleo_mi355x_min_decrypt(void);
 int32_t aleo_mi355x_record_fields(const char* record1, void* fields_out, size_t cap, size_t* n_fields_out);
 int32_t aleo_mi355x_record_plaintext(const char* record1, const void* plain_fields, size_t n_fields, const void* address_x32, char* out, size_t* out_len);
 int32_t aleo_mi355x_record_decrypt(const char* record1, const void* view_key32, const void* address_x32, char* out, size_t* out_len);
+/* The records ONE account owns among n strings, decrypted, in one call (csrc/records_found.hip): the scan of records_scan_strings, and then — on the device, from
+ * the symbols the scan has left there — the private fields of every record with flag 1, their decryption, and the `microcredits` entry.  Only the owned records
+ * come back.  text / offsets: the contract of records_scan_strings; the same arguments are refused with the same messages; n = 0 gives an empty result.
+ *   *out          a result the library owns (its size is known only after the scan): read it through the accessors, whose pointers are valid until found_free.
+ *                 The c records whose scan flag is 1 (a public owner equal to the address included), in ascending record index:
+ *     found_count         c
+ *     found_index         uint32_t[c]       the record indices, ascending
+ *     found_kind          int8_t[c]         0 public owner, 1 private owner
+ *     found_rvk           uint8_t[c][32]    the scan's row: the record view key's x, zeros where a public owner's nonce is not on the curve
+ *     found_offsets       uint32_t[c + 1]   record k has the plain fields offsets[k] .. offsets[k + 1];  found_fields = offsets[c]
+ *     found_plain         uint8_t[fields][32]   the decrypted private fields in randomizer order; a private owner's first one is the address x
+ *     found_status        uint8_t[c]        0 decrypted; 2 malformed, as records_decrypt_fields flags it, and a public owner with private fields whose nonce
+ *                                           is not on the curve: the rows are zeros; 4 record_fields refuses the string's structure (an entry without a valid
+ *                                           name or a known visibility, a private entry whose length is not that of its field count or that holds a field not
+ *                                           below r): no fields
+ *     found_microcredits  uint64_t[c]       the value of the record's last entry named microcredits if it is a u64 literal — private: read from its plain
+ *                                           fields' bits; constant or public: from its plaintext bytes — else 0, and 0 where the status is not 0.  What
+ *                                           RecordPlaintext.microcredits() reads from the string of record_plaintext, with ONE difference: only that entry is
+ *                                           examined, so a record in which ANOTHER entry cannot be rendered still reports its microcredits here.
+ *     found_unparsed, found_first_unparsed   how many strings do not parse (flag 3 of the scan), and the first of them (n if none)
+ *   records_decrypt_strings   n below min_records runs on the calling thread; else per chunk of whole records (the caps of records_scan_strings): parse, scan and
+ *                 resolve as records_scan_strings, a count walk and a two-level prefix sum, one 16-byte read, a gather walk into compacted arrays,
+ *                 k_records_decrypt over them in place (several launches above 2^22 fields; ALEO_MI355X_DECRYPT_CHUNK_FIELDS applies), the microcredits, and the
+ *                 download of the compacted arrays.  Returns byte for byte what records_decrypt_strings_host returns.  Thread-safe (one slot per call).
+ *   records_decrypt_strings_host   the existing host calls put together: the host scan, record_fields' structure, records_decrypt_fields_host; touches no device. */
+typedef struct aleo_mi355x_found aleo_mi355x_found;
+int32_t aleo_mi355x_records_decrypt_strings(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_key32, const void* address_x32);
+int32_t aleo_mi355x_records_decrypt_strings_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_key32, const void* address_x32);
+void aleo_mi355x_found_free(aleo_mi355x_found* found);
+size_t aleo_mi355x_found_count(const aleo_mi355x_found* found);
+const uint32_t* aleo_mi355x_found_index(const aleo_mi355x_found* found);
+const int8_t* aleo_mi355x_found_kind(const aleo_mi355x_found* found);
+const uint8_t* aleo_mi355x_found_rvk(const aleo_mi355x_found* found);
+const uint32_t* aleo_mi355x_found_offsets(const aleo_mi355x_found* found);
+size_t aleo_mi355x_found_fields(const aleo_mi355x_found* found);
+const uint8_t* aleo_mi355x_found_plain(const aleo_mi355x_found* found);
+const uint8_t* aleo_mi355x_found_status(const aleo_mi355x_found* found);
+const uint64_t* aleo_mi355x_found_microcredits(const aleo_mi355x_found* found);
+size_t aleo_mi355x_found_unparsed(const aleo_mi355x_found* found);
+size_t aleo_mi355x_found_first_unparsed(const aleo_mi355x_found* found);
 
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */

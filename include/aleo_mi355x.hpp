@@ -12,7 +12,7 @@
 //       to one circuit, `prove_batch(&[assignment])` -> Proof, Proof Display as bech32m `proof1…`; `prove_batch(keys -> assignments)` over several
 //       keys and `Trace::prove_execution / prove_fee` above it (rows a6 / a7 of SURVEY.md §8)
 //   snarkvm_console_program::Record<N, Ciphertext<N>>::{from_str, is_owner, decrypt} and the record search around it (RecordCiphertext, RecordPlaintext,
-//   find_owned, find_owned_many, decrypt_owned; RecordBatch: the same three straight from "record1…" strings)
+//   find_owned, find_owned_many, decrypt_owned; RecordBatch: the same three straight from "record1…" strings; decrypt_strings, balance: one call down to plain fields)
 // Layouts are snarkVM's: Fr = 4 x u64 Montgomery, scalar = 4 x u64 canonical, G1Affine = 104 bytes, Projective = 144 bytes.
 #pragma once
 #include <chrono>
@@ -681,6 +681,52 @@ inline Result<std::vector<DecryptedRecord>> decrypt_owned(const RecordBatch& bat
   if (dec.value->size() != mine.size()) return Out{std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
   for (size_t j = 0; j < mine.size(); ++j) (*dec.value)[j].index = (*found.value)[j].index;
   return dec;
+}
+
+// What decrypt_strings returns: the records one account owns among a batch of strings, decrypted (aleo_mi355x_records_decrypt_strings).  Owns the library's
+// result; the pointers are valid while it lives.  Record k of the size() owned ones, in ascending index: index()[k], kind()[k] (0 public owner, 1 private),
+// rvk(k), its n_fields(k) plain fields from fields(k) on in randomizer order, status()[k] (0 decrypted, 2 malformed: zero rows, 4 the structure is refused: no
+// fields) and microcredits()[k].  unparsed() strings do not parse, first_unparsed() is the first of them (the batch's size if none).
+class FoundRecords {
+ public:
+  explicit FoundRecords(aleo_mi355x_found* f) : f_(f) {}
+  FoundRecords(FoundRecords&& o) noexcept : f_(o.f_) { o.f_ = nullptr; }
+  FoundRecords& operator=(FoundRecords&& o) noexcept { if (this != &o) { aleo_mi355x_found_free(f_); f_ = o.f_; o.f_ = nullptr; } return *this; }
+  FoundRecords(const FoundRecords&) = delete; FoundRecords& operator=(const FoundRecords&) = delete;
+  ~FoundRecords() { aleo_mi355x_found_free(f_); }
+  size_t size() const { return aleo_mi355x_found_count(f_); }
+  const uint32_t* index() const { return aleo_mi355x_found_index(f_); }
+  const int8_t* kind() const { return aleo_mi355x_found_kind(f_); }
+  const uint8_t* rvk(size_t k) const { return aleo_mi355x_found_rvk(f_) + 32 * k; }
+  const uint32_t* offsets() const { return aleo_mi355x_found_offsets(f_); }
+  size_t total_fields() const { return aleo_mi355x_found_fields(f_); }
+  size_t n_fields(size_t k) const { return offsets()[k + 1] - offsets()[k]; }
+  const uint8_t* fields(size_t k) const { return aleo_mi355x_found_plain(f_) + 32 * (size_t)offsets()[k]; }
+  const uint8_t* status() const { return aleo_mi355x_found_status(f_); }
+  const uint64_t* microcredits() const { return aleo_mi355x_found_microcredits(f_); }
+  size_t unparsed() const { return aleo_mi355x_found_unparsed(f_); }
+  size_t first_unparsed() const { return aleo_mi355x_found_first_unparsed(f_); }
+ private:
+  aleo_mi355x_found* f_;
+};
+// One call: scan, gather, decrypt and microcredits on the device; only the owned records come back.  A string that does not parse is counted, not an error.
+inline Result<FoundRecords> decrypt_strings(const RecordBatch& batch, const ViewKey& vk, const Address& address) {
+  aleo_mi355x_found* f = nullptr;
+  int32_t rc = aleo_mi355x_records_decrypt_strings(&f, batch.text(), batch.offsets(), batch.size(), vk.scalar, address.x);
+  if (rc) return {std::nullopt, Error{rc}};
+  return {FoundRecords(f), Error{0}};
+}
+// The sum of the microcredits of the records the account owns (those with status 0) and the indices of all it owns: the reference's get_unspent_records sum
+// (rust/src/api/blocking.rs:274-283) without the spent check.  A string that does not parse fails the call with what RecordCiphertext::from_string returns for it.
+struct Balance { unsigned __int128 microcredits; std::vector<size_t> indices; };
+inline Result<Balance> balance(const RecordBatch& batch, const ViewKey& vk, const Address& address) {
+  auto found = decrypt_strings(batch, vk, address);
+  if (!found.is_ok()) return {std::nullopt, found.error};
+  const FoundRecords& f = *found.value;
+  if (f.unparsed()) { auto r = RecordCiphertext::from_string(batch.string(f.first_unparsed())); return {std::nullopt, r.is_ok() ? Error{ALEO_MI355X_ERR_BAD_ARG} : r.error}; }
+  Balance b{0, {}};
+  for (size_t k = 0; k < f.size(); ++k) { b.indices.push_back(f.index()[k]); if (f.status()[k] == 0) b.microcredits += f.microcredits()[k]; }
+  return {std::move(b), Error{0}};
 }
 
 }  // namespace aleo_mi355x
