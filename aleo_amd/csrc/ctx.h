@@ -215,6 +215,9 @@ int32_t msm_run1_split(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const
 // msm.hip: self-tests of the device group law
 int32_t selftest_madd28(Ctx* c, uint32_t lanes, uint32_t steps, uint64_t seed, uint32_t* failures);
 int32_t selftest_addquad(Ctx* c, uint32_t ops, uint64_t seed, uint32_t* failures);
+// selftest_f28.hip: the formulas of fp28.h on rows of raw limbs from the host (pair and quad additions, mixed additions), raw limbs back
+int32_t selftest_f28_rows(Ctx* c, const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224,
+                          const void* acc224, const void* pt112, uint32_t n_madd, void* out_acc224, uint8_t* ok_u8);
 // msm_sort.hip: the slice stage (bucket scan, top scan, slice ordering) on a host histogram, checked against a host recount
 int32_t selftest_slice_order(Ctx* c, const uint32_t* h_hist, uint32_t M, uint32_t pairs, bool fused, uint32_t* violations);
 // g1_setup.hip: synthetic base sets, the fixed-base tables, row formats

@@ -13,7 +13,12 @@
 // a squaring doubles the cross terms: 7 * 2 * k^2 + 14 < 256 (L3: 140, L4: 238); muladd adds both products' terms.
 // sub<K, S>(a, b) = a - b + K*q limb-wise, with K*q spread so that every limb of the constant is >= S * 2^28 - S:
 // needs b's limbs < S * 2^28 - S + (K*q)_i and b < K*q as a value; the result's limbs are < a_max + (S + 1) * 2^28.
+//
+// Two parts.  Everything that touches F28::v or a device builtin sits behind ALEO_F28_PROVIDED; the four point formulas below it use only those
+// names.  tests/cpp/fp28_bounds_emul.cpp defines the macro, supplies the same names on the host over limbs that carry their bounds along, and
+// includes this file: every "class Lk", "< k q" and column claim of the formulas is then checked mechanically (tests/test_fp28_bounds.py).
 #pragma once
+#ifndef ALEO_F28_PROVIDED
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fp.h"
@@ -131,34 +136,7 @@ __device__ __forceinline__ void store_affine28(void* p, const F28& x, const F28&
   for (int i = 0; i < 7; ++i) d[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
 }
 
-// ---- the mixed addition of the accumulation loop (EFD madd-2008-s, same formulas as ec.h xyzz_madd_fast) -----------------
-// Invariant of acc between additions: X exact digits < 12q; Y < 2q as exact digits (or the first point's 2q - y, class L2);
-// ZZ, ZZZ exact digits < 2q.  x2, y2: table entries, canonical exact digits (y2 may be the L2 negation 2q - y).
-// Returns false — acc untouched — when P == +-acc (ZZ3 == 0 mod q); the caller finishes the slice with the general 32-bit code.
 struct XYZZ28 { F28 X, Y, ZZ, ZZZ; };
-
-__device__ __forceinline__ bool xyzz28_madd_fast(XYZZ28& acc, const F28& x2, const F28& y2) {
-  // operand order: the product block works in place on its FIRST argument, so the argument that dies there goes first
-  F28 U2 = f28_mul(x2, acc.ZZ);                              // < 2q
-  F28 S2 = f28_mul(y2, acc.ZZZ);                             // L2 x L1 -> < 2q
-  F28 P = f28_sub<16, 1>(U2, acc.X);                         // U2 + 16q - X1 < 18q, class L3
-  F28 R = f28_sub<4, 2>(S2, acc.Y);                          // Y1 limbs < 2^29 - 2; S2 + 4q - Y1 < 6q, class L4
-  F28 PP = f28_sqr(P);                                       // L3 squared: 140 < 256; 324/38000 + 1 -> < 2q
-  F28 ZZ3 = f28_mul(acc.ZZ, PP);                             // < 2q (copy: acc must survive a failed check)
-  if (__builtin_expect(f28_is_zero_mod_lt2q(ZZ3), 0)) return false;
-  F28 PPP = f28_mul(P, PP);                                  // L3 x L1 -> < 2q
-  F28 Q = f28_mul(acc.X, PP);                                // < 2q
-  F28 RR = f28_sqr(R);                                       // L4 squared: 238 < 256 -> < 2q
-  F28 t0 = f28_sub<4, 1>(RR, PPP);                           // < 6q, class L3
-  F28 X3 = f28_normalise(f28_sub<6, 2>(t0, f28_add(Q, Q)));  // 2Q: class L2, < 4q; X3 < 12q; exact digits (it is the next P's subtrahend)
-  F28 t1 = f28_sub<16, 1>(Q, X3);                            // Q + 16q - X3 < 18q, class L3
-  F28 nY = f28_sub<4, 2>(f28_const(Limbs14{}), acc.Y);       // 4q - Y1 <= 4q, class L3
-  acc.Y = f28_muladd(R, t1, nY, PPP);                        // R*t1 - Y1*PPP: 14*(4*3 + 3*1) + 14 = 224 < 256; (108 + 8)/38000 + 1 -> < 2q
-  acc.X = X3;
-  acc.ZZ = ZZ3;
-  acc.ZZZ = f28_mul(acc.ZZZ, PPP);                           // < 2q
-  return true;
-}
 
 // ---- XYZZ points stored in the 28-bit form: 224 bytes, X[14] | Y[14] | ZZ[14] | ZZZ[14] --------------------------------
 // Stored invariant: X exact digits < 12q; Y class L3, < 6q; ZZ, ZZZ exact digits < 2q; infinity <=> ZZ all zero.
@@ -191,7 +169,16 @@ __device__ __forceinline__ XYZZ load_xyzz_from28(const void* p) {
   return r;
 }
 
-// ---- lane-pair cooperative addition in the 28-bit form (same level plan as ec.h xyzz_add_pair) ---------------------------
+// exact-digit value equals k*q for k in {1, 2, 3}
+__device__ __forceinline__ bool f28_is_small_multiple_of_q(const F28& a) {
+  constexpr Limbs14 q1 = spread_kq(1, 0), q2 = spread_kq(2, 0), q3 = spread_kq(3, 0);
+  uint32_t e1 = 0, e2 = 0, e3 = 0;
+#pragma unroll
+  for (int i = 0; i < 14; ++i) { e1 |= a.v[i] ^ q1.v[i]; e2 |= a.v[i] ^ q2.v[i]; e3 |= a.v[i] ^ q3.v[i]; }
+  return e1 == 0 || e2 == 0 || e3 == 0;
+}
+
+// ---- what the lane-pair and lane-quad forms need from the wave: exchanges, selects, their lane number, raw copies ------------------------
 __device__ __forceinline__ F28 f28_xchg(const F28& a) {
   F28 r;
 #ifdef ALEO_XCHG_BPERMUTE
@@ -209,6 +196,66 @@ __device__ __forceinline__ F28 f28_sel(bool take_b, const F28& a, const F28& b) 
   for (int i = 0; i < 14; ++i) r.v[i] = take_b ? b.v[i] : a.v[i];
   return r;
 }
+template <int S0, int S1, int S2, int S3> __device__ __forceinline__ F28 f28_qperm(const F28& a) {
+  F28 r;
+#pragma unroll
+  for (int i = 0; i < 14; ++i) r.v[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)a.v[i], S0 | (S1 << 2) | (S2 << 4) | (S3 << 6), 0xF, 0xF, true);
+  return r;
+}
+__device__ __forceinline__ uint32_t f28_lane() { return threadIdx.x; }      // the formulas mask it themselves (& 1, & 3): a helper that masks changes the quad kernels' registers
+// the flag of the pair's even lane / of lane 1 of the quad, in every lane of it
+__device__ __forceinline__ int f28_pair_flag_of_even(int z) { return __shfl(z, (int)(threadIdx.x & 63u & ~1u)); }
+__device__ __forceinline__ int f28_quad_flag_of_lane1(int z) { return __builtin_amdgcn_mov_dpp(z, 1 | (1 << 2) | (1 << 4) | (1 << 6), 0xF, 0xF, true); }
+// half a stored point (X | Y or ZZ | ZZZ) zeroed; the half / the quarter (one coordinate) at byte `off` copied from one point to another
+__device__ __forceinline__ void f28_zero_half(char* d) {
+  uint4* d4 = (uint4*)d;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) d4[i] = make_uint4(0, 0, 0, 0);
+}
+__device__ __forceinline__ void f28_copy_half(char* out, const char* src, uint32_t off) {
+  const uint4* s4 = (const uint4*)(src + off); uint4* d4 = (uint4*)(out + off);
+#pragma unroll
+  for (int i = 0; i < 7; ++i) d4[i] = s4[i];
+}
+__device__ __forceinline__ void f28_copy_quarter(char* out, const char* src, uint32_t off) {
+  const uint2* s2 = (const uint2*)(src + off); uint2* d2 = (uint2*)(out + off);
+#pragma unroll
+  for (int i = 0; i < 7; ++i) d2[i] = s2[i];
+}
+
+}  // namespace aleo_mi355x
+#endif  // ALEO_F28_PROVIDED
+
+namespace aleo_mi355x {
+
+// ---- the mixed addition of the accumulation loop (EFD madd-2008-s, same formulas as ec.h xyzz_madd_fast) -----------------
+// Invariant of acc between additions: X exact digits < 12q; Y < 2q as exact digits (or the first point's 2q - y, class L2);
+// ZZ, ZZZ exact digits < 2q.  x2, y2: table entries, canonical exact digits (y2 may be the L2 negation 2q - y).
+// Returns false — acc untouched — when P == +-acc (ZZ3 == 0 mod q); the caller finishes the slice with the general 32-bit code.
+__device__ __forceinline__ bool xyzz28_madd_fast(XYZZ28& acc, const F28& x2, const F28& y2) {
+  // operand order: the product block works in place on its FIRST argument, so the argument that dies there goes first
+  F28 U2 = f28_mul(x2, acc.ZZ);                              // < 2q
+  F28 S2 = f28_mul(y2, acc.ZZZ);                             // L2 x L1 -> < 2q
+  F28 P = f28_sub<16, 1>(U2, acc.X);                         // U2 + 16q - X1 < 18q, class L3
+  F28 R = f28_sub<4, 2>(S2, acc.Y);                          // Y1 limbs < 2^29 - 2; S2 + 4q - Y1 < 6q, class L4
+  F28 PP = f28_sqr(P);                                       // L3 squared: 140 < 256; 324/38000 + 1 -> < 2q
+  F28 ZZ3 = f28_mul(acc.ZZ, PP);                             // < 2q (copy: acc must survive a failed check)
+  if (__builtin_expect(f28_is_zero_mod_lt2q(ZZ3), 0)) return false;
+  F28 PPP = f28_mul(P, PP);                                  // L3 x L1 -> < 2q
+  F28 Q = f28_mul(acc.X, PP);                                // < 2q
+  F28 RR = f28_sqr(R);                                       // L4 squared: 238 < 256 -> < 2q
+  F28 t0 = f28_sub<4, 1>(RR, PPP);                           // < 6q, class L3
+  F28 X3 = f28_normalise(f28_sub<6, 2>(t0, f28_add(Q, Q)));  // 2Q: class L2, < 4q; X3 < 12q; exact digits (it is the next P's subtrahend)
+  F28 t1 = f28_sub<16, 1>(Q, X3);                            // Q + 16q - X3 < 18q, class L3
+  F28 nY = f28_sub<4, 2>(f28_const(Limbs14{}), acc.Y);       // 4q - Y1 <= 4q, class L3
+  acc.Y = f28_muladd(R, t1, nY, PPP);                        // R*t1 - Y1*PPP: 14*(4*3 + 3*1) + 14 = 224 < 256; (108 + 8)/38000 + 1 -> < 2q
+  acc.X = X3;
+  acc.ZZ = ZZ3;
+  acc.ZZZ = f28_mul(acc.ZZZ, PPP);                           // < 2q
+  return true;
+}
+
+// ---- lane-pair cooperative addition in the 28-bit form (same level plan as ec.h xyzz_add_pair) ---------------------------
 // 2P for a stored 28-bit XYZZ point (EFD dbl-2008-s-1, a = 0), the same-point case of the pair addition.  Both lanes of the pair run
 // the whole doubling on the same operands (8.5 product times, no exchanges) and each stores its half of the result: the case is
 // rare on dense data but systematic on sparse data, where the running sum of a bucket chunk meets an unchanged `run` a second time
@@ -216,15 +263,13 @@ __device__ __forceinline__ F28 f28_sel(bool take_b, const F28& a, const F28& b) 
 // (~40 us, once per chunk): 4 x 2^15 sparse buckets took 339 us against 86 us for dense ones.
 // Bounds: X exact < 12q, Y class L3 < 6q, ZZ / ZZZ exact < 2q (the stored invariant); results satisfy it again.
 __device__ __forceinline__ void xyzz28_double_both(const char* pa, char* out) {
-  const bool odd = threadIdx.x & 1;
+  const bool odd = f28_lane() & 1;
   const F28 X = load_f28(pa), Y = load_f28(pa + 56), ZZ = load_f28(pa + 112), ZZZ = load_f28(pa + 168);
   const F28 U = f28_normalise(f28_add(Y, Y));                            // 2Y < 12q, exact digits
   const F28 V = f28_sqr(U);                                              // 144/38000 + 1 -> < 2q
   const F28 ZZ3 = f28_mul(ZZ, V);                                        // < 2q
   if (__builtin_expect(f28_is_zero_mod_lt2q(ZZ3), 0)) {                  // Y == 0: a 2-torsion point doubles to the identity
-    uint4* d4 = (uint4*)(out + (odd ? 112 : 0));
-#pragma unroll
-    for (int i = 0; i < 7; ++i) d4[i] = make_uint4(0, 0, 0, 0);
+    f28_zero_half(out + (odd ? 112 : 0));
     return;
   }
   const F28 W = f28_mul(U, V);                                           // < 2q
@@ -240,25 +285,13 @@ __device__ __forceinline__ void xyzz28_double_both(const char* pa, char* out) {
   if (odd) { store_f28(out, X3); store_f28(out + 56, Y3); }
   else { store_f28(out + 112, ZZ3); store_f28(out + 168, ZZZ3); }
 }
-// exact-digit value equals k*q for k in {1, 2, 3}
-__device__ __forceinline__ bool f28_is_small_multiple_of_q(const F28& a) {
-  constexpr Limbs14 q1 = spread_kq(1, 0), q2 = spread_kq(2, 0), q3 = spread_kq(3, 0);
-  uint32_t e1 = 0, e2 = 0, e3 = 0;
-#pragma unroll
-  for (int i = 0; i < 14; ++i) { e1 |= a.v[i] ^ q1.v[i]; e2 |= a.v[i] ^ q2.v[i]; e3 |= a.v[i] ^ q3.v[i]; }
-  return e1 == 0 || e2 == 0 || e3 == 0;
-}
 __device__ __forceinline__ void xyzz28_add_pair(const char* pa, const char* pb, char* out) {
-  const bool odd = threadIdx.x & 1;
+  const bool odd = f28_lane() & 1;
   const F28 zzA = load_f28(pa + 112), zzB = load_f28(pb + 112);
   const bool infA = f28_is_zero_raw(zzA), infB = f28_is_zero_raw(zzB);
   if (infA || infB) {              // pair-uniform: both lanes see the same two points
     const char* src = infB ? pa : pb;          // A + O = A ; O + B = B ; O + O = O (either)
-    if (src != out) {              // each lane copies half of the 224 bytes
-      const uint4* s4 = (const uint4*)(src + (odd ? 112 : 0)); uint4* d4 = (uint4*)(out + (odd ? 112 : 0));
-#pragma unroll
-      for (int i = 0; i < 7; ++i) d4[i] = s4[i];
-    }
+    if (src != out) f28_copy_half(out, src, odd ? 112 : 0);      // each lane copies half of the 224 bytes
     return;
   }
   const char* own = odd ? pb : pa; const char* oth = odd ? pa : pb;
@@ -281,14 +314,10 @@ __device__ __forceinline__ void xyzz28_add_pair(const char* pa, const char* pb, 
   // same-x case: ZZ3 == 0 mod q, seen by the even lane.  Same point (S1 == S2 mod q: S2 + 2q - S1 is q, 2q or 3q) -> doubling;
   // opposite points -> the identity.  Both in the 28-bit form, in line.
   int z = (!odd && f28_is_zero_mod_lt2q(t6)) ? 1 : 0;
-  z = __shfl(z, (int)(threadIdx.x & 63u & ~1u));
+  z = f28_pair_flag_of_even(z);
   if (__builtin_expect(z, 0)) {
     if (f28_is_small_multiple_of_q(f28_normalise(f28_sub<2, 1>(S2, S1)))) xyzz28_double_both(pa, out);
-    else {
-      uint4* d4 = (uint4*)(out + (odd ? 112 : 0));
-#pragma unroll
-      for (int i = 0; i < 7; ++i) d4[i] = make_uint4(0, 0, 0, 0);
-    }
+    else f28_zero_half(out + (odd ? 112 : 0));
     return;
   }
   if (odd) { store_f28(out, X3); store_f28(out + 56, f28_sub<4, 1>(t7, t6)); }   // Y3 = Rt - SP: class L3, < 6q
@@ -304,23 +333,13 @@ __device__ __forceinline__ void xyzz28_add_pair(const char* pa, const char* pb, 
 //   level 4   q0: R (Q - X3)      q1: ZZ3 = ZZ12 PP    q2: S1 PPP           q3: ZZZ3 = ZZZ12 PPP    (X3 = RR - PPP - 2Q in every lane)
 // with quad_perm DPP moves between the levels (values never leave the quad's registers).  Same formulas, bounds and stored invariants as
 // xyzz28_add_pair; the rare same-x case (doubling / identity) is handed to the pair form on lanes 0, 1 of the quad.
-template <int S0, int S1, int S2, int S3> __device__ __forceinline__ F28 f28_qperm(const F28& a) {
-  F28 r;
-#pragma unroll
-  for (int i = 0; i < 14; ++i) r.v[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)a.v[i], S0 | (S1 << 2) | (S2 << 4) | (S3 << 6), 0xF, 0xF, true);
-  return r;
-}
 __device__ __forceinline__ void xyzz28_add_quad(const char* pa, const char* pb, char* out) {
-  const uint32_t q = threadIdx.x & 3u; const bool odd = q & 1u, hi = q & 2u;
+  const uint32_t q = f28_lane() & 3u; const bool odd = q & 1u, hi = q & 2u;
   const F28 zzA = load_f28(pa + 112), zzB = load_f28(pb + 112);
   const bool infA = f28_is_zero_raw(zzA), infB = f28_is_zero_raw(zzB);
   if (infA || infB) {              // quad-uniform: all four lanes see the same two points
     const char* src = infB ? pa : pb;          // A + O = A ; O + B = B ; O + O = O (either)
-    if (src != out) {              // each lane copies a quarter of the 224 bytes
-      const uint2* s2 = (const uint2*)(src + 56 * q); uint2* d2 = (uint2*)(out + 56 * q);
-#pragma unroll
-      for (int i = 0; i < 7; ++i) d2[i] = s2[i];
-    }
+    if (src != out) f28_copy_quarter(out, src, 56 * q);      // each lane copies a quarter of the 224 bytes
     return;
   }
   const char* own = odd ? pb : pa; const char* oth = odd ? pa : pb;
@@ -343,7 +362,7 @@ __device__ __forceinline__ void xyzz28_add_quad(const char* pa, const char* pb, 
   const F28 t4 = f28_mul(a4, b4);                                               // q0: Rt   q1: ZZ3   q2: SP   q3: ZZZ3
   // same-x case: ZZ3 == 0 mod q, seen by lane 1 of the quad
   int z = (q == 1 && f28_is_zero_mod_lt2q(t4)) ? 1 : 0;
-  z = __builtin_amdgcn_mov_dpp(z, 1 | (1 << 2) | (1 << 4) | (1 << 6), 0xF, 0xF, true);
+  z = f28_quad_flag_of_lane1(z);
   if (__builtin_expect(z, 0)) {
     if (q < 2) xyzz28_add_pair(pa, pb, out);      // lanes 0, 1 of the quad are a lane pair: the pair form doubles or writes the identity
     return;

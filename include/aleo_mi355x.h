@@ -484,6 +484,14 @@ int32_t aleo_mi355x_selftest_madd28(uint32_t lanes, uint32_t steps, uint64_t see
 /* The lane-quad XYZZ addition of the reduction chains against the lane-pair one on `ops` random operand pairs and the special cases
  * (identity operands, equal points, opposite points): *failures = number of disagreements (mod q, all four coordinates). */
 int32_t aleo_mi355x_selftest_addquad(uint32_t ops, uint64_t seed, uint32_t* failures);
+/* The same formulas on rows the caller built, raw 28-bit limbs in and out (host memory; the device converts nothing), so that a test can place
+ * representatives at the edges of the stored invariant (X exact digits < 12q; Y limbs < 3 * 2^28, < 6q; ZZ, ZZZ exact digits < 2q; identity <=> ZZ all zero)
+ * and compare with the group law in integers.  Additions: a224[i] + b224[i] (224-byte rows X | Y | ZZ | ZZZ of 14 limbs each) by one lane quad per row, into
+ * out_quad224[i]; lanes 0 and 1 of the quad run the lane-pair form into out_pair224[i].  Mixed additions: acc224[i] (X exact < 12q, Y exact < 2q or the
+ * limb-wise 2q - y, ZZ / ZZZ exact < 2q) + pt112[i] (x | y canonical, or y the limb-wise 2q - y) by one lane per row; out_acc224[i] = acc afterwards,
+ * ok_u8[i] = what the formula returned (0: the point is +-acc and acc is untouched).  Either count may be 0 (its pointers are then ignored); at most 2^20. */
+int32_t aleo_mi355x_selftest_f28_rows(const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224,
+                                      const void* acc224, const void* pt112, uint32_t n_madd, void* out_acc224, uint8_t* ok_u8);
 
 /* The slice stage of the MSM sort alone (bucket scan, top scan, slice ordering) on a histogram from the host: hist[g] = points of bucket g, n_buckets <= 2^20,
  * total_pairs = the pair count the slice rule is picked from (the sum of hist or more: less is refused); fused != 0 runs the top scan inside the ordering kernel, as the
