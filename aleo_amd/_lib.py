@@ -31,6 +31,7 @@ EXPORTS = [
     'aleo_mi355x_records_decrypt_strings', 'aleo_mi355x_records_decrypt_strings_host', 'aleo_mi355x_found_free', 'aleo_mi355x_found_count', 'aleo_mi355x_found_index',
     'aleo_mi355x_found_kind', 'aleo_mi355x_found_rvk', 'aleo_mi355x_found_offsets', 'aleo_mi355x_found_fields', 'aleo_mi355x_found_plain', 'aleo_mi355x_found_status',
     'aleo_mi355x_found_microcredits', 'aleo_mi355x_found_unparsed', 'aleo_mi355x_found_first_unparsed',
+    'aleo_mi355x_records_decrypt_strings_many', 'aleo_mi355x_records_decrypt_strings_many_host',
 ]
 
 
@@ -188,6 +189,8 @@ def lib():
         'aleo_mi355x_record_decrypt': ([ctypes.c_char_p, vp, vp, ctypes.c_char_p, ctypes.POINTER(sz)], i32),
         'aleo_mi355x_records_decrypt_strings': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp], i32),
         'aleo_mi355x_records_decrypt_strings_host': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp], i32),
+        'aleo_mi355x_records_decrypt_strings_many': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, sz], i32),
+        'aleo_mi355x_records_decrypt_strings_many_host': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, sz], i32),
         'aleo_mi355x_found_free': ([vp], None),
         **{'aleo_mi355x_found_' + name: ([vp], sz) for name in ('count', 'fields', 'unparsed', 'first_unparsed')},
         **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits')},

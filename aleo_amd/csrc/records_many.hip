@@ -148,6 +148,22 @@ void launch_scan_one_key(hipStream_t s, uint8_t* dflags, char* drvk, const char*
   launch_many<1>(s, dflags, drvk, dc0, dnx, m, dK, dkey, 1);
 }
 
+// for records_found_many.hip, which runs the K-key scan between a parse and a walk of its own: the records of one launch and the keys of one lane, as
+// scan_many_on_device above settles them, and the launch over m records already on the device (dkeys: n_keys entries padded with zero entries to a multiple of W)
+size_t scan_many_plan(size_t n, size_t n_keys, uint32_t* W) {
+  size_t chunk = SCAN_MANY_PAIRS / n_keys; if (chunk > SCAN_MANY_RECORDS) chunk = SCAN_MANY_RECORDS; if (chunk > n) chunk = n;
+  *W = scan_many_width(chunk, n_keys);
+  return chunk;
+}
+void launch_scan_keys(hipStream_t s, uint32_t W, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkeys, size_t n_keys) {
+  switch (W) {
+    case 8: launch_many<8>(s, dflags, drvk, dc0, dnx, m, dK, dkeys, n_keys); break;
+    case 4: launch_many<4>(s, dflags, drvk, dc0, dnx, m, dK, dkeys, n_keys); break;
+    case 2: launch_many<2>(s, dflags, drvk, dc0, dnx, m, dK, dkeys, n_keys); break;
+    default: launch_many<1>(s, dflags, drvk, dc0, dnx, m, dK, dkeys, n_keys);
+  }
+}
+
 }  // namespace aleo_mi355x
 
 using namespace aleo_mi355x;

@@ -37,6 +37,11 @@ int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32
 int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings = nullptr);
 // the one-key launch of k_records_scan_many over m records already on the device (flags m B, rvk m x 32 B); the caller checks hipGetLastError
 void launch_scan_one_key(hipStream_t s, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkey);
+// the plan of a K-key scan over n records — the records of one launch (the pair cap, the record cap, n) and *W, the keys one lane takes — and that launch over
+// m records already on the device (flags m x n_keys B, rvk m x n_keys x 32 B, [key][record]; dkeys padded with zero entries to a multiple of W); the caller
+// checks hipGetLastError
+size_t scan_many_plan(size_t n, size_t n_keys, uint32_t* W);
+void launch_scan_keys(hipStream_t s, uint32_t W, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkeys, size_t n_keys);
 
 // records_decrypt.hip
 size_t decrypt_chunk_fields();                                // the field cap of one k_records_decrypt launch (ALEO_MI355X_DECRYPT_CHUNK_FIELDS, read per call)

@@ -11,7 +11,9 @@ Callers that hold "record1…" strings — what the chain hands out — pass the
 (aleo_mi355x_records_parse_many, aleo_mi355x_records_scan_strings: csrc/records_strings.hip) decode them on the device, and find_owned, find_owned_many and
 decrypt_owned take that road for a RecordBatch or a sequence of strings, building RecordCiphertext objects only for the records they return or decrypt.
 decrypt_strings and balance (aleo_mi355x_records_decrypt_strings: csrc/records_found.hip) go from the strings of one account's search to the plain fields and
-microcredits of the records it owns in one call, and bring back only those; decrypt_owned on strings is that call and the rendering of the strings."""
+microcredits of the records it owns in one call, and bring back only those; decrypt_owned on strings is that call and the rendering of the strings.
+decrypt_strings_many, balances and decrypt_owned_many (aleo_mi355x_records_decrypt_strings_many: csrc/records_found_many.hip) are the same for several accounts
+over the same strings: one upload and parse, one grouped scan, one gather and decryption of every owned (account, record) pair."""
 from __future__ import annotations
 import ctypes
 import numpy as np
@@ -291,6 +293,11 @@ def decrypt_strings(batch, view_key, address, host: bool = False) -> FoundRecord
     L = lib(); out = ctypes.c_void_p()
     f = L.aleo_mi355x_records_decrypt_strings_host if host else L.aleo_mi355x_records_decrypt_strings
     check(f(ctypes.byref(out), _text_p(b), _p(b.offsets), len(b), _p(vk), _p(ax)), 'records_decrypt_strings')
+    return _found_of(L, out)
+
+
+def _found_of(L, out) -> FoundRecords:
+    """The numpy copies of a result of the library, which is released."""
     try:
         c, nf = int(L.aleo_mi355x_found_count(out)), int(L.aleo_mi355x_found_fields(out))
         def copy(name, dtype, count, shape):
@@ -303,15 +310,54 @@ def decrypt_strings(batch, view_key, address, host: bool = False) -> FoundRecord
         L.aleo_mi355x_found_free(out)
 
 
+def decrypt_strings_many(batch, view_keys, addresses, host: bool = False) -> list:
+    """decrypt_strings for several accounts over the same RecordBatch (or sequence of strings) in one call (aleo_mi355x_records_decrypt_strings_many / _many_host):
+    the text goes up and is parsed once, one grouped scan answers all keys, and the owned (account, record) pairs of all accounts are gathered and decrypted in
+    one pass.  Entry j of the list is, byte for byte, what decrypt_strings returns for (view_keys[j], addresses[j]) alone.  1 <= K <= 64; keys may repeat."""
+    b = _as_batch(batch)
+    if b is None: raise TypeError('decrypt_strings_many takes a RecordBatch or a sequence of strings')
+    if len(view_keys) != len(addresses): raise ValueError('view_keys and addresses differ in length')
+    k = len(view_keys)
+    vk = np.frombuffer(b''.join(view_key_bytes(v) for v in view_keys), dtype=np.uint8); ax = np.frombuffer(b''.join(address_x_bytes(a) for a in addresses), dtype=np.uint8)
+    L = lib(); out = (ctypes.c_void_p * max(k, 1))()
+    f = L.aleo_mi355x_records_decrypt_strings_many_host if host else L.aleo_mi355x_records_decrypt_strings_many
+    check(f(out, _text_p(b), _p(b.offsets), len(b), _p(vk), _p(ax), k), 'records_decrypt_strings_many')
+    found = []
+    try:
+        for j in range(k): found.append(_found_of(L, ctypes.c_void_p(out[j])))
+    finally:
+        for j in range(len(found) + 1, k): L.aleo_mi355x_found_free(ctypes.c_void_p(out[j]))      # _found_of released the one it was reading
+    return found
+
+
+def _found_many(batch: RecordBatch, accounts):
+    """decrypt_strings_many for any number of (view key, address x) pairs: 64 to a call."""
+    found = []
+    for at in range(0, len(accounts), 64): found += decrypt_strings_many(batch, [vk for vk, _ in accounts[at:at + 64]], [ax for _, ax in accounts[at:at + 64]])
+    return found
+
+
 def balance(ciphertexts, view_key, address):
     """(the sum of the microcredits of the records the account owns, their indices) over a RecordBatch or a sequence of strings: the reference's
     get_unspent_records sum (rust/src/api/blocking.rs:274-283) without the spent check, in one decrypt_strings call.  Only records with status 0 count; a
     string that does not parse raises what RecordCiphertext.from_string raises."""
     b = _as_batch(ciphertexts)
     if b is None: b = RecordBatch.from_strings([str(c) for c in ciphertexts])
-    found = decrypt_strings(b, view_key, address)
+    return _balance_of(b, decrypt_strings(b, view_key, address))
+
+
+def _balance_of(b: RecordBatch, found: FoundRecords):
     if found.unparsed: RecordCiphertext.from_string(b.string(found.first_unparsed))
     return sum(int(v) for v in found.microcredits[found.status == 0]), found.index.tolist()
+
+
+def balances(ciphertexts, accounts):
+    """balance for several accounts over the same records: `accounts` is a sequence of (view_key, address) pairs, the result a list with, for each of them, what
+    balance returns — from one decrypt_strings_many call per 64 accounts.  What balance would raise for an account alone is raised, for the first such account."""
+    accounts = [(vk, address_x_bytes(a)) for vk, a in accounts]
+    b = _as_batch(ciphertexts)
+    if b is None: b = RecordBatch.from_strings([str(c) for c in ciphertexts])
+    return [_balance_of(b, found) for found in _found_many(b, accounts)]
 
 
 def decrypt_owned(ciphertexts, view_key, address):
@@ -339,11 +385,27 @@ def decrypt_owned(ciphertexts, view_key, address):
     return _decrypt_found(recs, fields, rvks, ax)
 
 
+def decrypt_owned_many(ciphertexts, accounts):
+    """decrypt_owned for several accounts over the same records: `accounts` is a sequence of (view_key, address) pairs, the result a list with, for each of them,
+    what decrypt_owned returns.  From strings or a RecordBatch it is one decrypt_strings_many call per 64 accounts and the rendering of every account's owned
+    records; RecordCiphertext objects take decrypt_owned's road account by account.  What decrypt_owned would raise for an account alone is raised, for the first
+    such account."""
+    accounts = [(vk, address_x_bytes(a)) for vk, a in accounts]
+    batch = _as_batch(ciphertexts)
+    if batch is None:
+        recs = [c if isinstance(c, RecordCiphertext) else RecordCiphertext.from_string(c) for c in ciphertexts]
+        return [decrypt_owned(recs, vk, ax) for vk, ax in accounts]
+    return [_render_found(batch, found, ax) for found, (_, ax) in zip(_found_many(batch, accounts), accounts)]
+
+
 def _decrypt_owned_strings(batch: RecordBatch, view_key, ax: bytes):
     """decrypt_owned from strings: one decrypt_strings call finds, gathers and decrypts; the host renders the owned records' strings and nothing else.  What the
     road over scan_strings raised is raised still, in the same order: the first string that does not parse, then per owned record what record_fields refuses or
     the nonce that is not on the curve, then a malformed record, then what record_plaintext refuses."""
-    found = decrypt_strings(batch, view_key, ax)
+    return _render_found(batch, decrypt_strings(batch, view_key, ax), ax)
+
+
+def _render_found(batch: RecordBatch, found: FoundRecords, ax: bytes):
     if found.unparsed: RecordCiphertext.from_string(batch.string(found.first_unparsed))
     for k, i in enumerate(found.index.tolist()):
         if found.status[k] == 4: RecordCiphertext.from_string(batch.string(i)).fields()

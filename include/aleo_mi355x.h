@@ -658,6 +658,21 @@ const uint8_t* aleo_mi355x_found_status(const aleo_mi355x_found* found);
 const uint64_t* aleo_mi355x_found_microcredits(const aleo_mi355x_found* found);
 size_t aleo_mi355x_found_unparsed(const aleo_mi355x_found* found);
 size_t aleo_mi355x_found_first_unparsed(const aleo_mi355x_found* found);
+/* records_decrypt_strings for SEVERAL accounts in one call (csrc/records_found_many.hip): what a front end asks that serves K accounts over the same blocks and
+ * needs each one's decrypted records and balance, not flags.  view_keys32 / address_xs32: n_keys x 32 bytes, 1 <= n_keys <= 64; keys, text and offsets are refused as
+ * records_scan_strings refuses them (same status, same message, "key j" included).
+ *   out           room for n_keys results: out[j] is byte for byte — every array, unparsed and first_unparsed — what records_decrypt_strings_host returns for key j
+ *                 alone over the same strings; read it through the found_* accessors above and release each with found_free.  A key that appears twice gets two equal
+ *                 results; a record that two keys own appears in both.  n = 0 gives n_keys empty results.  On any failure every out[j] is null (all n_keys of them, also
+ *                 where n_keys itself is what is refused: out has room for as many entries as the caller says).
+ *   records_decrypt_strings_many   n * n_keys below min_records (pairs, as records_scan_strings counts), or n = 0, runs on the calling thread; else per chunk of whole
+ *                 records (the caps of records_scan_strings for n_keys keys; ALEO_MI355X_SCAN_CHUNK_CHARS and ALEO_MI355X_SCAN_KEYS_PER_LANE apply): ONE upload and
+ *                 parse of the text, the grouped scan of records_scan_many, the resolve, then the count walk, prefix sums, gather walk, decryption and microcredits of
+ *                 records_decrypt_strings over every (key, record) pair that is owned — compacted by key, then by record, and sized from the pairs there are — one
+ *                 download, and the split into the n_keys results on the host.  Thread-safe (one slot per call).
+ *   records_decrypt_strings_many_host   n_keys passes of records_decrypt_strings_host's path; touches no device. */
+int32_t aleo_mi355x_records_decrypt_strings_many(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys);
+int32_t aleo_mi355x_records_decrypt_strings_many_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys);
 
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */

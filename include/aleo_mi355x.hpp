@@ -12,7 +12,8 @@
 //       to one circuit, `prove_batch(&[assignment])` -> Proof, Proof Display as bech32m `proof1…`; `prove_batch(keys -> assignments)` over several
 //       keys and `Trace::prove_execution / prove_fee` above it (rows a6 / a7 of SURVEY.md §8)
 //   snarkvm_console_program::Record<N, Ciphertext<N>>::{from_str, is_owner, decrypt} and the record search around it (RecordCiphertext, RecordPlaintext,
-//   find_owned, find_owned_many, decrypt_owned; RecordBatch: the same three straight from "record1…" strings; decrypt_strings, balance: one call down to plain fields)
+//   find_owned, find_owned_many, decrypt_owned; RecordBatch: the same three straight from "record1…" strings; decrypt_strings, balance: one call down to plain fields;
+//   decrypt_strings_many, balances: the same for several accounts in one call)
 // Layouts are snarkVM's: Fr = 4 x u64 Montgomery, scalar = 4 x u64 canonical, G1Affine = 104 bytes, Projective = 144 bytes.
 #pragma once
 #include <chrono>
@@ -727,6 +728,33 @@ inline Result<Balance> balance(const RecordBatch& batch, const ViewKey& vk, cons
   Balance b{0, {}};
   for (size_t k = 0; k < f.size(); ++k) { b.indices.push_back(f.index()[k]); if (f.status()[k] == 0) b.microcredits += f.microcredits()[k]; }
   return {std::move(b), Error{0}};
+}
+// decrypt_strings and balance for several accounts (at most 64) over the same batch in one aleo_mi355x_records_decrypt_strings_many call: the text goes up and is
+// parsed once, one grouped scan answers every account, and all owned (account, record) pairs are gathered and decrypted in one pass.  (*result)[a] is what
+// decrypt_strings / balance returns for accounts[a]; no account gives an empty list.
+inline Result<std::vector<FoundRecords>> decrypt_strings_many(const RecordBatch& batch, const std::vector<Account>& accounts) {
+  std::vector<FoundRecords> out;
+  if (accounts.empty()) return {std::move(out), Error{0}};
+  std::vector<uint8_t> vks, axs;
+  for (const auto& a : accounts) { vks.insert(vks.end(), a.view_key.scalar, a.view_key.scalar + 32); axs.insert(axs.end(), a.address.x, a.address.x + 32); }
+  std::vector<aleo_mi355x_found*> f(accounts.size(), nullptr);
+  int32_t rc = aleo_mi355x_records_decrypt_strings_many(f.data(), batch.text(), batch.offsets(), batch.size(), vks.data(), axs.data(), accounts.size());
+  if (rc) return {std::nullopt, Error{rc}};
+  out.reserve(f.size());
+  for (aleo_mi355x_found* p : f) out.emplace_back(p);
+  return {std::move(out), Error{0}};
+}
+inline Result<std::vector<Balance>> balances(const RecordBatch& batch, const std::vector<Account>& accounts) {
+  auto found = decrypt_strings_many(batch, accounts);
+  if (!found.is_ok()) return {std::nullopt, found.error};
+  std::vector<Balance> out;
+  for (const FoundRecords& f : *found.value) {
+    if (f.unparsed()) { auto r = RecordCiphertext::from_string(batch.string(f.first_unparsed())); return {std::nullopt, r.is_ok() ? Error{ALEO_MI355X_ERR_BAD_ARG} : r.error}; }
+    Balance b{0, {}};
+    for (size_t k = 0; k < f.size(); ++k) { b.indices.push_back(f.index()[k]); if (f.status()[k] == 0) b.microcredits += f.microcredits()[k]; }
+    out.push_back(std::move(b));
+  }
+  return {std::move(out), Error{0}};
 }
 
 }  // namespace aleo_mi355x
