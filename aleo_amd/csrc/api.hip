@@ -665,7 +665,6 @@ const char* aleo_mi355x_strerror(int32_t status) {
 }
 // The sizes from which the drop-in's two arms should take the GPU: measured crossovers of the COLD one-shot calls against the CPU
 // path on the same box (bench.py cpu_baseline.crossover, profiles/r04_crossover.json), overridable per deployment.
-static size_t env_size(const char* name, size_t dflt) { const char* e = std::getenv(name); if (!e || !*e) return dflt; char* end = nullptr; const unsigned long long v = std::strtoull(e, &end, 10); return end && *end == 0 ? (size_t)v : dflt; }
 size_t aleo_mi355x_min_msm(void) { return env_size("ALEO_MI355X_MIN_MSM", (size_t)1 << 10); }
 size_t aleo_mi355x_min_ntt(void) { return env_size("ALEO_MI355X_MIN_NTT", (size_t)1 << 12); }
 int32_t aleo_mi355x_selftest_host_inverse(uint32_t count, uint64_t seed, uint32_t* failures, double* ns_per_inverse) {

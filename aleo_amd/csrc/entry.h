@@ -2,6 +2,7 @@
 // on, its stream, handle lookup, and the functions that cross between those four files.  (Kernels and their hosts: ctx.h.)
 #pragma once
 #include "ctx.h"
+#include <cstdlib>
 
 namespace aleo_mi355x {
 
@@ -9,6 +10,9 @@ namespace aleo_mi355x {
 template <class F> int32_t guarded(F&& body, int32_t on_throw = ALEO_MI355X_ERR_HIP) { try { return body(); } catch (...) { return on_throw; } }
 
 inline int32_t bad_arg(const char* why) { g_last_error = why; return ALEO_MI355X_ERR_BAD_ARG; }      // a refused argument and the text that says which
+
+// A size from the environment, read per call: `dflt` where the variable is unset, empty or no decimal number.
+inline size_t env_size(const char* name, size_t dflt) { const char* e = std::getenv(name); if (!e || !*e) return dflt; char* end = nullptr; const unsigned long long v = std::strtoull(e, &end, 10); return end && *end == 0 ? (size_t)v : dflt; }
 
 // The entry behind a handle in one of the handle tables (pinned G1 and G2 sets, circuit indices, sharded sets); `take` removes it from the table as well.  The caller
 // holds the table's mutex; *out is the caller's, so what a `take` frees is freed after that lock is dropped, once no call uses it (hipFree synchronises).
@@ -36,5 +40,8 @@ int32_t one_shot_bases(Ctx* c, const void* bases, size_t stride, size_t n, std::
 int32_t one_shot_bases_g2(Ctx* c, const void* bases, size_t stride, size_t n, const void** d_xy, const uint8_t** d_inf);
 // api.hip
 int32_t batch_args_ok(const void* out, const void* const* ptrs, const size_t* lens, size_t k);
+// records.hip: *dK, the slot's device copy of the records constants (records_lane.h RK_*), uploaded on the slot's first use; every flow of the records units
+// (scan, scan_many, scan_strings, decrypt_fields, decrypt_strings) gets the table here and nowhere else
+int32_t records_constants(Ctx* c, const uint32_t** dK);
 
 }  // namespace aleo_mi355x

@@ -41,32 +41,38 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_records_scan(uint8_t* __restrict
   flags[i] = (uint8_t)flag;
 }
 
+// The constants on the device, once per slot: the flag is set only when the slot's stream has completed the copy, so a copy that fails is made again by the slot's
+// next call and never leaves an unfilled table in service.  The slot is the caller's for the duration of its call (entry.h Slot), so nothing else runs between.
+int32_t records_constants(Ctx* c, const uint32_t** dK) {
+  if (!c->records_k_ready) {
+    if (int32_t rc = c->records_k.reserve(RK_WORDS * 4)) return rc;
+    HIPCHK(hipMemcpyAsync(c->records_k.p, records_consts().words.data(), RK_WORDS * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->records_k_ready = true;
+  }
+  *dK = c->records_k.as<uint32_t>();
+  return ALEO_MI355X_OK;
+}
+
 static int32_t records_scan_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ScanArgs& a) {
-  const RecordsConsts& C = records_consts();
   const size_t chunk = n < SCAN_CHUNK ? n : SCAN_CHUNK;
   hipStream_t s = c->stream;
   int32_t rc;
-  if (!c->records_k_ready) {                                   // once per slot; the flag is set only when the stream has completed the copy (below), so a copy that
-    if ((rc = c->records_k.reserve(RK_WORDS * 4))) return rc;  // fails is made again by the slot's next scan and never leaves an unfilled table in service
-    HIPCHK(hipMemcpyAsync(c->records_k.p, C.words.data(), RK_WORDS * 4, hipMemcpyHostToDevice, s));
-  }
+  const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
   if ((rc = c->scalars_stage.reserve(chunk * 97))) return rc;
-  const char* dK = c->records_k.as<char>(); char* dc0 = c->scalars_stage.as<char>(); char* dnx = dc0 + chunk * 32; char* drvk = dnx + chunk * 32; uint8_t* dfl = (uint8_t*)(drvk + chunk * 32);
+  char* dc0 = c->scalars_stage.as<char>(); char* dnx = dc0 + chunk * 32; char* drvk = dnx + chunk * 32; uint8_t* dfl = (uint8_t*)(drvk + chunk * 32);
   for (size_t at = 0; at < n; at += chunk) {
     const size_t m = n - at < chunk ? n - at : chunk;
     HIPCHK(hipMemcpyAsync(dc0, (const char*)owner_c0 + at * 32, m * 32, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dnx, (const char*)nonce_x + at * 32, m * 32, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_records_scan, dim3((uint32_t)((m + SCAN_BLOCK - 1) / SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, s, dfl, drvk, (const char*)dc0, (const char*)dnx, (uint32_t)m, (const uint32_t*)dK, a);
+    hipLaunchKernelGGL(k_records_scan, dim3((uint32_t)((m + SCAN_BLOCK - 1) / SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, s, dfl, drvk, (const char*)dc0, (const char*)dnx, (uint32_t)m, dK, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));
     if (rvk_out) HIPCHK(hipMemcpyAsync((char*)rvk_out + at * 32, drvk, m * 32, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
-    c->records_k_ready = true;                               // the constants arrived: this chunk ran behind their copy on the same stream
   }
   return ALEO_MI355X_OK;
 }
-
-static size_t env_size(const char* name, size_t dflt) { const char* e = std::getenv(name); if (!e || !*e) return dflt; char* end = nullptr; const unsigned long long v = std::strtoull(e, &end, 10); return end && *end == 0 ? (size_t)v : dflt; }
 
 }  // namespace aleo_mi355x
 

@@ -25,8 +25,6 @@ static constexpr uint32_t DECRYPT_BLOCK = 256;
 static constexpr size_t DECRYPT_CHUNK_RECORDS = (size_t)1 << 20, DECRYPT_CHUNK_FIELDS = (size_t)1 << 22;      // per launch: 37 B a record and 32 B a field of slot scratch (~170 MB)
 static constexpr size_t DECRYPT_MAX_FIELDS = 65535;        // of one record: upstream's u16 field count
 
-static size_t env_size(const char* name, size_t dflt) { const char* e = std::getenv(name); if (!e || !*e) return dflt; char* end = nullptr; const unsigned long long v = std::strtoull(e, &end, 10); return end && *end == 0 ? (size_t)v : dflt; }
-
 // what both paths refuse before they compute; *perms: the permutations of the call, sum of ceil(m / 8)
 static int32_t decrypt_args_ok(const void* plain_out, const uint8_t* flags, const void* rvk, const uint32_t* offsets, const void* fields, size_t n, size_t* perms) {
   *perms = 0;
@@ -75,7 +73,6 @@ void launch_records_decrypt(hipStream_t s, char* io, uint8_t* dflags, const char
 // Copies, launch and synchronisation as records_scan_on_device (records.hip).  A chunk: as many whole records as stay within DECRYPT_CHUNK_RECORDS and the field
 // cap, and one at least.  ALEO_MI355X_DECRYPT_CHUNK_FIELDS (read per call) lowers the field cap; the bytes do not depend on it.
 static int32_t decrypt_on_device(Ctx* c, uint8_t* plain, uint8_t* flags, const uint8_t* rvk, const uint32_t* offsets, const uint8_t* fields, size_t n) {
-  const RecordsConsts& C = records_consts();
   const size_t cap = decrypt_chunk_fields();
   std::vector<size_t> cut{0};                                 // chunk k: records cut[k] .. cut[k + 1]
   size_t max_records = 0, max_fields = 0;
@@ -88,13 +85,9 @@ static int32_t decrypt_on_device(Ctx* c, uint8_t* plain, uint8_t* flags, const u
   }
   hipStream_t s = c->stream;
   int32_t rc;
-  if (!c->records_k_ready) {                                   // records.hip's protocol: the flag is set only once the stream has completed the copy
-    if ((rc = c->records_k.reserve(RK_WORDS * 4))) return rc;
-    HIPCHK(hipMemcpyAsync(c->records_k.p, C.words.data(), RK_WORDS * 4, hipMemcpyHostToDevice, s));
-  }
+  const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
   if ((rc = c->scalars_stage.reserve(max_fields * 32 + max_records * 32 + (max_records + 1) * 4 + max_records))) return rc;
   char* dio = c->scalars_stage.as<char>(); char* drvk = dio + max_fields * 32; uint32_t* doff = (uint32_t*)(drvk + max_records * 32); uint8_t* dfl = (uint8_t*)(doff + max_records + 1);
-  const uint32_t* dK = c->records_k.as<uint32_t>();
   for (size_t k = 0; k + 1 < cut.size(); ++k) {
     const size_t at = cut[k], m = cut[k + 1] - at, first = offsets[at], nf = offsets[at + m] - first;
     if (nf) HIPCHK(hipMemcpyAsync(dio, fields + first * 32, nf * 32, hipMemcpyHostToDevice, s));
@@ -105,7 +98,6 @@ static int32_t decrypt_on_device(Ctx* c, uint8_t* plain, uint8_t* flags, const u
     if (nf) HIPCHK(hipMemcpyAsync(plain + first * 32, dio, nf * 32, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
-    c->records_k_ready = true;
   }
   return ALEO_MI355X_OK;
 }

@@ -1,61 +1,186 @@
-// records_found.hip — decrypt_strings: the records ONE account owns among n "record1…" strings, decrypted, in one call: their indices, record view keys,
-// plain private fields and microcredits, and nothing of the records it does not own.
+// records_found.hip — decrypt_strings and decrypt_strings_many: the records each of K accounts owns among n "record1…" strings, decrypted, in one call: per
+// account their indices, record view keys, plain private fields and microcredits, and nothing of the records it does not own.  The one-account call is K = 1.
 //
 // The reference's unspent-record search does this record by record behind the ownership test (rust/src/api/blocking.rs:274-283: `if is_owner {
-// record.decrypt(&view_key) … microcredits() }`).  scan_strings (records_strings.hip) stops at "which records"; from there a caller parsed every owned string
-// again for its fields, sent them up for records_decrypt_fields and read the microcredits out of the rendered string.  Everything that tail needs is on the
-// device when the scan kernel finishes — the symbols in the chunk's text, the record view keys, the flags — so per chunk of the StringSource:
-//   fill / scan / resolve   records_strings.hip and records_many.hip, unchanged; the scan's own flags are kept aside (a public owner's flag is overwritten by
-//                           the resolve, and whether its nonce was on the curve decides its status when it has private fields)
-//   (the bodies of the four k_found_* kernels are records_found_blocks.h's, which records_found_many.hip runs over several accounts' rows)
-//   k_found_count           one lane per record (records_found_lane.h): an owned record's number of private fields and whether record_fields would refuse it;
-//                           the block's span staged in LDS as k_records_parse stages it (blocks without an owned record skip that); then the first level of the
-//                           exclusive sums of the field counts and of the owned bits, within the block
-//   k_found_offsets         the second level over the block totals (one block), and the two totals
-//   — one 16-byte read: owned records, their fields, unparsed strings and the first of those; the host sizes the field buffer —
-//   k_found_gather          the second walk: a lane writes its fields at its offset and its index, kind and key row at its rank among the owned
-//   k_records_decrypt       records_decrypt.hip, unchanged, over the compacted records in place; several launches when the fields exceed the launch cap
-//   k_found_microcredits    the status of every owned record, zero rows for a malformed one, and the microcredits entry from the plain fields
-//   — the compacted arrays come down and are appended, the chunk's base added to indices and offsets —
-// The host path puts the existing host calls together (the lane parse and host scan of scan_strings_host, records_plaintext.hpp's structure as record_fields
-// reads it, the host decryption); it shares no code with the walk above, which is what the device tests compare it with.
+// record.decrypt(&view_key) … microcredits() }`), and its dev server runs find_one_record -> get_unspent_records on every deploy, execute and transfer request
+// that brings no fee record (rust/develop/src/routes.rs:112, :143, :194-220; rust/src/api/blocking.rs:229-292), each walking the same blocks.  scan_strings
+// (records_strings.hip) stops at "which records"; from there a caller parsed every owned string again for its fields, sent them up for records_decrypt_fields
+// and read the microcredits out of the rendered string, and K one-account calls upload and parse the text K times and scan at width 1.  Everything that tail
+// needs is on the device when the scan kernel finishes — the symbols in the chunk's text, the record view keys, the flags — so per chunk of whole records (cut
+// as scan_many_on_device cuts them for K keys):
+//   fill                    records_strings.hip, once: the text goes up and is parsed once for all keys
+//   k_records_scan_many<W>  records_many.hip, unchanged, at the width it would pick itself; flags and key rows [key][record]; the scan's own flags are kept aside
+//                           (a public owner's flag is overwritten by the resolve, and whether its nonce was on the curve decides its status when it has
+//                           private fields)
+//   resolve                 records_strings.hip, with K keys
+//   k_found_count           grid (record blocks, keys), one lane per (key, record) pair (records_found_lane.h): an owned pair's number of private fields and
+//                           whether record_fields would refuse it; the block's span staged in LDS as k_records_parse stages it (blocks without an owned pair
+//                           skip that); then the first level of the exclusive sums of the field counts and of the owned bits, within the block.  Its block
+//                           totals lie at [key][block], so the sums below run in [key][record] order.  Row 0 counts the strings that do not parse: they are
+//                           the same for every key
+//   k_found_offsets         one block: the second level over the K x nb block totals; the totals, and what lies before each key's row (its first rank, its
+//                           first field): the per-key totals are their differences
+//   — one read of 16 + 8 K bytes; the host sizes the compacted arrays from it, for the owned pairs there are and not for m x K —
+//   k_found_gather          the same grid, the second walk: a lane writes its fields at its offset and its index, kind and key row at its rank among the
+//                           owned; a pair's rank and first field are global, so the compacted arrays hold key 0's records, then key 1's, each in record order
+//   k_records_decrypt       records_decrypt.hip, unchanged, over ALL keys' compacted records in place; several launches when the fields exceed the launch cap
+//   k_found_microcredits    the status of every owned pair, zero rows for a malformed one, and the microcredits entry from the plain fields
+//   — the compacted arrays come down once; the host splits them at the per-key totals into the K results, the chunk's base added to the indices and each
+//   result's own field count to its offsets —
+// The host path is K passes of records_found_host.hpp's found_on_host, which puts the existing host calls together (the lane parse and host scan of
+// scan_strings_host, records_plaintext.hpp's structure as record_fields reads it, the host decryption); it shares no code with the walk above, which is what
+// the device tests compare it with.
 #include "records_strings.h"
-#include "records_found_blocks.h"
 #include "records_found_host.hpp"
+#include <memory>
 
 namespace aleo_mi355x {
 
-static constexpr size_t FOUND_CHUNK_RECORDS = (size_t)1 << 20;      // FOUND_TOP lanes cover its 4096 blocks four each
+static constexpr uint32_t FOUND_BLOCK = 256, FOUND_TOP = 1024;
+static constexpr uint32_t FOUND_LDS_BYTES = 64 * 1024;              // k_records_parse's budget
+
+// The exclusive sums of two values over the block's 256 lanes (wave shuffles, then the four wave totals through LDS); *ta / *tb: the block's totals.
+__device__ __forceinline__ void block_exclusive2(uint32_t& a, uint32_t& b, uint32_t (*wave_tot)[FOUND_BLOCK / 64], uint32_t* ta, uint32_t* tb) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t ia = a, ib = b;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t ua = __shfl_up(ia, d, 64), ub = __shfl_up(ib, d, 64);
+    if (lane >= (uint32_t)d) { ia += ua; ib += ub; }
+  }
+  if (lane == 63) { wave_tot[0][wave] = ia; wave_tot[1][wave] = ib; }
+  __syncthreads();
+  uint32_t ba = 0, bb = 0, sa = 0, sb = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < FOUND_BLOCK / 64; ++w) { if (w < wave) { ba += wave_tot[0][w]; bb += wave_tot[1][w]; } sa += wave_tot[0][w]; sb += wave_tot[1][w]; }
+  a = ba + ia - a; b = bb + ib - b; *ta = sa; *tb = sb;
+}
+
+// The block's span of the text into LDS where it fits, as k_records_parse stages it: text readable up to the next multiple of 16 past the chunk's last character.
+__device__ __forceinline__ bool stage_span(uint4* stage, const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t b0, uint32_t n, uint32_t* lo_out) {
+  const uint32_t b1 = b0 + FOUND_BLOCK < n ? b0 + FOUND_BLOCK : n;
+  const uint32_t lo = off[b0] & ~15u, hi = off[b1];            // uniform
+  *lo_out = lo;
+  if (hi - lo > FOUND_LDS_BYTES) return false;
+  for (uint32_t t = threadIdx.x; lo + 16 * t < hi; t += FOUND_BLOCK) stage[t] = *(const uint4*)(text + lo + 16 * (size_t)t);
+  __syncthreads();
+  return true;
+}
 
 // ---- the kernels ------------------------------------------------------------------------------------------------------------------------------------
-// Their bodies are records_found_blocks.h's, over the one row of flags there is here: a block's totals lie at its own index among gridDim.x.
-// cnt / pos: the exclusive sums of the field counts and of the owned bits WITHIN the block; blk: [fields | owned][block], the block totals.
-// stat: [2] the unparsed strings, [3] n - (the first of them), both through one atomic per wave that holds one; zeroed before the launch.
+// A block is (blockIdx.x, key blockIdx.y): the records b0 .. b0 + 256 of row `key` of the [key][record] matrices (n per row); its totals lie at bi among the
+// gridDim.x x gridDim.y of all blocks.
+//
+// The counting walk.  cnt / pos: the exclusive sums of the field counts and of the owned bits WITHIN the block; blk: [fields | owned][key][block], the block
+// totals.  stat: [2] the unparsed strings, [3] n - (the first of them), both through one atomic per wave that holds one, zeroed before the launch — counted by
+// row 0 alone (the strings are the same for every row).
 __global__ void __launch_bounds__(FOUND_BLOCK) k_found_count(uint32_t* __restrict__ cnt, uint32_t* __restrict__ pos, uint8_t* __restrict__ pre, uint32_t* __restrict__ blk, uint32_t* __restrict__ stat,
                                                             const uint8_t* __restrict__ flags, const uint8_t* __restrict__ scan_flags, const int8_t* __restrict__ kinds,
                                                             const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t n) {
   __shared__ uint4 stage[FOUND_LDS_BYTES / 16];
   __shared__ uint32_t wave_tot[2][FOUND_BLOCK / 64];
-  found_count_block(stage, wave_tot, cnt, pos, pre, blk, blockIdx.x, gridDim.x, stat, true, flags, scan_flags, kinds, text, off, blockIdx.x * FOUND_BLOCK, n);
+  const size_t row = (size_t)blockIdx.y * n;
+  const uint32_t bi = blockIdx.y * gridDim.x + blockIdx.x, rows = gridDim.x * gridDim.y, b0 = blockIdx.x * FOUND_BLOCK;
+  cnt += row; pos += row; pre += row; flags += row; scan_flags += row;
+  const uint32_t i = b0 + threadIdx.x;
+  const bool live = i < n;
+  const int32_t kind = live ? kinds[i] : 0;
+  const bool owned = live && flags[i] == 1;
+  if (blockIdx.y == 0) {                                       // uniform
+    const unsigned long long refused = __ballot(live && kind < 0);
+    if (refused && (threadIdx.x & 63u) == 0) {
+      atomicAdd(&stat[2], (uint32_t)__popcll(refused));
+      atomicMax(&stat[3], n - (i + (uint32_t)__ffsll(refused) - 1u));
+    }
+  }
+  uint32_t m = 0, status = FOUND_OK;
+  if (__syncthreads_or(owned)) {                               // uniform
+    uint32_t lo;
+    const bool staged = stage_span(stage, text, off, b0, n, &lo);
+    if (owned) {
+      const uint32_t first = off[i], len = off[i + 1] - first;
+      auto nothing = [](uint32_t, const uint32_t (&)[8]) {};
+      FoundWalk w;
+      if (staged) { const uint8_t* mine = (const uint8_t*)stage + (first - lo); w = records_found_walk([&](uint32_t j) { return mine[j]; }, len, kind, nothing); }
+      else { const uint8_t* __restrict__ mine = (const uint8_t*)text + first; w = records_found_walk([&](uint32_t j) { return mine[j]; }, len, kind, nothing); }
+      m = w.fields; status = w.status;
+      if (kind == 0 && m && scan_flags[i] == 2) status = FOUND_MALFORMED;
+    }
+  }
+  if (live) pre[i] = (uint8_t)status;
+  uint32_t a = m, b = owned ? 1u : 0u, ta, tb;
+  block_exclusive2(a, b, wave_tot, &ta, &tb);
+  if (live) { cnt[i] = a; pos[i] = b; }
+  if (threadIdx.x == 0) { blk[bi] = ta; blk[rows + bi] = tb; }
 }
 
-// One block: blk's two rows of nb block totals become their exclusive sums, the totals go to stat[0] (owned records) and stat[1] (fields).
-__global__ void __launch_bounds__(FOUND_TOP) k_found_offsets(uint32_t* __restrict__ blk, uint32_t* __restrict__ stat, uint32_t nb) {
+// One block of FOUND_TOP lanes over the rows = n_keys x nb block totals: blk's two rows of them become their exclusive sums, the totals go to stat[0] (owned
+// pairs) and stat[1] (fields), and what lies before each key's row — its two sums at its first block — to stat[4 + key] (owned) and stat[4 + n_keys + key] (fields).
+__global__ void __launch_bounds__(FOUND_TOP) k_found_offsets(uint32_t* __restrict__ blk, uint32_t* __restrict__ stat, uint32_t rows, uint32_t nb) {
   __shared__ uint32_t wave_tot[2][FOUND_TOP / 64];
-  found_offsets_block(wave_tot, blk, stat, nb, 0);
+  const uint32_t per = (rows + FOUND_TOP - 1) / FOUND_TOP, first = threadIdx.x * per, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t* f = blk; uint32_t* o = blk + rows;
+  uint32_t sf = 0, so = 0;
+  for (uint32_t k = first; k < first + per && k < rows; ++k) { sf += f[k]; so += o[k]; }
+  uint32_t af = sf, ao = so;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t uf = __shfl_up(af, d, 64), uo = __shfl_up(ao, d, 64);
+    if (lane >= (uint32_t)d) { af += uf; ao += uo; }
+  }
+  if (lane == 63) { wave_tot[0][wave] = af; wave_tot[1][wave] = ao; }
+  __syncthreads();
+  uint32_t bf = 0, bo = 0, tf = 0, to = 0;
+  for (uint32_t w = 0; w < FOUND_TOP / 64; ++w) { if (w < wave) { bf += wave_tot[0][w]; bo += wave_tot[1][w]; } tf += wave_tot[0][w]; to += wave_tot[1][w]; }
+  uint32_t rf = bf + af - sf, ro = bo + ao - so;
+  for (uint32_t k = first; k < first + per && k < rows; ++k) {
+    const uint32_t vf = f[k], vo = o[k]; f[k] = rf; o[k] = ro;
+    if (k % nb == 0) { stat[4 + k / nb] = ro; stat[4 + rows / nb + k / nb] = rf; }
+    rf += vf; ro += vo;
+  }
+  if (threadIdx.x == 0) { stat[0] = to; stat[1] = tf; }
 }
 
-// An owned record's rank among the chunk's owned is j = blk[owned row][block] + pos[i], its first field f = blk[fields row][block] + cnt[i].  fields: room for
-// n_fields rows; the c_* arrays: n_owned entries (c_off one more: the total).  c_mc: the value of a public microcredits entry, else 0; c_mc_at / c_mc_n: where a
-// private one's fields lie among the chunk's fields (n 0: none).
+// The gathering walk.  An owned pair's rank among ALL rows' owned is j = blk[owned row][bi] + pos[i], its first field f = blk[fields row][bi] + cnt[i].  fields:
+// room for n_fields rows; the c_* arrays: n_owned entries (c_off one more: the total, written by row 0).  rvk: the scan's rows [key][record].  c_mc: the value of
+// a public microcredits entry, else 0; c_mc_at / c_mc_n: where a private one's fields lie among the gathered fields (n 0: none).
 __global__ void __launch_bounds__(FOUND_BLOCK) k_found_gather(char* __restrict__ fields, uint32_t* __restrict__ c_index, int8_t* __restrict__ c_kind, char* __restrict__ c_rvk, uint32_t* __restrict__ c_off,
                                                              uint8_t* __restrict__ c_pre, uint64_t* __restrict__ c_mc, uint32_t* __restrict__ c_mc_at, uint32_t* __restrict__ c_mc_n,
                                                              const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ pos, const uint8_t* __restrict__ pre, const uint32_t* __restrict__ blk,
                                                              const uint8_t* __restrict__ flags, const int8_t* __restrict__ kinds, const char* __restrict__ rvk,
                                                              const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t n, uint32_t n_owned, uint32_t n_fields) {
   __shared__ uint4 stage[FOUND_LDS_BYTES / 16];
-  found_gather_block(stage, fields, c_index, c_kind, c_rvk, c_off, c_pre, c_mc, c_mc_at, c_mc_n, cnt, pos, pre, blk, blockIdx.x, gridDim.x, true, flags, kinds, rvk, text, off,
-                     blockIdx.x * FOUND_BLOCK, n, n_owned, n_fields);
+  const size_t row = (size_t)blockIdx.y * n;
+  const uint32_t bi = blockIdx.y * gridDim.x + blockIdx.x, rows = gridDim.x * gridDim.y, b0 = blockIdx.x * FOUND_BLOCK;
+  cnt += row; pos += row; pre += row; flags += row; rvk += row * 32;
+  const uint32_t i = b0 + threadIdx.x;
+  if (blockIdx.y == 0 && i == 0) c_off[n_owned] = n_fields;
+  const bool owned = i < n && flags[i] == 1;
+  if (!__syncthreads_or(owned)) return;                        // uniform
+  uint32_t lo;
+  const bool staged = stage_span(stage, text, off, b0, n, &lo);
+  if (!owned) return;                                          // no barrier below
+  const uint32_t j = blk[rows + bi] + pos[i], f = blk[bi] + cnt[i];
+  if (j >= n_owned) return;                                    // cannot happen: the totals are these sums
+  const int32_t kind = kinds[i];
+  const uint32_t status = pre[i];
+  c_index[j] = i; c_kind[j] = (int8_t)kind; c_off[j] = f; c_pre[j] = (uint8_t)status;
+  const uint4* r = (const uint4*)(rvk + (size_t)i * 32); uint4* ro = (uint4*)(c_rvk + (size_t)j * 32);
+  ro[0] = r[0]; ro[1] = r[1];
+  FoundWalk w{0, status, FOUND_MC_NONE, 0, 0, 0};
+  if (status != FOUND_REFUSED) {
+    const uint32_t first_char = off[i], len = off[i + 1] - first_char;
+    auto store = [&](uint32_t k, const uint32_t (&v)[8]) {
+      if (f + k >= n_fields) return;                           // cannot happen: the count walk counted them
+      uint4* o = (uint4*)(fields + (size_t)(f + k) * 32);
+      o[0] = make_uint4(v[0], v[1], v[2], v[3]); o[1] = make_uint4(v[4], v[5], v[6], v[7]);
+    };
+    if (staged) { const uint8_t* mine = (const uint8_t*)stage + (first_char - lo); w = records_found_walk([&](uint32_t q) { return mine[q]; }, len, kind, store); }
+    else { const uint8_t* __restrict__ mine = (const uint8_t*)text + first_char; w = records_found_walk([&](uint32_t q) { return mine[q]; }, len, kind, store); }
+  }
+  c_mc[j] = w.mc_kind == FOUND_MC_PUBLIC ? w.mc_value : 0;
+  c_mc_at[j] = w.mc_kind == FOUND_MC_PRIVATE ? f + w.mc_at : 0;
+  c_mc_n[j] = w.mc_kind == FOUND_MC_PRIVATE ? w.mc_n : 0;
 }
 
 // Behind k_records_decrypt, one lane per owned record: status = what the walk found, else the decryption's flag; the rows of a record the walk marked malformed are
@@ -65,80 +190,102 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_found_microcredits(uint8_t* __r
                                                                    const uint32_t* __restrict__ c_mc_n, uint32_t n_owned) {
   const uint32_t j = blockIdx.x * FOUND_BLOCK + threadIdx.x;
   if (j >= n_owned) return;
-  found_microcredits_lane(j, c_status, c_mc, fields, c_pre, c_dec, c_off, c_mc_at, c_mc_n);
+  const uint32_t pre = c_pre[j], status = pre ? pre : c_dec[j];
+  c_status[j] = (uint8_t)status;
+  if (pre == FOUND_MALFORMED)
+    for (uint32_t k = c_off[j]; k < c_off[j + 1]; ++k) { uint4* o = (uint4*)(fields + (size_t)k * 32); o[0] = make_uint4(0, 0, 0, 0); o[1] = make_uint4(0, 0, 0, 0); }
+  if (status != FOUND_OK) { c_mc[j] = 0; return; }
+  const uint32_t mn = c_mc_n[j];
+  if (!mn) return;                                             // a public entry's value, or 0, stands
+  const char* at = fields + (size_t)c_mc_at[j] * 32;
+  c_mc[j] = found_microcredits_private(mn, [&](uint32_t k, uint32_t (&w)[8]) {
+    const uint4* p = (const uint4*)(at + (size_t)k * 32); const uint4 l = p[0], h = p[1];
+    w[0] = l.x; w[1] = l.y; w[2] = l.z; w[3] = l.w; w[4] = h.x; w[5] = h.y; w[6] = h.z; w[7] = h.w; });
 }
 
 // ---- the device flow ----------------------------------------------------------------------------------------------------------------------------------
-static int32_t found_on_device(Ctx* c, Found& R, const char* text, const uint64_t* offsets, size_t n, const ScanArgs& key) {
-  const RecordsConsts& C = records_consts();
+static int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>& R, const char* text, const uint64_t* offsets, size_t n, const ManyKeys& k) {
+  const size_t K = k.args.size();
+  uint32_t W;
+  const size_t chunk = scan_many_plan(n, K, &W);
   StringSource src{text, offsets, nullptr};
-  src.cut_chunks(n, FOUND_CHUNK_RECORDS);
-  const size_t M = src.max_records, NB = (M + FOUND_BLOCK - 1) / FOUND_BLOCK;
+  src.cut_chunks(n, chunk);
+  std::vector<ScanArgs> table((K + W - 1) / W * W, ScanArgs{});      // the padding: no digits at all
+  std::copy(k.args.begin(), k.args.end(), table.begin());
+  const size_t M = src.max_records, NB = (M + FOUND_BLOCK - 1) / FOUND_BLOCK, P = M * K;
   hipStream_t s = c->stream;
   int32_t rc;
-  if (!c->records_k_ready) {                                   // records.hip's protocol: the flag is set only once the stream has completed the copy
-    if ((rc = c->records_k.reserve(RK_WORDS * 4))) return rc;
-    HIPCHK(hipMemcpyAsync(c->records_k.p, C.words.data(), RK_WORDS * 4, hipMemcpyHostToDevice, s));
-  }
-  if ((rc = ensure_host_pinned(c, 16))) return rc;
+  const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
+  const size_t stat_words = 4 + 2 * K;
+  if ((rc = ensure_host_pinned(c, stat_words * 4))) return rc;
+  // the scan's own scratch (64 B per record, 33 B per pair) and 10 B per pair for the walk: the scan's flags, the pre-status, the two first-level sums
   size_t total = 0;
   auto part = [&](size_t bytes) { const size_t at = total; total += (bytes + 31) & ~(size_t)31; return at; };
-  const size_t o_key = part(sizeof(ScanArgs)), o_c0 = part(M * 32), o_nx = part(M * 32), o_rvk = part(M * 32), o_fl = part(M), o_scan = part(M), o_pre = part(M), o_cnt = part(M * 4),
-               o_pos = part(M * 4), o_blk = part(2 * NB * 4), o_stat = part(16), o_index = part(M * 4), o_off = part((M + 1) * 4), o_mc_at = part(M * 4), o_mc_n = part(M * 4), o_mc = part(M * 8),
-               o_crvk = part(M * 32), o_kind = part(M), o_cpre = part(M), o_dec = part(M), o_status = part(M), o_str = part(src.scratch_bytes());
+  const size_t o_keys = part(table.size() * sizeof(ScanArgs)), o_c0 = part(M * 32), o_nx = part(M * 32), o_rvk = part(P * 32), o_fl = part(P), o_scan = part(P), o_pre = part(P), o_cnt = part(P * 4),
+               o_pos = part(P * 4), o_blk = part(2 * K * NB * 4), o_stat = part(stat_words * 4), o_str = part(src.scratch_bytes());
   if ((rc = c->scalars_stage.reserve(total))) return rc;
   char* base = c->scalars_stage.as<char>();
-  const ScanArgs* dkey = (const ScanArgs*)(base + o_key);
-  char* dc0 = base + o_c0; char* dnx = base + o_nx; char* drvk = base + o_rvk; char* dstr = base + o_str; char* dcrvk = base + o_crvk;
-  uint8_t* dfl = (uint8_t*)(base + o_fl); uint8_t* dscan = (uint8_t*)(base + o_scan); uint8_t* dpre = (uint8_t*)(base + o_pre); uint8_t* dcpre = (uint8_t*)(base + o_cpre);
-  uint8_t* ddec = (uint8_t*)(base + o_dec); uint8_t* dstatus = (uint8_t*)(base + o_status); int8_t* dkind = (int8_t*)(base + o_kind);
+  const ScanArgs* dkeys = (const ScanArgs*)(base + o_keys);
+  char* dc0 = base + o_c0; char* dnx = base + o_nx; char* drvk = base + o_rvk; char* dstr = base + o_str;
+  uint8_t* dfl = (uint8_t*)(base + o_fl); uint8_t* dscan = (uint8_t*)(base + o_scan); uint8_t* dpre = (uint8_t*)(base + o_pre);
   uint32_t* dcnt = (uint32_t*)(base + o_cnt); uint32_t* dpos = (uint32_t*)(base + o_pos); uint32_t* dblk = (uint32_t*)(base + o_blk); uint32_t* dstat = (uint32_t*)(base + o_stat);
-  uint32_t* dindex = (uint32_t*)(base + o_index); uint32_t* doff = (uint32_t*)(base + o_off); uint32_t* dmc_at = (uint32_t*)(base + o_mc_at); uint32_t* dmc_n = (uint32_t*)(base + o_mc_n);
-  uint64_t* dmc = (uint64_t*)(base + o_mc);
-  HIPCHK(hipMemcpyAsync(base + o_key, &key, sizeof(ScanArgs), hipMemcpyHostToDevice, s));      // `key` outlives the call's last synchronisation
-  const uint32_t* dK = c->records_k.as<uint32_t>();
+  HIPCHK(hipMemcpyAsync(base + o_keys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, s));      // `table` outlives the call's last synchronisation
   const uint32_t* dsoff; const int8_t* dkinds; const char* dtext; src.parts(dstr, &dsoff, &dkinds, &dtext);
   const size_t cap = decrypt_chunk_fields();
-  uint32_t* stat = (uint32_t*)c->h_pinned;
-  std::vector<uint32_t> cut_off;
-  R.first_unparsed = n;
+  const uint32_t* stat = (const uint32_t*)c->h_pinned;
+  // Where a chunk's compacted arrays come down, all keys' one after another: staging arrays that are split into the K results below — or, when there is one
+  // key and everything is its own, the tail of its result, which saves a host copy of everything owned (120 MB at 2^20 records all owned).
+  Found staged;
+  Found& to = K == 1 ? *R[0] : staged;
+  for (auto& r : R) r->first_unparsed = n;
   for (size_t ck = 0; ck + 1 < src.cut.size(); ++ck) {
     const size_t at = src.cut[ck], m = src.cut[ck + 1] - at;
     const uint32_t nb = (uint32_t)((m + FOUND_BLOCK - 1) / FOUND_BLOCK);
+    const dim3 pairs(nb, (uint32_t)K);
     if ((rc = src.fill(s, ck, dstr, dc0, dnx))) return rc;
-    launch_scan_one_key(s, dfl, drvk, dc0, dnx, m, dK, dkey);
+    launch_scan_keys(s, W, dfl, drvk, dc0, dnx, m, dK, dkeys, K);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dscan, dfl, m, hipMemcpyDeviceToDevice, s));
-    if ((rc = src.resolve(s, ck, dstr, dfl, drvk, dc0, dkey, 1))) return rc;
+    HIPCHK(hipMemcpyAsync(dscan, dfl, m * K, hipMemcpyDeviceToDevice, s));      // rows of m: a public owner's status depends on the flag the resolve overwrites
+    if ((rc = src.resolve(s, ck, dstr, dfl, drvk, dc0, dkeys, K))) return rc;
     HIPCHK(hipMemsetAsync(dstat, 0, 16, s));
-    hipLaunchKernelGGL(k_found_count, dim3(nb), dim3(FOUND_BLOCK), 0, s, dcnt, dpos, dpre, dblk, dstat, (const uint8_t*)dfl, (const uint8_t*)dscan, dkinds, dtext, dsoff, (uint32_t)m);
+    hipLaunchKernelGGL(k_found_count, pairs, dim3(FOUND_BLOCK), 0, s, dcnt, dpos, dpre, dblk, dstat, (const uint8_t*)dfl, (const uint8_t*)dscan, dkinds, dtext, dsoff, (uint32_t)m);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_found_offsets, dim3(1), dim3(FOUND_TOP), 0, s, dblk, dstat, nb);
+    hipLaunchKernelGGL(k_found_offsets, dim3(1), dim3(FOUND_TOP), 0, s, dblk, dstat, nb * (uint32_t)K, nb);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(stat, dstat, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                           // the one wait before the gather: the host sizes the field buffer
-    c->records_k_ready = true;
+    HIPCHK(hipMemcpyAsync(c->h_pinned, dstat, stat_words * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                           // the one wait before the gather: the host sizes the compacted arrays
     const size_t owned = stat[0], nf = stat[1];
-    if (stat[2]) { if (!R.unparsed) R.first_unparsed = at + (m - stat[3]); R.unparsed += stat[2]; }
+    if (stat[2]) for (auto& r : R) { if (!r->unparsed) r->first_unparsed = at + (m - stat[3]); r->unparsed += stat[2]; }
     if (!owned) continue;
-    if (R.index.size() + owned > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 owned records");
-    if ((size_t)R.offsets.back() + nf > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 private fields");
-    if ((rc = c->out_stage.reserve(nf * 32 + 32))) return rc;
-    char* dfields = c->out_stage.as<char>();
-    hipLaunchKernelGGL(k_found_gather, dim3(nb), dim3(FOUND_BLOCK), 0, s, dfields, dindex, dkind, dcrvk, doff, dcpre, dmc, dmc_at, dmc_n, (const uint32_t*)dcnt, (const uint32_t*)dpos,
+    for (size_t j = 0; j < K; ++j) {
+      const size_t mine = (j + 1 < K ? stat[4 + j + 1] : owned) - stat[4 + j], mine_f = (j + 1 < K ? stat[4 + K + j + 1] : nf) - stat[4 + K + j];
+      if (R[j]->index.size() + mine > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 owned records");
+      if ((size_t)R[j]->offsets.back() + mine_f > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 private fields");
+    }
+    size_t ctotal = 0;
+    auto cpart = [&](size_t bytes) { const size_t a = ctotal; ctotal += (bytes + 31) & ~(size_t)31; return a; };
+    const size_t o_fields = cpart(nf * 32), o_index = cpart(owned * 4), o_off = cpart((owned + 1) * 4), o_mc_at = cpart(owned * 4), o_mc_n = cpart(owned * 4), o_mc = cpart(owned * 8),
+                 o_crvk = cpart(owned * 32), o_kind = cpart(owned), o_cpre = cpart(owned), o_dec = cpart(owned), o_status = cpart(owned);
+    if ((rc = c->out_stage.reserve(ctotal))) return rc;
+    char* cb = c->out_stage.as<char>();
+    char* dfields = cb + o_fields; char* dcrvk = cb + o_crvk;
+    uint32_t* dindex = (uint32_t*)(cb + o_index); uint32_t* doff = (uint32_t*)(cb + o_off); uint32_t* dmc_at = (uint32_t*)(cb + o_mc_at); uint32_t* dmc_n = (uint32_t*)(cb + o_mc_n);
+    uint64_t* dmc = (uint64_t*)(cb + o_mc); int8_t* dkind = (int8_t*)(cb + o_kind);
+    uint8_t* dcpre = (uint8_t*)(cb + o_cpre); uint8_t* ddec = (uint8_t*)(cb + o_dec); uint8_t* dstatus = (uint8_t*)(cb + o_status);
+    hipLaunchKernelGGL(k_found_gather, pairs, dim3(FOUND_BLOCK), 0, s, dfields, dindex, dkind, dcrvk, doff, dcpre, dmc, dmc_at, dmc_n, (const uint32_t*)dcnt, (const uint32_t*)dpos,
                        (const uint8_t*)dpre, (const uint32_t*)dblk, (const uint8_t*)dfl, dkinds, (const char*)drvk, dtext, dsoff, (uint32_t)m, (uint32_t)owned, (uint32_t)nf);
     HIPCHK(hipGetLastError());
-    const size_t have = R.index.size(), have_f = R.offsets.back();
-    R.index.resize(have + owned); R.offsets.resize(have + owned + 1); R.kind.resize(have + owned); R.rvk.resize((have + owned) * 32); R.status.resize(have + owned);
-    R.microcredits.resize(have + owned); R.plain.resize((have_f + nf) * 32);
-    HIPCHK(hipMemcpyAsync(R.offsets.data() + have, doff, (owned + 1) * 4, hipMemcpyDeviceToHost, s));      // chunk-relative until the base is added below
+    const size_t put = K == 1 ? to.index.size() : 0, put_f = K == 1 ? to.offsets.back() : 0;      // `staged` starts over with every chunk
+    to.index.resize(put + owned); to.offsets.resize(put + owned + 1); to.kind.resize(put + owned); to.rvk.resize((put + owned) * 32); to.status.resize(put + owned);
+    to.microcredits.resize(put + owned); to.plain.resize((put_f + nf) * 32);
+    uint32_t* h_off = to.offsets.data() + put;                // chunk-relative until a base is added below
+    HIPCHK(hipMemcpyAsync(h_off, doff, (owned + 1) * 4, hipMemcpyDeviceToHost, s));
     if (nf <= cap) launch_records_decrypt(s, dfields, ddec, dcrvk, doff, 0, owned, dK);
-    else {                                                     // launches of whole records within the cap, one record at least: the host needs the offsets to cut
+    else {                                                     // launches of whole records within the cap, one record at least, across key boundaries: the host needs the offsets to cut
       HIPCHK(hipStreamSynchronize(s));
-      const uint32_t* off = R.offsets.data() + have;
       for (size_t a = 0; a < owned;) {
         size_t e = a + 1;
-        while (e < owned && (size_t)off[e + 1] - off[a] <= cap) ++e;
+        while (e < owned && (size_t)h_off[e + 1] - h_off[a] <= cap) ++e;
         launch_records_decrypt(s, dfields, ddec + a, dcrvk + a * 32, doff + a, 0, e - a, dK);
         HIPCHK(hipGetLastError());
         a = e;
@@ -148,32 +295,54 @@ static int32_t found_on_device(Ctx* c, Found& R, const char* text, const uint64_
     hipLaunchKernelGGL(k_found_microcredits, dim3((uint32_t)((owned + FOUND_BLOCK - 1) / FOUND_BLOCK)), dim3(FOUND_BLOCK), 0, s, dstatus, dmc, dfields, (const uint8_t*)dcpre, (const uint8_t*)ddec,
                        (const uint32_t*)doff, (const uint32_t*)dmc_at, (const uint32_t*)dmc_n, (uint32_t)owned);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(R.index.data() + have, dindex, owned * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(R.kind.data() + have, dkind, owned, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(R.rvk.data() + have * 32, dcrvk, owned * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(R.status.data() + have, dstatus, owned, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(R.microcredits.data() + have, dmc, owned * 8, hipMemcpyDeviceToHost, s));
-    if (nf) HIPCHK(hipMemcpyAsync(R.plain.data() + have_f * 32, dfields, nf * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers
-    for (size_t q = 0; q < owned; ++q) { R.index[have + q] += (uint32_t)at; R.offsets[have + q] += (uint32_t)have_f; }
-    R.offsets[have + owned] += (uint32_t)have_f;
+    HIPCHK(hipMemcpyAsync(to.index.data() + put, dindex, owned * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(to.kind.data() + put, dkind, owned, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(to.rvk.data() + put * 32, dcrvk, owned * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(to.status.data() + put, dstatus, owned, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(to.microcredits.data() + put, dmc, owned * 8, hipMemcpyDeviceToHost, s));
+    if (nf) HIPCHK(hipMemcpyAsync(to.plain.data() + put_f * 32, dfields, nf * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers; h_pinned is read below and not written before the next chunk's copy
+    if (K == 1) {                                              // in place already: the split is the two bases
+      for (size_t q = 0; q < owned; ++q) { to.index[put + q] += (uint32_t)at; h_off[q] += (uint32_t)put_f; }
+      h_off[owned] += (uint32_t)put_f;
+    } else for (size_t j = 0; j < K; ++j) {                    // key j's records: the ranks a .. e, the fields fa .. fe
+      const size_t a = stat[4 + j], e = j + 1 < K ? stat[4 + j + 1] : owned, fa = stat[4 + K + j], fe = j + 1 < K ? stat[4 + K + j + 1] : nf;
+      if (a == e) continue;
+      Found& r = *R[j];
+      const size_t have = r.index.size(), have_f = r.offsets.back();
+      r.index.resize(have + (e - a)); r.offsets.resize(have + (e - a) + 1);
+      for (size_t q = a; q < e; ++q) { r.index[have + (q - a)] = staged.index[q] + (uint32_t)at; r.offsets[have + (q - a) + 1] = (uint32_t)(have_f + (h_off[q + 1] - fa)); }
+      r.kind.insert(r.kind.end(), staged.kind.begin() + a, staged.kind.begin() + e);
+      r.rvk.insert(r.rvk.end(), staged.rvk.begin() + a * 32, staged.rvk.begin() + e * 32);
+      r.status.insert(r.status.end(), staged.status.begin() + a, staged.status.begin() + e);
+      r.microcredits.insert(r.microcredits.end(), staged.microcredits.begin() + a, staged.microcredits.begin() + e);
+      r.plain.insert(r.plain.end(), staged.plain.begin() + fa * 32, staged.plain.begin() + fe * 32);
+    }
   }
   return ALEO_MI355X_OK;
 }
 
-static int32_t decrypt_strings(Found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_key32, const void* address_x32, bool may_route) {
-  if (!out) return bad_arg("records_decrypt_strings: null result pointer");
-  *out = nullptr;
-  ManyKeys k; if (int32_t rc = many_keys(k, view_key32, address_x32, 1)) return rc;
+static int32_t decrypt_strings_many(Found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys, bool may_route) {
+  if (!out) return bad_arg("records_decrypt_strings_many: null result pointer");
+  for (size_t j = 0; j < n_keys; ++j) out[j] = nullptr;
+  ManyKeys k; if (int32_t rc = many_keys(k, view_keys32, address_xs32, n_keys)) return rc;
   if (int32_t rc = strings_args_ok("records_scan_strings", text, offsets, n)) return rc;
   if (n > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 records");
-  Found* R = new Found;
-  int32_t rc;
-  if (!may_route || n < aleo_mi355x_min_records() || n == 0) rc = found_on_host(*R, text, offsets, n, k.args[0], k.addr[0]);
-  else { Slot sl; rc = sl.rc ? sl.rc : found_on_device(sl.c, *R, text, offsets, n, k.args[0]); }
-  if (rc) { delete R; return rc; }
-  *out = R;
+  std::vector<std::unique_ptr<Found>> R(n_keys);
+  for (auto& r : R) r.reset(new Found);
+  int32_t rc = ALEO_MI355X_OK;
+  if (!may_route || n * n_keys < aleo_mi355x_min_records() || n == 0)      // in pairs, as records_scan_strings counts
+    for (size_t j = 0; j < n_keys && !rc; ++j) rc = found_on_host(*R[j], text, offsets, n, k.args[j], k.addr[j]);
+  else { Slot sl; rc = sl.rc ? sl.rc : found_many_on_device(sl.c, R, text, offsets, n, k); }
+  if (rc) return rc;
+  for (size_t j = 0; j < n_keys; ++j) out[j] = R[j].release();
   return ALEO_MI355X_OK;
+}
+
+// one account: the call above with one key; only the refusal of a null result pointer names the call
+static int32_t decrypt_strings(Found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_key32, const void* address_x32, bool may_route) {
+  if (!out) return bad_arg("records_decrypt_strings: null result pointer");
+  return decrypt_strings_many(out, text, offsets, n, view_key32, address_x32, 1, may_route);
 }
 
 }  // namespace aleo_mi355x
@@ -182,6 +351,12 @@ using namespace aleo_mi355x;
 
 extern "C" {
 
+int32_t aleo_mi355x_records_decrypt_strings_many(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys) {
+  return guarded([&] { return decrypt_strings_many(out, text, offsets, n, view_keys32, address_xs32, n_keys, true); });
+}
+int32_t aleo_mi355x_records_decrypt_strings_many_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys) {
+  return guarded([&] { return decrypt_strings_many(out, text, offsets, n, view_keys32, address_xs32, n_keys, false); });
+}
 int32_t aleo_mi355x_records_decrypt_strings(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_key32, const void* address_x32) {
   return guarded([&] { return decrypt_strings(out, text, offsets, n, view_key32, address_x32, true); });
 }

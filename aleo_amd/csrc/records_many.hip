@@ -96,60 +96,9 @@ static uint32_t scan_many_width(size_t records_per_launch, size_t n_keys) {
   return 1;
 }
 
-// The records of a chunk reach dc0 / dnx either as the caller's rows, by two copies, or from `strings` (records_strings.h): its text goes up and k_records_parse
-// writes the rows; its chunks are cut at the character cap as well, and k_records_resolve follows the scan kernel.
-int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings) {
-  const RecordsConsts& C = records_consts();
-  const size_t n_keys = k.args.size();
-  size_t chunk = SCAN_MANY_PAIRS / n_keys; if (chunk > SCAN_MANY_RECORDS) chunk = SCAN_MANY_RECORDS; if (chunk > n) chunk = n;
-  if (strings) strings->cut_chunks(n, chunk);
-  const uint32_t W = scan_many_width(chunk, n_keys);
-  std::vector<ScanArgs> table((n_keys + W - 1) / W * W, ScanArgs{});      // the padding: no digits at all
-  std::copy(k.args.begin(), k.args.end(), table.begin());
-  hipStream_t s = c->stream;
-  int32_t rc;
-  if (!c->records_k_ready) {                                   // records.hip's protocol: the flag is set only once the stream has completed the copy
-    if ((rc = c->records_k.reserve(RK_WORDS * 4))) return rc;
-    HIPCHK(hipMemcpyAsync(c->records_k.p, C.words.data(), RK_WORDS * 4, hipMemcpyHostToDevice, s));
-  }
-  const size_t keys_bytes = (table.size() * sizeof(ScanArgs) + 31) & ~(size_t)31;
-  const size_t rows_bytes = (keys_bytes + chunk * 64 + chunk * n_keys * 33 + 31) & ~(size_t)31;
-  if ((rc = c->scalars_stage.reserve(rows_bytes + (strings ? strings->scratch_bytes() : 0)))) return rc;
-  char* dkeys = c->scalars_stage.as<char>(); char* dc0 = dkeys + keys_bytes; char* dnx = dc0 + chunk * 32; char* drvk = dnx + chunk * 32; uint8_t* dfl = (uint8_t*)(drvk + chunk * n_keys * 32);
-  char* dstr = dkeys + rows_bytes;
-  HIPCHK(hipMemcpyAsync(dkeys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, s));
-  const uint32_t* dK = c->records_k.as<uint32_t>();
-  for (size_t at = 0, ck = 0, m; at < n; at += m, ++ck) {
-    m = strings ? strings->cut[ck + 1] - at : (n - at < chunk ? n - at : chunk);
-    if (strings) { if ((rc = strings->fill(s, ck, dstr, dc0, dnx))) return rc; }
-    else {
-      HIPCHK(hipMemcpyAsync(dc0, (const char*)owner_c0 + at * 32, m * 32, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(dnx, (const char*)nonce_x + at * 32, m * 32, hipMemcpyHostToDevice, s));
-    }
-    switch (W) {
-      case 8: launch_many<8>(s, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys); break;
-      case 4: launch_many<4>(s, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys); break;
-      case 2: launch_many<2>(s, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys); break;
-      default: launch_many<1>(s, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys);
-    }
-    HIPCHK(hipGetLastError());
-    if (strings && (rc = strings->resolve(s, ck, dstr, dfl, drvk, dc0, (const ScanArgs*)dkeys, n_keys))) return rc;
-    // rows of m on the device, rows of n at the caller
-    HIPCHK(hipMemcpy2DAsync(flags + at, n, dfl, m, m, n_keys, hipMemcpyDeviceToHost, s));
-    if (rvk_out) HIPCHK(hipMemcpy2DAsync((char*)rvk_out + at * 32, n * 32, drvk, m * 32, m * 32, n_keys, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers; the table is a local of this call
-    c->records_k_ready = true;
-  }
-  return ALEO_MI355X_OK;
-}
-
-// for records_found.hip, which runs the one-key scan between a parse and a walk of its own
-void launch_scan_one_key(hipStream_t s, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkey) {
-  launch_many<1>(s, dflags, drvk, dc0, dnx, m, dK, dkey, 1);
-}
-
-// for records_found_many.hip, which runs the K-key scan between a parse and a walk of its own: the records of one launch and the keys of one lane, as
-// scan_many_on_device above settles them, and the launch over m records already on the device (dkeys: n_keys entries padded with zero entries to a multiple of W)
+// The plan of a K-key scan over n records — the records of one launch (the pair cap, the record cap, n) and *W, the keys one lane takes — and that launch over m
+// records already on the device (dkeys: n_keys entries padded with zero entries to a multiple of W): scan_many_on_device below and records_found.hip, which runs
+// the scan between a parse and a walk of its own, both go through these two.
 size_t scan_many_plan(size_t n, size_t n_keys, uint32_t* W) {
   size_t chunk = SCAN_MANY_PAIRS / n_keys; if (chunk > SCAN_MANY_RECORDS) chunk = SCAN_MANY_RECORDS; if (chunk > n) chunk = n;
   *W = scan_many_width(chunk, n_keys);
@@ -162,6 +111,42 @@ void launch_scan_keys(hipStream_t s, uint32_t W, uint8_t* dflags, char* drvk, co
     case 2: launch_many<2>(s, dflags, drvk, dc0, dnx, m, dK, dkeys, n_keys); break;
     default: launch_many<1>(s, dflags, drvk, dc0, dnx, m, dK, dkeys, n_keys);
   }
+}
+
+// The records of a chunk reach dc0 / dnx either as the caller's rows, by two copies, or from `strings` (records_strings.h): its text goes up and k_records_parse
+// writes the rows; its chunks are cut at the character cap as well, and k_records_resolve follows the scan kernel.
+int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings) {
+  const size_t n_keys = k.args.size();
+  uint32_t W;
+  const size_t chunk = scan_many_plan(n, n_keys, &W);
+  if (strings) strings->cut_chunks(n, chunk);
+  std::vector<ScanArgs> table((n_keys + W - 1) / W * W, ScanArgs{});      // the padding: no digits at all
+  std::copy(k.args.begin(), k.args.end(), table.begin());
+  hipStream_t s = c->stream;
+  int32_t rc;
+  const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
+  const size_t keys_bytes = (table.size() * sizeof(ScanArgs) + 31) & ~(size_t)31;
+  const size_t rows_bytes = (keys_bytes + chunk * 64 + chunk * n_keys * 33 + 31) & ~(size_t)31;
+  if ((rc = c->scalars_stage.reserve(rows_bytes + (strings ? strings->scratch_bytes() : 0)))) return rc;
+  char* dkeys = c->scalars_stage.as<char>(); char* dc0 = dkeys + keys_bytes; char* dnx = dc0 + chunk * 32; char* drvk = dnx + chunk * 32; uint8_t* dfl = (uint8_t*)(drvk + chunk * n_keys * 32);
+  char* dstr = dkeys + rows_bytes;
+  HIPCHK(hipMemcpyAsync(dkeys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, s));
+  for (size_t at = 0, ck = 0, m; at < n; at += m, ++ck) {
+    m = strings ? strings->cut[ck + 1] - at : (n - at < chunk ? n - at : chunk);
+    if (strings) { if ((rc = strings->fill(s, ck, dstr, dc0, dnx))) return rc; }
+    else {
+      HIPCHK(hipMemcpyAsync(dc0, (const char*)owner_c0 + at * 32, m * 32, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(dnx, (const char*)nonce_x + at * 32, m * 32, hipMemcpyHostToDevice, s));
+    }
+    launch_scan_keys(s, W, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys);
+    HIPCHK(hipGetLastError());
+    if (strings && (rc = strings->resolve(s, ck, dstr, dfl, drvk, dc0, (const ScanArgs*)dkeys, n_keys))) return rc;
+    // rows of m on the device, rows of n at the caller
+    HIPCHK(hipMemcpy2DAsync(flags + at, n, dfl, m, m, n_keys, hipMemcpyDeviceToHost, s));
+    if (rvk_out) HIPCHK(hipMemcpy2DAsync((char*)rvk_out + at * 32, n * 32, drvk, m * 32, m * 32, n_keys, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers; the table is a local of this call
+  }
+  return ALEO_MI355X_OK;
 }
 
 }  // namespace aleo_mi355x

@@ -50,8 +50,6 @@ static int32_t serial_tables_on_device(int device, const uint32_t** out) {
   *out = it->second; return ALEO_MI355X_OK;
 }
 
-static size_t env_size(const char* name, size_t dflt) { const char* e = std::getenv(name); if (!e || !*e) return dflt; char* end = nullptr; const unsigned long long v = std::strtoull(e, &end, 10); return end && *end == 0 ? (size_t)v : dflt; }
-
 static int32_t serials_on_device(Ctx* c, void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const SerialArgs& a) {
   const uint32_t* dK; if (int32_t rc = serial_tables_on_device(c->device, &dK)) return rc;
   size_t cap = env_size("ALEO_MI355X_SERIAL_CHUNK", SERIAL_CHUNK); if (cap == 0 || cap > SERIAL_CHUNK) cap = SERIAL_CHUNK;

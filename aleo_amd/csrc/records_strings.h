@@ -35,8 +35,6 @@ int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offse
 int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32, size_t n_keys);
 // the records come as rows (owner_c0, nonce_x) or, when `strings` is given, from it
 int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings = nullptr);
-// the one-key launch of k_records_scan_many over m records already on the device (flags m B, rvk m x 32 B); the caller checks hipGetLastError
-void launch_scan_one_key(hipStream_t s, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkey);
 // the plan of a K-key scan over n records — the records of one launch (the pair cap, the record cap, n) and *W, the keys one lane takes — and that launch over
 // m records already on the device (flags m x n_keys B, rvk m x n_keys x 32 B, [key][record]; dkeys padded with zero entries to a multiple of W); the caller
 // checks hipGetLastError

@@ -23,8 +23,6 @@ static constexpr uint32_t PARSE_BLOCK = 256;
 static constexpr size_t PARSE_CHUNK_RECORDS = (size_t)1 << 20;
 static constexpr size_t STRINGS_CHUNK_CHARS = (size_t)256 << 20;
 
-static size_t env_size(const char* name, size_t dflt) { const char* e = std::getenv(name); if (!e || !*e) return dflt; char* end = nullptr; const unsigned long long v = std::strtoull(e, &end, 10); return end && *end == 0 ? (size_t)v : dflt; }
-
 // what both paths refuse before they look at a string
 int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offsets, size_t n) {
   if (!n) return ALEO_MI355X_OK;

@@ -12,7 +12,7 @@ Callers that hold "record1…" strings — what the chain hands out — pass the
 decrypt_owned take that road for a RecordBatch or a sequence of strings, building RecordCiphertext objects only for the records they return or decrypt.
 decrypt_strings and balance (aleo_mi355x_records_decrypt_strings: csrc/records_found.hip) go from the strings of one account's search to the plain fields and
 microcredits of the records it owns in one call, and bring back only those; decrypt_owned on strings is that call and the rendering of the strings.
-decrypt_strings_many, balances and decrypt_owned_many (aleo_mi355x_records_decrypt_strings_many: csrc/records_found_many.hip) are the same for several accounts
+decrypt_strings_many, balances and decrypt_owned_many (aleo_mi355x_records_decrypt_strings_many: csrc/records_found.hip, the same flow with K keys) are the same for several accounts
 over the same strings: one upload and parse, one grouped scan, one gather and decryption of every owned (account, record) pair.
 What the reference needs before it can use an owned record — its serial number, to ask the chain whether it is spent (rust/src/api/blocking.rs:277-278;
 RecordPlaintext.serialNumberString of the wasm) — is serial_numbers, found_serial_numbers and unspent here (aleo_mi355x_records_serial_numbers,

@@ -658,7 +658,7 @@ const uint8_t* aleo_mi355x_found_status(const aleo_mi355x_found* found);
 const uint64_t* aleo_mi355x_found_microcredits(const aleo_mi355x_found* found);
 size_t aleo_mi355x_found_unparsed(const aleo_mi355x_found* found);
 size_t aleo_mi355x_found_first_unparsed(const aleo_mi355x_found* found);
-/* records_decrypt_strings for SEVERAL accounts in one call (csrc/records_found_many.hip): what a front end asks that serves K accounts over the same blocks and
+/* records_decrypt_strings for SEVERAL accounts in one call (csrc/records_found.hip): what a front end asks that serves K accounts over the same blocks and
  * needs each one's decrypted records and balance, not flags.  view_keys32 / address_xs32: n_keys x 32 bytes, 1 <= n_keys <= 64; keys, text and offsets are refused as
  * records_scan_strings refuses them (same status, same message, "key j" included).
  *   out           room for n_keys results: out[j] is byte for byte — every array, unparsed and first_unparsed — what records_decrypt_strings_host returns for key j

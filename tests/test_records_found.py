@@ -301,10 +301,12 @@ def test_found_kernels_are_gfx950_and_have_no_scratch():
                        check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         asm = open(out).read()
     assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
+    metas = re.findall(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S)
+    assert len(metas) == len(NEW_KERNELS)                                                                           # these four and no other
     for kernel in NEW_KERNELS:
-        meta = [m for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S) if kernel in m.group(0)]
+        meta = [m for m in metas if kernel in m]
         assert len(meta) == 1, kernel + ' is not in the code object'
-        field = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0].group(0)).group(1))
+        field = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0]).group(1))
         print('%s: vgpr_count %d, agpr_count %d, sgpr_count %d, group_segment_fixed_size %d, private_segment_fixed_size %d' % (
             kernel, field('vgpr_count'), field('agpr_count'), field('sgpr_count'), field('group_segment_fixed_size'), field('private_segment_fixed_size')))
         assert field('private_segment_fixed_size') == 0 and field('vgpr_spill_count') == 0 and field('sgpr_spill_count') == 0

@@ -61,6 +61,7 @@ def main():
         base.aleo_mi355x_poseidon_hash_fr.restype = ctypes.c_int32
         base.aleo_mi355x_poseidon_hash_fr.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
         base.aleo_mi355x_version.restype = ctypes.c_char_p
+        base.aleo_mi355x_records_decrypt_fields.restype = ctypes.c_int32; base.aleo_mi355x_records_decrypt_fields.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t]
     pool = ThreadPoolExecutor(16)
     lines = ['records_decrypt_bench: aleo_mi355x_records_decrypt_fields (host buffers, upload and download inside the timed call, threshold 0) against one',
              'aleo_mi355x_poseidon_hash_fr call per record on one thread (%s; the subtraction left out),' % ('baseline library: %s' % base.aleo_mi355x_version().decode() if a.baseline_lib else 'this build'),
@@ -83,7 +84,9 @@ def main():
         hash_fr, pin, prnd = base.aleo_mi355x_poseidon_hash_fr, [inp[i].ctypes.data for i in range(n)] if lg <= a.host_lg else [], rnd.ctypes.data
         def baseline():
             for q in pin: hash_fr(8, q, 2, prnd, m)
+        def gpu_base(): assert base.aleo_mi355x_records_decrypt_fields(p(plain), p(flags), p(rvk), p(off), p(fields), n) == 0
         fns = {'gpu': gpu}
+        if a.baseline_lib: fns['gpu, baseline library'] = gpu_base      # the same call through the other build: whether the call itself moved
         if lg <= a.host_lg: fns.update({'baseline': baseline, 'host x1': host1, 'host x16': host16})
         r = median_of(fns, a.rounds)
         if lg <= a.host_lg:
@@ -97,6 +100,7 @@ def main():
             else: t, mark, spread = rates[k] * n, '~', ''
             out[k] = t
             row += ' %s %10.3f%s%s %7.2fx |' % (k, t * 1e3, mark, spread, t / g)
+        if a.baseline_lib: row += ' gpu, baseline library %9.3f (%.3f..%.3f) |' % tuple(v * 1e3 for v in r['gpu, baseline library'][:3])
         lines.append(row); print(row, flush=True)
         return g, out
 

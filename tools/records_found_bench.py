@@ -18,10 +18,11 @@ random bytes in the same layout.  Two roads to the plain fields and microcredits
 and, up to --python-n strings, records.decrypt_owned of this build on a RecordBatch beside them (it renders every owned record's string on the host).
 With --keys K: K accounts under the reference's generator, each owning the given fraction of the strings (a credits record of its own, private owner, encrypted
 here with oracle/poseidon.py), and three roads to every account's owned records, plain fields and microcredits:
-  many     aleo_mi355x_records_decrypt_strings_many and K x aleo_mi355x_found_free
+  many     aleo_mi355x_records_decrypt_strings_many and K x aleo_mi355x_found_free; with --baseline-lib the same road through the baseline library beside it
+           ("many, baseline"), which shows whether the K-account call itself moved
   calls    K calls of aleo_mi355x_records_decrypt_strings of the baseline library (road a)
   scan     one aleo_mi355x_records_scan_strings of the baseline library with K keys, then per account the host tail of `parent` above (road b)
-and road (a) once more through this build, which shows whether the one-account call itself moved.
+and road (a) once more through this build, with its own min..max, which shows whether the one-account call itself moved.
 Every timing: host buffers, copies inside the timed call, one warm call, the median of --reps with min..max, the roads alternating, no profiler.  Bytes downloaded
 per call are counted from the sizes, not measured.  Needs a gfx950 device: there is no fallback."""
 import argparse, ctypes, json, os, random, statistics, sys, time
@@ -127,11 +128,11 @@ def roads_many(L, B, batch, accounts):
     state = {}
     def summary(Lib, out): return (int(Lib.aleo_mi355x_found_count(out)), int(Lib.aleo_mi355x_found_fields(out)), int(np.frombuffer(ctypes.string_at(Lib.aleo_mi355x_found_microcredits(out), 8), dtype=np.uint64)[0]))
 
-    def many():
+    def many(Lib=L, name='many'):
         out = (ctypes.c_void_p * K)()
-        aleo_amd._lib.check(L.aleo_mi355x_records_decrypt_strings_many(out, tp, p(batch.offsets), n, p(vks), p(axs), K), 'records_decrypt_strings_many')
-        state['many'] = [summary(L, ctypes.c_void_p(out[j])) for j in range(K)]
-        for j in range(K): L.aleo_mi355x_found_free(ctypes.c_void_p(out[j]))
+        assert Lib.aleo_mi355x_records_decrypt_strings_many(out, tp, p(batch.offsets), n, p(vks), p(axs), K) == 0
+        state[name] = [summary(Lib, ctypes.c_void_p(out[j])) for j in range(K)]
+        for j in range(K): Lib.aleo_mi355x_found_free(ctypes.c_void_p(out[j]))
 
     def calls(Lib=B, name='calls'):
         got = []
@@ -156,20 +157,21 @@ def roads_many(L, B, batch, accounts):
             got.append((len(idx), at))
         state['scan'] = got
 
-    return many, calls, scan, (lambda: calls(L, 'calls_here')), state
+    return many, calls, scan, (lambda: calls(L, 'calls_here')), (lambda: many(B, 'many_base')), state
 
 
 def main_many(a, L, pool):
     K = a.keys; accounts = accounts_of(K)
     if a.trace_case:
         batch, per = make_many(1 << 20, 0.01, pool, accounts)
-        many, _, _, _, state = roads_many(L, L, batch, accounts)
+        many, _, _, _, _, state = roads_many(L, L, batch, accounts)
         for _ in range(4): many()
         print('trace case: 2^20 strings, %d accounts, %d owned and %d fields each' % ((K,) + state['many'][0][:2]))
         return
     B = bind(a.baseline_lib) if a.baseline_lib else L
     vp, sz = ctypes.c_void_p, ctypes.c_size_t
     B.aleo_mi355x_records_decrypt_strings.argtypes = [ctypes.POINTER(vp), vp, vp, sz, vp, vp]
+    B.aleo_mi355x_records_decrypt_strings_many.argtypes = [ctypes.POINTER(vp), vp, vp, sz, vp, vp, sz]
     for name in ('count', 'fields'): getattr(B, 'aleo_mi355x_found_' + name).argtypes = [vp]; getattr(B, 'aleo_mi355x_found_' + name).restype = sz
     B.aleo_mi355x_found_microcredits.argtypes = [vp]; B.aleo_mi355x_found_microcredits.restype = vp; B.aleo_mi355x_found_free.argtypes = [vp]; B.aleo_mi355x_found_free.restype = None
     lines = ['# records_found_bench --keys %d --sizes %s --fractions %s --reps %d%s' % (K, a.sizes, a.fractions, a.reps, ' --baseline-lib (the parent commit\'s build)' if a.baseline_lib else ''),
@@ -179,16 +181,19 @@ def main_many(a, L, pool):
         n = 1 << lg
         for fr in [float(v) for v in a.fractions.split(',')]:
             batch, per = make_many(n, fr, pool, accounts)
-            many, calls, scan, calls_here, state = roads_many(L, B, batch, accounts)
-            r = timed({'many': many, 'calls': calls, 'scan': scan, 'calls_here': calls_here}, a.reps)
+            many, calls, scan, calls_here, many_base, state = roads_many(L, B, batch, accounts)
+            fns = {'many': many, 'calls': calls, 'scan': scan, 'calls_here': calls_here}
+            if a.baseline_lib: fns['many_base'] = many_base
+            r = timed(fns, a.reps)
             want = [(per, 2 * per, acc[3]) for acc in accounts]
-            assert state['many'] == want == state['calls'] == state['calls_here'] and state['scan'] == [w[:2] for w in want], (state, per)
+            assert state['many'] == want == state['calls'] == state['calls_here'] == state.get('many_base', want) and state['scan'] == [w[:2] for w in want], (state, per)
             c = per * K
             down_many = 16 + 8 * K + c * (4 + 1 + 32 + 4 + 1 + 8) + 4 + 32 * 2 * c; down_calls = K * 16 + c * (4 + 1 + 32 + 4 + 1 + 8) + 4 * K + 32 * 2 * c; down_scan = n * (33 * K + 1) + 32 * 2 * c + c
             best = min(r['calls'][0], r['scan'][0])
-            row = '2^%-2d x %d keys %5.1f %% owned (%7d each)  many %9.3f (%.3f..%.3f)  calls (a) %10.3f (%.3f..%.3f)  scan (b) %10.3f (%.3f..%.3f)  %5.2fx of the better   (a) through this build %10.3f   down: many %10d B  (a) %10d B  (b) %10d B' % (
+            row = '2^%-2d x %d keys %5.1f %% owned (%7d each)  many %9.3f (%.3f..%.3f)  calls (a) %10.3f (%.3f..%.3f)  scan (b) %10.3f (%.3f..%.3f)  %5.2fx of the better   (a) through this build %10.3f (%.3f..%.3f)%s   down: many %10d B  (a) %10d B  (b) %10d B' % (
                 lg, K, 100 * fr, per, r['many'][0] * 1e3, r['many'][1] * 1e3, r['many'][2] * 1e3, r['calls'][0] * 1e3, r['calls'][1] * 1e3, r['calls'][2] * 1e3, r['scan'][0] * 1e3, r['scan'][1] * 1e3, r['scan'][2] * 1e3,
-                best / r['many'][0], r['calls_here'][0] * 1e3, down_many, down_calls, down_scan)
+                best / r['many'][0], r['calls_here'][0] * 1e3, r['calls_here'][1] * 1e3, r['calls_here'][2] * 1e3,
+                '   many, baseline %9.3f (%.3f..%.3f)' % tuple(v * 1e3 for v in r['many_base']) if a.baseline_lib else '', down_many, down_calls, down_scan)
             lines.append(row); print(row, flush=True)
         lines.append('')
     if a.out:
@@ -198,9 +203,9 @@ def main_many(a, L, pool):
 def timed(fns, reps):
     for f in fns.values(): f()
     ts = {k: [] for k in fns}
-    order = list(fns.items())
-    for rep in range(reps):                                     # the roads alternate and the round starts one road later every time: none always runs behind the same one
-        for k, f in order[rep % len(order):] + order[:rep % len(order)]:
+    for rep in range(reps):                                     # the roads alternate in a new order every round (seeded): none always runs behind the same one
+        order = list(fns.items()); random.Random(rep).shuffle(order)
+        for k, f in order:
             t0 = time.perf_counter(); f(); ts[k].append(time.perf_counter() - t0)
     return {k: (statistics.median(v), min(v), max(v)) for k, v in ts.items()}
 

@@ -15,7 +15,7 @@ above it, and for 16 threads everywhere, the host time is the measured rate time
 
 With --keys the tool measures the grouped scan instead (aleo_mi355x_records_scan_many: K accounts over the same records in one call) against what it replaces,
 K calls of aleo_mi355x_records_scan over those records — made through --baseline-lib when given (another build of the library, for instance the parent
-commit's), else through this build, whose single-key kernel is the same code.  Shapes are lg n:K pairs; at each shape the baseline, the library's own rule and
+commit's; its own grouped scan is then timed too, as "rule, baseline"), else through this build, whose single-key kernel is the same code.  Shapes are lg n:K pairs; at each shape the baseline, the library's own rule and
 every forced width (ALEO_MI355X_SCAN_KEYS_PER_LANE = 1, 2, 4, 8) are warmed up once and then timed in turn, round after round, so that whatever else the
 machine does falls on all of them alike; output buffers are allocated once, outside the timed calls.  A figure is the median over the rounds, with min..max.
 
@@ -74,7 +74,8 @@ def bench_many(a):
     base = L
     if a.baseline_lib:
         base = ctypes.CDLL(os.path.abspath(a.baseline_lib))
-        for name in ('aleo_mi355x_records_scan', 'aleo_mi355x_init_device'): getattr(base, name).restype = ctypes.c_int32
+        for name in ('aleo_mi355x_records_scan', 'aleo_mi355x_records_scan_many', 'aleo_mi355x_init_device'): getattr(base, name).restype = ctypes.c_int32
+        base.aleo_mi355x_records_scan_many.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t]
         base.aleo_mi355x_records_scan.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2
         base.aleo_mi355x_init_device.argtypes = [ctypes.c_int32]
         base.aleo_mi355x_version.restype = ctypes.c_char_p
@@ -82,7 +83,7 @@ def bench_many(a):
     shapes = [tuple(int(v) for v in s.split(':')) for s in a.shapes.split(',')]
     c0, nx, _, _ = make_records(1 << max(lg for lg, _ in shapes))
     p = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
-    configs = ['K single scans', 'rule', 'W=1', 'W=2', 'W=4', 'W=8']
+    configs = ['K single scans', 'rule', 'W=1', 'W=2', 'W=4', 'W=8'] + (['rule, baseline'] if a.baseline_lib else [])      # the last: the grouped scan of the baseline library
     lines = ['records_scan_bench --keys: aleo_mi355x_records_scan_many (K accounts, n records, one call; host buffers, upload and download inside the timed call) against',
              'K calls of aleo_mi355x_records_scan over the same records (%s).  ms per call: median (min..max) over %d rounds, the configurations timed in turn within a round;'
              % ('baseline library: %s' % base.aleo_mi355x_version().decode() if a.baseline_lib else 'this build', a.rounds),
@@ -97,9 +98,10 @@ def bench_many(a):
             if cfg == 'K single scans':
                 for j in range(k): assert base.aleo_mi355x_records_scan(p(bflags[j]), p(brvk[j]), p(C0), p(NX), n, p(vk[j]), p(ax[j])) == 0
                 return
-            if cfg == 'rule': os.environ.pop('ALEO_MI355X_SCAN_KEYS_PER_LANE', None)
+            if cfg.startswith('rule'): os.environ.pop('ALEO_MI355X_SCAN_KEYS_PER_LANE', None)
             else: os.environ['ALEO_MI355X_SCAN_KEYS_PER_LANE'] = cfg[2:]
-            aleo_amd._lib.check(L.aleo_mi355x_records_scan_many(p(flags), p(rvk), p(C0), p(NX), n, p(vk), p(ax), k), 'records_scan_many')
+            if cfg == 'rule, baseline': assert base.aleo_mi355x_records_scan_many(p(flags), p(rvk), p(C0), p(NX), n, p(vk), p(ax), k) == 0
+            else: aleo_amd._lib.check(L.aleo_mi355x_records_scan_many(p(flags), p(rvk), p(C0), p(NX), n, p(vk), p(ax), k), 'records_scan_many')
         run(configs[0])
         for cfg in configs[1:]:                              # warm-up of every shape and width, and the parity of what is about to be timed
             flags[:] = 7; run(cfg)
