@@ -34,6 +34,8 @@ EXPORTS = [
     'aleo_mi355x_records_decrypt_strings_many', 'aleo_mi355x_records_decrypt_strings_many_host',
     'aleo_mi355x_records_serial_numbers', 'aleo_mi355x_records_serial_numbers_host', 'aleo_mi355x_min_serials', 'aleo_mi355x_found_serial_numbers',
     'aleo_mi355x_record_commitment', 'aleo_mi355x_record_checksum', 'aleo_mi355x_account_from_private_key',
+    'aleo_mi355x_records_unspent_strings', 'aleo_mi355x_records_unspent_strings_host', 'aleo_mi355x_records_unspent_strings_many', 'aleo_mi355x_records_unspent_strings_many_host',
+    'aleo_mi355x_found_serials', 'aleo_mi355x_found_owned',
 ]
 
 
@@ -200,9 +202,13 @@ def lib():
         'aleo_mi355x_record_commitment': ([vp, ctypes.c_char_p, vp, sz, ctypes.c_char_p, ctypes.c_char_p], i32),
         'aleo_mi355x_record_checksum': ([vp, ctypes.c_char_p], i32),
         'aleo_mi355x_account_from_private_key': ([ctypes.c_char_p, vp, vp, vp], i32),
+        'aleo_mi355x_records_unspent_strings': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, vp, vp, vp, sz], i32),
+        'aleo_mi355x_records_unspent_strings_host': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, vp, vp, vp, sz], i32),
+        'aleo_mi355x_records_unspent_strings_many': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, vp, vp, sz, vp, sz], i32),
+        'aleo_mi355x_records_unspent_strings_many_host': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, vp, vp, sz, vp, sz], i32),
         'aleo_mi355x_found_free': ([vp], None),
-        **{'aleo_mi355x_found_' + name: ([vp], sz) for name in ('count', 'fields', 'unparsed', 'first_unparsed')},
-        **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits')},
+        **{'aleo_mi355x_found_' + name: ([vp], sz) for name in ('count', 'fields', 'unparsed', 'first_unparsed', 'owned')},
+        **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits', 'serials')},
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name); f.argtypes = args; f.restype = res

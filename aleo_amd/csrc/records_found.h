@@ -1,0 +1,59 @@
+// records_found.h — what records_found.hip shares with records_unspent.hip: the device flow of decrypt_strings[_many] with an optional stage between
+// k_found_microcredits and the downloads, the second level of its exclusive sums, and the block-level sums both files' kernels run.  From records_serial.hip:
+// the resident tables of the serial-number lane and the launch cap.
+#pragma once
+#include "records_strings.h"
+#include "records_found_host.hpp"
+#include <memory>
+
+namespace aleo_mi355x {
+
+static constexpr uint32_t FOUND_BLOCK = 256, FOUND_TOP = 1024;
+
+#ifdef __HIPCC__
+// The exclusive sums of two values over the block's 256 lanes (wave shuffles, then the four wave totals through LDS); *ta / *tb: the block's totals.
+__device__ __forceinline__ void block_exclusive2(uint32_t& a, uint32_t& b, uint32_t (*wave_tot)[FOUND_BLOCK / 64], uint32_t* ta, uint32_t* tb) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t ia = a, ib = b;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t ua = __shfl_up(ia, d, 64), ub = __shfl_up(ib, d, 64);
+    if (lane >= (uint32_t)d) { ia += ua; ib += ub; }
+  }
+  if (lane == 63) { wave_tot[0][wave] = ia; wave_tot[1][wave] = ib; }
+  __syncthreads();
+  uint32_t ba = 0, bb = 0, sa = 0, sb = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < FOUND_BLOCK / 64; ++w) { if (w < wave) { ba += wave_tot[0][w]; bb += wave_tot[1][w]; } sa += wave_tot[0][w]; sb += wave_tot[1][w]; }
+  a = ba + ia - a; b = bb + ib - b; *ta = sa; *tb = sb;
+}
+#endif
+
+// One chunk's compacted arrays on the device, all keys' one after another (key 0's records, then key 1's, each in record order): `owned` records with `nf`
+// fields; key j's are the ranks first[j] .. first[j + 1] and the fields first_f[j] .. first_f[j + 1] (K + 1 entries each).  index is chunk-relative, off has
+// owned + 1 entries.  status null: every record's is 0.  serials null: there are none.
+struct FoundChunk {
+  char* fields; uint32_t* index; int8_t* kind; char* rvk; uint32_t* off; uint64_t* mc; uint8_t* status; char* serials;
+  size_t at, owned, nf;                                        // at: the chunk's first record among the call's strings
+  std::vector<uint32_t> first, first_f;
+};
+
+// The optional stage of found_many_on_device.  gathered: behind k_found_gather, before the decryption is launched (ch.index is written; the stage may wait for
+// it while the decryption's kernels are still to come).  filter: behind k_found_microcredits, on the same stream: it may replace every pointer, count and
+// boundary of `ch` by those of the records it keeps, in buffers of its own; it returns with the stream idle.  What `ch` then holds is what comes down.
+struct FoundStage {
+  virtual int32_t gathered(Ctx* c, hipStream_t s, const FoundChunk& ch) = 0;
+  virtual int32_t filter(Ctx* c, hipStream_t s, FoundChunk& ch) = 0;
+  virtual ~FoundStage() = default;
+};
+
+// records_found.hip: the flow of decrypt_strings_many over K = k.args.size() keys into R[0 .. K); R[j]->owned counts what key j owned before any stage
+int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>& R, const char* text, const uint64_t* offsets, size_t n, const ManyKeys& k, FoundStage* stage = nullptr);
+// k_found_offsets over `rows` block totals of two kinds (blk: [fields | owned][rows]) in groups of nb: see the kernel; the caller checks hipGetLastError
+void launch_found_offsets(hipStream_t s, uint32_t* blk, uint32_t* stat, uint32_t rows, uint32_t nb);
+
+// records_serial.hip: the lane's tables on this device (uploaded once per device), and the commitments one launch may take (ALEO_MI355X_SERIAL_CHUNK, read per call)
+int32_t serial_tables_on_device(int device, const uint32_t** out);
+size_t serial_chunk_cap();
+
+}  // namespace aleo_mi355x

@@ -30,31 +30,13 @@
 // The host path is K passes of records_found_host.hpp's found_on_host, which puts the existing host calls together (the lane parse and host scan of
 // scan_strings_host, records_plaintext.hpp's structure as record_fields reads it, the host decryption); it shares no code with the walk above, which is what
 // the device tests compare it with.
-#include "records_strings.h"
-#include "records_found_host.hpp"
-#include <memory>
+// records_unspent_strings[_many] (records_unspent.hip) is this flow with one more stage (records_found.h FoundStage) between k_found_microcredits and the
+// downloads: what comes down is then what the stage kept.
+#include "records_found.h"
 
 namespace aleo_mi355x {
 
-static constexpr uint32_t FOUND_BLOCK = 256, FOUND_TOP = 1024;
 static constexpr uint32_t FOUND_LDS_BYTES = 64 * 1024;              // k_records_parse's budget
-
-// The exclusive sums of two values over the block's 256 lanes (wave shuffles, then the four wave totals through LDS); *ta / *tb: the block's totals.
-__device__ __forceinline__ void block_exclusive2(uint32_t& a, uint32_t& b, uint32_t (*wave_tot)[FOUND_BLOCK / 64], uint32_t* ta, uint32_t* tb) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t ia = a, ib = b;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t ua = __shfl_up(ia, d, 64), ub = __shfl_up(ib, d, 64);
-    if (lane >= (uint32_t)d) { ia += ua; ib += ub; }
-  }
-  if (lane == 63) { wave_tot[0][wave] = ia; wave_tot[1][wave] = ib; }
-  __syncthreads();
-  uint32_t ba = 0, bb = 0, sa = 0, sb = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < FOUND_BLOCK / 64; ++w) { if (w < wave) { ba += wave_tot[0][w]; bb += wave_tot[1][w]; } sa += wave_tot[0][w]; sb += wave_tot[1][w]; }
-  a = ba + ia - a; b = bb + ib - b; *ta = sa; *tb = sb;
-}
 
 // The block's span of the text into LDS where it fits, as k_records_parse stages it: text readable up to the next multiple of 16 past the chunk's last character.
 __device__ __forceinline__ bool stage_span(uint4* stage, const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t b0, uint32_t n, uint32_t* lo_out) {
@@ -203,8 +185,12 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_found_microcredits(uint8_t* __r
     w[0] = l.x; w[1] = l.y; w[2] = l.z; w[3] = l.w; w[4] = h.x; w[5] = h.y; w[6] = h.z; w[7] = h.w; });
 }
 
+void launch_found_offsets(hipStream_t s, uint32_t* blk, uint32_t* stat, uint32_t rows, uint32_t nb) {
+  hipLaunchKernelGGL(k_found_offsets, dim3(1), dim3(FOUND_TOP), 0, s, blk, stat, rows, nb);
+}
+
 // ---- the device flow ----------------------------------------------------------------------------------------------------------------------------------
-static int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>& R, const char* text, const uint64_t* offsets, size_t n, const ManyKeys& k) {
+int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>& R, const char* text, const uint64_t* offsets, size_t n, const ManyKeys& k, FoundStage* stage) {
   const size_t K = k.args.size();
   uint32_t W;
   const size_t chunk = scan_many_plan(n, K, &W);
@@ -250,15 +236,20 @@ static int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>&
     HIPCHK(hipMemsetAsync(dstat, 0, 16, s));
     hipLaunchKernelGGL(k_found_count, pairs, dim3(FOUND_BLOCK), 0, s, dcnt, dpos, dpre, dblk, dstat, (const uint8_t*)dfl, (const uint8_t*)dscan, dkinds, dtext, dsoff, (uint32_t)m);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_found_offsets, dim3(1), dim3(FOUND_TOP), 0, s, dblk, dstat, nb * (uint32_t)K, nb);
+    launch_found_offsets(s, dblk, dstat, nb * (uint32_t)K, nb);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->h_pinned, dstat, stat_words * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));                           // the one wait before the gather: the host sizes the compacted arrays
     const size_t owned = stat[0], nf = stat[1];
     if (stat[2]) for (auto& r : R) { if (!r->unparsed) r->first_unparsed = at + (m - stat[3]); r->unparsed += stat[2]; }
     if (!owned) continue;
+    // key j's records: the ranks first[j] .. first[j + 1], the fields first_f[j] .. first_f[j + 1] (a stage may use h_pinned, and moves these boundaries)
+    FoundChunk ch{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, at, owned, nf, std::vector<uint32_t>(K + 1), std::vector<uint32_t>(K + 1)};
+    for (size_t j = 0; j < K; ++j) { ch.first[j] = stat[4 + j]; ch.first_f[j] = stat[4 + K + j]; }
+    ch.first[K] = (uint32_t)owned; ch.first_f[K] = (uint32_t)nf;
     for (size_t j = 0; j < K; ++j) {
-      const size_t mine = (j + 1 < K ? stat[4 + j + 1] : owned) - stat[4 + j], mine_f = (j + 1 < K ? stat[4 + K + j + 1] : nf) - stat[4 + K + j];
+      const size_t mine = ch.first[j + 1] - ch.first[j], mine_f = ch.first_f[j + 1] - ch.first_f[j];
+      R[j]->owned += mine;
       if (R[j]->index.size() + mine > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 owned records");
       if ((size_t)R[j]->offsets.back() + mine_f > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 private fields");
     }
@@ -275,11 +266,20 @@ static int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>&
     hipLaunchKernelGGL(k_found_gather, pairs, dim3(FOUND_BLOCK), 0, s, dfields, dindex, dkind, dcrvk, doff, dcpre, dmc, dmc_at, dmc_n, (const uint32_t*)dcnt, (const uint32_t*)dpos,
                        (const uint8_t*)dpre, (const uint32_t*)dblk, (const uint8_t*)dfl, dkinds, (const char*)drvk, dtext, dsoff, (uint32_t)m, (uint32_t)owned, (uint32_t)nf);
     HIPCHK(hipGetLastError());
+    ch.fields = dfields; ch.index = dindex; ch.kind = dkind; ch.rvk = dcrvk; ch.off = doff; ch.mc = dmc; ch.status = dstatus;
+    if (stage && (rc = stage->gathered(c, s, ch))) return rc;
     const size_t put = K == 1 ? to.index.size() : 0, put_f = K == 1 ? to.offsets.back() : 0;      // `staged` starts over with every chunk
-    to.index.resize(put + owned); to.offsets.resize(put + owned + 1); to.kind.resize(put + owned); to.rvk.resize((put + owned) * 32); to.status.resize(put + owned);
-    to.microcredits.resize(put + owned); to.plain.resize((put_f + nf) * 32);
-    uint32_t* h_off = to.offsets.data() + put;                // chunk-relative until a base is added below
-    HIPCHK(hipMemcpyAsync(h_off, doff, (owned + 1) * 4, hipMemcpyDeviceToHost, s));
+    auto size_to = [&](size_t records, size_t fields) {
+      to.index.resize(put + records); to.offsets.resize(put + records + 1); to.kind.resize(put + records); to.rvk.resize((put + records) * 32); to.status.resize(put + records);
+      to.microcredits.resize(put + records); to.plain.resize((put_f + fields) * 32);
+      if (stage) to.serials.resize((put + records) * 32);
+    };
+    // without a stage everything owned comes down, and the offsets come first; with one the result is sized for what it keeps, and the unfiltered offsets, which
+    // only the cut of the decryption's launches reads, go aside
+    std::vector<uint32_t> off_aside;
+    if (stage) off_aside.resize(nf > cap ? owned + 1 : 0); else size_to(owned, nf);
+    uint32_t* h_off = stage ? off_aside.data() : to.offsets.data() + put;      // chunk-relative until a base is added below
+    if (!stage || nf > cap) HIPCHK(hipMemcpyAsync(h_off, doff, (owned + 1) * 4, hipMemcpyDeviceToHost, s));
     if (nf <= cap) launch_records_decrypt(s, dfields, ddec, dcrvk, doff, 0, owned, dK);
     else {                                                     // launches of whole records within the cap, one record at least, across key boundaries: the host needs the offsets to cut
       HIPCHK(hipStreamSynchronize(s));
@@ -295,18 +295,27 @@ static int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>&
     hipLaunchKernelGGL(k_found_microcredits, dim3((uint32_t)((owned + FOUND_BLOCK - 1) / FOUND_BLOCK)), dim3(FOUND_BLOCK), 0, s, dstatus, dmc, dfields, (const uint8_t*)dcpre, (const uint8_t*)ddec,
                        (const uint32_t*)doff, (const uint32_t*)dmc_at, (const uint32_t*)dmc_n, (uint32_t)owned);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(to.index.data() + put, dindex, owned * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(to.kind.data() + put, dkind, owned, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(to.rvk.data() + put * 32, dcrvk, owned * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(to.status.data() + put, dstatus, owned, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(to.microcredits.data() + put, dmc, owned * 8, hipMemcpyDeviceToHost, s));
-    if (nf) HIPCHK(hipMemcpyAsync(to.plain.data() + put_f * 32, dfields, nf * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers; h_pinned is read below and not written before the next chunk's copy
+    if (stage) {                                               // from here on `ch` is what the stage kept
+      if ((rc = stage->filter(c, s, ch))) return rc;
+      if (!ch.owned) continue;
+      size_to(ch.owned, ch.nf);
+      h_off = to.offsets.data() + put;
+      HIPCHK(hipMemcpyAsync(h_off, ch.off, (ch.owned + 1) * 4, hipMemcpyDeviceToHost, s));
+    }
+    const size_t got = ch.owned, got_f = ch.nf;
+    HIPCHK(hipMemcpyAsync(to.index.data() + put, ch.index, got * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(to.kind.data() + put, ch.kind, got, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(to.rvk.data() + put * 32, ch.rvk, got * 32, hipMemcpyDeviceToHost, s));
+    if (ch.status) HIPCHK(hipMemcpyAsync(to.status.data() + put, ch.status, got, hipMemcpyDeviceToHost, s));      // else zeros, as the resize left them
+    HIPCHK(hipMemcpyAsync(to.microcredits.data() + put, ch.mc, got * 8, hipMemcpyDeviceToHost, s));
+    if (ch.serials) HIPCHK(hipMemcpyAsync(to.serials.data() + put * 32, ch.serials, got * 32, hipMemcpyDeviceToHost, s));
+    if (got_f) HIPCHK(hipMemcpyAsync(to.plain.data() + put_f * 32, ch.fields, got_f * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers
     if (K == 1) {                                              // in place already: the split is the two bases
-      for (size_t q = 0; q < owned; ++q) { to.index[put + q] += (uint32_t)at; h_off[q] += (uint32_t)put_f; }
-      h_off[owned] += (uint32_t)put_f;
+      for (size_t q = 0; q < got; ++q) { to.index[put + q] += (uint32_t)at; h_off[q] += (uint32_t)put_f; }
+      h_off[got] += (uint32_t)put_f;
     } else for (size_t j = 0; j < K; ++j) {                    // key j's records: the ranks a .. e, the fields fa .. fe
-      const size_t a = stat[4 + j], e = j + 1 < K ? stat[4 + j + 1] : owned, fa = stat[4 + K + j], fe = j + 1 < K ? stat[4 + K + j + 1] : nf;
+      const size_t a = ch.first[j], e = ch.first[j + 1], fa = ch.first_f[j], fe = ch.first_f[j + 1];
       if (a == e) continue;
       Found& r = *R[j];
       const size_t have = r.index.size(), have_f = r.offsets.back();
@@ -317,6 +326,7 @@ static int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>&
       r.status.insert(r.status.end(), staged.status.begin() + a, staged.status.begin() + e);
       r.microcredits.insert(r.microcredits.end(), staged.microcredits.begin() + a, staged.microcredits.begin() + e);
       r.plain.insert(r.plain.end(), staged.plain.begin() + fa * 32, staged.plain.begin() + fe * 32);
+      if (stage) r.serials.insert(r.serials.end(), staged.serials.begin() + a * 32, staged.serials.begin() + e * 32);
     }
   }
   return ALEO_MI355X_OK;

@@ -17,6 +17,9 @@ struct aleo_mi355x_found {
   std::vector<uint8_t> rvk, plain, status;
   std::vector<uint64_t> microcredits;
   size_t unparsed = 0, first_unparsed = 0;
+  // records_unspent_strings[_many] (records_unspent.hip): the result holds the records that are left of `owned`, and their serial numbers
+  bool filtered = false; size_t owned = 0;
+  std::vector<uint8_t> serials;
 };
 
 namespace aleo_mi355x {

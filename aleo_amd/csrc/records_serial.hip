@@ -6,7 +6,7 @@
 // The kernel (one commitment per lane: records_serial_lane.h), the same bytes on the host (serial_host.hpp — what small batches take, and the checker), the
 // routing threshold, and the host-only calls around them: a record's commitment and checksum (records_bits.hpp) and the account of a private key.
 // The lane's tables (181 KB: serial_host.hpp serial_tables) are built on the host at first use and stay resident per device for the life of the process.
-#include "entry.h"
+#include "records_found.h"
 #include "records_bits.hpp"
 #include <cstdlib>
 
@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(SERIAL_BLOCK) k_records_serial(char* __restric
 }
 
 // The tables of one device: uploaded once, under the lock, and never freed; the copy is complete before the pointer is handed out.
-static int32_t serial_tables_on_device(int device, const uint32_t** out) {
+int32_t serial_tables_on_device(int device, const uint32_t** out) {
   static std::mutex mu; static std::map<int, const uint32_t*> resident;
   std::lock_guard<std::mutex> lk(mu);
   auto it = resident.find(device);
@@ -50,9 +50,11 @@ static int32_t serial_tables_on_device(int device, const uint32_t** out) {
   *out = it->second; return ALEO_MI355X_OK;
 }
 
+size_t serial_chunk_cap() { const size_t cap = env_size("ALEO_MI355X_SERIAL_CHUNK", SERIAL_CHUNK); return cap == 0 || cap > SERIAL_CHUNK ? SERIAL_CHUNK : cap; }
+
 static int32_t serials_on_device(Ctx* c, void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const SerialArgs& a) {
   const uint32_t* dK; if (int32_t rc = serial_tables_on_device(c->device, &dK)) return rc;
-  size_t cap = env_size("ALEO_MI355X_SERIAL_CHUNK", SERIAL_CHUNK); if (cap == 0 || cap > SERIAL_CHUNK) cap = SERIAL_CHUNK;
+  const size_t cap = serial_chunk_cap();
   const size_t chunk = n < cap ? n : cap;
   hipStream_t s = c->stream;
   if (int32_t rc = c->scalars_stage.reserve(chunk * 65)) return rc;

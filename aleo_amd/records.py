@@ -299,11 +299,14 @@ def decrypt_fields(rvk: np.ndarray, offsets, fields: np.ndarray, host: bool = Fa
 class FoundRecords:
     """What decrypt_strings returns, as numpy copies: for the c records the account owns, in ascending record index, index (uint32[c]), kind (int8[c]: 0 public
     owner, 1 private), rvk (uint8[c, 32]), offsets (uint32[c + 1]) into plain (uint8[fields, 32]: the decrypted private fields in randomizer order), status
-    (uint8[c]: 0 decrypted, 2 malformed, 4 the structure is refused) and microcredits (uint64[c]); unparsed / first_unparsed: the strings that do not parse."""
+    (uint8[c]: 0 decrypted, 2 malformed, 4 the structure is refused) and microcredits (uint64[c]); unparsed / first_unparsed: the strings that do not parse.
+    From unspent_strings[_many] the c records are those left of the `owned` the account owns, and serials (uint8[c, 32]) their serial numbers; from any other
+    call serials is None and owned is c."""
 
-    def __init__(self, index, kind, rvk, offsets, plain, status, microcredits, unparsed: int, first_unparsed: int):
+    def __init__(self, index, kind, rvk, offsets, plain, status, microcredits, unparsed: int, first_unparsed: int, serials=None, owned=None):
         self.index, self.kind, self.rvk, self.offsets, self.plain, self.status, self.microcredits = index, kind, rvk, offsets, plain, status, microcredits
         self.unparsed, self.first_unparsed = unparsed, first_unparsed
+        self.serials, self.owned = serials, len(index) if owned is None else owned
 
     def __len__(self): return len(self.index)
 
@@ -336,7 +339,8 @@ def _found_of(L, out) -> FoundRecords:
             return np.frombuffer(ctypes.string_at(getattr(L, 'aleo_mi355x_found_' + name)(out), size) if size else b'', dtype=dtype).reshape(shape).copy()
         return FoundRecords(copy('index', np.uint32, c, (c,)), copy('kind', np.int8, c, (c,)), copy('rvk', np.uint8, 32 * c, (c, 32)), copy('offsets', np.uint32, c + 1, (c + 1,)),
                             copy('plain', np.uint8, 32 * nf, (nf, 32)), copy('status', np.uint8, c, (c,)), copy('microcredits', np.uint64, c, (c,)),
-                            int(L.aleo_mi355x_found_unparsed(out)), int(L.aleo_mi355x_found_first_unparsed(out)))
+                            int(L.aleo_mi355x_found_unparsed(out)), int(L.aleo_mi355x_found_first_unparsed(out)),
+                            copy('serials', np.uint8, 32 * c, (c, 32)) if L.aleo_mi355x_found_serials(out) else None, int(L.aleo_mi355x_found_owned(out)))
     finally:
         L.aleo_mi355x_found_free(out)
 
@@ -600,3 +604,40 @@ def unspent(batch, commitments, account, is_spent, host: bool = False):
         s = sn[k].tobytes()
         if not is_spent(s): out.append((i, s, int(found.microcredits[k])))
     return out, sum(m for _, _, m in out)
+
+
+def _unspent_found(b: RecordBatch, commitments, accounts, spent, host: bool) -> list:
+    """The call behind unspent_strings[_many]: one FoundRecords per account, unparsed strings counted and not raised.  One account takes the one-account entry."""
+    k = len(accounts)
+    cm = _rows32(commitments); sp = _rows32(spent)
+    if cm.shape[0] < len(b): raise ValueError('fewer commitments than strings')
+    if not cm.shape[0]: cm = np.zeros((1, 32), dtype=np.uint8)                                  # no string: a row nobody reads, the pointer is not null
+    sk, vk, ax = (np.frombuffer(b''.join(getattr(a, name) for a in accounts), dtype=np.uint8) for name in ('sk_sig', 'view_key', 'address_x'))
+    L = lib(); out = (ctypes.c_void_p * max(k, 1))()
+    head = (out, _text_p(b), _p(b.offsets), len(b), _p(cm), _p(sk), _p(vk), _p(ax)); tail = (_p(sp) if sp.shape[0] else None, sp.shape[0])
+    if k == 1: check((L.aleo_mi355x_records_unspent_strings_host if host else L.aleo_mi355x_records_unspent_strings)(*head, *tail), 'records_unspent_strings')
+    else: check((L.aleo_mi355x_records_unspent_strings_many_host if host else L.aleo_mi355x_records_unspent_strings_many)(*head, k, *tail), 'records_unspent_strings_many')
+    found = []
+    try:
+        for j in range(k): found.append(_found_of(L, ctypes.c_void_p(out[j])))
+    finally:
+        for j in range(len(found) + 1, k): L.aleo_mi355x_found_free(ctypes.c_void_p(out[j]))      # _found_of released the one it was reading
+    return found
+
+
+def unspent_strings_many(batch, commitments, accounts, spent=(), host: bool = False) -> list:
+    """The unspent records of several accounts (Account objects or private key strings, at most 64) over the same RecordBatch (or sequence of strings) in ONE
+    call (aleo_mi355x_records_unspent_strings_many / _many_host): the search, the decryption, the serial numbers of all accounts' owned records in one launch, and
+    the check against `spent` — bytes, an array, or a list of 32-byte serial numbers, in any order — all on the device; only the unspent records come down.
+    commitments: those of all strings of the batch.  Entry j is a FoundRecords of account j's records that decrypt (status 0), whose serial number computes and is
+    not in `spent`, with .serials and .owned.  A string that does not parse raises, as `unspent` raises."""
+    b = _as_batch(batch)
+    if b is None: raise TypeError('unspent_strings_many takes a RecordBatch or a sequence of strings')
+    found = _unspent_found(b, commitments, [a if isinstance(a, Account) else Account.from_private_key(a) for a in accounts], spent, host)
+    if found and found[0].unparsed: RecordCiphertext.from_string(b.string(found[0].first_unparsed))
+    return found
+
+
+def unspent_strings(batch, commitments, account, spent=(), host: bool = False) -> FoundRecords:
+    """unspent_strings_many for one account (an Account or a private key string): aleo_mi355x_records_unspent_strings, that call with one key."""
+    return unspent_strings_many(batch, commitments, [account], spent, host=host)[0]

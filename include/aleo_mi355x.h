@@ -711,6 +711,43 @@ int32_t aleo_mi355x_found_serial_numbers(const aleo_mi355x_found* found, const v
 int32_t aleo_mi355x_record_commitment(void* out32, const char* record1, const void* plain_fields, size_t n_fields, const char* program_id, const char* record_name);
 int32_t aleo_mi355x_record_checksum(void* out32, const char* record1);
 int32_t aleo_mi355x_account_from_private_key(const char* private_key, void* sk_sig32, void* view_key32, void* address_x32);
+/* The unspent records of one or several accounts in one call: the reference's get_unspent_records (rust/src/api/blocking.rs:229-325) behind the fetch of the
+ * blocks — is_owner, decrypt, serial_number and the spent check — where records_decrypt_strings[_many] + found_serial_numbers + a host filter bring every owned
+ * record down, run the serial-number kernel once per account and ask a callback per record.
+ *   records_unspent_strings_many   n strings as records_decrypt_strings_many takes them; commitments32: their n commitments (the chain's record ids), n x 32 B —
+ *                  the buffer has no length of its own: it must hold a row for every string; n_keys accounts, 1..64, account j = (sk_sigs32, view_keys32,
+ *                  address_xs32) row j, 32 B each; spent32: a set S of n_spent spent serial numbers, n_spent x 32 B, in any order, duplicates allowed (a caller
+ *                  that walks blocks reads them from the inputs of the transitions).  n_spent = 0 with spent32 NULL is legal: the result is then every owned record
+ *                  that decrypts, with its serial number — for a caller who, like the reference, asks the chain per record.
+ *                  For account j let F be what records_decrypt_strings_host returns for its view key and address, and for record k of F let (sn, flag) be what
+ *                  records_serial_numbers_host returns for commitments32[F.index[k]] under sk_sig j.  Record k is KEPT iff F.status[k] == 0 && flag == 0 && sn
+ *                  is not a row of S (a comparison of 32 bytes: a row of S that is no canonical field element matches nothing) — what the reference's `.ok()?`
+ *                  and `if let Ok` keep.  out[j] is an aleo_mi355x_found of the kept records in record order: index, kind, rvk, offsets (rebased), plain, status
+ *                  (all 0) and microcredits are byte for byte the kept rows of F, unparsed and first_unparsed are F's; found_serials is their serial numbers,
+ *                  found_owned is F's count.
+ *                  Refused: what records_decrypt_strings_many refuses; a null commitments32, sk_sigs32, view_keys32 or address_xs32; an sk_sig that is not
+ *                  below the subgroup order (last_error names the key); spent32 NULL with n_spent > 0; n_spent > 2^30.  A malformed commitment row (not below
+ *                  r, or an input Elligator2 refuses) never fails the call: its flag is 2 and its record is dropped.
+ *                  n * n_keys below min_records, or n = 0, runs on the calling thread.  Else the flow of records_decrypt_strings_many, and per chunk behind it:
+ *                  one serial-number launch over the owned pairs of ALL accounts (a wave holds one account's pairs; below min_serials owned pairs the calling
+ *                  thread computes them instead, the same bytes), the spent check, and the compaction of the kept records on the device, so only they come
+ *                  down.  Launches of at most ALEO_MI355X_SERIAL_CHUNK pairs.  Thread-safe (one slot per call).
+ *                  The spent set on the device (csrc/records_spent_lane.h) — the slot rule, so that a test can build chains on purpose: a table of cap uint32
+ *                  slots, cap the smallest power of two >= 2 n_spent and at least 64, zero = empty, else a row's number + 1; a row's (and a serial number's)
+ *                  first slot is its first little-endian 32-bit word & (cap - 1), the next slot (slot + 1) & (cap - 1); an insert takes the first empty slot
+ *                  (duplicates take one each), a probe walks to the first empty slot and hits where all 32 bytes are equal.  Rows that share their first word
+ *                  lengthen chains and change no answer.
+ *   records_unspent_strings_many_host   the same bytes: records_decrypt_strings_host's path per account, records_serial_numbers_host's per owned record, a sorted
+ *                  copy of S; touches no device and shares no code with the device's spent set.
+ *   records_unspent_strings[_host]   one account: the call above with n_keys = 1.
+ *   found_serials  count x 32 B: the kept records' serial numbers; NULL for the result of any other call.
+ *   found_owned    how many records the account owned before the filter; for the result of any other call, its count. */
+int32_t aleo_mi355x_records_unspent_strings(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* commitments32, const void* sk_sig32, const void* view_key32, const void* address_x32, const void* spent32, size_t n_spent);
+int32_t aleo_mi355x_records_unspent_strings_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* commitments32, const void* sk_sig32, const void* view_key32, const void* address_x32, const void* spent32, size_t n_spent);
+int32_t aleo_mi355x_records_unspent_strings_many(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* commitments32, const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent);
+int32_t aleo_mi355x_records_unspent_strings_many_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* commitments32, const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent);
+const uint8_t* aleo_mi355x_found_serials(const aleo_mi355x_found* found);
+size_t aleo_mi355x_found_owned(const aleo_mi355x_found* found);
 
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */

@@ -707,6 +707,10 @@ class FoundRecords {
   const uint64_t* microcredits() const { return aleo_mi355x_found_microcredits(f_); }
   size_t unparsed() const { return aleo_mi355x_found_unparsed(f_); }
   size_t first_unparsed() const { return aleo_mi355x_found_first_unparsed(f_); }
+  // of unspent_strings[_many]: the kept records' serial numbers (32 bytes each; a null pointer from any other call) and how many records the account owned
+  const uint8_t* serials() const { return aleo_mi355x_found_serials(f_); }
+  const uint8_t* serial(size_t k) const { return aleo_mi355x_found_serials(f_) + 32 * k; }
+  size_t owned() const { return aleo_mi355x_found_owned(f_); }
   const aleo_mi355x_found* handle() const { return f_; }
  private:
   aleo_mi355x_found* f_;
@@ -795,6 +799,33 @@ inline Result<std::array<uint8_t, 32>> record_checksum(const std::string& record
   int32_t rc = aleo_mi355x_record_checksum(out.data(), record1.c_str());
   if (rc) return {std::nullopt, Error{rc}};
   return {out, Error{0}};
+}
+
+// The unspent records of several accounts (at most 64) over the same batch in ONE aleo_mi355x_records_unspent_strings_many call: the reference's
+// get_unspent_records behind the fetch of the blocks.  commitments32: those of all strings of the batch (batch.size() x 32 bytes); spent32: n_spent spent serial
+// numbers in any order (null with n_spent = 0: every owned record that decrypts is kept).  (*result)[a] holds accounts[a]'s records with status 0 whose serial
+// number computes and is not spent, their serials() and what it owned().  A string that does not parse fails the call as balance fails.
+inline Result<std::vector<FoundRecords>> unspent_strings_many(const RecordBatch& batch, const uint8_t* commitments32, const std::vector<PrivateAccount>& accounts,
+                                                              const uint8_t* spent32 = nullptr, size_t n_spent = 0) {
+  std::vector<FoundRecords> out;
+  if (accounts.empty()) return {std::move(out), Error{0}};
+  std::vector<uint8_t> sks, vks, axs;
+  for (const auto& a : accounts) { sks.insert(sks.end(), a.sk_sig, a.sk_sig + 32); vks.insert(vks.end(), a.view_key.scalar, a.view_key.scalar + 32); axs.insert(axs.end(), a.address.x, a.address.x + 32); }
+  std::vector<aleo_mi355x_found*> f(accounts.size(), nullptr);
+  int32_t rc = aleo_mi355x_records_unspent_strings_many(f.data(), batch.text(), batch.offsets(), batch.size(), commitments32, sks.data(), vks.data(), axs.data(), accounts.size(), spent32, n_spent);
+  if (rc) return {std::nullopt, Error{rc}};
+  out.reserve(f.size());
+  for (aleo_mi355x_found* p : f) out.emplace_back(p);
+  if (out[0].unparsed()) { auto r = RecordCiphertext::from_string(batch.string(out[0].first_unparsed())); return {std::nullopt, r.is_ok() ? Error{ALEO_MI355X_ERR_BAD_ARG} : r.error}; }
+  return {std::move(out), Error{0}};
+}
+inline Result<FoundRecords> unspent_strings(const RecordBatch& batch, const uint8_t* commitments32, const PrivateAccount& account, const uint8_t* spent32 = nullptr, size_t n_spent = 0) {
+  aleo_mi355x_found* f = nullptr;
+  int32_t rc = aleo_mi355x_records_unspent_strings(&f, batch.text(), batch.offsets(), batch.size(), commitments32, account.sk_sig, account.view_key.scalar, account.address.x, spent32, n_spent);
+  if (rc) return {std::nullopt, Error{rc}};
+  FoundRecords found(f);
+  if (found.unparsed()) { auto r = RecordCiphertext::from_string(batch.string(found.first_unparsed())); return {std::nullopt, r.is_ok() ? Error{ALEO_MI355X_ERR_BAD_ARG} : r.error}; }
+  return {std::move(found), Error{0}};
 }
 
 }  // namespace aleo_mi355x
