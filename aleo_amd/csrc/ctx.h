@@ -44,6 +44,9 @@ struct DevBuf {
   template <class T> T* as() const { return (T*)p; }
 };
 
+// Carves one such buffer into parts: part() returns the offset of the next part, every part on a 32-byte boundary; `total` is what to reserve.
+struct Carve { size_t total = 0; size_t part(size_t bytes) { const size_t at = total; total += (bytes + 31) & ~(size_t)31; return at; } };
+
 // A temporary device allocation that is freed on every return path (setup code: base generation, table builds).
 struct DevTmp {
   void* p = nullptr;

@@ -10,35 +10,24 @@
 // (x, -y) = -(x, y) + (0, -1), k (0, -1) = (0, -1) for odd k, and -(a, b) + (0, -1) = (a, -b).  Where a prime-order N with this x exists, l N = O makes the
 // value x(view_key * N).  So the scan needs neither a subgroup check nor a choice of root, and is defined for every x on the curve.
 //
-// Three entry points: the kernel (one record per lane: records_lane.h, edwards29.h), the same computation on the host (host_field.hpp, poseidon.hpp —
-// the fallback, what small batches take, and the checker), and the routing threshold between them.
-#include "entry.h"
-#include "records_host.hpp"
-#include <cstdlib>
+// Here: the computation on the host (host_field.hpp, poseidon.hpp — the fallback, what small batches take, and the checker), the lane's constants on the device, the routing
+// threshold and the one-account entry points, which take the kernel (one record per lane: records_lane.h, edwards29.h) and the device flow of the K-account scan (records_many.hip) with one key.
+#include "records_strings.h"
 
 namespace aleo_mi355x {
 
-static int32_t records_scan_on_host(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_key32, const void* address_x32) {
+static int32_t records_scan(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_key32, const void* address_x32, bool may_route) {
   if (!view_key32 || !address_x32 || ((!flags || !owner_c0 || !nonce_x) && n)) return bad_arg("records_scan: null buffer");
   ScanArgs a; HFr addr; if (const char* why = scan_args(a, addr, view_key32, address_x32)) return bad_arg(why);
+  if (may_route && n && n >= aleo_mi355x_min_records()) {
+    const ManyKeys k{{a}, {addr}};
+    Slot sl; if (sl.rc) return sl.rc;
+    return scan_many_on_device(sl.c, flags, rvk_out, owner_c0, nonce_x, n, k);
+  }
   const RecordsConsts& C = records_consts();
   for (size_t i = 0; i < n; ++i)
     flags[i] = scan_one_host(rvk_out ? (uint8_t*)rvk_out + 32 * i : nullptr, (const uint8_t*)owner_c0 + 32 * i, (const uint8_t*)nonce_x + 32 * i, a, addr, C);
   return ALEO_MI355X_OK;
-}
-
-// ---- the kernel -----------------------------------------------------------------------------------------------------------------------------------
-static constexpr uint32_t SCAN_BLOCK = 256;
-static constexpr size_t SCAN_CHUNK = (size_t)1 << 20;       // records per launch: 97 bytes of slot scratch each
-
-__global__ void __launch_bounds__(SCAN_BLOCK) k_records_scan(uint8_t* __restrict__ flags, char* __restrict__ rvk, const char* __restrict__ c0, const char* __restrict__ nx,
-                                                             uint32_t n, const uint32_t* __restrict__ K, ScanArgs A) {
-  const uint32_t i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const Fr c = load_fp<Fr>(c0 + (size_t)i * 32), x = load_fp<Fr>(nx + (size_t)i * 32);
-  char* out = rvk + (size_t)i * 32;
-  const uint32_t flag = records_scan_lane(c.v, x.v, K, A, [&](const F29& v) { store_fp<Fr>(out, f29_to_fr(v)); });
-  flags[i] = (uint8_t)flag;
 }
 
 // The constants on the device, once per slot: the flag is set only when the slot's stream has completed the copy, so a copy that fails is made again by the slot's
@@ -54,26 +43,6 @@ int32_t records_constants(Ctx* c, const uint32_t** dK) {
   return ALEO_MI355X_OK;
 }
 
-static int32_t records_scan_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ScanArgs& a) {
-  const size_t chunk = n < SCAN_CHUNK ? n : SCAN_CHUNK;
-  hipStream_t s = c->stream;
-  int32_t rc;
-  const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
-  if ((rc = c->scalars_stage.reserve(chunk * 97))) return rc;
-  char* dc0 = c->scalars_stage.as<char>(); char* dnx = dc0 + chunk * 32; char* drvk = dnx + chunk * 32; uint8_t* dfl = (uint8_t*)(drvk + chunk * 32);
-  for (size_t at = 0; at < n; at += chunk) {
-    const size_t m = n - at < chunk ? n - at : chunk;
-    HIPCHK(hipMemcpyAsync(dc0, (const char*)owner_c0 + at * 32, m * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dnx, (const char*)nonce_x + at * 32, m * 32, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_records_scan, dim3((uint32_t)((m + SCAN_BLOCK - 1) / SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, s, dfl, drvk, (const char*)dc0, (const char*)dnx, (uint32_t)m, dK, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));
-    if (rvk_out) HIPCHK(hipMemcpyAsync((char*)rvk_out + at * 32, drvk, m * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
-  }
-  return ALEO_MI355X_OK;
-}
-
 }  // namespace aleo_mi355x
 
 using namespace aleo_mi355x;
@@ -85,17 +54,11 @@ extern "C" {
 size_t aleo_mi355x_min_records(void) { return env_size("ALEO_MI355X_MIN_RECORDS", (size_t)1 << 6); }
 
 int32_t aleo_mi355x_records_scan_host(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_key32, const void* address_x32) {
-  return guarded([&] { return records_scan_on_host(flags, rvk_out, owner_c0, nonce_x, n, view_key32, address_x32); });
+  return guarded([&] { return records_scan(flags, rvk_out, owner_c0, nonce_x, n, view_key32, address_x32, false); });
 }
 
 int32_t aleo_mi355x_records_scan(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const void* view_key32, const void* address_x32) {
-  return guarded([&] {
-    if (n < aleo_mi355x_min_records() || n == 0) return records_scan_on_host(flags, rvk_out, owner_c0, nonce_x, n, view_key32, address_x32);
-    if (!view_key32 || !address_x32 || !flags || !owner_c0 || !nonce_x) return bad_arg("records_scan: null buffer");
-    ScanArgs a; HFr addr; if (const char* why = scan_args(a, addr, view_key32, address_x32)) return bad_arg(why);
-    Slot sl; if (sl.rc) return sl.rc;
-    return records_scan_on_device(sl.c, flags, rvk_out, owner_c0, nonce_x, n, a);
-  });
+  return guarded([&] { return records_scan(flags, rvk_out, owner_c0, nonce_x, n, view_key32, address_x32, true); });
 }
 
 }  // extern "C"

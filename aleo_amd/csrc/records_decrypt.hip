@@ -64,21 +64,23 @@ __global__ void __launch_bounds__(DECRYPT_BLOCK) k_records_decrypt(char* __restr
   flags[i] = (uint8_t)flag;
 }
 
-// the field cap of a launch, and the launch itself for records_found.hip, whose records are on the device already
+// the field cap of a launch, the cut of records into launches, and the launch itself: for decrypt_on_device and for records_found.hip, whose records are on the device
+size_t decrypt_cut(const uint32_t* offsets, size_t at, size_t n, size_t record_cap, size_t field_cap) {
+  size_t e = at + 1; while (e < n && e - at < record_cap && (size_t)offsets[e + 1] - offsets[at] <= field_cap) ++e; return e;
+}
 size_t decrypt_chunk_fields() { size_t cap = env_size("ALEO_MI355X_DECRYPT_CHUNK_FIELDS", DECRYPT_CHUNK_FIELDS); return cap < 1 || cap > DECRYPT_CHUNK_FIELDS ? DECRYPT_CHUNK_FIELDS : cap; }
 void launch_records_decrypt(hipStream_t s, char* io, uint8_t* dflags, const char* drvk, const uint32_t* doffsets, uint32_t base, size_t n, const uint32_t* dK) {
   hipLaunchKernelGGL(k_records_decrypt, dim3((uint32_t)((n + DECRYPT_BLOCK - 1) / DECRYPT_BLOCK)), dim3(DECRYPT_BLOCK), 0, s, io, dflags, drvk, doffsets, base, (uint32_t)n, dK);
 }
 
-// Copies, launch and synchronisation as records_scan_on_device (records.hip).  A chunk: as many whole records as stay within DECRYPT_CHUNK_RECORDS and the field
+// Copies, launch and synchronisation per chunk as scan_many_on_device (records_many.hip).  A chunk: as many whole records as stay within DECRYPT_CHUNK_RECORDS and the field
 // cap, and one at least.  ALEO_MI355X_DECRYPT_CHUNK_FIELDS (read per call) lowers the field cap; the bytes do not depend on it.
 static int32_t decrypt_on_device(Ctx* c, uint8_t* plain, uint8_t* flags, const uint8_t* rvk, const uint32_t* offsets, const uint8_t* fields, size_t n) {
   const size_t cap = decrypt_chunk_fields();
   std::vector<size_t> cut{0};                                 // chunk k: records cut[k] .. cut[k + 1]
   size_t max_records = 0, max_fields = 0;
   for (size_t at = 0; at < n;) {
-    size_t e = at + 1;
-    while (e < n && e - at < DECRYPT_CHUNK_RECORDS && (size_t)offsets[e + 1] - offsets[at] <= cap) ++e;
+    const size_t e = decrypt_cut(offsets, at, n, DECRYPT_CHUNK_RECORDS, cap);
     if (e - at > max_records) max_records = e - at;
     if ((size_t)offsets[e] - offsets[at] > max_fields) max_fields = offsets[e] - offsets[at];
     cut.push_back(e); at = e;
@@ -86,14 +88,17 @@ static int32_t decrypt_on_device(Ctx* c, uint8_t* plain, uint8_t* flags, const u
   hipStream_t s = c->stream;
   int32_t rc;
   const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
-  if ((rc = c->scalars_stage.reserve(max_fields * 32 + max_records * 32 + (max_records + 1) * 4 + max_records))) return rc;
-  char* dio = c->scalars_stage.as<char>(); char* drvk = dio + max_fields * 32; uint32_t* doff = (uint32_t*)(drvk + max_records * 32); uint8_t* dfl = (uint8_t*)(doff + max_records + 1);
+  Carve cv;
+  const size_t o_io = cv.part(max_fields * 32), o_rvk = cv.part(max_records * 32), o_off = cv.part((max_records + 1) * 4), o_fl = cv.part(max_records);
+  if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
+  char* base = c->scalars_stage.as<char>();
+  char* dio = base + o_io; char* drvk = base + o_rvk; uint32_t* doff = (uint32_t*)(base + o_off); uint8_t* dfl = (uint8_t*)(base + o_fl);
   for (size_t k = 0; k + 1 < cut.size(); ++k) {
     const size_t at = cut[k], m = cut[k + 1] - at, first = offsets[at], nf = offsets[at + m] - first;
     if (nf) HIPCHK(hipMemcpyAsync(dio, fields + first * 32, nf * 32, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(drvk, rvk + at * 32, m * 32, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(doff, offsets + at, (m + 1) * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_records_decrypt, dim3((uint32_t)((m + DECRYPT_BLOCK - 1) / DECRYPT_BLOCK)), dim3(DECRYPT_BLOCK), 0, s, dio, dfl, (const char*)drvk, (const uint32_t*)doff, (uint32_t)first, (uint32_t)m, dK);
+    launch_records_decrypt(s, dio, dfl, drvk, doff, (uint32_t)first, m, dK);
     HIPCHK(hipGetLastError());
     if (nf) HIPCHK(hipMemcpyAsync(plain + first * 32, dio, nf * 32, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));

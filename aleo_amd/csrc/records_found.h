@@ -1,14 +1,15 @@
 // records_found.h — what records_found.hip shares with records_unspent.hip: the device flow of decrypt_strings[_many] with an optional stage between
 // k_found_microcredits and the downloads, the second level of its exclusive sums, and the block-level sums both files' kernels run.  From records_serial.hip:
-// the resident tables of the serial-number lane and the launch cap.
+// the resident tables of the serial-number lane and the one serial-number kernel's launches over key segments.
 #pragma once
 #include "records_strings.h"
 #include "records_found_host.hpp"
+#include "records_serial_lane.h"
 #include <memory>
 
 namespace aleo_mi355x {
 
-static constexpr uint32_t FOUND_BLOCK = 256, FOUND_TOP = 1024;
+static constexpr uint32_t FOUND_BLOCK = SPAN_BLOCK, FOUND_TOP = 1024;      // FOUND_BLOCK: the walks stage their block's span (records_strings.h stage_span)
 
 #ifdef __HIPCC__
 // The exclusive sums of two values over the block's 256 lanes (wave shuffles, then the four wave totals through LDS); *ta / *tb: the block's totals.
@@ -33,8 +34,8 @@ __device__ __forceinline__ void block_exclusive2(uint32_t& a, uint32_t& b, uint3
 // fields; key j's are the ranks first[j] .. first[j + 1] and the fields first_f[j] .. first_f[j + 1] (K + 1 entries each).  index is chunk-relative, off has
 // owned + 1 entries.  status null: every record's is 0.  serials null: there are none.
 struct FoundChunk {
-  char* fields; uint32_t* index; int8_t* kind; char* rvk; uint32_t* off; uint64_t* mc; uint8_t* status; char* serials;
-  size_t at, owned, nf;                                        // at: the chunk's first record among the call's strings
+  char* fields = nullptr; uint32_t* index = nullptr; int8_t* kind = nullptr; char* rvk = nullptr; uint32_t* off = nullptr; uint64_t* mc = nullptr; uint8_t* status = nullptr; char* serials = nullptr;
+  size_t at = 0, owned = 0, nf = 0;                                        // at: the chunk's first record among the call's strings
   std::vector<uint32_t> first, first_f;
 };
 
@@ -52,8 +53,17 @@ int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>& R, con
 // k_found_offsets over `rows` block totals of two kinds (blk: [fields | owned][rows]) in groups of nb: see the kernel; the caller checks hipGetLastError
 void launch_found_offsets(hipStream_t s, uint32_t* blk, uint32_t* stat, uint32_t rows, uint32_t nb);
 
-// records_serial.hip: the lane's tables on this device (uploaded once per device), and the commitments one launch may take (ALEO_MI355X_SERIAL_CHUNK, read per call)
+// records_serial.hip: the lane's tables on this device (uploaded once per device)
 int32_t serial_tables_on_device(int device, const uint32_t** out);
-size_t serial_chunk_cap();
+
+// Where the keys' segments lie among commitment rows in rank order: key j's rows are the ranks rank0[j] .. rank0[j + 1], and the waves wave0[j] .. wave0[j + 1]
+// of the padded grid (ceil(rows / 64) waves each), so a wave has one key.
+struct UnspentSegs { uint32_t n_keys, wave0[SCAN_MANY_KEYS + 1], rank0[SCAN_MANY_KEYS + 1]; };
+// the digits of a key made by serial::serial_key, as the kernel's key table holds them
+inline SerialArgs serial_args_of(const ScanArgs& a) {
+  SerialArgs r; std::memcpy(r.naf_pos, a.naf_pos, sizeof r.naf_pos); std::memcpy(r.naf_neg, a.naf_neg, sizeof r.naf_neg); r.naf_len = a.naf_len; return r;
+}
+// k_records_serial over every segment, key j's digits at dkeys[j] in device memory: launches of at most ALEO_MI355X_SERIAL_CHUNK lanes (read per call), which may span key boundaries
+int32_t launch_records_serial(hipStream_t s, char* dsn, uint8_t* dflags, const char* dcm, const uint32_t* dK, const SerialArgs* dkeys, const UnspentSegs& seg);
 
 }  // namespace aleo_mi355x

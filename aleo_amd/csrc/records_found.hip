@@ -14,7 +14,7 @@
 //                           private fields)
 //   resolve                 records_strings.hip, with K keys
 //   k_found_count           grid (record blocks, keys), one lane per (key, record) pair (records_found_lane.h): an owned pair's number of private fields and
-//                           whether record_fields would refuse it; the block's span staged in LDS as k_records_parse stages it (blocks without an owned pair
+//                           whether record_fields would refuse it; the block's span staged in LDS by the stage_span of k_records_parse (blocks without an owned pair
 //                           skip that); then the first level of the exclusive sums of the field counts and of the owned bits, within the block.  Its block
 //                           totals lie at [key][block], so the sums below run in [key][record] order.  Row 0 counts the strings that do not parse: they are
 //                           the same for every key
@@ -36,19 +36,6 @@
 
 namespace aleo_mi355x {
 
-static constexpr uint32_t FOUND_LDS_BYTES = 64 * 1024;              // k_records_parse's budget
-
-// The block's span of the text into LDS where it fits, as k_records_parse stages it: text readable up to the next multiple of 16 past the chunk's last character.
-__device__ __forceinline__ bool stage_span(uint4* stage, const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t b0, uint32_t n, uint32_t* lo_out) {
-  const uint32_t b1 = b0 + FOUND_BLOCK < n ? b0 + FOUND_BLOCK : n;
-  const uint32_t lo = off[b0] & ~15u, hi = off[b1];            // uniform
-  *lo_out = lo;
-  if (hi - lo > FOUND_LDS_BYTES) return false;
-  for (uint32_t t = threadIdx.x; lo + 16 * t < hi; t += FOUND_BLOCK) stage[t] = *(const uint4*)(text + lo + 16 * (size_t)t);
-  __syncthreads();
-  return true;
-}
-
 // ---- the kernels ------------------------------------------------------------------------------------------------------------------------------------
 // A block is (blockIdx.x, key blockIdx.y): the records b0 .. b0 + 256 of row `key` of the [key][record] matrices (n per row); its totals lie at bi among the
 // gridDim.x x gridDim.y of all blocks.
@@ -59,7 +46,7 @@ __device__ __forceinline__ bool stage_span(uint4* stage, const char* __restrict_
 __global__ void __launch_bounds__(FOUND_BLOCK) k_found_count(uint32_t* __restrict__ cnt, uint32_t* __restrict__ pos, uint8_t* __restrict__ pre, uint32_t* __restrict__ blk, uint32_t* __restrict__ stat,
                                                             const uint8_t* __restrict__ flags, const uint8_t* __restrict__ scan_flags, const int8_t* __restrict__ kinds,
                                                             const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t n) {
-  __shared__ uint4 stage[FOUND_LDS_BYTES / 16];
+  __shared__ uint4 stage[SPAN_LDS_BYTES / 16];
   __shared__ uint32_t wave_tot[2][FOUND_BLOCK / 64];
   const size_t row = (size_t)blockIdx.y * n;
   const uint32_t bi = blockIdx.y * gridDim.x + blockIdx.x, rows = gridDim.x * gridDim.y, b0 = blockIdx.x * FOUND_BLOCK;
@@ -131,7 +118,7 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_found_gather(char* __restrict__
                                                              const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ pos, const uint8_t* __restrict__ pre, const uint32_t* __restrict__ blk,
                                                              const uint8_t* __restrict__ flags, const int8_t* __restrict__ kinds, const char* __restrict__ rvk,
                                                              const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t n, uint32_t n_owned, uint32_t n_fields) {
-  __shared__ uint4 stage[FOUND_LDS_BYTES / 16];
+  __shared__ uint4 stage[SPAN_LDS_BYTES / 16];
   const size_t row = (size_t)blockIdx.y * n;
   const uint32_t bi = blockIdx.y * gridDim.x + blockIdx.x, rows = gridDim.x * gridDim.y, b0 = blockIdx.x * FOUND_BLOCK;
   cnt += row; pos += row; pre += row; flags += row; rvk += row * 32;
@@ -190,144 +177,167 @@ void launch_found_offsets(hipStream_t s, uint32_t* blk, uint32_t* stat, uint32_t
 }
 
 // ---- the device flow ----------------------------------------------------------------------------------------------------------------------------------
+// What one call holds on the device, in the slot's scalars_stage: the scan's own scratch (64 B per record, 33 B per pair), 10 B per pair for the walk (the scan's
+// flags, the pre-status, the two first-level sums), the block totals, the statistics (read through h_pinned) and the source's scratch.
+struct FoundCall {
+  Ctx* c; hipStream_t s; FoundStage* stage; size_t K, cap, stat_words; uint32_t W;      // cap: the fields of one decryption launch
+  const uint32_t* dK; const ScanArgs* dkeys;
+  char* dc0; char* dnx; char* drvk; char* dstr; uint8_t* dfl; uint8_t* dscan; uint8_t* dpre; uint32_t* dcnt; uint32_t* dpos; uint32_t* dblk; uint32_t* dstat;
+  uint32_t* dsoff; int8_t* dkinds; char* dtext;
+};
+
+// `to` sized for records / fields in all, what it held before included
+static void found_size(Found& to, size_t records, size_t fields, bool serials) {
+  to.index.resize(records); to.offsets.resize(records + 1); to.kind.resize(records); to.rvk.resize(records * 32); to.status.resize(records);
+  to.microcredits.resize(records); to.plain.resize(fields * 32);
+  if (serials) to.serials.resize(records * 32);
+}
+
+// Chunk ck up to the one wait before the gather: parse, scan, resolve, the counting walk and its sums; the unparsed strings into every result; into `ch` the totals
+// and the keys' boundaries (key j: the ranks first[j] .. first[j + 1], the fields first_f[j] .. first_f[j + 1]), from which the host sizes what follows.  ch.owned 0: done.
+static int32_t found_count(const FoundCall& f, StringSource& src, size_t ck, std::vector<std::unique_ptr<Found>>& R, FoundChunk& ch) {
+  const size_t K = f.K, at = src.cut[ck], m = src.cut[ck + 1] - at;
+  const uint32_t nb = (uint32_t)((m + FOUND_BLOCK - 1) / FOUND_BLOCK);
+  hipStream_t s = f.s;
+  if (int32_t rc = src.fill(s, ck, f.dstr, f.dc0, f.dnx)) return rc;
+  launch_scan_keys(s, f.W, f.dfl, f.drvk, f.dc0, f.dnx, m, f.dK, f.dkeys, K);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(f.dscan, f.dfl, m * K, hipMemcpyDeviceToDevice, s));      // rows of m: a public owner's status depends on the flag the resolve overwrites
+  if (int32_t rc = src.resolve(s, ck, f.dstr, f.dfl, f.drvk, f.dc0, f.dkeys, K)) return rc;
+  HIPCHK(hipMemsetAsync(f.dstat, 0, 16, s));
+  hipLaunchKernelGGL(k_found_count, dim3(nb, (uint32_t)K), dim3(FOUND_BLOCK), 0, s, f.dcnt, f.dpos, f.dpre, f.dblk, f.dstat, (const uint8_t*)f.dfl, (const uint8_t*)f.dscan, (const int8_t*)f.dkinds,
+                     (const char*)f.dtext, (const uint32_t*)f.dsoff, (uint32_t)m);
+  HIPCHK(hipGetLastError());
+  launch_found_offsets(s, f.dblk, f.dstat, nb * (uint32_t)K, nb);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(f.c->h_pinned, f.dstat, f.stat_words * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));                           // the one wait before the gather: the host sizes the compacted arrays
+  const uint32_t* stat = (const uint32_t*)f.c->h_pinned;
+  const size_t owned = stat[0], nf = stat[1];
+  if (stat[2]) for (auto& r : R) { if (!r->unparsed) r->first_unparsed = at + (m - stat[3]); r->unparsed += stat[2]; }
+  ch.at = at; ch.owned = owned; ch.nf = nf; ch.first.assign(K + 1, 0); ch.first_f.assign(K + 1, 0);
+  if (!owned) return ALEO_MI355X_OK;
+  for (size_t j = 0; j < K; ++j) { ch.first[j] = stat[4 + j]; ch.first_f[j] = stat[4 + K + j]; }      // a stage may use h_pinned, and moves these boundaries
+  ch.first[K] = (uint32_t)owned; ch.first_f[K] = (uint32_t)nf;
+  for (size_t j = 0; j < K; ++j) {
+    const size_t mine = ch.first[j + 1] - ch.first[j], mine_f = ch.first_f[j + 1] - ch.first_f[j];
+    R[j]->owned += mine;
+    if (R[j]->index.size() + mine > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 owned records");
+    if ((size_t)R[j]->offsets.back() + mine_f > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 private fields");
+  }
+  return ALEO_MI355X_OK;
+}
+
+// The chunk's m records behind the count: the compacted arrays in the slot's out_stage (`ch` gets their pointers), the gathering walk, the decryption over all keys'
+// records in place and k_found_microcredits.  Without a stage everything owned comes down, so `to` is sized here, behind put records and put_f fields, and the offsets
+// come down first; with one the result is sized later, for what it keeps, and the unfiltered offsets, which only the cut of the decryption's launches reads, go aside.
+static int32_t found_gather_decrypt(const FoundCall& f, size_t m, FoundChunk& ch, Found& to, size_t put, size_t put_f) {
+  const size_t owned = ch.owned, nf = ch.nf;
+  hipStream_t s = f.s;
+  Carve cv;
+  const size_t o_fields = cv.part(nf * 32), o_index = cv.part(owned * 4), o_off = cv.part((owned + 1) * 4), o_mc_at = cv.part(owned * 4), o_mc_n = cv.part(owned * 4), o_mc = cv.part(owned * 8),
+               o_crvk = cv.part(owned * 32), o_kind = cv.part(owned), o_cpre = cv.part(owned), o_dec = cv.part(owned), o_status = cv.part(owned);
+  if (int32_t rc = f.c->out_stage.reserve(cv.total)) return rc;
+  char* cb = f.c->out_stage.as<char>();
+  uint32_t* dmc_at = (uint32_t*)(cb + o_mc_at); uint32_t* dmc_n = (uint32_t*)(cb + o_mc_n); uint8_t* dcpre = (uint8_t*)(cb + o_cpre); uint8_t* ddec = (uint8_t*)(cb + o_dec);
+  ch.fields = cb + o_fields; ch.index = (uint32_t*)(cb + o_index); ch.kind = (int8_t*)(cb + o_kind); ch.rvk = cb + o_crvk; ch.off = (uint32_t*)(cb + o_off); ch.mc = (uint64_t*)(cb + o_mc);
+  ch.status = (uint8_t*)(cb + o_status);
+  hipLaunchKernelGGL(k_found_gather, dim3((uint32_t)((m + FOUND_BLOCK - 1) / FOUND_BLOCK), (uint32_t)f.K), dim3(FOUND_BLOCK), 0, s, ch.fields, ch.index, ch.kind, ch.rvk, ch.off, dcpre, ch.mc, dmc_at,
+                     dmc_n, (const uint32_t*)f.dcnt, (const uint32_t*)f.dpos, (const uint8_t*)f.dpre, (const uint32_t*)f.dblk, (const uint8_t*)f.dfl, (const int8_t*)f.dkinds, (const char*)f.drvk, (const char*)f.dtext, (const uint32_t*)f.dsoff,
+                     (uint32_t)m, (uint32_t)owned, (uint32_t)nf);
+  HIPCHK(hipGetLastError());
+  if (f.stage) { if (int32_t rc = f.stage->gathered(f.c, s, ch)) return rc; }
+  std::vector<uint32_t> off_aside;
+  if (f.stage) off_aside.resize(nf > f.cap ? owned + 1 : 0); else found_size(to, put + owned, put_f + nf, false);
+  uint32_t* h_off = f.stage ? off_aside.data() : to.offsets.data() + put;      // chunk-relative until found_download adds a base
+  if (!f.stage || nf > f.cap) HIPCHK(hipMemcpyAsync(h_off, ch.off, (owned + 1) * 4, hipMemcpyDeviceToHost, s));
+  if (nf <= f.cap) launch_records_decrypt(s, ch.fields, ddec, ch.rvk, ch.off, 0, owned, f.dK);
+  else {                                                     // launches of whole records within the cap, across key boundaries: the host needs the offsets to cut
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t a = 0, e; a < owned; a = e) {
+      e = decrypt_cut(h_off, a, owned, owned, f.cap);
+      launch_records_decrypt(s, ch.fields, ddec + a, ch.rvk + a * 32, ch.off + a, 0, e - a, f.dK);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_found_microcredits, dim3((uint32_t)((owned + FOUND_BLOCK - 1) / FOUND_BLOCK)), dim3(FOUND_BLOCK), 0, s, ch.status, ch.mc, ch.fields, (const uint8_t*)dcpre, (const uint8_t*)ddec,
+                     (const uint32_t*)ch.off, (const uint32_t*)dmc_at, (const uint32_t*)dmc_n, (uint32_t)owned);
+  HIPCHK(hipGetLastError());
+  return ALEO_MI355X_OK;
+}
+
+// What `ch` holds — everything owned, or what the stage kept — comes down into `to` behind put records and put_f fields, and is split: with one key it lies in
+// its result's tail already and the split is the two bases; with several, `to` is the staging of this chunk and key j's part is appended to R[j].
+static int32_t found_download(const FoundCall& f, const FoundChunk& ch, Found& to, size_t put, size_t put_f, std::vector<std::unique_ptr<Found>>& R) {
+  const size_t K = f.K, at = ch.at, got = ch.owned, got_f = ch.nf;
+  hipStream_t s = f.s;
+  if (f.stage) found_size(to, put + got, put_f + got_f, true);
+  uint32_t* h_off = to.offsets.data() + put;                 // chunk-relative until a base is added below
+  if (f.stage) HIPCHK(hipMemcpyAsync(h_off, ch.off, (got + 1) * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(to.index.data() + put, ch.index, got * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(to.kind.data() + put, ch.kind, got, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(to.rvk.data() + put * 32, ch.rvk, got * 32, hipMemcpyDeviceToHost, s));
+  if (ch.status) HIPCHK(hipMemcpyAsync(to.status.data() + put, ch.status, got, hipMemcpyDeviceToHost, s));      // else zeros, as the resize left them
+  HIPCHK(hipMemcpyAsync(to.microcredits.data() + put, ch.mc, got * 8, hipMemcpyDeviceToHost, s));
+  if (ch.serials) HIPCHK(hipMemcpyAsync(to.serials.data() + put * 32, ch.serials, got * 32, hipMemcpyDeviceToHost, s));
+  if (got_f) HIPCHK(hipMemcpyAsync(to.plain.data() + put_f * 32, ch.fields, got_f * 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers
+  if (K == 1) {
+    for (size_t q = 0; q < got; ++q) { to.index[put + q] += (uint32_t)at; h_off[q] += (uint32_t)put_f; }
+    h_off[got] += (uint32_t)put_f;
+  } else for (size_t j = 0; j < K; ++j) {                    // key j's records: the ranks a .. e, the fields fa .. fe
+    const size_t a = ch.first[j], e = ch.first[j + 1], fa = ch.first_f[j], fe = ch.first_f[j + 1];
+    if (a == e) continue;
+    Found& r = *R[j];
+    const size_t have = r.index.size(), have_f = r.offsets.back();
+    r.index.resize(have + (e - a)); r.offsets.resize(have + (e - a) + 1);
+    for (size_t q = a; q < e; ++q) { r.index[have + (q - a)] = to.index[q] + (uint32_t)at; r.offsets[have + (q - a) + 1] = (uint32_t)(have_f + (h_off[q + 1] - fa)); }
+    r.kind.insert(r.kind.end(), to.kind.begin() + a, to.kind.begin() + e);
+    r.rvk.insert(r.rvk.end(), to.rvk.begin() + a * 32, to.rvk.begin() + e * 32);
+    r.status.insert(r.status.end(), to.status.begin() + a, to.status.begin() + e);
+    r.microcredits.insert(r.microcredits.end(), to.microcredits.begin() + a, to.microcredits.begin() + e);
+    r.plain.insert(r.plain.end(), to.plain.begin() + fa * 32, to.plain.begin() + fe * 32);
+    if (f.stage) r.serials.insert(r.serials.end(), to.serials.begin() + a * 32, to.serials.begin() + e * 32);
+  }
+  return ALEO_MI355X_OK;
+}
+
 int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>& R, const char* text, const uint64_t* offsets, size_t n, const ManyKeys& k, FoundStage* stage) {
-  const size_t K = k.args.size();
-  uint32_t W;
-  const size_t chunk = scan_many_plan(n, K, &W);
+  FoundCall f{}; f.c = c; f.s = c->stream; f.stage = stage; f.K = k.args.size(); f.cap = decrypt_chunk_fields(); f.stat_words = 4 + 2 * f.K;
+  std::vector<ScanArgs> table;                                // outlives the call's last synchronisation
+  const size_t K = f.K, chunk = scan_many_plan(n, k, &f.W, &table);
   StringSource src{text, offsets, nullptr};
   src.cut_chunks(n, chunk);
-  std::vector<ScanArgs> table((K + W - 1) / W * W, ScanArgs{});      // the padding: no digits at all
-  std::copy(k.args.begin(), k.args.end(), table.begin());
   const size_t M = src.max_records, NB = (M + FOUND_BLOCK - 1) / FOUND_BLOCK, P = M * K;
-  hipStream_t s = c->stream;
   int32_t rc;
-  const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
-  const size_t stat_words = 4 + 2 * K;
-  if ((rc = ensure_host_pinned(c, stat_words * 4))) return rc;
-  // the scan's own scratch (64 B per record, 33 B per pair) and 10 B per pair for the walk: the scan's flags, the pre-status, the two first-level sums
-  size_t total = 0;
-  auto part = [&](size_t bytes) { const size_t at = total; total += (bytes + 31) & ~(size_t)31; return at; };
-  const size_t o_keys = part(table.size() * sizeof(ScanArgs)), o_c0 = part(M * 32), o_nx = part(M * 32), o_rvk = part(P * 32), o_fl = part(P), o_scan = part(P), o_pre = part(P), o_cnt = part(P * 4),
-               o_pos = part(P * 4), o_blk = part(2 * K * NB * 4), o_stat = part(stat_words * 4), o_str = part(src.scratch_bytes());
-  if ((rc = c->scalars_stage.reserve(total))) return rc;
+  if ((rc = records_constants(c, &f.dK))) return rc;
+  if ((rc = ensure_host_pinned(c, f.stat_words * 4))) return rc;
+  Carve cv;
+  const size_t o_keys = cv.part(table.size() * sizeof(ScanArgs)), o_c0 = cv.part(M * 32), o_nx = cv.part(M * 32), o_rvk = cv.part(P * 32), o_fl = cv.part(P), o_scan = cv.part(P), o_pre = cv.part(P),
+               o_cnt = cv.part(P * 4), o_pos = cv.part(P * 4), o_blk = cv.part(2 * K * NB * 4), o_stat = cv.part(f.stat_words * 4), o_str = cv.part(src.scratch_bytes());
+  if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
   char* base = c->scalars_stage.as<char>();
-  const ScanArgs* dkeys = (const ScanArgs*)(base + o_keys);
-  char* dc0 = base + o_c0; char* dnx = base + o_nx; char* drvk = base + o_rvk; char* dstr = base + o_str;
-  uint8_t* dfl = (uint8_t*)(base + o_fl); uint8_t* dscan = (uint8_t*)(base + o_scan); uint8_t* dpre = (uint8_t*)(base + o_pre);
-  uint32_t* dcnt = (uint32_t*)(base + o_cnt); uint32_t* dpos = (uint32_t*)(base + o_pos); uint32_t* dblk = (uint32_t*)(base + o_blk); uint32_t* dstat = (uint32_t*)(base + o_stat);
-  HIPCHK(hipMemcpyAsync(base + o_keys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, s));      // `table` outlives the call's last synchronisation
-  const uint32_t* dsoff; const int8_t* dkinds; const char* dtext; src.parts(dstr, &dsoff, &dkinds, &dtext);
-  const size_t cap = decrypt_chunk_fields();
-  const uint32_t* stat = (const uint32_t*)c->h_pinned;
-  // Where a chunk's compacted arrays come down, all keys' one after another: staging arrays that are split into the K results below — or, when there is one
-  // key and everything is its own, the tail of its result, which saves a host copy of everything owned (120 MB at 2^20 records all owned).
+  f.dkeys = (const ScanArgs*)(base + o_keys); f.dc0 = base + o_c0; f.dnx = base + o_nx; f.drvk = base + o_rvk; f.dstr = base + o_str;
+  f.dfl = (uint8_t*)(base + o_fl); f.dscan = (uint8_t*)(base + o_scan); f.dpre = (uint8_t*)(base + o_pre);
+  f.dcnt = (uint32_t*)(base + o_cnt); f.dpos = (uint32_t*)(base + o_pos); f.dblk = (uint32_t*)(base + o_blk); f.dstat = (uint32_t*)(base + o_stat);
+  HIPCHK(hipMemcpyAsync(base + o_keys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, f.s));
+  src.parts(f.dstr, &f.dsoff, &f.dkinds, &f.dtext);
+  // Where a chunk's compacted arrays come down, all keys' one after another: staging arrays that are split into the K results — or, when there is one key and
+  // everything is its own, the tail of its result, which saves a host copy of everything owned (120 MB at 2^20 records all owned).
   Found staged;
   Found& to = K == 1 ? *R[0] : staged;
   for (auto& r : R) r->first_unparsed = n;
   for (size_t ck = 0; ck + 1 < src.cut.size(); ++ck) {
-    const size_t at = src.cut[ck], m = src.cut[ck + 1] - at;
-    const uint32_t nb = (uint32_t)((m + FOUND_BLOCK - 1) / FOUND_BLOCK);
-    const dim3 pairs(nb, (uint32_t)K);
-    if ((rc = src.fill(s, ck, dstr, dc0, dnx))) return rc;
-    launch_scan_keys(s, W, dfl, drvk, dc0, dnx, m, dK, dkeys, K);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dscan, dfl, m * K, hipMemcpyDeviceToDevice, s));      // rows of m: a public owner's status depends on the flag the resolve overwrites
-    if ((rc = src.resolve(s, ck, dstr, dfl, drvk, dc0, dkeys, K))) return rc;
-    HIPCHK(hipMemsetAsync(dstat, 0, 16, s));
-    hipLaunchKernelGGL(k_found_count, pairs, dim3(FOUND_BLOCK), 0, s, dcnt, dpos, dpre, dblk, dstat, (const uint8_t*)dfl, (const uint8_t*)dscan, dkinds, dtext, dsoff, (uint32_t)m);
-    HIPCHK(hipGetLastError());
-    launch_found_offsets(s, dblk, dstat, nb * (uint32_t)K, nb);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_pinned, dstat, stat_words * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                           // the one wait before the gather: the host sizes the compacted arrays
-    const size_t owned = stat[0], nf = stat[1];
-    if (stat[2]) for (auto& r : R) { if (!r->unparsed) r->first_unparsed = at + (m - stat[3]); r->unparsed += stat[2]; }
-    if (!owned) continue;
-    // key j's records: the ranks first[j] .. first[j + 1], the fields first_f[j] .. first_f[j + 1] (a stage may use h_pinned, and moves these boundaries)
-    FoundChunk ch{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, at, owned, nf, std::vector<uint32_t>(K + 1), std::vector<uint32_t>(K + 1)};
-    for (size_t j = 0; j < K; ++j) { ch.first[j] = stat[4 + j]; ch.first_f[j] = stat[4 + K + j]; }
-    ch.first[K] = (uint32_t)owned; ch.first_f[K] = (uint32_t)nf;
-    for (size_t j = 0; j < K; ++j) {
-      const size_t mine = ch.first[j + 1] - ch.first[j], mine_f = ch.first_f[j + 1] - ch.first_f[j];
-      R[j]->owned += mine;
-      if (R[j]->index.size() + mine > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 owned records");
-      if ((size_t)R[j]->offsets.back() + mine_f > UINT32_MAX) return bad_arg("records_decrypt_strings: more than 2^32 - 1 private fields");
-    }
-    size_t ctotal = 0;
-    auto cpart = [&](size_t bytes) { const size_t a = ctotal; ctotal += (bytes + 31) & ~(size_t)31; return a; };
-    const size_t o_fields = cpart(nf * 32), o_index = cpart(owned * 4), o_off = cpart((owned + 1) * 4), o_mc_at = cpart(owned * 4), o_mc_n = cpart(owned * 4), o_mc = cpart(owned * 8),
-                 o_crvk = cpart(owned * 32), o_kind = cpart(owned), o_cpre = cpart(owned), o_dec = cpart(owned), o_status = cpart(owned);
-    if ((rc = c->out_stage.reserve(ctotal))) return rc;
-    char* cb = c->out_stage.as<char>();
-    char* dfields = cb + o_fields; char* dcrvk = cb + o_crvk;
-    uint32_t* dindex = (uint32_t*)(cb + o_index); uint32_t* doff = (uint32_t*)(cb + o_off); uint32_t* dmc_at = (uint32_t*)(cb + o_mc_at); uint32_t* dmc_n = (uint32_t*)(cb + o_mc_n);
-    uint64_t* dmc = (uint64_t*)(cb + o_mc); int8_t* dkind = (int8_t*)(cb + o_kind);
-    uint8_t* dcpre = (uint8_t*)(cb + o_cpre); uint8_t* ddec = (uint8_t*)(cb + o_dec); uint8_t* dstatus = (uint8_t*)(cb + o_status);
-    hipLaunchKernelGGL(k_found_gather, pairs, dim3(FOUND_BLOCK), 0, s, dfields, dindex, dkind, dcrvk, doff, dcpre, dmc, dmc_at, dmc_n, (const uint32_t*)dcnt, (const uint32_t*)dpos,
-                       (const uint8_t*)dpre, (const uint32_t*)dblk, (const uint8_t*)dfl, dkinds, (const char*)drvk, dtext, dsoff, (uint32_t)m, (uint32_t)owned, (uint32_t)nf);
-    HIPCHK(hipGetLastError());
-    ch.fields = dfields; ch.index = dindex; ch.kind = dkind; ch.rvk = dcrvk; ch.off = doff; ch.mc = dmc; ch.status = dstatus;
-    if (stage && (rc = stage->gathered(c, s, ch))) return rc;
+    FoundChunk ch;
+    if ((rc = found_count(f, src, ck, R, ch))) return rc;
+    if (!ch.owned) continue;
     const size_t put = K == 1 ? to.index.size() : 0, put_f = K == 1 ? to.offsets.back() : 0;      // `staged` starts over with every chunk
-    auto size_to = [&](size_t records, size_t fields) {
-      to.index.resize(put + records); to.offsets.resize(put + records + 1); to.kind.resize(put + records); to.rvk.resize((put + records) * 32); to.status.resize(put + records);
-      to.microcredits.resize(put + records); to.plain.resize((put_f + fields) * 32);
-      if (stage) to.serials.resize((put + records) * 32);
-    };
-    // without a stage everything owned comes down, and the offsets come first; with one the result is sized for what it keeps, and the unfiltered offsets, which
-    // only the cut of the decryption's launches reads, go aside
-    std::vector<uint32_t> off_aside;
-    if (stage) off_aside.resize(nf > cap ? owned + 1 : 0); else size_to(owned, nf);
-    uint32_t* h_off = stage ? off_aside.data() : to.offsets.data() + put;      // chunk-relative until a base is added below
-    if (!stage || nf > cap) HIPCHK(hipMemcpyAsync(h_off, doff, (owned + 1) * 4, hipMemcpyDeviceToHost, s));
-    if (nf <= cap) launch_records_decrypt(s, dfields, ddec, dcrvk, doff, 0, owned, dK);
-    else {                                                     // launches of whole records within the cap, one record at least, across key boundaries: the host needs the offsets to cut
-      HIPCHK(hipStreamSynchronize(s));
-      for (size_t a = 0; a < owned;) {
-        size_t e = a + 1;
-        while (e < owned && (size_t)h_off[e + 1] - h_off[a] <= cap) ++e;
-        launch_records_decrypt(s, dfields, ddec + a, dcrvk + a * 32, doff + a, 0, e - a, dK);
-        HIPCHK(hipGetLastError());
-        a = e;
-      }
-    }
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_found_microcredits, dim3((uint32_t)((owned + FOUND_BLOCK - 1) / FOUND_BLOCK)), dim3(FOUND_BLOCK), 0, s, dstatus, dmc, dfields, (const uint8_t*)dcpre, (const uint8_t*)ddec,
-                       (const uint32_t*)doff, (const uint32_t*)dmc_at, (const uint32_t*)dmc_n, (uint32_t)owned);
-    HIPCHK(hipGetLastError());
+    if ((rc = found_gather_decrypt(f, src.cut[ck + 1] - src.cut[ck], ch, to, put, put_f))) return rc;
     if (stage) {                                               // from here on `ch` is what the stage kept
-      if ((rc = stage->filter(c, s, ch))) return rc;
+      if ((rc = stage->filter(c, f.s, ch))) return rc;
       if (!ch.owned) continue;
-      size_to(ch.owned, ch.nf);
-      h_off = to.offsets.data() + put;
-      HIPCHK(hipMemcpyAsync(h_off, ch.off, (ch.owned + 1) * 4, hipMemcpyDeviceToHost, s));
     }
-    const size_t got = ch.owned, got_f = ch.nf;
-    HIPCHK(hipMemcpyAsync(to.index.data() + put, ch.index, got * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(to.kind.data() + put, ch.kind, got, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(to.rvk.data() + put * 32, ch.rvk, got * 32, hipMemcpyDeviceToHost, s));
-    if (ch.status) HIPCHK(hipMemcpyAsync(to.status.data() + put, ch.status, got, hipMemcpyDeviceToHost, s));      // else zeros, as the resize left them
-    HIPCHK(hipMemcpyAsync(to.microcredits.data() + put, ch.mc, got * 8, hipMemcpyDeviceToHost, s));
-    if (ch.serials) HIPCHK(hipMemcpyAsync(to.serials.data() + put * 32, ch.serials, got * 32, hipMemcpyDeviceToHost, s));
-    if (got_f) HIPCHK(hipMemcpyAsync(to.plain.data() + put_f * 32, ch.fields, got_f * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers
-    if (K == 1) {                                              // in place already: the split is the two bases
-      for (size_t q = 0; q < got; ++q) { to.index[put + q] += (uint32_t)at; h_off[q] += (uint32_t)put_f; }
-      h_off[got] += (uint32_t)put_f;
-    } else for (size_t j = 0; j < K; ++j) {                    // key j's records: the ranks a .. e, the fields fa .. fe
-      const size_t a = ch.first[j], e = ch.first[j + 1], fa = ch.first_f[j], fe = ch.first_f[j + 1];
-      if (a == e) continue;
-      Found& r = *R[j];
-      const size_t have = r.index.size(), have_f = r.offsets.back();
-      r.index.resize(have + (e - a)); r.offsets.resize(have + (e - a) + 1);
-      for (size_t q = a; q < e; ++q) { r.index[have + (q - a)] = staged.index[q] + (uint32_t)at; r.offsets[have + (q - a) + 1] = (uint32_t)(have_f + (h_off[q + 1] - fa)); }
-      r.kind.insert(r.kind.end(), staged.kind.begin() + a, staged.kind.begin() + e);
-      r.rvk.insert(r.rvk.end(), staged.rvk.begin() + a * 32, staged.rvk.begin() + e * 32);
-      r.status.insert(r.status.end(), staged.status.begin() + a, staged.status.begin() + e);
-      r.microcredits.insert(r.microcredits.end(), staged.microcredits.begin() + a, staged.microcredits.begin() + e);
-      r.plain.insert(r.plain.end(), staged.plain.begin() + fa * 32, staged.plain.begin() + fe * 32);
-      if (stage) r.serials.insert(r.serials.end(), staged.serials.begin() + a * 32, staged.serials.begin() + e * 32);
-    }
+    if ((rc = found_download(f, ch, to, put, put_f, R))) return rc;
   }
   return ALEO_MI355X_OK;
 }

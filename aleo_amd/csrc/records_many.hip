@@ -7,18 +7,16 @@
 // (records_many_lane.h), which shares the root, the doublings and the inversion among them.
 //
 // k_records_scan_many<W>: grid = (record blocks, key groups); a block's group is blockIdx.y.  The key table (K x ScanArgs, padded with zero entries to a
-// multiple of W) lies in device memory and is read through uniform loads.  W = 1 is records_scan_lane itself over the same grid.  Results are written
-// [key][record of the chunk] and copied to the caller's [key][record] rows.
+// multiple of W) lies in device memory and is read through uniform loads.  W = 1 is records_scan_lane itself over the same grid, and the one-account scan's only
+// kernel (records.hip calls scan_many_on_device with one key).  Results are written [key][record of the chunk] and copied to the caller's [key][record] rows.
 // A launch covers at most SCAN_MANY_PAIRS = 2^22 pairs and 2^20 records: 64 B per record and 33 B per pair keep the slot's grow-only scratch near 200 MB.
 #include "records_strings.h"
 #include "records_many_lane.h"
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 namespace aleo_mi355x {
 
-static constexpr size_t SCAN_MANY_KEYS = 64;
 static constexpr uint32_t SCAN_BLOCK = 256;
 static constexpr size_t SCAN_MANY_PAIRS = (size_t)1 << 22, SCAN_MANY_RECORDS = (size_t)1 << 20;
 static constexpr size_t SCAN_FULL_LANES = 65536;            // 256 CUs x 4 SIMDs x 64 lanes at one wave per SIMD: below it a call's time is one lane's chain, which a group makes ~W times longer
@@ -84,24 +82,25 @@ template <int W> static void launch_many(hipStream_t s, uint8_t* dfl, char* drvk
                      dfl, drvk, dc0, dnx, (uint32_t)m, dK, dkeys, (uint32_t)n_keys);
 }
 
-// The keys one lane takes.  ALEO_MI355X_SCAN_KEYS_PER_LANE (1, 2, 4, 8; read per call) forces it; otherwise the widest group that still leaves the launch
+// The keys one lane takes.  ALEO_MI355X_SCAN_KEYS_PER_LANE (1, 2, 4, 8; read per call) forces it, for one key as well (padded; same bytes); otherwise the widest group that still leaves the launch
 // SCAN_FULL_LANES lanes, among the widths that a call of n_keys keys can fill more than half of.
 static uint32_t scan_many_width(size_t records_per_launch, size_t n_keys) {
-  if (const char* e = std::getenv("ALEO_MI355X_SCAN_KEYS_PER_LANE")) {
-    char* end = nullptr; const unsigned long v = std::strtoul(e, &end, 10);
-    if (*e && end && *end == 0 && (v == 1 || v == 2 || v == 4 || v == 8)) return (uint32_t)v;
-  }
+  const size_t forced = env_size("ALEO_MI355X_SCAN_KEYS_PER_LANE", 0);
+  if (forced == 1 || forced == 2 || forced == 4 || forced == 8) return (uint32_t)forced;
   for (uint32_t w = 8; w > 1; w >>= 1)
     if (w / 2 < n_keys && records_per_launch * ((n_keys + w - 1) / w) >= SCAN_FULL_LANES) return w;
   return 1;
 }
 
-// The plan of a K-key scan over n records — the records of one launch (the pair cap, the record cap, n) and *W, the keys one lane takes — and that launch over m
-// records already on the device (dkeys: n_keys entries padded with zero entries to a multiple of W): scan_many_on_device below and records_found.hip, which runs
-// the scan between a parse and a walk of its own, both go through these two.
-size_t scan_many_plan(size_t n, size_t n_keys, uint32_t* W) {
+// The plan of a scan of k's keys over n records — the records of one launch (the pair cap, the record cap, n), *W, the keys one lane takes, and the key table of
+// that width (padded to a multiple of W with zero entries, which have no digits at all) — and that launch over m records already on the device: scan_many_on_device
+// below and records_found.hip, which runs the scan between a parse and a walk of its own, both go through these two.
+size_t scan_many_plan(size_t n, const ManyKeys& k, uint32_t* W, std::vector<ScanArgs>* table) {
+  const size_t n_keys = k.args.size();
   size_t chunk = SCAN_MANY_PAIRS / n_keys; if (chunk > SCAN_MANY_RECORDS) chunk = SCAN_MANY_RECORDS; if (chunk > n) chunk = n;
   *W = scan_many_width(chunk, n_keys);
+  table->assign((n_keys + *W - 1) / *W * *W, ScanArgs{});
+  std::copy(k.args.begin(), k.args.end(), table->begin());
   return chunk;
 }
 void launch_scan_keys(hipStream_t s, uint32_t W, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkeys, size_t n_keys) {
@@ -117,19 +116,18 @@ void launch_scan_keys(hipStream_t s, uint32_t W, uint8_t* dflags, char* drvk, co
 // writes the rows; its chunks are cut at the character cap as well, and k_records_resolve follows the scan kernel.
 int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings) {
   const size_t n_keys = k.args.size();
-  uint32_t W;
-  const size_t chunk = scan_many_plan(n, n_keys, &W);
+  uint32_t W; std::vector<ScanArgs> table;                    // the table is a local of this call: it outlives every chunk's synchronisation
+  const size_t chunk = scan_many_plan(n, k, &W, &table);
   if (strings) strings->cut_chunks(n, chunk);
-  std::vector<ScanArgs> table((n_keys + W - 1) / W * W, ScanArgs{});      // the padding: no digits at all
-  std::copy(k.args.begin(), k.args.end(), table.begin());
   hipStream_t s = c->stream;
   int32_t rc;
   const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
-  const size_t keys_bytes = (table.size() * sizeof(ScanArgs) + 31) & ~(size_t)31;
-  const size_t rows_bytes = (keys_bytes + chunk * 64 + chunk * n_keys * 33 + 31) & ~(size_t)31;
-  if ((rc = c->scalars_stage.reserve(rows_bytes + (strings ? strings->scratch_bytes() : 0)))) return rc;
-  char* dkeys = c->scalars_stage.as<char>(); char* dc0 = dkeys + keys_bytes; char* dnx = dc0 + chunk * 32; char* drvk = dnx + chunk * 32; uint8_t* dfl = (uint8_t*)(drvk + chunk * n_keys * 32);
-  char* dstr = dkeys + rows_bytes;
+  Carve cv;
+  const size_t o_keys = cv.part(table.size() * sizeof(ScanArgs)), o_c0 = cv.part(chunk * 32), o_nx = cv.part(chunk * 32), o_rvk = cv.part(chunk * n_keys * 32), o_fl = cv.part(chunk * n_keys),
+               o_str = cv.part(strings ? strings->scratch_bytes() : 0);
+  if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
+  char* base = c->scalars_stage.as<char>();
+  char* dkeys = base + o_keys; char* dc0 = base + o_c0; char* dnx = base + o_nx; char* drvk = base + o_rvk; uint8_t* dfl = (uint8_t*)(base + o_fl); char* dstr = base + o_str;
   HIPCHK(hipMemcpyAsync(dkeys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, s));
   for (size_t at = 0, ck = 0, m; at < n; at += m, ++ck) {
     m = strings ? strings->cut[ck + 1] - at : (n - at < chunk ? n - at : chunk);
@@ -144,7 +142,7 @@ int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* o
     // rows of m on the device, rows of n at the caller
     HIPCHK(hipMemcpy2DAsync(flags + at, n, dfl, m, m, n_keys, hipMemcpyDeviceToHost, s));
     if (rvk_out) HIPCHK(hipMemcpy2DAsync((char*)rvk_out + at * 32, n * 32, drvk, m * 32, m * 32, n_keys, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers; the table is a local of this call
+    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
   }
   return ALEO_MI355X_OK;
 }

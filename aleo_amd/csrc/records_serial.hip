@@ -3,7 +3,8 @@
 // serialNumberString, wasm/src/record/record_plaintext.rs:64-82) — snarkVM 0.14.5 console/program/src/data/record/serial_number.rs [UPSTREAM-RECALL], pinned by the
 // reference's own vectors stage by stage (serial_host.hpp, tests/serial_ref.py).
 //
-// The kernel (one commitment per lane: records_serial_lane.h), the same bytes on the host (serial_host.hpp — what small batches take, and the checker), the
+// The kernel (one commitment per lane: records_serial_lane.h; one kernel for this call's one key and for the key segments of records_unspent.hip, which launches
+// it through launch_records_serial), the same bytes on the host (serial_host.hpp — what small batches take, and the checker), the
 // routing threshold, and the host-only calls around them: a record's commitment and checksum (records_bits.hpp) and the account of a private key.
 // The lane's tables (181 KB: serial_host.hpp serial_tables) are built on the host at first use and stay resident per device for the life of the process.
 #include "records_found.h"
@@ -14,26 +15,26 @@ namespace aleo_mi355x {
 
 using serial::SerialTables;
 
-static int32_t serials_on_host(void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const void* sk_sig32) {
-  if (!sk_sig32 || ((!sn_out || !flags || !commitments32) && n)) return bad_arg("records_serial_numbers: null buffer");
-  ScanArgs key; if (!serial::serial_key(key, sk_sig32)) return bad_arg("records_serial_numbers: sk_sig is not a canonical scalar below the subgroup order");
-  const SerialTables& T = serial::serial_tables();
-  for (size_t i = 0; i < n; ++i) flags[i] = serial::serial_one_host((uint8_t*)sn_out + 32 * i, (const uint8_t*)commitments32 + 32 * i, key, T);
-  return ALEO_MI355X_OK;
-}
-
 // ---- the kernel -----------------------------------------------------------------------------------------------------------------------------------
 static constexpr uint32_t SERIAL_BLOCK = 256;
 static constexpr size_t SERIAL_CHUNK = (size_t)1 << 20;     // commitments per launch: 65 bytes of slot scratch each
 
-__global__ void __launch_bounds__(SERIAL_BLOCK) k_records_serial(char* __restrict__ sn, uint8_t* __restrict__ flags, const char* __restrict__ cm, uint32_t n,
-                                                                 const uint32_t* __restrict__ K, SerialArgs A) {
-  const uint32_t i = blockIdx.x * SERIAL_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const Fr c = load_fp<Fr>(cm + (size_t)i * 32);
-  char* out = sn + (size_t)i * 32;
-  const uint32_t flag = records_serial_lane(c.v, K, A, [&](const F29& v) { store_fp<Fr>(out, f29_to_fr(v)); });
-  flags[i] = (uint8_t)flag;
+// The one serial-number kernel, over the waves wave_lo .. wave_hi of the padded grid of `seg` (records_found.h): a wave finds its key among the n_keys + 1
+// boundaries (kernel arguments; with one segment the search runs zero times), reads that key's digits from the table in device memory through uniform loads, and
+// the ladder's digit tests stay uniform branches.  cm: the commitment rows in rank order; sn / flags: per rank.
+__global__ void __launch_bounds__(SERIAL_BLOCK) k_records_serial(char* __restrict__ sn, uint8_t* __restrict__ flags, const char* __restrict__ cm, const uint32_t* __restrict__ K,
+                                                                 const SerialArgs* __restrict__ keys, UnspentSegs seg, uint32_t wave_lo, uint32_t wave_hi) {
+  const uint32_t w = __builtin_amdgcn_readfirstlane(wave_lo + blockIdx.x * (SERIAL_BLOCK / 64) + (threadIdx.x >> 6));
+  if (w >= wave_hi) return;                                    // uniform; no barrier below
+  uint32_t key = 0;
+  for (uint32_t k = 1; k < seg.n_keys; ++k) if (seg.wave0[k] <= w) key = k;      // the last key that starts at or before this wave: keys without rows have no wave
+  key = __builtin_amdgcn_readfirstlane(key);
+  const uint32_t rank = seg.rank0[key] + (w - seg.wave0[key]) * 64u + (threadIdx.x & 63u);
+  if (rank >= seg.rank0[key + 1]) return;                      // the padding of the key's last wave
+  const Fr c = load_fp<Fr>(cm + (size_t)rank * 32);
+  char* out = sn + (size_t)rank * 32;
+  const uint32_t flag = records_serial_lane(c.v, K, keys[key], [&](const F29& v) { store_fp<Fr>(out, f29_to_fr(v)); });
+  flags[rank] = (uint8_t)flag;
 }
 
 // The tables of one device: uploaded once, under the lock, and never freed; the copy is complete before the pointer is handed out.
@@ -50,24 +51,54 @@ int32_t serial_tables_on_device(int device, const uint32_t** out) {
   *out = it->second; return ALEO_MI355X_OK;
 }
 
-size_t serial_chunk_cap() { const size_t cap = env_size("ALEO_MI355X_SERIAL_CHUNK", SERIAL_CHUNK); return cap == 0 || cap > SERIAL_CHUNK ? SERIAL_CHUNK : cap; }
+static size_t serial_chunk_cap() { const size_t cap = env_size("ALEO_MI355X_SERIAL_CHUNK", SERIAL_CHUNK); return cap == 0 || cap > SERIAL_CHUNK ? SERIAL_CHUNK : cap; }
 
+int32_t launch_records_serial(hipStream_t s, char* dsn, uint8_t* dflags, const char* dcm, const uint32_t* dK, const SerialArgs* dkeys, const UnspentSegs& seg) {
+  const uint32_t waves = seg.wave0[seg.n_keys], per = serial_chunk_cap() < 64 ? 1 : (uint32_t)(serial_chunk_cap() / 64);
+  for (uint32_t lo = 0; lo < waves; lo += per) {
+    const uint32_t hi = waves - lo < per ? waves : lo + per;
+    hipLaunchKernelGGL(k_records_serial, dim3((hi - lo + SERIAL_BLOCK / 64 - 1) / (SERIAL_BLOCK / 64)), dim3(SERIAL_BLOCK), 0, s, dsn, dflags, dcm, dK, dkeys, seg, lo, hi);
+    HIPCHK(hipGetLastError());
+  }
+  return ALEO_MI355X_OK;
+}
+
+// One key: a table of one row and, per chunk, one segment over the chunk.  `a` outlives the call's last synchronisation.
 static int32_t serials_on_device(Ctx* c, void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const SerialArgs& a) {
   const uint32_t* dK; if (int32_t rc = serial_tables_on_device(c->device, &dK)) return rc;
   const size_t cap = serial_chunk_cap();
   const size_t chunk = n < cap ? n : cap;
   hipStream_t s = c->stream;
-  if (int32_t rc = c->scalars_stage.reserve(chunk * 65)) return rc;
-  char* dcm = c->scalars_stage.as<char>(); char* dsn = dcm + chunk * 32; uint8_t* dfl = (uint8_t*)(dsn + chunk * 32);
+  Carve cv;
+  const size_t o_key = cv.part(sizeof(SerialArgs)), o_cm = cv.part(chunk * 32), o_sn = cv.part(chunk * 32), o_fl = cv.part(chunk);
+  if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
+  char* base = c->scalars_stage.as<char>();
+  char* dcm = base + o_cm; char* dsn = base + o_sn; uint8_t* dfl = (uint8_t*)(base + o_fl);
+  HIPCHK(hipMemcpyAsync(base + o_key, &a, sizeof a, hipMemcpyHostToDevice, s));
   for (size_t at = 0; at < n; at += chunk) {
     const size_t m = n - at < chunk ? n - at : chunk;
+    UnspentSegs seg{}; seg.n_keys = 1; seg.rank0[1] = (uint32_t)m; seg.wave0[1] = (uint32_t)((m + 63) / 64);
     HIPCHK(hipMemcpyAsync(dcm, (const char*)commitments32 + at * 32, m * 32, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_records_serial, dim3((uint32_t)((m + SERIAL_BLOCK - 1) / SERIAL_BLOCK)), dim3(SERIAL_BLOCK), 0, s, dsn, dfl, (const char*)dcm, (uint32_t)m, dK, a);
-    HIPCHK(hipGetLastError());
+    if (int32_t rc = launch_records_serial(s, dsn, dfl, dcm, dK, (const SerialArgs*)(base + o_key), seg)) return rc;
     HIPCHK(hipMemcpyAsync((char*)sn_out + at * 32, dsn, m * 32, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
   }
+  return ALEO_MI355X_OK;
+}
+
+static int32_t serial_numbers(void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const void* sk_sig32, bool may_route) {
+  if (!sk_sig32 || ((!sn_out || !flags || !commitments32) && n)) return bad_arg("records_serial_numbers: null buffer");
+  ScanArgs key; if (!serial::serial_key(key, sk_sig32)) return bad_arg("records_serial_numbers: sk_sig is not a canonical scalar below the subgroup order");
+  if (may_route && n && n >= aleo_mi355x_min_serials()) {
+    const SerialArgs a = serial_args_of(key);
+    Slot sl; if (sl.rc) return sl.rc;
+    const int32_t rc = serials_on_device(sl.c, sn_out, flags, commitments32, n, a);
+    if (rc) (void)hipStreamSynchronize(sl.c->stream);        // the key's row may still be on its way up
+    return rc;
+  }
+  const SerialTables& T = serial::serial_tables();
+  for (size_t i = 0; i < n; ++i) flags[i] = serial::serial_one_host((uint8_t*)sn_out + 32 * i, (const uint8_t*)commitments32 + 32 * i, key, T);
   return ALEO_MI355X_OK;
 }
 
@@ -101,18 +132,11 @@ extern "C" {
 size_t aleo_mi355x_min_serials(void) { return env_size("ALEO_MI355X_MIN_SERIALS", (size_t)1 << 6); }
 
 int32_t aleo_mi355x_records_serial_numbers_host(void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const void* sk_sig32) {
-  return guarded([&] { return serials_on_host(sn_out, flags, commitments32, n, sk_sig32); });
+  return guarded([&] { return serial_numbers(sn_out, flags, commitments32, n, sk_sig32, false); });
 }
 
 int32_t aleo_mi355x_records_serial_numbers(void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const void* sk_sig32) {
-  return guarded([&] {
-    if (n < aleo_mi355x_min_serials() || n == 0) return serials_on_host(sn_out, flags, commitments32, n, sk_sig32);
-    if (!sk_sig32 || !sn_out || !flags || !commitments32) return bad_arg("records_serial_numbers: null buffer");
-    ScanArgs key; if (!serial::serial_key(key, sk_sig32)) return bad_arg("records_serial_numbers: sk_sig is not a canonical scalar below the subgroup order");
-    SerialArgs a; std::memcpy(a.naf_pos, key.naf_pos, sizeof a.naf_pos); std::memcpy(a.naf_neg, key.naf_neg, sizeof a.naf_neg); a.naf_len = key.naf_len;
-    Slot sl; if (sl.rc) return sl.rc;
-    return serials_on_device(sl.c, sn_out, flags, commitments32, n, a);
-  });
+  return guarded([&] { return serial_numbers(sn_out, flags, commitments32, n, sk_sig32, true); });
 }
 
 int32_t aleo_mi355x_found_serial_numbers(const aleo_mi355x_found* found, const void* commitments32, size_t n, const void* sk_sig32, void* sn_out, uint8_t* flags) {

@@ -8,7 +8,26 @@
 
 namespace aleo_mi355x {
 
+static constexpr uint32_t SCAN_MANY_KEYS = 64;               // the accounts of one call: many_keys refuses more, and the per-key tables are sized by it
 struct ManyKeys { std::vector<ScanArgs> args; std::vector<HFr> addr; };
+
+static constexpr uint32_t SPAN_BLOCK = 256, SPAN_LDS_BYTES = 64 * 1024;      // the lanes, and strings, of a block that reads the text; the LDS it spends on its span
+
+#ifdef __HIPCC__
+// A block's strings (b0 .. b0 + SPAN_BLOCK of the chunk's n) are one contiguous span of the text: where it fits SPAN_LDS_BYTES the block copies it to LDS with
+// 16-byte loads, every lane of a wave reading its neighbours' lines, and string i lies at stage + (off[i] - *lo_out); a lane's own byte loads from global memory
+// touch 64 cache lines per instruction of a wave (measured: DESIGN §11).  A longer span — 256 strings of more than 255 characters on average — gets false and is
+// read from global memory.  Every lane of the block calls it (a barrier follows the copy); text: readable up to the next multiple of 16 past its last character.
+__device__ __forceinline__ bool stage_span(uint4* stage, const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t b0, uint32_t n, uint32_t* lo_out) {
+  const uint32_t b1 = b0 + SPAN_BLOCK < n ? b0 + SPAN_BLOCK : n;
+  const uint32_t lo = off[b0] & ~15u, hi = off[b1];            // uniform: the block's span, from a 16-byte boundary
+  *lo_out = lo;
+  if (hi - lo > SPAN_LDS_BYTES) return false;
+  for (uint32_t t = threadIdx.x; lo + 16 * t < hi; t += SPAN_BLOCK) stage[t] = *(const uint4*)(text + lo + 16 * (size_t)t);
+  __syncthreads();
+  return true;
+}
+#endif
 
 // n strings one after another in `text`, string i at text[offsets[i] .. offsets[i + 1]), cut into chunks of whole records: chunk k holds the records
 // cut[k] .. cut[k + 1], at most `record_cap` of them and, unless it is one record, at most the character cap (ALEO_MI355X_SCAN_CHUNK_CHARS, read per call; 256 MiB)
@@ -25,7 +44,7 @@ struct StringSource {
   // behind the scan kernel: k_records_resolve over flags / rvk ([key][record of the chunk]), then the copy of the kinds to the caller
   int32_t resolve(hipStream_t s, size_t k, char* scratch, uint8_t* dflags, char* drvk, const char* dc0, const ScanArgs* dkeys, size_t n_keys);
   // where fill left the chunk's relative offsets, kinds and text inside `scratch` (records_found.hip walks the owned records from them)
-  void parts(char* scratch, const uint32_t** off, const int8_t** kinds, const char** text) const;
+  void parts(char* scratch, uint32_t** off, int8_t** kinds, char** text) const;
 };
 
 // records_strings.hip: what both paths of a call over strings refuse before they look at one
@@ -35,14 +54,16 @@ int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offse
 int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32, size_t n_keys);
 // the records come as rows (owner_c0, nonce_x) or, when `strings` is given, from it
 int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings = nullptr);
-// the plan of a K-key scan over n records — the records of one launch (the pair cap, the record cap, n) and *W, the keys one lane takes — and that launch over
-// m records already on the device (flags m x n_keys B, rvk m x n_keys x 32 B, [key][record]; dkeys padded with zero entries to a multiple of W); the caller
-// checks hipGetLastError
-size_t scan_many_plan(size_t n, size_t n_keys, uint32_t* W);
+// the plan of a scan of k's keys over n records — the records of one launch (the pair cap, the record cap, n), *W, the keys one lane takes, and the table of the
+// keys padded with zero entries to a multiple of W — and that launch over m records already on the device (flags m x n_keys B, rvk m x n_keys x 32 B,
+// [key][record]; dkeys: the table); the caller checks hipGetLastError
+size_t scan_many_plan(size_t n, const ManyKeys& k, uint32_t* W, std::vector<ScanArgs>* table);
 void launch_scan_keys(hipStream_t s, uint32_t W, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkeys, size_t n_keys);
 
 // records_decrypt.hip
 size_t decrypt_chunk_fields();                                // the field cap of one k_records_decrypt launch (ALEO_MI355X_DECRYPT_CHUNK_FIELDS, read per call)
+// the end of the launch that starts at record `at` of n (offsets: n + 1 field boundaries): whole records within the two caps, one at least
+size_t decrypt_cut(const uint32_t* offsets, size_t at, size_t n, size_t record_cap, size_t field_cap);
 // k_records_decrypt over n records already on the device: io the fields from offsets[0] on, in place; the caller checks hipGetLastError
 void launch_records_decrypt(hipStream_t s, char* io, uint8_t* dflags, const char* drvk, const uint32_t* doffsets, uint32_t base, size_t n, const uint32_t* dK);
 

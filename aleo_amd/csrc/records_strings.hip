@@ -19,7 +19,7 @@
 
 namespace aleo_mi355x {
 
-static constexpr uint32_t PARSE_BLOCK = 256;
+static constexpr uint32_t PARSE_BLOCK = SPAN_BLOCK;
 static constexpr size_t PARSE_CHUNK_RECORDS = (size_t)1 << 20;
 static constexpr size_t STRINGS_CHUNK_CHARS = (size_t)256 << 20;
 
@@ -70,21 +70,12 @@ static int32_t scan_strings_on_host(uint8_t* flags, int8_t* kinds, void* rvk_out
 
 // ---- the kernels ------------------------------------------------------------------------------------------------------------------------------------
 // text: the chunk's characters, readable up to the next multiple of 16 past the last of them; off: n + 1 chunk-relative offsets.  c0 / nx: 32-byte aligned rows.
-// A block's strings are one contiguous span of the text: where it fits PARSE_LDS_BYTES the block copies it to LDS with 16-byte loads, every lane of a wave reading
-// its neighbours' lines, and the lanes parse from there; a lane's own byte loads from global memory touch 64 cache lines per instruction of a wave (measured:
-// DESIGN §11).  A block whose span is longer — 256 strings of more than 255 characters on average — parses straight from global memory.
-static constexpr uint32_t PARSE_LDS_BYTES = 64 * 1024;
-
 __global__ void __launch_bounds__(PARSE_BLOCK) k_records_parse(int8_t* __restrict__ kinds, char* __restrict__ c0, char* __restrict__ nx, const char* __restrict__ text,
                                                                const uint32_t* __restrict__ off, uint32_t n) {
-  __shared__ uint4 stage[PARSE_LDS_BYTES / 16];
-  const uint32_t b0 = blockIdx.x * PARSE_BLOCK, b1 = b0 + PARSE_BLOCK < n ? b0 + PARSE_BLOCK : n;
-  const uint32_t lo = off[b0] & ~15u, hi = off[b1];          // uniform: the block's span, from a 16-byte boundary
-  const bool staged = hi - lo <= PARSE_LDS_BYTES;
-  if (staged) {
-    for (uint32_t t = threadIdx.x; lo + 16 * t < hi; t += PARSE_BLOCK) stage[t] = *(const uint4*)(text + lo + 16 * (size_t)t);
-    __syncthreads();
-  }
+  __shared__ uint4 stage[SPAN_LDS_BYTES / 16];
+  const uint32_t b0 = blockIdx.x * PARSE_BLOCK;
+  uint32_t lo;
+  const bool staged = stage_span(stage, text, off, b0, n, &lo);
   const uint32_t i = b0 + threadIdx.x;
   if (i >= n) return;                                        // no barrier below
   const uint32_t first = off[i], len = off[i + 1] - first;
@@ -122,7 +113,6 @@ __global__ void __launch_bounds__(PARSE_BLOCK) k_records_resolve(uint8_t* __rest
 }
 
 // ---- the source of strings of the scan's device flow (records_strings.h) -------------------------------------------------------------------------------
-static inline size_t up32(size_t v) { return (v + 31) & ~(size_t)31; }
 static inline size_t uploaded(const uint64_t* offsets, size_t i) { const uint64_t span = offsets[i + 1] - offsets[i]; return span > RS_MAX_CHARS ? 0 : (size_t)span; }
 
 void StringSource::cut_chunks(size_t n, size_t record_cap) {
@@ -138,11 +128,11 @@ void StringSource::cut_chunks(size_t n, size_t record_cap) {
 }
 
 // scratch: [offsets (max_records + 1) x 4 B][kinds max_records B][text max_chars B], each part 32-byte aligned (k_records_parse reads the text in 16-byte pieces)
-size_t StringSource::scratch_bytes() const { return up32((max_records + 1) * 4) + up32(max_records) + up32(max_chars); }
+size_t StringSource::scratch_bytes() const { Carve cv; cv.part((max_records + 1) * 4); cv.part(max_records); cv.part(max_chars); return cv.total; }
 
 int32_t StringSource::fill(hipStream_t s, size_t k, char* scratch, char* dc0, char* dnx) {
   const size_t at = cut[k], m = cut[k + 1] - at;
-  uint32_t* doff = (uint32_t*)scratch; int8_t* dkinds = (int8_t*)(scratch + up32((max_records + 1) * 4)); char* dtext = (char*)dkinds + up32(max_records);
+  uint32_t* doff; int8_t* dkinds; char* dtext; parts(scratch, &doff, &dkinds, &dtext);
   rel.resize(m + 1);
   size_t pos = 0, run_dev = 0; uint64_t run_host = offsets[at];      // a run: strings that go up in one copy; an over-long string ends it
   auto flush = [&](uint64_t host_end) -> int32_t {
@@ -165,15 +155,16 @@ int32_t StringSource::fill(hipStream_t s, size_t k, char* scratch, char* dc0, ch
 
 int32_t StringSource::resolve(hipStream_t s, size_t k, char* scratch, uint8_t* dflags, char* drvk, const char* dc0, const ScanArgs* dkeys, size_t n_keys) {
   const size_t at = cut[k], m = cut[k + 1] - at;
-  const int8_t* dkinds = (const int8_t*)(scratch + up32((max_records + 1) * 4));
-  hipLaunchKernelGGL(k_records_resolve, dim3((uint32_t)((m + PARSE_BLOCK - 1) / PARSE_BLOCK), (uint32_t)n_keys), dim3(PARSE_BLOCK), 0, s, dflags, drvk, dkinds, dc0, (uint32_t)m, dkeys);
+  uint32_t* doff; int8_t* dkinds; char* dtext; parts(scratch, &doff, &dkinds, &dtext);
+  hipLaunchKernelGGL(k_records_resolve, dim3((uint32_t)((m + PARSE_BLOCK - 1) / PARSE_BLOCK), (uint32_t)n_keys), dim3(PARSE_BLOCK), 0, s, dflags, drvk, (const int8_t*)dkinds, dc0, (uint32_t)m, dkeys);
   HIPCHK(hipGetLastError());
   if (kinds) HIPCHK(hipMemcpyAsync(kinds + at, dkinds, m, hipMemcpyDeviceToHost, s));
   return ALEO_MI355X_OK;
 }
 
-void StringSource::parts(char* scratch, const uint32_t** off, const int8_t** kinds_, const char** text_) const {
-  *off = (const uint32_t*)scratch; *kinds_ = (const int8_t*)(scratch + up32((max_records + 1) * 4)); *text_ = (const char*)*kinds_ + up32(max_records);
+void StringSource::parts(char* scratch, uint32_t** off, int8_t** kinds_, char** text_) const {
+  Carve cv;
+  *off = (uint32_t*)(scratch + cv.part((max_records + 1) * 4)); *kinds_ = (int8_t*)(scratch + cv.part(max_records)); *text_ = scratch + cv.part(max_chars);
 }
 
 // parse_many on the device: the chunks of a scan over strings, the parse kernel alone, the rows copied back
@@ -181,10 +172,11 @@ static int32_t parse_many_on_device(Ctx* c, int8_t* kinds, void* owner32, void* 
   StringSource src{text, offsets, kinds};
   src.cut_chunks(n, PARSE_CHUNK_RECORDS);
   hipStream_t s = c->stream;
-  const size_t rows = src.max_records * 32;
-  if (int32_t rc = c->scalars_stage.reserve(2 * rows + src.scratch_bytes())) return rc;
-  char* dc0 = c->scalars_stage.as<char>(); char* dnx = dc0 + rows; char* dstr = dnx + rows;
-  const int8_t* dkinds = (const int8_t*)(dstr + up32((src.max_records + 1) * 4));
+  Carve cv;
+  const size_t o_c0 = cv.part(src.max_records * 32), o_nx = cv.part(src.max_records * 32), o_str = cv.part(src.scratch_bytes());
+  if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
+  char* base = c->scalars_stage.as<char>(); char* dc0 = base + o_c0; char* dnx = base + o_nx; char* dstr = base + o_str;
+  uint32_t* doff; int8_t* dkinds; char* dtext; src.parts(dstr, &doff, &dkinds, &dtext);
   for (size_t k = 0; k + 1 < src.cut.size(); ++k) {
     const size_t at = src.cut[k], m = src.cut[k + 1] - at;
     if (int32_t rc = src.fill(s, k, dstr, dc0, dnx)) return rc;

@@ -7,10 +7,8 @@
 // per chunk, behind k_found_microcredits (records_found.h FoundStage):
 //   — the compacted `index` comes down behind the gather, while the decryption's kernels are still to run; the host gathers the owned records' commitment rows
 //   (owned x 32 B go up instead of the chunk's m x 32 B: a wallet owns a small part of what it scans) —
-//   k_found_serial      ONE launch over the owned pairs of ALL keys, one pair per lane, records_serial_lane.h unchanged.  Every key's segment of the compacted
-//                       arrays is padded to whole waves, so a wave has one key: the wave finds it among the K + 1 boundaries (kernel arguments), reads that key's
-//                       digits from a K-row table in device memory through uniform loads, and the ladder's digit tests stay uniform branches.  Launches of at
-//                       most ALEO_MI355X_SERIAL_CHUNK lanes; a launch may span key boundaries.
+//   k_records_serial    records_serial.hip's, the kernel of the one-account serial numbers too: ONE launch over the owned pairs of ALL keys, one pair per lane,
+//                       every key's segment of the compacted arrays padded to whole waves so that a wave has one key (launch_records_serial, records_found.h)
 //                       Below aleo_mi355x_min_serials() owned pairs the host computes the serial numbers inside the call (the rows are there already) and
 //                       uploads them: the kernel's chain costs the same for 1 pair as for 2^14.  The bytes are the same either way.
 //   k_unspent_keep      one lane per owned pair: keep = status 0, flag 0 and not in S (records_spent_lane.h; no S: no probe); then the first level of the exclusive
@@ -22,7 +20,6 @@
 // S goes up once per call: its rows, and an open-addressing table over them built by k_spent_insert (one row per lane, atomicCAS).  n_spent = 0: neither.
 // The host path is found_on_host per key, serial_one_host per owned record and a sorted vector of S's rows; it shares no code with the above.
 #include "records_found.h"
-#include "records_serial_lane.h"
 #include "records_spent_lane.h"
 #include "serial_host.hpp"
 #include <algorithm>
@@ -31,29 +28,7 @@
 
 namespace aleo_mi355x {
 
-static constexpr uint32_t UNSPENT_MAX_KEYS = 64;
-
-// Where the keys' segments lie: key j's pairs are the ranks rank0[j] .. rank0[j + 1] of the compacted arrays and the waves wave0[j] .. wave0[j + 1] of the
-// padded grid (ceil(pairs / 64) waves each).
-struct UnspentSegs { uint32_t n_keys, wave0[UNSPENT_MAX_KEYS + 1], rank0[UNSPENT_MAX_KEYS + 1]; };
-
 // ---- the kernels ------------------------------------------------------------------------------------------------------------------------------------
-// The waves wave_lo .. wave_hi of the padded grid.  cm: the owned pairs' commitment rows in rank order; sn / flags: per rank.
-__global__ void __launch_bounds__(FOUND_BLOCK) k_found_serial(char* __restrict__ sn, uint8_t* __restrict__ flags, const char* __restrict__ cm, const uint32_t* __restrict__ K,
-                                                             const SerialArgs* __restrict__ keys, UnspentSegs seg, uint32_t wave_lo, uint32_t wave_hi) {
-  const uint32_t w = __builtin_amdgcn_readfirstlane(wave_lo + blockIdx.x * (FOUND_BLOCK / 64) + (threadIdx.x >> 6));
-  if (w >= wave_hi) return;                                    // uniform; no barrier below
-  uint32_t key = 0;
-  for (uint32_t k = 1; k < seg.n_keys; ++k) if (seg.wave0[k] <= w) key = k;      // the last key that starts at or before this wave: keys without pairs have no wave
-  key = __builtin_amdgcn_readfirstlane(key);
-  const uint32_t rank = seg.rank0[key] + (w - seg.wave0[key]) * 64u + (threadIdx.x & 63u);
-  if (rank >= seg.rank0[key + 1]) return;                      // the padding of the key's last wave
-  const Fr c = load_fp<Fr>(cm + (size_t)rank * 32);
-  char* out = sn + (size_t)rank * 32;
-  const uint32_t flag = records_serial_lane(c.v, K, keys[key], [&](const F29& v) { store_fp<Fr>(out, f29_to_fr(v)); });
-  flags[rank] = (uint8_t)flag;
-}
-
 // One row of S per lane.
 __global__ void __launch_bounds__(FOUND_BLOCK) k_spent_insert(uint32_t* __restrict__ table, uint32_t cap, const uint32_t* __restrict__ rows, uint32_t n_spent) {
   const uint32_t i = blockIdx.x * FOUND_BLOCK + threadIdx.x;
@@ -94,7 +69,7 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_unspent_scatter(char* __restric
   if (blockIdx.x == 0 && threadIdx.x <= seg.n_keys) {
     const uint32_t r = seg.rank0[threadIdx.x];
     stat[8 + threadIdx.x] = r >= n_owned ? n_kept : blk[nb + r / FOUND_BLOCK] + pos[r];
-    stat[8 + UNSPENT_MAX_KEYS + 1 + threadIdx.x] = r >= n_owned ? n_fields : blk[r / FOUND_BLOCK] + cnt[r];
+    stat[8 + SCAN_MANY_KEYS + 1 + threadIdx.x] = r >= n_owned ? n_fields : blk[r / FOUND_BLOCK] + cnt[r];
     if (threadIdx.x == 0) o_off[n_kept] = n_fields;
   }
   if (j >= n_owned || !keep[j]) return;
@@ -127,10 +102,11 @@ struct UnspentStage : FoundStage {
     if (int32_t rc = ensure_host_pinned(c, 8192)) return rc;
     const size_t K = keys.serial.size();
     table.resize(K);
-    for (size_t j = 0; j < K; ++j) { const ScanArgs& a = keys.serial[j]; std::memcpy(table[j].naf_pos, a.naf_pos, sizeof table[j].naf_pos); std::memcpy(table[j].naf_neg, a.naf_neg, sizeof table[j].naf_neg); table[j].naf_len = a.naf_len; }
+    for (size_t j = 0; j < K; ++j) table[j] = serial_args_of(keys.serial[j]);
     cap = n_spent ? spent_capacity(n_spent) : 0;
-    const size_t o_keys = 0, o_rows = (K * sizeof(SerialArgs) + 31) & ~(size_t)31, o_table = o_rows + n_spent * 32;
-    if (int32_t rc = c->unspent_set.reserve(o_table + (size_t)cap * 4)) return rc;
+    Carve cv;
+    const size_t o_keys = cv.part(K * sizeof(SerialArgs)), o_rows = cv.part(n_spent * 32), o_table = cv.part((size_t)cap * 4);
+    if (int32_t rc = c->unspent_set.reserve(cv.total)) return rc;
     char* base = c->unspent_set.as<char>();
     dkeys = (const SerialArgs*)(base + o_keys);
     HIPCHK(hipMemcpyAsync(base + o_keys, table.data(), K * sizeof(SerialArgs), hipMemcpyHostToDevice, s));
@@ -159,13 +135,12 @@ struct UnspentStage : FoundStage {
     UnspentSegs seg{}; seg.n_keys = (uint32_t)K;
     for (size_t j = 0; j <= K; ++j) seg.rank0[j] = ch.first[j];
     for (size_t j = 0; j < K; ++j) seg.wave0[j + 1] = seg.wave0[j] + (ch.first[j + 1] - ch.first[j] + 63) / 64;
-    const size_t stat_words = 8 + 2 * (UNSPENT_MAX_KEYS + 1);
-    size_t total = 0;
-    auto part = [&](size_t bytes) { const size_t a = total; total += (bytes + 31) & ~(size_t)31; return a; };
-    const size_t o_cm = part(owned * 32), o_sn = part(owned * 32), o_fl = part(owned), o_keep = part(owned), o_cnt = part(owned * 4), o_pos = part(owned * 4), o_blk = part((size_t)2 * nb * 4),
-                 o_stat = part(stat_words * 4), k_fields = part(nf * 32), k_index = part(owned * 4), k_off = part((owned + 1) * 4), k_mc = part(owned * 8), k_rvk = part(owned * 32),
-                 k_kind = part(owned), k_sn = part(owned * 32);
-    if (int32_t rc = c->unspent_ws.reserve(total)) return rc;
+    const size_t stat_words = 8 + 2 * (SCAN_MANY_KEYS + 1);
+    Carve cv;
+    const size_t o_cm = cv.part(owned * 32), o_sn = cv.part(owned * 32), o_fl = cv.part(owned), o_keep = cv.part(owned), o_cnt = cv.part(owned * 4), o_pos = cv.part(owned * 4), o_blk = cv.part((size_t)2 * nb * 4),
+                 o_stat = cv.part(stat_words * 4), k_fields = cv.part(nf * 32), k_index = cv.part(owned * 4), k_off = cv.part((owned + 1) * 4), k_mc = cv.part(owned * 8), k_rvk = cv.part(owned * 32),
+                 k_kind = cv.part(owned), k_sn = cv.part(owned * 32);
+    if (int32_t rc = c->unspent_ws.reserve(cv.total)) return rc;
     char* b = c->unspent_ws.as<char>();
     char* dsn = b + o_sn; uint8_t* dfl = (uint8_t*)(b + o_fl); uint8_t* dkeep = (uint8_t*)(b + o_keep);
     uint32_t* dcnt = (uint32_t*)(b + o_cnt); uint32_t* dpos = (uint32_t*)(b + o_pos); uint32_t* dblk = (uint32_t*)(b + o_blk); uint32_t* dstat = (uint32_t*)(b + o_stat);
@@ -178,12 +153,7 @@ struct UnspentStage : FoundStage {
       HIPCHK(hipMemcpyAsync(dfl, h_fl.data(), owned, hipMemcpyHostToDevice, s));
     } else {
       HIPCHK(hipMemcpyAsync(b + o_cm, h_cm.data(), owned * 32, hipMemcpyHostToDevice, s));
-      const uint32_t waves = seg.wave0[K], per = (uint32_t)std::max<size_t>(1, serial_chunk_cap() / 64);
-      for (uint32_t lo = 0; lo < waves; lo += per) {
-        const uint32_t hi = waves - lo < per ? waves : lo + per;
-        hipLaunchKernelGGL(k_found_serial, dim3((hi - lo + FOUND_BLOCK / 64 - 1) / (FOUND_BLOCK / 64)), dim3(FOUND_BLOCK), 0, s, dsn, dfl, (const char*)(b + o_cm), dK, dkeys, seg, lo, hi);
-        HIPCHK(hipGetLastError());
-      }
+      if (int32_t rc = launch_records_serial(s, dsn, dfl, b + o_cm, dK, dkeys, seg)) return rc;
     }
     hipLaunchKernelGGL(k_unspent_keep, dim3(nb), dim3(FOUND_BLOCK), 0, s, dcnt, dpos, dkeep, dblk, (const uint8_t*)ch.status, (const uint8_t*)dfl, (const uint32_t*)dsn, (const uint32_t*)ch.off,
                        dtable, cap, dspent, (uint32_t)owned);
@@ -201,7 +171,7 @@ struct UnspentStage : FoundStage {
     HIPCHK(hipMemcpyAsync(stat, dstat, stat_words * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     kept.owned = stat[0]; kept.nf = stat[1];
-    for (size_t j = 0; j <= K; ++j) { kept.first[j] = stat[8 + j]; kept.first_f[j] = stat[8 + UNSPENT_MAX_KEYS + 1 + j]; }
+    for (size_t j = 0; j <= K; ++j) { kept.first[j] = stat[8 + j]; kept.first_f[j] = stat[8 + SCAN_MANY_KEYS + 1 + j]; }
     ch = std::move(kept);
     return ALEO_MI355X_OK;
   }

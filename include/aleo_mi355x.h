@@ -534,6 +534,7 @@ size_t aleo_mi355x_min_ntt(void);
  *                  host decrypts an owned record with — zeros where the flag is 2.  Defined for EVERY on-curve x: where upstream would have refused the record
  *                  on parsing (no prime-order point with that x) the scan answers by the same formula; full validation stays with decryption.  Batches
  *                  below min_records run on the host inside the call.  Thread-safe (one slot per call); n = 0 is fine; large n goes through in chunks.
+ *                  On the device it is records_scan_many with one key: ALEO_MI355X_SCAN_KEYS_PER_LANE (there) reaches it too, and the bytes do not depend on it.
  *   records_scan_host   the same bytes out, computed on the CPU by the calling thread; touches no device.
  *   min_records    the batch size from which records_scan takes the GPU: 64, the measured crossover against the host path on one thread (profiles/records_scan.txt: 0.88x at 2^5, 2.0x at 2^6); ALEO_MI355X_MIN_RECORDS overrides it, read per call. */
 int32_t aleo_mi355x_record_parse(const char* record1, int32_t* owner_kind, void* owner32, void* nonce32);

@@ -200,17 +200,17 @@ def test_routing_threshold_and_its_environment_override():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_scan_kernel_code_object_is_gfx950_and_has_no_scratch():
     with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, 'records.s')
-        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, os.path.join(CSRC, 'records.hip'), '-o', out],
+        out = os.path.join(d, 'records_many.s')                     # the one-account scan runs the K-account kernel at one key per lane
+        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, os.path.join(CSRC, 'records_many.hip'), '-o', out],
                        check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         asm = open(out).read()
     assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    meta = [m for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S) if 'k_records_scan' in m.group(0)]
+    meta = [m for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S) if 'k_records_scan_manyILi1E' in m.group(0)]
     assert len(meta) == 1, 'the scan kernel is not in the code object'
     field = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0].group(0)).group(1))
-    print('k_records_scan: vgpr_count %d, agpr_count %d, sgpr_count %d, private_segment_fixed_size %d' % (field('vgpr_count'), field('agpr_count'), field('sgpr_count'), field('private_segment_fixed_size')))
+    print('k_records_scan_many<1>: vgpr_count %d, agpr_count %d, sgpr_count %d, private_segment_fixed_size %d' % (field('vgpr_count'), field('agpr_count'), field('sgpr_count'), field('private_segment_fixed_size')))
     assert field('private_segment_fixed_size') == 0 and field('vgpr_spill_count') == 0
-    start = re.search(r'^_Z\w*k_records_scan\w*:', asm, flags=re.M).start()
+    start = re.search(r'^_Z\w*k_records_scan_manyILi1E\w*:', asm, flags=re.M).start()
     body = asm[start:asm.index('.Lfunc_end', start)]
     code = [l.split(';')[0].strip() for l in body.split('\n')]
     assert sum(1 for l in code if l.startswith('v_mad_u64_u32')) > 10000                                   # the arithmetic is there, inline
@@ -306,6 +306,33 @@ def test_kernel_small_behaviours(on_kernel):
     # another view key on the same records right after: neither stale digits nor a stale state
     again = records.scan(C0, NX, sets[1][2], ax); want = records.scan(C0, NX, sets[1][2], ax, host=True)
     assert again[0].tobytes() == want[0].tobytes() and again[1].tobytes() == want[1].tobytes() and again[1].tobytes() != rvk.tobytes()
+
+
+@pytest.mark.gpu
+def test_one_account_scan_through_the_many_key_flow_at_every_width(on_kernel, monkeypatch):
+    """records.scan runs scan_many_on_device with a table of one key: at ALEO_MI355X_SCAN_KEYS_PER_LANE = 2, 4, 8 that key is padded with zero entries."""
+    G = account_generator()
+    vk = 0x2468ACE | 1
+    c0s, nxs, ax, owned, where = big_batch(257, vk, 31337, G)
+    C0, NX = rows(c0s), rows(nxs)
+    hf, _ = records.scan(C0, NX, vk, ax, host=True)
+    own, bad = np.nonzero(hf == 1)[0].tolist(), np.nonzero(hf == 2)[0].tolist()
+    assert len(own) >= 3 and bad
+    order = list(range(257))
+    for src, dst in ((own[0], 0), (bad[0], 1), (own[1], 64), (own[2], 256)):      # an owned record first, a malformed nonce, an owned record in the last partial wave of 65 and of 257
+        a, b = order.index(src), dst
+        order[a], order[b] = order[b], order[a]
+    C0, NX = C0[order].copy(), NX[order].copy()
+    hf, hr = records.scan(C0, NX, vk, ax, host=True)
+    assert hf[0] == 1 and hf[1] == 2 and hf[64] == 1 and hf[256] == 1
+    for width in (None, '2', '4', '8'):
+        if width is None: monkeypatch.delenv('ALEO_MI355X_SCAN_KEYS_PER_LANE', raising=False)
+        else: monkeypatch.setenv('ALEO_MI355X_SCAN_KEYS_PER_LANE', width)
+        for n in (1, 64, 65, 257):
+            f, r = records.scan(C0[:n], NX[:n], vk, ax)
+            assert f.tobytes() == hf[:n].tobytes() and r.tobytes() == hr[:n].tobytes(), (width, n)
+            only_flags, none = records.scan(C0[:n], NX[:n], vk, ax, want_rvk=False)
+            assert none is None and only_flags.tobytes() == hf[:n].tobytes(), (width, n)
 
 
 @pytest.mark.gpu

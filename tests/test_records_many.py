@@ -103,8 +103,7 @@ def test_grouped_lane_emulated_on_the_host_matches_the_host_path(tmp_path):
 # ---- 4: the code object -----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_grouped_kernels_are_gfx950_and_have_no_scratch_at_any_width():
-    """The kernels live in a unit of their own (records_many.hip), so that records.hip's code object — one kernel, its figures asserted by
-    tests/test_records.py — is the one it was."""
+    """The kernels of records_many.hip; the figures of W = 1, which is the one-account scan's kernel too, are asserted by tests/test_records.py as well."""
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, 'records_many.s')
         subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, os.path.join(CSRC, 'records_many.hip'), '-o', out],

@@ -261,6 +261,16 @@ def test_kernel_equals_the_host_path_at_wave_and_block_edges(on_kernel, n):
 
 
 @pytest.mark.gpu
+def test_one_key_through_the_segmented_kernel_in_one_wave_launches(on_kernel):
+    """One key is one segment of the kernel that records_unspent.hip launches over several: at ALEO_MI355X_SERIAL_CHUNK=64, 129 commitments are chunks of 64, 64 and 1,
+    each one launch of one wave over one segment, the last wave holding one lane."""
+    on_kernel.setenv('ALEO_MI355X_SERIAL_CHUNK', '64')
+    cm, sk = with_edges(129, 229, {}), le32(reference_sk_sig())
+    sn, flags = check_kernel_equals_host(cm, sk)
+    assert not flags.any() and len({r.tobytes() for r in sn}) == 129
+
+
+@pytest.mark.gpu
 def test_kernel_malformed_rows_at_lane_0_at_lane_63_and_in_the_last_partial_wave(on_kernel):
     at = {0: R, 63: 2 ** 256 - 1, 64: R + 1, 297: 2 ** 256 - 1, 299: R}
     cm = with_edges(300, 7, at)

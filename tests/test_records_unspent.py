@@ -213,7 +213,7 @@ def test_new_kernels_code_objects_are_gfx950_and_have_no_scratch(tmp_path):
     asm = open(out).read()
     assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
     blocks = re.findall(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S)
-    for kernel in ('k_found_serial', 'k_spent_insert', 'k_unspent_keep', 'k_unspent_scatter'):
+    for kernel in ('k_spent_insert', 'k_unspent_keep', 'k_unspent_scatter'):      # the serial-number kernel is records_serial.hip's: tests/test_records_serial.py
         meta = [m for m in blocks if kernel in m]
         assert len(meta) == 1, '%s is not in the code object' % kernel
         get = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0]).group(1))
