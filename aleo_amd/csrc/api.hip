@@ -335,7 +335,7 @@ int32_t aleo_mi355x_varuna_prove(const aleo_mi355x_varuna_index* index, const vo
     for (size_t i = 0; i < n_instances && i < 32; ++i) if (!assignments[i]) return bad_arg("varuna_prove: null assignment");
     Slot sl; if (sl.rc) return sl.rc;
     FoundBases fb(sl.d, index->committer_key); if (fb.rc) return fb.rc;
-    return varuna_prove(sl.c, fb.pb, *index, assignments, n_instances, seed, (uint8_t*)out_proof, len);
+    return varuna_prove_batch(sl.c, fb.pb, &index, 1, assignments, &n_instances, seed, (uint8_t*)out_proof, len);
   });
 }
 
@@ -398,7 +398,7 @@ int32_t aleo_mi355x_varuna_prove_indexed(uint64_t index_handle, const void* cons
     std::shared_ptr<VarunaIndexOwner> ixk; { int32_t rci = find_varuna(sl.d, index_handle, &ixk); if (rci) return rci; }
     const aleo_mi355x_varuna_index* ix = varuna_index_view(ixk.get());
     FoundBases fb(sl.d, ix->committer_key); if (fb.rc) return fb.rc;
-    return varuna_prove(sl.c, fb.pb, *ix, assignments, n_instances, seed, (uint8_t*)out_proof, len);
+    return varuna_prove_batch(sl.c, fb.pb, &ix, 1, assignments, &n_instances, seed, (uint8_t*)out_proof, len);
   });
 }
 

@@ -177,7 +177,7 @@ struct Device {
   std::vector<SrsCacheEntry> srs_cache; uint64_t srs_clock = 0;
   std::map<uint64_t, std::shared_ptr<PinnedG2>> g2_bases;      // handles share next_handle's counter with `bases`
   std::map<uint64_t, NttTables*> ntt_tables;
-  std::map<uint64_t, std::shared_ptr<struct VarunaIndexOwner>> varuna; uint64_t next_varuna = 1;      // circuit indices (varuna.hip)
+  std::map<uint64_t, std::shared_ptr<struct VarunaIndexOwner>> varuna; uint64_t next_varuna = 1;      // circuit indices (varuna_index.hip)
   std::atomic<int> ntt_attr_mask{0};   // which NTT kernel instances had their LDS limit raised on THIS device
   Ctx slots[MAX_SLOTS];
   std::vector<std::unique_ptr<ShardWs>> shard_ws;     // grown under mu; used only by the one sharded transform in flight (sharded.hip g_ntt_sh_mu)
@@ -190,7 +190,7 @@ struct HelperSet { std::vector<Ctx*> ctx; std::vector<std::unique_lock<std::mute
 int32_t acquire_helpers(Device* d, int want, HelperSet& hs);
 
 extern thread_local MsmTiming g_last_msm;   // phase times of the calling thread's most recent MSM
-// Host-side trace of one proof (ALEO_MI355X_HOSTTRACE=1): labelled timestamps of the calling thread, printed to stderr by varuna_prove_batch — where the
+// Host-side trace of one proof (ALEO_MI355X_HOSTTRACE=1): labelled timestamps of the calling thread, printed to stderr by the prover's driver (varuna.hip) — where the
 // host spends the turn-arounds between a commitment's last kernel and the next round's first (tools/proof_timeline_full.py shows the GPU's side of the same gaps).
 // f(i) for i in [0, n) on the calling thread and up to 3 parked helper threads of the library (created on first use, never destroyed); returns when all are done.
 // For the host tails of many-result launch chains (a lockstep round's 8 x k results: ~15 us of Horner each while every other thread of the call waits at a barrier).
@@ -275,8 +275,7 @@ int32_t fr_scale_rows(Ctx* c, void* d_dst, const void* d_src, size_t n, size_t r
 int32_t fr_split_quotient(Ctx* c, void* d_hq, void* d_rq, const void* d_q, const void* d_mask, size_t n, void* host_sum_devptr, hipStream_t s);
 int32_t fr_sub_mul(Ctx* c, void* d_dst, const void* d_a, const void* d_b, const void* d_m, size_t n, hipStream_t s);
 int32_t fr_pick(Ctx* c, void* dst_devptr, const void* const* d_src, size_t count, hipStream_t s);
-// varuna.hip (jacobian_rows_to_affine104: api.hip)
-int32_t varuna_prove(Ctx* c, const PinnedBases& pb, const aleo_mi355x_varuna_index& ix, const void* const* assignments, size_t k, const uint8_t* seed32, uint8_t* out, size_t* out_len);
+// varuna.hip; the index: varuna_index.hip (jacobian_rows_to_affine104: api.hip)
 // one request of a lockstep call (varuna_prove_many): the circuits of ONE proof, its assignments, seed and output; status / error come back per request
 struct ProveRequest { std::vector<const aleo_mi355x_varuna_index*> ixs; const void* const* assignments = nullptr; const size_t* ks = nullptr; const uint8_t* seed32 = nullptr;
                       uint8_t* out = nullptr; size_t* out_len = nullptr; int32_t status = 0; std::string error; };

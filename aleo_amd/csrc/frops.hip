@@ -661,7 +661,7 @@ int32_t fr_lincomb(Ctx* c, void* d_dst, size_t n, const void* c0, const void* co
 }
 
 // dst[i] += src[i mod n_src] (n_src a power of two dividing n): multiplication of a block of n_src coefficients by 1 + X^n_src + X^(2 n_src) + ...,
-// the selector v_{H*} / v_H that puts a smaller circuit's remainder on the largest constraint domain of a proof (varuna.hip).
+// the selector v_{H*} / v_H that puts a smaller circuit's remainder on the largest constraint domain of a proof (varuna_proof.hip).
 __global__ void __launch_bounds__(256) k_fr_add_tiled(char* dst, size_t n, const char* __restrict__ src, size_t mask) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
     store_fp<Fr>(dst + i * 32, Fr::cond_sub<1>(Fr::add(load_fp<Fr>(dst + i * 32), load_fp<Fr>(src + (i & mask) * 32))));      // canonical inputs: < 2r
@@ -815,7 +815,7 @@ int32_t fr_batch_inverse(Ctx* c, void* d_inout, size_t n, hipStream_t s) {
   return scratch_release(c, s);
 }
 
-// ---- key synthesis: the integer side of the arithmetisation (varuna.hip varuna_index_build) -----------------------------------------------------
+// ---- key synthesis: the integer side of the arithmetisation (varuna_index.hip varuna_index_build) -----------------------------------------------------
 // One lane per CSR row (rows of an R1CS matrix are short; the few long linear combinations cost their lane a loop, not the launch).
 __global__ void __launch_bounds__(256) k_index_expand_rows(const uint32_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, const uint32_t* __restrict__ positions, uint32_t rows,
                                                            uint32_t* __restrict__ k_row, uint32_t* __restrict__ k_col, uint32_t* __restrict__ cpos, uint32_t* __restrict__ count_plus1) {

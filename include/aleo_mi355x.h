@@ -366,7 +366,7 @@ typedef struct {
 } aleo_mi355x_proof_parts;
 int32_t aleo_mi355x_proof_to_bytes(void* out, size_t* len, const aleo_mi355x_proof_parts* parts);
 
-/* ---- one proof in one call: the host side of Varuna::prove_batch, native (aleo_amd/csrc/varuna.hip) -------------------------------
+/* ---- one proof in one call: the host side of Varuna::prove_batch, native (aleo_amd/csrc/varuna*.hip) ------------------------------
  * Replaces the CPU work snarkVM 0.14.5 does in algorithms/src/snark/varuna/{varuna.rs, ahp/prover/round_functions} [UPSTREAM-RECALL]
  * under /root/reference/rust/src/program/execute.rs:74 and transfer.rs:99 — for one circuit with 1..32 instances, upstream's Fiat-Shamir construction (the Poseidon
  * sponge over Fq, rate 2: aleo_mi355x_fs_* below) and the committer key the caller pinned (DESIGN.md 4d lists what differs from upstream).  The index is the prover-key material of the

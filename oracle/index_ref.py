@@ -13,7 +13,7 @@ Array layouts are the device view's (include/aleo_mi355x.h aleo_mi355x_varuna_in
   k_evals   Fr, matrix after matrix (from 4·off_M): row, col, val, row_col on K_M (|K_M| values each); padding row = col = 1, val = 0
   k_polys   the same four polynomials as coefficients (inverse NTT over K_M), same layout
   k2_evals  (from 8·off_M) each polynomial's values on the subgroup of size 2|K_M|, natural order: the first |K_M| coefficients zero-padded
-            to 2|K_M| and transformed forward without a coset shift — what varuna.hip's p_ntt(..., lg + 1, 4, 0, 0) computes
+            to 2|K_M| and transformed forward without a coset shift — what varuna_index.hip's p_ntt(..., lg + 1, 4, 0, 0) computes
   vx_inv    1 / v_X(h) for h in H, natural order (h = w_H^p), and 0 on X (where v_X vanishes)
 with off_M = |K_A| + ... (the earlier matrices' domains)."""
 from __future__ import annotations

@@ -400,6 +400,53 @@ def test_unsatisfied_assignment_is_refused():
         ck.close()
 
 
+@pytest.mark.gpu
+def test_last_timing_after_a_single_proof_and_after_a_lockstep_call():
+    """aleo_mi355x_varuna_last_timing on the calling thread: a single proof leaves the time of each of the four rounds and of the openings (all
+    positive, together no more than the total: they are consecutive stretches of it; + 1 ms for rounding), a lockstep call zeros in those
+    five — its proofs' rounds interleave — and its own total."""
+    from aleo_amd import varuna
+    csr, z, c = _circuit(24, 3, 5)
+    ck = varuna.synthetic_committer_key(TAU, S_GAMMA, _max_degree(c))
+    parts = ('round1', 'round2', 'round3', 'round4', 'openings')
+    try:
+        ix = varuna.CircuitIndex(csr, 24, 3, len(z) - 3, ck)
+        zz = np.stack([synth.int_to_limbs(v, 4) for v in z])
+        varuna.prove_native(ix, zz, 105)
+        t = varuna.native_timing()
+        print('single', t)
+        assert all(t[p] > 0 for p in parts) and sum(t[p] for p in parts) <= t['total'] + 1.0
+        with varuna.NativeCircuitIndex(csr, 24, 3, len(z) - 3, ck) as nx:
+            got = varuna.prove_many_native([([nx], [[zz]], 105), ([nx], [[zz]], 106)])
+            t = varuna.native_timing()
+        print('lockstep', t)
+        assert all(isinstance(p, bytes) for p in got)
+        assert all(t[p] == 0 for p in parts) and t['total'] > 0
+    finally:
+        ck.close()
+
+
+@pytest.mark.gpu
+def test_a_refused_single_proof_leaves_the_slot_usable():
+    """A single proof that stops at the first sumcheck (the corruption of test_unsatisfied_assignment_is_refused) leaves nothing behind in the
+    driver it shares with the lockstep call — no hook, no arena, no barrier state: the next proof on the same thread is the restatement's."""
+    from aleo_amd import varuna
+    csr, z, c = _circuit(24, 3, 5)
+    D = _max_degree(c)
+    setup = V.Setup(TAU, S_GAMMA, D); idx = V.Index(c, setup)
+    want = V.prove(idx, setup, z, _rand(c, 105))[1]
+    ck = varuna.synthetic_committer_key(TAU, S_GAMMA, D)
+    try:
+        ix = varuna.CircuitIndex(csr, 24, 3, len(z) - 3, ck)
+        lim = lambda a: np.stack([synth.int_to_limbs(v, 4) for v in a])
+        bad = list(z); bad[9] = (bad[9] + 1) % V.R
+        with pytest.raises(aleo_amd.UnsatisfiedAssignment) as e: varuna.prove_native(ix, lim(bad), 105)
+        assert e.value.status == 6 and 'the assignment does not satisfy the circuit (first sumcheck: the sum over H is not zero)' in str(e.value)
+        assert varuna.prove_native(ix, lim(z), 105) == want
+    finally:
+        ck.close()
+
+
 def _golden_cases():
     g = json.load(open(os.path.join(os.path.dirname(__file__), 'golden', 'varuna_small.json')))
     return int(g['tau'], 16), int(g['s_gamma'], 16), g['cases']
