@@ -36,6 +36,9 @@ EXPORTS = [
     'aleo_mi355x_record_commitment', 'aleo_mi355x_record_checksum', 'aleo_mi355x_account_from_private_key',
     'aleo_mi355x_records_unspent_strings', 'aleo_mi355x_records_unspent_strings_host', 'aleo_mi355x_records_unspent_strings_many', 'aleo_mi355x_records_unspent_strings_many_host',
     'aleo_mi355x_found_serials', 'aleo_mi355x_found_owned',
+    'aleo_mi355x_records_commitments_found', 'aleo_mi355x_records_commitments_found_host', 'aleo_mi355x_min_commitments',
+    'aleo_mi355x_records_unspent_named', 'aleo_mi355x_records_unspent_named_host', 'aleo_mi355x_records_unspent_named_many', 'aleo_mi355x_records_unspent_named_many_host',
+    'aleo_mi355x_found_commitments',
 ]
 
 
@@ -206,9 +209,16 @@ def lib():
         'aleo_mi355x_records_unspent_strings_host': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, vp, vp, vp, sz], i32),
         'aleo_mi355x_records_unspent_strings_many': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, vp, vp, sz, vp, sz], i32),
         'aleo_mi355x_records_unspent_strings_many_host': ([ctypes.POINTER(vp), vp, vp, sz, vp, vp, vp, vp, sz, vp, sz], i32),
+        'aleo_mi355x_records_commitments_found': ([vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p], i32),
+        'aleo_mi355x_records_commitments_found_host': ([vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p], i32),
+        'aleo_mi355x_min_commitments': ([], sz),
+        'aleo_mi355x_records_unspent_named': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, vp, sz], i32),
+        'aleo_mi355x_records_unspent_named_host': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, vp, sz], i32),
+        'aleo_mi355x_records_unspent_named_many': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, sz, vp, sz], i32),
+        'aleo_mi355x_records_unspent_named_many_host': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, sz, vp, sz], i32),
         'aleo_mi355x_found_free': ([vp], None),
         **{'aleo_mi355x_found_' + name: ([vp], sz) for name in ('count', 'fields', 'unparsed', 'first_unparsed', 'owned')},
-        **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits', 'serials')},
+        **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits', 'serials', 'commitments')},
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name); f.argtypes = args; f.restype = res

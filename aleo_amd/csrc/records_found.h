@@ -5,6 +5,7 @@
 #include "records_strings.h"
 #include "records_found_host.hpp"
 #include "records_serial_lane.h"
+#include "records_commit_lane.h"
 #include <memory>
 
 namespace aleo_mi355x {
@@ -32,9 +33,11 @@ __device__ __forceinline__ void block_exclusive2(uint32_t& a, uint32_t& b, uint3
 
 // One chunk's compacted arrays on the device, all keys' one after another (key 0's records, then key 1's, each in record order): `owned` records with `nf`
 // fields; key j's are the ranks first[j] .. first[j + 1] and the fields first_f[j] .. first_f[j + 1] (K + 1 entries each).  index is chunk-relative, off has
-// owned + 1 entries.  status null: every record's is 0.  serials null: there are none.
+// owned + 1 entries.  status null: every record's is 0.  serials, commitments null: there are none.  text / soff: the chunk's strings on the device, record i of the
+// chunk the characters soff[i] .. soff[i + 1].
 struct FoundChunk {
   char* fields = nullptr; uint32_t* index = nullptr; int8_t* kind = nullptr; char* rvk = nullptr; uint32_t* off = nullptr; uint64_t* mc = nullptr; uint8_t* status = nullptr; char* serials = nullptr;
+  char* commitments = nullptr; const char* text = nullptr; const uint32_t* soff = nullptr;
   size_t at = 0, owned = 0, nf = 0;                                        // at: the chunk's first record among the call's strings
   std::vector<uint32_t> first, first_f;
 };
@@ -65,5 +68,18 @@ inline SerialArgs serial_args_of(const ScanArgs& a) {
 }
 // k_records_serial over every segment, key j's digits at dkeys[j] in device memory: launches of at most ALEO_MI355X_SERIAL_CHUNK lanes (read per call), which may span key boundaries
 int32_t launch_records_serial(hipStream_t s, char* dsn, uint8_t* dflags, const char* dcm, const uint32_t* dK, const SerialArgs* dkeys, const UnspentSegs& seg);
+
+// records_commit.hip: what a call's (program id, record name) comes to — refused with the reference's two texts — and the commitments of owned records
+struct CommitCall { std::vector<uint8_t> name_bits; CommitArgs args; };
+int32_t commit_call(CommitCall& cc, const char* program_id, const char* record_name);
+// one record on the host, as aleo_mi355x_record_commitment computes it: the flag (0, or 4 with a row of zeros); plain: its n_fields decrypted fields
+uint8_t commit_one_host(uint8_t* out32, const char* record1, size_t chars, const uint8_t* plain, size_t n_fields, const CommitCall& cc);
+// What commit_rows_of_chunk keeps on the host; the stage that owns it outlives the call's last synchronisation.
+struct CommitScratch { std::vector<uint32_t> index, off; std::vector<int8_t> kind; std::vector<uint8_t> status, fields, cm, flags; };
+// The rows (dcm: owned x 32 B) and flags (dflags: owned) of the chunk's records behind k_found_microcredits, on the device when the stream has run: from
+// k_records_commit, or from the calling thread below aleo_mi355x_min_commitments() records and for the records the lane routes (text / offsets: the call's strings).
+// want_host: H.cm holds the rows on return.  droute: one word of device scratch.
+int32_t commit_rows_of_chunk(Ctx* c, hipStream_t s, const FoundChunk& ch, const CommitCall& cc, const char* text, const uint64_t* offsets, char* dcm, uint8_t* dflags, uint32_t* droute,
+                             CommitScratch& H, bool want_host);
 
 }  // namespace aleo_mi355x

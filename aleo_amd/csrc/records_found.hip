@@ -187,10 +187,11 @@ struct FoundCall {
 };
 
 // `to` sized for records / fields in all, what it held before included
-static void found_size(Found& to, size_t records, size_t fields, bool serials) {
+static void found_size(Found& to, size_t records, size_t fields, bool serials, bool commitments = false) {
   to.index.resize(records); to.offsets.resize(records + 1); to.kind.resize(records); to.rvk.resize(records * 32); to.status.resize(records);
   to.microcredits.resize(records); to.plain.resize(fields * 32);
   if (serials) to.serials.resize(records * 32);
+  if (commitments) to.commitments.resize(records * 32);
 }
 
 // Chunk ck up to the one wait before the gather: parse, scan, resolve, the counting walk and its sums; the unparsed strings into every result; into `ch` the totals
@@ -241,7 +242,7 @@ static int32_t found_gather_decrypt(const FoundCall& f, size_t m, FoundChunk& ch
   char* cb = f.c->out_stage.as<char>();
   uint32_t* dmc_at = (uint32_t*)(cb + o_mc_at); uint32_t* dmc_n = (uint32_t*)(cb + o_mc_n); uint8_t* dcpre = (uint8_t*)(cb + o_cpre); uint8_t* ddec = (uint8_t*)(cb + o_dec);
   ch.fields = cb + o_fields; ch.index = (uint32_t*)(cb + o_index); ch.kind = (int8_t*)(cb + o_kind); ch.rvk = cb + o_crvk; ch.off = (uint32_t*)(cb + o_off); ch.mc = (uint64_t*)(cb + o_mc);
-  ch.status = (uint8_t*)(cb + o_status);
+  ch.status = (uint8_t*)(cb + o_status); ch.text = f.dtext; ch.soff = f.dsoff;
   hipLaunchKernelGGL(k_found_gather, dim3((uint32_t)((m + FOUND_BLOCK - 1) / FOUND_BLOCK), (uint32_t)f.K), dim3(FOUND_BLOCK), 0, s, ch.fields, ch.index, ch.kind, ch.rvk, ch.off, dcpre, ch.mc, dmc_at,
                      dmc_n, (const uint32_t*)f.dcnt, (const uint32_t*)f.dpos, (const uint8_t*)f.dpre, (const uint32_t*)f.dblk, (const uint8_t*)f.dfl, (const int8_t*)f.dkinds, (const char*)f.drvk, (const char*)f.dtext, (const uint32_t*)f.dsoff,
                      (uint32_t)m, (uint32_t)owned, (uint32_t)nf);
@@ -271,7 +272,7 @@ static int32_t found_gather_decrypt(const FoundCall& f, size_t m, FoundChunk& ch
 static int32_t found_download(const FoundCall& f, const FoundChunk& ch, Found& to, size_t put, size_t put_f, std::vector<std::unique_ptr<Found>>& R) {
   const size_t K = f.K, at = ch.at, got = ch.owned, got_f = ch.nf;
   hipStream_t s = f.s;
-  if (f.stage) found_size(to, put + got, put_f + got_f, true);
+  if (f.stage) found_size(to, put + got, put_f + got_f, true, ch.commitments != nullptr);
   uint32_t* h_off = to.offsets.data() + put;                 // chunk-relative until a base is added below
   if (f.stage) HIPCHK(hipMemcpyAsync(h_off, ch.off, (got + 1) * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(to.index.data() + put, ch.index, got * 4, hipMemcpyDeviceToHost, s));
@@ -280,6 +281,7 @@ static int32_t found_download(const FoundCall& f, const FoundChunk& ch, Found& t
   if (ch.status) HIPCHK(hipMemcpyAsync(to.status.data() + put, ch.status, got, hipMemcpyDeviceToHost, s));      // else zeros, as the resize left them
   HIPCHK(hipMemcpyAsync(to.microcredits.data() + put, ch.mc, got * 8, hipMemcpyDeviceToHost, s));
   if (ch.serials) HIPCHK(hipMemcpyAsync(to.serials.data() + put * 32, ch.serials, got * 32, hipMemcpyDeviceToHost, s));
+  if (ch.commitments) HIPCHK(hipMemcpyAsync(to.commitments.data() + put * 32, ch.commitments, got * 32, hipMemcpyDeviceToHost, s));
   if (got_f) HIPCHK(hipMemcpyAsync(to.plain.data() + put_f * 32, ch.fields, got_f * 32, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers
   if (K == 1) {
@@ -298,6 +300,7 @@ static int32_t found_download(const FoundCall& f, const FoundChunk& ch, Found& t
     r.microcredits.insert(r.microcredits.end(), to.microcredits.begin() + a, to.microcredits.begin() + e);
     r.plain.insert(r.plain.end(), to.plain.begin() + fa * 32, to.plain.begin() + fe * 32);
     if (f.stage) r.serials.insert(r.serials.end(), to.serials.begin() + a * 32, to.serials.begin() + e * 32);
+    if (ch.commitments) r.commitments.insert(r.commitments.end(), to.commitments.begin() + a * 32, to.commitments.begin() + e * 32);
   }
   return ALEO_MI355X_OK;
 }

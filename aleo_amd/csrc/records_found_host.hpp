@@ -20,6 +20,9 @@ struct aleo_mi355x_found {
   // records_unspent_strings[_many] (records_unspent.hip): the result holds the records that are left of `owned`, and their serial numbers
   bool filtered = false; size_t owned = 0;
   std::vector<uint8_t> serials;
+  // records_unspent_named[_many]: their commitments as well, which the call computed itself
+  bool named = false;
+  std::vector<uint8_t> commitments;
 };
 
 namespace aleo_mi355x {

@@ -19,6 +19,9 @@
 //   — one read of the totals and boundaries; the kept arrays come down as decrypt_strings_many's would, and are split per key by the same code —
 // S goes up once per call: its rows, and an open-addressing table over them built by k_spent_insert (one row per lane, atomicCAS).  n_spent = 0: neither.
 // The host path is found_on_host per key, serial_one_host per owned record and a sorted vector of S's rows; it shares no code with the above.
+// unspent_named[_many] are the same flow without commitments from outside: the stage computes them (records_commit.hip commit_rows_of_chunk: k_records_commit over the
+// chunk's owned records, or the calling thread below aleo_mi355x_min_commitments() of them) where the other road gathers and uploads the caller's rows; there is then no
+// index download and no wait behind the gather, k_unspent_keep reads the commitment flags too, and k_unspent_scatter compacts the rows, which come down with the rest.
 #include "records_found.h"
 #include "records_spent_lane.h"
 #include "serial_host.hpp"
@@ -37,14 +40,15 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_spent_insert(uint32_t* __restri
 }
 
 // cnt / pos: the exclusive sums of the kept field counts and of the keep bits WITHIN the block; blk: [fields | kept][block], the block totals.  cap 0: no set.
+// cm_flags (unspent_named; else null): the flags of the commitments the call computed itself.
 __global__ void __launch_bounds__(FOUND_BLOCK) k_unspent_keep(uint32_t* __restrict__ cnt, uint32_t* __restrict__ pos, uint8_t* __restrict__ keep, uint32_t* __restrict__ blk,
-                                                             const uint8_t* __restrict__ status, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ sn,
+                                                             const uint8_t* __restrict__ status, const uint8_t* __restrict__ flags, const uint8_t* __restrict__ cm_flags, const uint32_t* __restrict__ sn,
                                                              const uint32_t* __restrict__ off, const uint32_t* __restrict__ table, uint32_t cap,
                                                              const uint32_t* __restrict__ spent, uint32_t n_owned) {
   __shared__ uint32_t wave_tot[2][FOUND_BLOCK / 64];
   const uint32_t j = blockIdx.x * FOUND_BLOCK + threadIdx.x;
   const bool live = j < n_owned;
-  bool kept = live && status[j] == FOUND_OK && flags[j] == 0;
+  bool kept = live && status[j] == FOUND_OK && flags[j] == 0 && (!cm_flags || cm_flags[j] == 0);
   if (kept && cap) {
     const uint4 l = *(const uint4*)(sn + (size_t)j * 8), h = *(const uint4*)(sn + (size_t)j * 8 + 4);
     const uint32_t mine[8] = {l.x, l.y, l.z, l.w, h.x, h.y, h.z, h.w};
@@ -59,10 +63,10 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_unspent_keep(uint32_t* __restri
 // Behind k_found_offsets over blk (stat[0]: the kept pairs, stat[1]: their fields).  A kept pair's rank among the kept is blk[kept row][block] + pos, its first
 // field blk[fields row][block] + cnt.  stat[8 + j] / stat[8 + 65 + j], j <= n_keys: the kept pairs / fields before key j's segment (j = n_keys: all of them).
 __global__ void __launch_bounds__(FOUND_BLOCK) k_unspent_scatter(char* __restrict__ o_fields, uint32_t* __restrict__ o_index, int8_t* __restrict__ o_kind, char* __restrict__ o_rvk,
-                                                                uint32_t* __restrict__ o_off, uint64_t* __restrict__ o_mc, char* __restrict__ o_sn, uint32_t* __restrict__ stat,
+                                                                uint32_t* __restrict__ o_off, uint64_t* __restrict__ o_mc, char* __restrict__ o_sn, char* __restrict__ o_cm, uint32_t* __restrict__ stat,
                                                                 const char* __restrict__ fields, const uint32_t* __restrict__ index, const int8_t* __restrict__ kind,
                                                                 const char* __restrict__ rvk, const uint32_t* __restrict__ off, const uint64_t* __restrict__ mc,
-                                                                const char* __restrict__ sn, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ pos,
+                                                                const char* __restrict__ sn, const char* __restrict__ cm, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ pos,
                                                                 const uint8_t* __restrict__ keep, const uint32_t* __restrict__ blk, UnspentSegs seg, uint32_t n_owned) {
   const uint32_t nb = gridDim.x, j = blockIdx.x * FOUND_BLOCK + threadIdx.x;
   const uint32_t n_kept = stat[0], n_fields = stat[1];
@@ -80,6 +84,7 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_unspent_scatter(char* __restric
   ro[0] = r[0]; ro[1] = r[1];
   const uint4* s = (const uint4*)(sn + (size_t)j * 32); uint4* so = (uint4*)(o_sn + (size_t)q * 32);
   so[0] = s[0]; so[1] = s[1];
+  if (o_cm) { const uint4* t = (const uint4*)(cm + (size_t)j * 32); uint4* to = (uint4*)(o_cm + (size_t)q * 32); to[0] = t[0]; to[1] = t[1]; }      // unspent_named
   for (uint32_t k = 0; k < m; ++k) {
     const uint4* p = (const uint4*)(fields + (size_t)(first + k) * 32); uint4* po = (uint4*)(o_fields + (size_t)(f + k) * 32);
     po[0] = p[0]; po[1] = p[1];
@@ -94,6 +99,8 @@ struct UnspentStage : FoundStage {
   const uint32_t* dK = nullptr; const SerialArgs* dkeys = nullptr; const uint32_t* dspent = nullptr; const uint32_t* dtable = nullptr; uint32_t cap = 0;
   std::vector<SerialArgs> table;                               // outlives the call's last synchronisation
   std::vector<uint32_t> h_index; std::vector<uint8_t> h_cm, h_sn, h_fl;
+  // unspent_named: no commitments come in; the stage computes them from the call's strings (records_commit.hip) in front of the serial numbers
+  const CommitCall* named = nullptr; const char* text = nullptr; const uint64_t* offsets = nullptr; CommitScratch H;
   UnspentStage(const uint8_t* cm, const UnspentKeys& k, const uint8_t* sp, size_t ns) : commitments(cm), keys(k), spent(sp), n_spent(ns) {}
 
   // once per call: the lane's tables, the keys' digits, and S with its table
@@ -121,6 +128,7 @@ struct UnspentStage : FoundStage {
 
   // the owned records' indices come down now: the host gathers their commitments while the decryption runs
   int32_t gathered(Ctx*, hipStream_t s, const FoundChunk& ch) override {
+    if (named) return ALEO_MI355X_OK;                          // nothing to gather: no wait
     h_index.resize(ch.owned);
     HIPCHK(hipMemcpyAsync(h_index.data(), ch.index, ch.owned * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -130,21 +138,27 @@ struct UnspentStage : FoundStage {
   int32_t filter(Ctx* c, hipStream_t s, FoundChunk& ch) override {
     const size_t K = keys.serial.size(), owned = ch.owned, nf = ch.nf;
     const uint32_t nb = (uint32_t)((owned + FOUND_BLOCK - 1) / FOUND_BLOCK);
-    h_cm.resize(owned * 32);
-    for (size_t q = 0; q < owned; ++q) std::memcpy(h_cm.data() + 32 * q, commitments + 32 * (ch.at + h_index[q]), 32);
+    const bool host_serials = owned < aleo_mi355x_min_serials();      // few pairs: the host's serial numbers, the same bytes
+    if (!named) {
+      h_cm.resize(owned * 32);
+      for (size_t q = 0; q < owned; ++q) std::memcpy(h_cm.data() + 32 * q, commitments + 32 * (ch.at + h_index[q]), 32);
+    }
     UnspentSegs seg{}; seg.n_keys = (uint32_t)K;
     for (size_t j = 0; j <= K; ++j) seg.rank0[j] = ch.first[j];
     for (size_t j = 0; j < K; ++j) seg.wave0[j + 1] = seg.wave0[j] + (ch.first[j + 1] - ch.first[j] + 63) / 64;
     const size_t stat_words = 8 + 2 * (SCAN_MANY_KEYS + 1);
     Carve cv;
-    const size_t o_cm = cv.part(owned * 32), o_sn = cv.part(owned * 32), o_fl = cv.part(owned), o_keep = cv.part(owned), o_cnt = cv.part(owned * 4), o_pos = cv.part(owned * 4), o_blk = cv.part((size_t)2 * nb * 4),
+    const size_t o_cm = cv.part(owned * 32), o_cf = cv.part(owned), o_route = cv.part(4), k_cm = cv.part(owned * 32), o_sn = cv.part(owned * 32), o_fl = cv.part(owned), o_keep = cv.part(owned), o_cnt = cv.part(owned * 4), o_pos = cv.part(owned * 4), o_blk = cv.part((size_t)2 * nb * 4),
                  o_stat = cv.part(stat_words * 4), k_fields = cv.part(nf * 32), k_index = cv.part(owned * 4), k_off = cv.part((owned + 1) * 4), k_mc = cv.part(owned * 8), k_rvk = cv.part(owned * 32),
                  k_kind = cv.part(owned), k_sn = cv.part(owned * 32);
     if (int32_t rc = c->unspent_ws.reserve(cv.total)) return rc;
     char* b = c->unspent_ws.as<char>();
     char* dsn = b + o_sn; uint8_t* dfl = (uint8_t*)(b + o_fl); uint8_t* dkeep = (uint8_t*)(b + o_keep);
     uint32_t* dcnt = (uint32_t*)(b + o_cnt); uint32_t* dpos = (uint32_t*)(b + o_pos); uint32_t* dblk = (uint32_t*)(b + o_blk); uint32_t* dstat = (uint32_t*)(b + o_stat);
-    if (owned < aleo_mi355x_min_serials()) {                   // few pairs: the host's serial numbers, the same bytes
+    const uint8_t* dcf = named ? (const uint8_t*)(b + o_cf) : nullptr;
+    if (named) if (int32_t rc = commit_rows_of_chunk(c, s, ch, *named, text, offsets, b + o_cm, (uint8_t*)(b + o_cf), (uint32_t*)(b + o_route), H, host_serials)) return rc;
+    const std::vector<uint8_t>& h_cm = named ? H.cm : this->h_cm;
+    if (host_serials) {
       const serial::SerialTables& T = serial::serial_tables();
       h_sn.resize(owned * 32); h_fl.resize(owned);
       for (size_t j = 0; j < K; ++j)
@@ -152,19 +166,19 @@ struct UnspentStage : FoundStage {
       HIPCHK(hipMemcpyAsync(dsn, h_sn.data(), owned * 32, hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(dfl, h_fl.data(), owned, hipMemcpyHostToDevice, s));
     } else {
-      HIPCHK(hipMemcpyAsync(b + o_cm, h_cm.data(), owned * 32, hipMemcpyHostToDevice, s));
+      if (!named) HIPCHK(hipMemcpyAsync(b + o_cm, h_cm.data(), owned * 32, hipMemcpyHostToDevice, s));
       if (int32_t rc = launch_records_serial(s, dsn, dfl, b + o_cm, dK, dkeys, seg)) return rc;
     }
-    hipLaunchKernelGGL(k_unspent_keep, dim3(nb), dim3(FOUND_BLOCK), 0, s, dcnt, dpos, dkeep, dblk, (const uint8_t*)ch.status, (const uint8_t*)dfl, (const uint32_t*)dsn, (const uint32_t*)ch.off,
+    hipLaunchKernelGGL(k_unspent_keep, dim3(nb), dim3(FOUND_BLOCK), 0, s, dcnt, dpos, dkeep, dblk, (const uint8_t*)ch.status, (const uint8_t*)dfl, dcf, (const uint32_t*)dsn, (const uint32_t*)ch.off,
                        dtable, cap, dspent, (uint32_t)owned);
     HIPCHK(hipGetLastError());
     launch_found_offsets(s, dblk, dstat, nb, nb);
     HIPCHK(hipGetLastError());
     FoundChunk kept = ch;
     kept.fields = b + k_fields; kept.index = (uint32_t*)(b + k_index); kept.off = (uint32_t*)(b + k_off); kept.mc = (uint64_t*)(b + k_mc); kept.rvk = b + k_rvk; kept.kind = (int8_t*)(b + k_kind);
-    kept.serials = b + k_sn; kept.status = nullptr;
-    hipLaunchKernelGGL(k_unspent_scatter, dim3(nb), dim3(FOUND_BLOCK), 0, s, kept.fields, kept.index, kept.kind, kept.rvk, kept.off, kept.mc, kept.serials, dstat, (const char*)ch.fields,
-                       (const uint32_t*)ch.index, (const int8_t*)ch.kind, (const char*)ch.rvk, (const uint32_t*)ch.off, (const uint64_t*)ch.mc, (const char*)dsn, (const uint32_t*)dcnt,
+    kept.serials = b + k_sn; kept.status = nullptr; kept.commitments = named ? b + k_cm : nullptr;
+    hipLaunchKernelGGL(k_unspent_scatter, dim3(nb), dim3(FOUND_BLOCK), 0, s, kept.fields, kept.index, kept.kind, kept.rvk, kept.off, kept.mc, kept.serials, kept.commitments, dstat, (const char*)ch.fields,
+                       (const uint32_t*)ch.index, (const int8_t*)ch.kind, (const char*)ch.rvk, (const uint32_t*)ch.off, (const uint64_t*)ch.mc, (const char*)dsn, (const char*)(b + o_cm), (const uint32_t*)dcnt,
                        (const uint32_t*)dpos, (const uint8_t*)dkeep, (const uint32_t*)dblk, seg, (uint32_t)owned);
     HIPCHK(hipGetLastError());
     uint32_t* stat = (uint32_t*)((char*)c->h_pinned + 4096);  // behind the flow's own words; begin() made the room
@@ -180,30 +194,37 @@ struct UnspentStage : FoundStage {
 // ---- the host path ------------------------------------------------------------------------------------------------------------------------------------
 using Row32 = std::array<uint8_t, 32>;
 
-static int32_t unspent_on_host(Found& R, const char* text, const uint64_t* offsets, size_t n, const uint8_t* commitments, const UnspentKeys& k, size_t j, const std::vector<Row32>& sorted_spent) {
+// named (unspent_named; else null): the commitment of an owned record is computed here, and a record whose commitment is refused is dropped
+static int32_t unspent_on_host(Found& R, const char* text, const uint64_t* offsets, size_t n, const uint8_t* commitments, const UnspentKeys& k, size_t j, const std::vector<Row32>& sorted_spent,
+                               const CommitCall* named) {
   Found F;
   if (int32_t rc = found_on_host(F, text, offsets, n, k.scan.args[j], k.scan.addr[j])) return rc;
   const serial::SerialTables& T = serial::serial_tables();
   R.unparsed = F.unparsed; R.first_unparsed = F.first_unparsed; R.owned = F.index.size();
   for (size_t q = 0; q < F.index.size(); ++q) {
-    Row32 sn;
-    const uint8_t flag = serial::serial_one_host(sn.data(), commitments + 32 * (size_t)F.index[q], k.serial[j], T);
+    Row32 sn, cm;
+    if (named) {
+      const size_t i = F.index[q];
+      if (F.status[q] != FOUND_OK || commit_one_host(cm.data(), text + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), F.plain.data() + 32 * (size_t)F.offsets[q], F.offsets[q + 1] - F.offsets[q], *named)) continue;
+    } else std::memcpy(cm.data(), commitments + 32 * (size_t)F.index[q], 32);
+    const uint8_t flag = serial::serial_one_host(sn.data(), cm.data(), k.serial[j], T);
     if (F.status[q] != FOUND_OK || flag != 0 || std::binary_search(sorted_spent.begin(), sorted_spent.end(), sn)) continue;
     R.index.push_back(F.index[q]); R.kind.push_back(F.kind[q]); R.status.push_back(0); R.microcredits.push_back(F.microcredits[q]);
     R.rvk.insert(R.rvk.end(), F.rvk.begin() + 32 * q, F.rvk.begin() + 32 * (q + 1));
     R.plain.insert(R.plain.end(), F.plain.begin() + 32 * (size_t)F.offsets[q], F.plain.begin() + 32 * (size_t)F.offsets[q + 1]);
     R.offsets.push_back(R.offsets.back() + (F.offsets[q + 1] - F.offsets[q]));
     R.serials.insert(R.serials.end(), sn.begin(), sn.end());
+    if (named) R.commitments.insert(R.commitments.end(), cm.begin(), cm.end());
   }
   return ALEO_MI355X_OK;
 }
 
 static int32_t unspent_strings_many(Found** out, const char* text, const uint64_t* offsets, size_t n, const void* commitments32, const void* sk_sigs32, const void* view_keys32,
-                                    const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent, bool may_route) {
+                                    const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent, bool may_route, const CommitCall* named = nullptr) {
   if (!out) return bad_arg("records_unspent_strings: null result pointer");
   for (size_t j = 0; j < n_keys; ++j) out[j] = nullptr;
   UnspentKeys k; if (int32_t rc = many_keys(k.scan, view_keys32, address_xs32, n_keys)) return rc;
-  if (!sk_sigs32 || !commitments32) return bad_arg("records_unspent_strings: null buffer");
+  if (!sk_sigs32 || (!commitments32 && !named)) return bad_arg("records_unspent_strings: null buffer");
   k.serial.resize(n_keys);
   for (size_t j = 0; j < n_keys; ++j)
     if (!serial::serial_key(k.serial[j], (const uint8_t*)sk_sigs32 + 32 * j)) {
@@ -215,16 +236,17 @@ static int32_t unspent_strings_many(Found** out, const char* text, const uint64_
   if (n_spent && !spent32) return bad_arg("records_unspent_strings: null spent set with n_spent > 0");
   if (n_spent > SPENT_MAX_ROWS) return bad_arg("records_unspent_strings: more than 2^30 spent serial numbers");
   std::vector<std::unique_ptr<Found>> R(n_keys);
-  for (auto& r : R) { r.reset(new Found); r->filtered = true; r->serials.reserve(32); }      // serials.data() is not null, whatever is kept
+  for (auto& r : R) { r.reset(new Found); r->filtered = true; r->serials.reserve(32); r->named = named != nullptr; r->commitments.reserve(32); }      // serials.data() is not null, whatever is kept
   int32_t rc = ALEO_MI355X_OK;
   if (!may_route || n * n_keys < aleo_mi355x_min_records() || n == 0) {
     std::vector<Row32> sorted_spent(n_spent);
     if (n_spent) std::memcpy(sorted_spent.data(), spent32, n_spent * 32);
     std::sort(sorted_spent.begin(), sorted_spent.end());
-    for (size_t j = 0; j < n_keys && !rc; ++j) rc = unspent_on_host(*R[j], text, offsets, n, (const uint8_t*)commitments32, k, j, sorted_spent);
+    for (size_t j = 0; j < n_keys && !rc; ++j) rc = unspent_on_host(*R[j], text, offsets, n, (const uint8_t*)commitments32, k, j, sorted_spent, named);
   } else {
     Slot sl; if (sl.rc) return sl.rc;
     UnspentStage stage((const uint8_t*)commitments32, k, (const uint8_t*)spent32, n_spent);
+    stage.named = named; stage.text = text; stage.offsets = offsets;
     rc = stage.begin(sl.c, sl.c->stream);
     if (!rc) rc = found_many_on_device(sl.c, R, text, offsets, n, k.scan, &stage);
     if (rc) (void)hipStreamSynchronize(sl.c->stream);        // the stage's host buffers may still be on their way up
@@ -232,6 +254,15 @@ static int32_t unspent_strings_many(Found** out, const char* text, const uint64_
   if (rc) return rc;
   for (size_t j = 0; j < n_keys; ++j) out[j] = R[j].release();
   return ALEO_MI355X_OK;
+}
+
+// unspent_named[_many]: the call above without commitments — every owned record's is computed from its string and its decrypted fields under (program id, record name)
+static int32_t unspent_named_many(Found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sigs32,
+                                  const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent, bool may_route) {
+  if (!out) return bad_arg("records_unspent_named: null result pointer");
+  for (size_t j = 0; j < n_keys; ++j) out[j] = nullptr;
+  CommitCall cc; if (int32_t rc = commit_call(cc, program_id, record_name)) return rc;
+  return unspent_strings_many(out, text, offsets, n, nullptr, sk_sigs32, view_keys32, address_xs32, n_keys, spent32, n_spent, may_route, &cc);
 }
 
 }  // namespace aleo_mi355x
@@ -256,6 +287,23 @@ int32_t aleo_mi355x_records_unspent_strings_host(aleo_mi355x_found** out, const 
                                                  const void* view_key32, const void* address_x32, const void* spent32, size_t n_spent) {
   return guarded([&] { return unspent_strings_many(out, text, offsets, n, commitments32, sk_sig32, view_key32, address_x32, 1, spent32, n_spent, false); });
 }
+int32_t aleo_mi355x_records_unspent_named_many(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name,
+                                               const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent) {
+  return guarded([&] { return unspent_named_many(out, text, offsets, n, program_id, record_name, sk_sigs32, view_keys32, address_xs32, n_keys, spent32, n_spent, true); });
+}
+int32_t aleo_mi355x_records_unspent_named_many_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name,
+                                                    const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent) {
+  return guarded([&] { return unspent_named_many(out, text, offsets, n, program_id, record_name, sk_sigs32, view_keys32, address_xs32, n_keys, spent32, n_spent, false); });
+}
+int32_t aleo_mi355x_records_unspent_named(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sig32,
+                                          const void* view_key32, const void* address_x32, const void* spent32, size_t n_spent) {
+  return guarded([&] { return unspent_named_many(out, text, offsets, n, program_id, record_name, sk_sig32, view_key32, address_x32, 1, spent32, n_spent, true); });
+}
+int32_t aleo_mi355x_records_unspent_named_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sig32,
+                                               const void* view_key32, const void* address_x32, const void* spent32, size_t n_spent) {
+  return guarded([&] { return unspent_named_many(out, text, offsets, n, program_id, record_name, sk_sig32, view_key32, address_x32, 1, spent32, n_spent, false); });
+}
+const uint8_t* aleo_mi355x_found_commitments(const aleo_mi355x_found* f) { return f && f->named ? f->commitments.data() : nullptr; }
 const uint8_t* aleo_mi355x_found_serials(const aleo_mi355x_found* f) { return f && f->filtered ? f->serials.data() : nullptr; }
 size_t aleo_mi355x_found_owned(const aleo_mi355x_found* f) { return !f ? 0 : f->filtered ? f->owned : f->index.size(); }
 

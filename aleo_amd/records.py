@@ -18,7 +18,7 @@ What the reference needs before it can use an owned record — its serial number
 RecordPlaintext.serialNumberString of the wasm) — is serial_numbers, found_serial_numbers and unspent here (aleo_mi355x_records_serial_numbers,
 aleo_mi355x_found_serial_numbers: csrc/records_serial.hip), with record_commitment, record_checksum and Account.from_private_key on the host beside them."""
 from __future__ import annotations
-import ctypes
+import ctypes, weakref
 import numpy as np
 from ._lib import lib, check, AleoMi355xError, NotOwner      # noqa: F401
 from . import wire
@@ -301,12 +301,14 @@ class FoundRecords:
     owner, 1 private), rvk (uint8[c, 32]), offsets (uint32[c + 1]) into plain (uint8[fields, 32]: the decrypted private fields in randomizer order), status
     (uint8[c]: 0 decrypted, 2 malformed, 4 the structure is refused) and microcredits (uint64[c]); unparsed / first_unparsed: the strings that do not parse.
     From unspent_strings[_many] the c records are those left of the `owned` the account owns, and serials (uint8[c, 32]) their serial numbers; from any other
-    call serials is None and owned is c."""
+    call serials is None and owned is c.  From unspent_named[_many] commitments (uint8[c, 32]) are the kept records' commitments as well; else None.
+    A result made with keep=True also holds the library's own copy (for found_commitments), released with the object."""
 
-    def __init__(self, index, kind, rvk, offsets, plain, status, microcredits, unparsed: int, first_unparsed: int, serials=None, owned=None):
+    def __init__(self, index, kind, rvk, offsets, plain, status, microcredits, unparsed: int, first_unparsed: int, serials=None, owned=None, commitments=None):
         self.index, self.kind, self.rvk, self.offsets, self.plain, self.status, self.microcredits = index, kind, rvk, offsets, plain, status, microcredits
         self.unparsed, self.first_unparsed = unparsed, first_unparsed
-        self.serials, self.owned = serials, len(index) if owned is None else owned
+        self.serials, self.owned, self.commitments = serials, len(index) if owned is None else owned, commitments
+        self._native = None
 
     def __len__(self): return len(self.index)
 
@@ -317,7 +319,7 @@ class FoundRecords:
     def arrays(self): return (self.index, self.kind, self.rvk, self.offsets, self.plain, self.status, self.microcredits)
 
 
-def decrypt_strings(batch, view_key, address, host: bool = False) -> FoundRecords:
+def decrypt_strings(batch, view_key, address, host: bool = False, keep: bool = False) -> FoundRecords:
     """The records one account owns among a RecordBatch (or a sequence of strings), decrypted, in one call (aleo_mi355x_records_decrypt_strings / _strings_host):
     the scan, the owned records' private fields, their decryption and their microcredits, all on the device; only the owned records come back.  A string that
     does not parse is counted (unparsed, first_unparsed), not raised."""
@@ -327,22 +329,27 @@ def decrypt_strings(batch, view_key, address, host: bool = False) -> FoundRecord
     L = lib(); out = ctypes.c_void_p()
     f = L.aleo_mi355x_records_decrypt_strings_host if host else L.aleo_mi355x_records_decrypt_strings
     check(f(ctypes.byref(out), _text_p(b), _p(b.offsets), len(b), _p(vk), _p(ax)), 'records_decrypt_strings')
-    return _found_of(L, out)
+    return _found_of(L, out, keep)
 
 
-def _found_of(L, out) -> FoundRecords:
-    """The numpy copies of a result of the library, which is released."""
+def _found_of(L, out, keep: bool = False) -> FoundRecords:
+    """The numpy copies of a result of the library, which is released — with `keep`, when the FoundRecords is."""
+    found = None
     try:
         c, nf = int(L.aleo_mi355x_found_count(out)), int(L.aleo_mi355x_found_fields(out))
         def copy(name, dtype, count, shape):
             size = count * np.dtype(dtype).itemsize
             return np.frombuffer(ctypes.string_at(getattr(L, 'aleo_mi355x_found_' + name)(out), size) if size else b'', dtype=dtype).reshape(shape).copy()
-        return FoundRecords(copy('index', np.uint32, c, (c,)), copy('kind', np.int8, c, (c,)), copy('rvk', np.uint8, 32 * c, (c, 32)), copy('offsets', np.uint32, c + 1, (c + 1,)),
+        found = FoundRecords(copy('index', np.uint32, c, (c,)), copy('kind', np.int8, c, (c,)), copy('rvk', np.uint8, 32 * c, (c, 32)), copy('offsets', np.uint32, c + 1, (c + 1,)),
                             copy('plain', np.uint8, 32 * nf, (nf, 32)), copy('status', np.uint8, c, (c,)), copy('microcredits', np.uint64, c, (c,)),
-                            int(L.aleo_mi355x_found_unparsed(out)), int(L.aleo_mi355x_found_first_unparsed(out)),
-                            copy('serials', np.uint8, 32 * c, (c, 32)) if L.aleo_mi355x_found_serials(out) else None, int(L.aleo_mi355x_found_owned(out)))
+                             int(L.aleo_mi355x_found_unparsed(out)), int(L.aleo_mi355x_found_first_unparsed(out)),
+                             copy('serials', np.uint8, 32 * c, (c, 32)) if L.aleo_mi355x_found_serials(out) else None, int(L.aleo_mi355x_found_owned(out)),
+                             copy('commitments', np.uint8, 32 * c, (c, 32)) if L.aleo_mi355x_found_commitments(out) else None)
+        return found
     finally:
-        L.aleo_mi355x_found_free(out)
+        if keep and found is not None:
+            found._native = out; weakref.finalize(found, L.aleo_mi355x_found_free, out)
+        else: L.aleo_mi355x_found_free(out)
 
 
 def decrypt_strings_many(batch, view_keys, addresses, host: bool = False) -> list:
@@ -641,3 +648,48 @@ def unspent_strings_many(batch, commitments, accounts, spent=(), host: bool = Fa
 def unspent_strings(batch, commitments, account, spent=(), host: bool = False) -> FoundRecords:
     """unspent_strings_many for one account (an Account or a private key string): aleo_mi355x_records_unspent_strings, that call with one key."""
     return unspent_strings_many(batch, commitments, [account], spent, host=host)[0]
+
+
+def found_commitments(batch, found: FoundRecords, program_id: str, record_name: str, host: bool = False):
+    """The commitments (uint8[c, 32]) and flags (uint8[c]: 0 computed; 4 refused as record_commitment refuses the record; a status that is not 0 is the flag;
+    a refused row is zeros) of the records a result holds, under (program_id, record_name), from the strings it was made from
+    (aleo_mi355x_records_commitments_found / _host).  `found`: a result that still holds the library's copy — decrypt_strings(..., keep=True).  A bad program id
+    or record name raises with the reference's message."""
+    b = _as_batch(batch)
+    if b is None: raise TypeError('found_commitments takes a RecordBatch or a sequence of strings')
+    if found._native is None: raise ValueError('found_commitments takes a result made with keep=True')
+    c = len(found); cm = np.zeros((c, 32), dtype=np.uint8); flags = np.zeros(c, dtype=np.uint8)
+    L = lib(); f = L.aleo_mi355x_records_commitments_found_host if host else L.aleo_mi355x_records_commitments_found
+    rc = f(_p(cm), _p(flags), found._native, _text_p(b), _p(b.offsets), len(b), program_id.encode(), record_name.encode())
+    if rc: _raise_reference_message()
+    check(rc, 'records_commitments_found')
+    return cm, flags
+
+
+def unspent_named_many(batch, program_id: str, record_name: str, accounts, spent=(), host: bool = False) -> list:
+    """unspent_strings_many for a caller that has no commitments — the position of the wasm SDK's findUnspentRecords: every owned record's commitment is computed
+    from its plaintext under (program_id, record_name), on the device, in front of the serial numbers (aleo_mi355x_records_unspent_named_many / _many_host).
+    Entry j is a FoundRecords of account j's unspent records with .serials, .commitments and .owned.  A string that does not parse raises."""
+    b = _as_batch(batch)
+    if b is None: raise TypeError('unspent_named_many takes a RecordBatch or a sequence of strings')
+    accounts = [a if isinstance(a, Account) else Account.from_private_key(a) for a in accounts]
+    k = len(accounts); sp = _rows32(spent)
+    sk, vk, ax = (np.frombuffer(b''.join(getattr(a, name) for a in accounts), dtype=np.uint8) for name in ('sk_sig', 'view_key', 'address_x'))
+    L = lib(); out = (ctypes.c_void_p * max(k, 1))()
+    head = (out, _text_p(b), _p(b.offsets), len(b), program_id.encode(), record_name.encode(), _p(sk), _p(vk), _p(ax)); tail = (_p(sp) if sp.shape[0] else None, sp.shape[0])
+    if k == 1: rc = (L.aleo_mi355x_records_unspent_named_host if host else L.aleo_mi355x_records_unspent_named)(*head, *tail)
+    else: rc = (L.aleo_mi355x_records_unspent_named_many_host if host else L.aleo_mi355x_records_unspent_named_many)(*head, k, *tail)
+    if rc: _raise_reference_message()
+    check(rc, 'records_unspent_named')
+    found = []
+    try:
+        for j in range(k): found.append(_found_of(L, ctypes.c_void_p(out[j])))
+    finally:
+        for j in range(len(found) + 1, k): L.aleo_mi355x_found_free(ctypes.c_void_p(out[j]))      # _found_of released the one it was reading
+    if found and found[0].unparsed: RecordCiphertext.from_string(b.string(found[0].first_unparsed))
+    return found
+
+
+def unspent_named(batch, program_id: str, record_name: str, account, spent=(), host: bool = False) -> FoundRecords:
+    """unspent_named_many for one account (an Account or a private key string): aleo_mi355x_records_unspent_named."""
+    return unspent_named_many(batch, program_id, record_name, [account], spent, host=host)[0]

@@ -749,6 +749,47 @@ int32_t aleo_mi355x_records_unspent_strings_many(aleo_mi355x_found** out, const 
 int32_t aleo_mi355x_records_unspent_strings_many_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const void* commitments32, const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent);
 const uint8_t* aleo_mi355x_found_serials(const aleo_mi355x_found* found);
 size_t aleo_mi355x_found_owned(const aleo_mi355x_found* found);
+/* Unspent records from the strings alone: the commitments the calls above take from the chain, computed from each owned record's plaintext — what the JS/wasm SDK's
+ * findUnspentRecords does, which has only the strings and the private key (sdk/src/aleo_network_client.ts:365-373: serialNumberString(privateKey, "credits.aleo",
+ * "credits"), that is to_commitment(program_id, record_name) followed by serial_number: wasm/src/record/record_plaintext.rs:64-82).  A caller in that position
+ * brought every owned record down with records_decrypt_strings, called record_commitment once per record on the host, and went back up for records_unspent_strings.
+ * program_id / record_name: the same for every record of a call, refused as record_commitment refuses them, with its two last_error texts.
+ *   records_commitments_found   the commitments of the records an aleo_mi355x_found holds (the result of any of the calls above), given the n strings it was made
+ *                  from: cm_out (found_count x 32 B, canonical little-endian) and flags (found_count).  flags[k] = 0 computed: the row is byte for byte what
+ *                  record_commitment returns for string found_index[k] and the record's plain fields; 4 refused where record_commitment refuses the record (a
+ *                  private entry without a terminus bit or of no fields, a constant or public entry that does not parse); a record whose found_status is not 0
+ *                  gets that status (2 or 4) as its flag and computes nothing.  A refused row is zeros and never fails the call.  Refused: a null result, a null
+ *                  buffer with a count above 0, what records_scan_strings refuses of text and offsets, a found_index not below n.
+ *                  One owned record per lane (csrc/records_commit_lane.h): the owned strings' text and the plain fields go up, one launch chain runs (launches of
+ *                  at most 2^20 records; ALEO_MI355X_COMMIT_CHUNK, read per call, lowers that cap: for tests; the bytes do not depend on it), rows and flags come
+ *                  down.  The lane's table (432 x 4 points of BHP1024, 217 KB with the scan's constants) is built at first use and stays resident per device.  A
+ *                  record with a constant or public entry is not walked on the device (the conversion of such an entry is recursive and UNPINNED,
+ *                  csrc/records_bits.hpp): the calling thread computes its row inside the call.  Fewer than min_commitments records run on the host.
+ *                  Thread-safe (one slot per call).
+ *   records_commitments_found_host   the same bytes, record_commitment's code per record on the calling thread; touches no device.
+ *   min_commitments   the number of owned records from which the commitments take the GPU: 32, the smallest power of two at which the stand-alone GPU call beats the
+ *                  host path on one thread in both of two timings (profiles/records_commit.txt: a call costs 1.2-1.5 ms; the host path 0.84 / 0.82 ms at 2^4, 0.57x
+ *                  and 0.56x, and 1.63 / 1.63 ms at 2^5, 1.15x and 1.12x); ALEO_MI355X_MIN_COMMITMENTS overrides it, read per call.
+ *   records_unspent_named_many   records_unspent_strings_many without commitments32.  For account j let F be what records_decrypt_strings_host returns, (cm, cf)
+ *                  row k of records_commitments_found_host over F, and (sn, sf) what records_serial_numbers_host returns for cm under sk_sig j.  Record k is KEPT
+ *                  iff F.status[k] == 0 && cf == 0 && sf == 0 && sn is not a row of S.  (A record dropped for cf is one the reference drops too: its plaintext does
+ *                  not parse, so record.decrypt fails.)  out[j] has the layout of records_unspent_strings_many's result; found_commitments is the kept records'
+ *                  commitments.  Refused: the program id and record name as above, and everything records_unspent_strings_many refuses (commitments32 aside).
+ *                  n * n_keys below min_records, or n = 0, runs on the calling thread.  Else the flow of records_unspent_strings_many with one more kernel per
+ *                  chunk, behind the decryption: the commitments of ALL accounts' owned records (below min_commitments of them, and for routed records, on the
+ *                  calling thread), which the serial numbers, the spent check and the compaction then run on; the index download and the commitment upload of
+ *                  records_unspent_strings_many fall away.
+ *   records_unspent_named_many_host   the same bytes from the host paths named in the definition; touches no device.
+ *   records_unspent_named[_host]   one account: the call above with n_keys = 1.
+ *   found_commitments   count x 32 B: the kept records' commitments; NULL for the result of any other call. */
+int32_t aleo_mi355x_records_commitments_found(void* cm_out, uint8_t* flags, const aleo_mi355x_found* found, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name);
+int32_t aleo_mi355x_records_commitments_found_host(void* cm_out, uint8_t* flags, const aleo_mi355x_found* found, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name);
+size_t aleo_mi355x_min_commitments(void);
+int32_t aleo_mi355x_records_unspent_named(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sig32, const void* view_key32, const void* address_x32, const void* spent32, size_t n_spent);
+int32_t aleo_mi355x_records_unspent_named_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sig32, const void* view_key32, const void* address_x32, const void* spent32, size_t n_spent);
+int32_t aleo_mi355x_records_unspent_named_many(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent);
+int32_t aleo_mi355x_records_unspent_named_many_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent);
+const uint8_t* aleo_mi355x_found_commitments(const aleo_mi355x_found* found);
 
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */

@@ -711,6 +711,9 @@ class FoundRecords {
   const uint8_t* serials() const { return aleo_mi355x_found_serials(f_); }
   const uint8_t* serial(size_t k) const { return aleo_mi355x_found_serials(f_) + 32 * k; }
   size_t owned() const { return aleo_mi355x_found_owned(f_); }
+  // of unspent_named[_many]: the kept records' commitments as well (32 bytes each; a null pointer from any other call)
+  const uint8_t* commitments() const { return aleo_mi355x_found_commitments(f_); }
+  const uint8_t* commitment(size_t k) const { return aleo_mi355x_found_commitments(f_) + 32 * k; }
   const aleo_mi355x_found* handle() const { return f_; }
  private:
   aleo_mi355x_found* f_;
@@ -822,6 +825,42 @@ inline Result<std::vector<FoundRecords>> unspent_strings_many(const RecordBatch&
 inline Result<FoundRecords> unspent_strings(const RecordBatch& batch, const uint8_t* commitments32, const PrivateAccount& account, const uint8_t* spent32 = nullptr, size_t n_spent = 0) {
   aleo_mi355x_found* f = nullptr;
   int32_t rc = aleo_mi355x_records_unspent_strings(&f, batch.text(), batch.offsets(), batch.size(), commitments32, account.sk_sig, account.view_key.scalar, account.address.x, spent32, n_spent);
+  if (rc) return {std::nullopt, Error{rc}};
+  FoundRecords found(f);
+  if (found.unparsed()) { auto r = RecordCiphertext::from_string(batch.string(found.first_unparsed())); return {std::nullopt, r.is_ok() ? Error{ALEO_MI355X_ERR_BAD_ARG} : r.error}; }
+  return {std::move(found), Error{0}};
+}
+
+// ---- unspent records from the strings alone (sdk/src/aleo_network_client.ts:365-373; aleo_mi355x_records_unspent_named) ------------------------------------------
+// The commitments (32 canonical little-endian bytes each) and flags of the records a result holds, under (program_id, record_name), from the batch it was made from:
+// 0 computed; 4 refused where record_commitment refuses the record; a status that is not 0 is the flag.  A refused row is zeros.
+struct Commitments { std::vector<uint8_t> rows, flags; const uint8_t* row(size_t i) const { return rows.data() + 32 * i; } size_t size() const { return flags.size(); } };
+inline Result<Commitments> found_commitments(const RecordBatch& batch, const FoundRecords& found, const std::string& program_id, const std::string& record_name) {
+  Commitments out{std::vector<uint8_t>(32 * found.size()), std::vector<uint8_t>(found.size())};
+  int32_t rc = aleo_mi355x_records_commitments_found(out.rows.data(), out.flags.data(), found.handle(), batch.text(), batch.offsets(), batch.size(), program_id.c_str(), record_name.c_str());
+  if (rc) return {std::nullopt, Error{rc}};
+  return {std::move(out), Error{0}};
+}
+// unspent_strings_many for a caller that has no commitments: every owned record's is computed from its plaintext under (program_id, record_name) inside the call.
+// (*result)[a] holds accounts[a]'s unspent records with their serials(), commitments() and what it owned().
+inline Result<std::vector<FoundRecords>> unspent_named_many(const RecordBatch& batch, const std::string& program_id, const std::string& record_name, const std::vector<PrivateAccount>& accounts,
+                                                            const uint8_t* spent32 = nullptr, size_t n_spent = 0) {
+  std::vector<FoundRecords> out;
+  if (accounts.empty()) return {std::move(out), Error{0}};
+  std::vector<uint8_t> sks, vks, axs;
+  for (const auto& a : accounts) { sks.insert(sks.end(), a.sk_sig, a.sk_sig + 32); vks.insert(vks.end(), a.view_key.scalar, a.view_key.scalar + 32); axs.insert(axs.end(), a.address.x, a.address.x + 32); }
+  std::vector<aleo_mi355x_found*> f(accounts.size(), nullptr);
+  int32_t rc = aleo_mi355x_records_unspent_named_many(f.data(), batch.text(), batch.offsets(), batch.size(), program_id.c_str(), record_name.c_str(), sks.data(), vks.data(), axs.data(), accounts.size(), spent32, n_spent);
+  if (rc) return {std::nullopt, Error{rc}};
+  out.reserve(f.size());
+  for (aleo_mi355x_found* p : f) out.emplace_back(p);
+  if (out[0].unparsed()) { auto r = RecordCiphertext::from_string(batch.string(out[0].first_unparsed())); return {std::nullopt, r.is_ok() ? Error{ALEO_MI355X_ERR_BAD_ARG} : r.error}; }
+  return {std::move(out), Error{0}};
+}
+inline Result<FoundRecords> unspent_named(const RecordBatch& batch, const std::string& program_id, const std::string& record_name, const PrivateAccount& account, const uint8_t* spent32 = nullptr,
+                                          size_t n_spent = 0) {
+  aleo_mi355x_found* f = nullptr;
+  int32_t rc = aleo_mi355x_records_unspent_named(&f, batch.text(), batch.offsets(), batch.size(), program_id.c_str(), record_name.c_str(), account.sk_sig, account.view_key.scalar, account.address.x, spent32, n_spent);
   if (rc) return {std::nullopt, Error{rc}};
   FoundRecords found(f);
   if (found.unparsed()) { auto r = RecordCiphertext::from_string(batch.string(found.first_unparsed())); return {std::nullopt, r.is_ok() ? Error{ALEO_MI355X_ERR_BAD_ARG} : r.error}; }
