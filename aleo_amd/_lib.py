@@ -37,6 +37,8 @@ EXPORTS = [
     'aleo_mi355x_records_unspent_strings', 'aleo_mi355x_records_unspent_strings_host', 'aleo_mi355x_records_unspent_strings_many', 'aleo_mi355x_records_unspent_strings_many_host',
     'aleo_mi355x_found_serials', 'aleo_mi355x_found_owned',
     'aleo_mi355x_records_commitments_found', 'aleo_mi355x_records_commitments_found_host', 'aleo_mi355x_min_commitments',
+    'aleo_mi355x_signature_sign', 'aleo_mi355x_signature_to_string', 'aleo_mi355x_signature_from_string', 'aleo_mi355x_signatures_verify',
+    'aleo_mi355x_signatures_verify_host', 'aleo_mi355x_min_signatures',
     'aleo_mi355x_records_unspent_named', 'aleo_mi355x_records_unspent_named_host', 'aleo_mi355x_records_unspent_named_many', 'aleo_mi355x_records_unspent_named_many_host',
     'aleo_mi355x_found_commitments',
 ]
@@ -212,6 +214,12 @@ def lib():
         'aleo_mi355x_records_commitments_found': ([vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p], i32),
         'aleo_mi355x_records_commitments_found_host': ([vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p], i32),
         'aleo_mi355x_min_commitments': ([], sz),
+        'aleo_mi355x_signature_sign': ([vp, ctypes.c_char_p, vp, sz, vp], i32),
+        'aleo_mi355x_signature_to_string': ([vp, sz, vp], i32),
+        'aleo_mi355x_signature_from_string': ([vp, ctypes.c_char_p], i32),
+        'aleo_mi355x_signatures_verify': ([vp, vp, vp, sz, vp, vp, sz], i32),
+        'aleo_mi355x_signatures_verify_host': ([vp, vp, vp, sz, vp, vp, sz], i32),
+        'aleo_mi355x_min_signatures': ([], sz),
         'aleo_mi355x_records_unspent_named': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, vp, sz], i32),
         'aleo_mi355x_records_unspent_named_host': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, vp, sz], i32),
         'aleo_mi355x_records_unspent_named_many': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, sz, vp, sz], i32),

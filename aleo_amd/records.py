@@ -543,6 +543,17 @@ class Account:
     @property
     def address(self) -> str: return wire.bech32m_encode('aleo', self.address_x)
 
+    def sign(self, message, seed: bytes = None):
+        """Account.sign of the reference's SDK (sdk/src/account.ts:195): aleo_amd.signature.sign under this account's private key."""
+        from . import signature
+        if self.private_key is None: raise ValueError('this account holds no private key')
+        return signature.sign(self.private_key, message, seed)
+
+    def verify(self, message, signature) -> bool:
+        """Account.verify (sdk/src/account.ts:211-213): does the signature (a Signature or a "sign1…" string) verify under this account's address?"""
+        from . import signature as sg
+        return (signature if isinstance(signature, sg.Signature) else sg.Signature.from_string(signature)).verify(self.address_x, message)
+
 
 def _raise_reference_message():
     """The two refusals whose text the reference's tests read are raised with that text alone."""

@@ -791,6 +791,44 @@ int32_t aleo_mi355x_records_unspent_named_many(aleo_mi355x_found** out, const ch
 int32_t aleo_mi355x_records_unspent_named_many_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent);
 const uint8_t* aleo_mi355x_found_commitments(const aleo_mi355x_found* found);
 
+/* ---- account signatures: sign, the sign1… string, and many verifications in one call ---------------------------------------------------------------------------
+ * The two account calls of the reference besides derivation, ownership and decryption (wasm/src/account/signature.rs:37-48 Signature::sign / verify,
+ * wasm/src/account/address.rs:69-71, wasm/src/account/private_key.rs:244-248, sdk/src/account.ts:195,211-213) — snarkVM 0.14.5 console/account/src/signature
+ * [UPSTREAM-RECALL].  A signature is 128 bytes: challenge | response | pk_sig.x | pr_sig.x, 32 bytes each, canonical little-endian; as a string it is bech32m
+ * under the prefix "sign".  With G the account generator and m the message's fields: sign takes a nonce k, g_r = k G,
+ * challenge = hash_to_scalar_psd8([g_r.x, pk_sig.x, pr_sig.x, address.x, m ...]), response = k - challenge sk_sig; verify takes g_r = response G + challenge pk_sig,
+ * the challenge again, sk_prf = hash_to_scalar_psd4([pk_sig.x, pr_sig.x]), and accepts iff the challenges are equal and x(pk_sig + pr_sig + sk_prf G) is the
+ * address.  A message's bytes become bits, little-endian within a byte, in fields of 252 bits, the last one short; no bytes, no fields.  Of the two points with
+ * a given x the one in the prime-order subgroup is taken.
+ * Pinned by the reference's data (three accounts): the generator, hash_to_scalar's 250 bits, rate 4 for sk_prf, the sum that makes the address, Poseidon at
+ * rates 2, 4 and 8.  The reference holds no signature; its own tests are round trips (signature.rs:98-115).  So:
+ *   UNPINNED  the order of the challenge's preimage
+ *   UNPINNED  the packing of bytes into fields
+ *   UNPINNED  the 128-byte layout and the "sign" prefix
+ *   UNPINNED  the cap: a message of more than MAX_DATA_SIZE_IN_FIELDS = 4161 fields (131071 bytes) is refused
+ *   signature_sign   host code.  out128: the signature of message[0 .. len) under the account of private_key ("APrivateKey1…").  The nonce is the first number below
+ *                  the group order in the ChaCha20 stream under seed32 (32-byte blocks, the low 251 bits of each; rejection, so it is uniform) and signing is
+ *                  a function of its arguments.  NEVER REUSE A SEED for two messages: two signatures under one nonce give the private key away.  Refused
+ *                  (ALEO_MI355X_ERR_BAD_ARG): a key account_from_private_key refuses, a message over the cap.
+ *   signature_to_string / signature_from_string   128 bytes <-> "sign1…" (cap: 219 bytes hold it).  from_string refuses a bad checksum, another prefix and a payload that is
+ *                  not 128 bytes.
+ *   signatures_verify   n signatures (sigs128: n x 128 B) under addresses_x32 — rows of 32 bytes address_stride apart: 0, one address for all; 32, one per signature —
+ *                  over messages: concatenated bytes with n + 1 offsets, as records_scan_strings takes its strings.  flags[i]: 0 signature i verifies; 1 it does
+ *                  not (a challenge or an address differs); 3 it is no signature (a scalar not below the group order, an x not below r or with no point in the
+ *                  subgroup, a message over the cap) — the value the record calls give to what does not parse.  Refused: null buffers, another stride,
+ *                  offsets that do not start at 0 or decrease.  n = 0 is fine.  Batches below min_signatures run the host code inside the call; else one kernel
+ *                  launch per 2^20 signatures (one signature per lane), the copies inside the call.  Thread-safe (one slot per call).
+ *   signatures_verify_host   the same flags, computed by the calling thread; touches no device.  It is the definition of the result.
+ *   min_signatures   the batch size from which signatures_verify takes the GPU: 32, the smallest power of two at which the GPU call beats the host path on one thread in
+ *                  both of two timings (profiles/signatures_verify.txt: a call costs 5.6-6.2 ms for any batch up to 2^10; the host path 3.75 / 3.75 ms at 2^4, 0.60x
+ *                  and 0.61x, and 7.75 / 7.75 ms at 2^5, 1.25x and 1.26x); ALEO_MI355X_MIN_SIGNATURES overrides it, read per call (a bad value: the default). */
+int32_t aleo_mi355x_signature_sign(void* out128, const char* private_key, const void* message, size_t len, const void* seed32);
+int32_t aleo_mi355x_signature_to_string(char* out, size_t cap, const void* sig128);
+int32_t aleo_mi355x_signature_from_string(void* out128, const char* s);
+int32_t aleo_mi355x_signatures_verify(uint8_t* flags, const void* sigs128, const void* addresses_x32, size_t address_stride, const void* messages, const uint64_t* offsets, size_t n);
+int32_t aleo_mi355x_signatures_verify_host(uint8_t* flags, const void* sigs128, const void* addresses_x32, size_t address_stride, const void* messages, const uint64_t* offsets, size_t n);
+size_t aleo_mi355x_min_signatures(void);
+
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */
 const char* aleo_mi355x_version(void);

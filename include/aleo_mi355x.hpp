@@ -767,9 +767,53 @@ inline Result<std::vector<Balance>> balances(const RecordBatch& batch, const std
 
 // ---- serial numbers: which of the found records are unspent (rust/src/api/blocking.rs:277-278; aleo_mi355x_records_serial_numbers) ------------------------------
 // What get_unspent_records is handed is a private key: sk_sig for the serial numbers, the view key and the address for the search.
-struct PrivateAccount { uint8_t sk_sig[32]; ViewKey view_key; Address address; };
+// ---- account signatures (aleo_mi355x_signature_*, aleo_mi355x_signatures_verify: the reference's Signature::sign / verify, wasm/src/account/signature.rs:37-48) ----
+// 128 bytes: challenge | response | pk_sig.x | pr_sig.x; as a string "sign1…"
+struct Signature {
+  uint8_t bytes[128];
+  static Result<Signature> from_string(const std::string& s) {
+    Signature g; int32_t rc = aleo_mi355x_signature_from_string(g.bytes, s.c_str());
+    if (rc) return {std::nullopt, Error{rc}};
+    return {g, Error{0}};
+  }
+  std::string to_string() const { char out[256]; return aleo_mi355x_signature_to_string(out, sizeof out, bytes) ? std::string() : std::string(out); }
+};
+// The signature of a message under the account of an "APrivateKey1…" string.  The nonce comes from seed32 alone: never use a seed for two messages.
+inline Result<Signature> sign(const std::string& private_key, const void* message, size_t len, const uint8_t* seed32) {
+  Signature g; int32_t rc = aleo_mi355x_signature_sign(g.bytes, private_key.c_str(), message, len, seed32);
+  if (rc) return {std::nullopt, Error{rc}};
+  return {g, Error{0}};
+}
+// flags[i]: 0 signature i verifies under its address over message i, 1 it does not, 3 it is no signature.  addresses: one for all, or one per signature.
+// Batches of aleo_mi355x_min_signatures() and more run on the GPU, one signature per lane.
+inline Result<std::vector<uint8_t>> verify_many(const std::vector<Signature>& signatures, const std::vector<Address>& addresses, const std::vector<std::string>& messages, bool host = false) {
+  const size_t n = signatures.size();
+  if (messages.size() != n || (addresses.size() != n && addresses.size() != 1)) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+  std::vector<uint8_t> flags(n), sg(128 * n), ax(32 * addresses.size()); std::vector<uint64_t> off(n + 1, 0); std::string text;
+  for (size_t i = 0; i < n; ++i) { std::memcpy(sg.data() + 128 * i, signatures[i].bytes, 128); text += messages[i]; off[i + 1] = text.size(); }
+  for (size_t i = 0; i < addresses.size(); ++i) std::memcpy(ax.data() + 32 * i, addresses[i].x, 32);
+  const size_t stride = addresses.size() == n && n != 1 ? 32 : 0;
+  int32_t rc = (host ? aleo_mi355x_signatures_verify_host : aleo_mi355x_signatures_verify)(flags.data(), sg.data(), ax.data(), stride, text.data(), off.data(), n);
+  if (rc) return {std::nullopt, Error{rc}};
+  return {std::move(flags), Error{0}};
+}
+// Signature::verify(address, message): one signature, on the calling thread
+inline bool verify(const Signature& signature, const Address& address, const void* message, size_t len) {
+  uint8_t flag = 1; const uint64_t off[2] = {0, len};
+  return aleo_mi355x_signatures_verify_host(&flag, signature.bytes, address.x, 0, message, off, 1) == 0 && flag == 0;
+}
+
+// private_key: the string the account was made from (empty when it was put together from its parts: such an account verifies and cannot sign)
+struct PrivateAccount {
+  uint8_t sk_sig[32]; ViewKey view_key; Address address; std::string private_key;
+  Result<Signature> sign(const void* message, size_t len, const uint8_t* seed32) const {
+    if (private_key.empty()) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+    return aleo_mi355x::sign(private_key, message, len, seed32);
+  }
+  bool verify(const void* message, size_t len, const Signature& signature) const { return aleo_mi355x::verify(signature, address, message, len); }
+};
 inline Result<PrivateAccount> account_from_private_key(const std::string& private_key) {
-  PrivateAccount a;
+  PrivateAccount a; a.private_key = private_key;
   int32_t rc = aleo_mi355x_account_from_private_key(private_key.c_str(), a.sk_sig, a.view_key.scalar, a.address.x);
   if (rc) return {std::nullopt, Error{rc}};
   return {a, Error{0}};
