@@ -22,16 +22,10 @@ static const CommitTables& commit_tables() {
     B.add_chunks(t.fixed, B.domain.data(), 3 * CM_DOMAIN_CHUNKS);
     B.add_chunks(t.fixed, zeros, sizeof zeros, CM_DOMAIN_CHUNKS + CM_LENGTH_CHUNKS);
     t.head = B.domain[3 * CM_DOMAIN_CHUNKS] | B.domain[3 * CM_DOMAIN_CHUNKS + 1] << 1;
-    t.words.assign(CK_WORDS, 0);
-    std::memcpy(t.words.data(), C.words.data(), RK_WORDS * 4);
-    auto put = [&](uint32_t idx, const HFr& v) { put29(t.words.data() + 9 * idx, v); };
-    put(CK_TWO, HFr::from_u64(2));
-    for (uint32_t c = 0; c < CM_CHUNKS; ++c)
-      for (uint32_t k = 0; k < 4; ++k) {
-        const EdH& p = B.lookup[4 * c + k];                    // Z = 1
-        const uint32_t idx = CK_TABLE + 3 * (4 * c + k);
-        put(idx, HFr::sub(p.Y, p.X)); put(idx + 1, HFr::add(p.Y, p.X)); put(idx + 2, HFr::mul(p.T, C.d2));
-      }
+    WordTable wt(CK_WORDS, C);
+    wt.put(CK_TWO, HFr::from_u64(2));
+    for (uint32_t e = 0; e < 4 * CM_CHUNKS; ++e) wt.put_cached(CK_TABLE + 3 * e, B.lookup[e]);
+    t.words = std::move(wt.words);
     return t;
   }();
   return T;

@@ -131,7 +131,6 @@ struct Ctx {                           // one concurrency slot
   DevBuf cold_raw, cold_xy, cold_xy28, cold_flags;      // the cold one-shot MSM (bases.hip cold_bases): the call's copy of the caller's bases, grow-only like every other workspace of the slot
   DevBuf ntt_tmp, ntt_stage;
   DevBuf unspent_ws, unspent_set;      // records_unspent.hip: a chunk's serial numbers, sums and kept arrays; the call's spent set and key table
-  DevBuf records_k; bool records_k_ready = false;      // records.hip records_constants: the records constants (30 KB), uploaded on the slot's first use and kept
   // ntt_tmp is scratch of the *_device entry points, which enqueue on the CALLER's stream and return without synchronising;
   // the slot is then handed to the next call, possibly on another stream.  scratch_ev is recorded after the last kernel that
   // touches the scratch; the next user waits on it (scratch_acquire) before its first kernel, or synchronises on it before

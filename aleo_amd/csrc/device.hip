@@ -67,6 +67,19 @@ int32_t ensure_host_pinned(Ctx* c, size_t bytes) {
   c->h_pinned_cap = want; return ALEO_MI355X_OK;
 }
 
+int32_t resident_table(int device, ResidentTable kind, const std::vector<uint32_t>& (*words)(), const uint32_t** out) {
+  static std::mutex mu; static std::map<std::pair<int, ResidentTable>, const uint32_t*> resident;
+  const std::vector<uint32_t>& w = words();                 // built on the host at first use (a function-local static of its unit), outside the lock
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = resident.find({device, kind});
+  if (it == resident.end()) {
+    DevTmp buf; if (int32_t rc = buf.alloc(w.size() * 4)) return rc;
+    HIPCHK(hipMemcpy(buf.p, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    it = resident.emplace(std::make_pair(device, kind), (const uint32_t*)buf.release()).first;
+  }
+  *out = it->second; return ALEO_MI355X_OK;
+}
+
 // ---- slot scratch shared by asynchronous calls (ctx.h) --------------------------------------------------
 int32_t scratch_acquire(Ctx* c, DevBuf& b, size_t bytes, hipStream_t s) {
   if (c->scratch_busy) {

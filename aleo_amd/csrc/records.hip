@@ -10,7 +10,7 @@
 // (x, -y) = -(x, y) + (0, -1), k (0, -1) = (0, -1) for odd k, and -(a, b) + (0, -1) = (a, -b).  Where a prime-order N with this x exists, l N = O makes the
 // value x(view_key * N).  So the scan needs neither a subgroup check nor a choice of root, and is defined for every x on the curve.
 //
-// Here: the computation on the host (host_field.hpp, poseidon.hpp — the fallback, what small batches take, and the checker), the lane's constants on the device, the routing
+// Here: the computation on the host (host_field.hpp, poseidon.hpp — the fallback, what small batches take, and the checker), the routing
 // threshold and the one-account entry points, which take the kernel (one record per lane: records_lane.h, edwards29.h) and the device flow of the K-account scan (records_many.hip) with one key.
 #include "records_strings.h"
 
@@ -20,26 +20,11 @@ static int32_t records_scan(uint8_t* flags, void* rvk_out, const void* owner_c0,
   if (!view_key32 || !address_x32 || ((!flags || !owner_c0 || !nonce_x) && n)) return bad_arg("records_scan: null buffer");
   ScanArgs a; HFr addr; if (const char* why = scan_args(a, addr, view_key32, address_x32)) return bad_arg(why);
   if (may_route && n && n >= aleo_mi355x_min_records()) {
-    const ManyKeys k{{a}, {addr}};
-    Slot sl; if (sl.rc) return sl.rc;
-    return scan_many_on_device(sl.c, flags, rvk_out, owner_c0, nonce_x, n, k);
+    return scan_many_on_device(flags, rvk_out, owner_c0, nonce_x, n, ManyKeys{{a}, {addr}});
   }
   const RecordsConsts& C = records_consts();
   for (size_t i = 0; i < n; ++i)
     flags[i] = scan_one_host(rvk_out ? (uint8_t*)rvk_out + 32 * i : nullptr, (const uint8_t*)owner_c0 + 32 * i, (const uint8_t*)nonce_x + 32 * i, a, addr, C);
-  return ALEO_MI355X_OK;
-}
-
-// The constants on the device, once per slot: the flag is set only when the slot's stream has completed the copy, so a copy that fails is made again by the slot's
-// next call and never leaves an unfilled table in service.  The slot is the caller's for the duration of its call (entry.h Slot), so nothing else runs between.
-int32_t records_constants(Ctx* c, const uint32_t** dK) {
-  if (!c->records_k_ready) {
-    if (int32_t rc = c->records_k.reserve(RK_WORDS * 4)) return rc;
-    HIPCHK(hipMemcpyAsync(c->records_k.p, records_consts().words.data(), RK_WORDS * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->records_k_ready = true;
-  }
-  *dK = c->records_k.as<uint32_t>();
   return ALEO_MI355X_OK;
 }
 

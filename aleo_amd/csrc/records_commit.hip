@@ -34,9 +34,7 @@ __global__ void __launch_bounds__(COMMIT_BLOCK) k_records_commit(char* __restric
     const uint8_t* __restrict__ mine = (const uint8_t*)text + first;
     const char* __restrict__ my_fields = fields + (size_t)f0 * 32;
     flag = records_commit_lane([&](uint32_t q) { return mine[q]; }, len, kind[j], off[j + 1] - f0,
-                               [&](uint32_t k, uint32_t (&w)[8]) {
-                                 const uint4* p = (const uint4*)(my_fields + (size_t)k * 32); const uint4 l = p[0], h = p[1];
-                                 w[0] = l.x; w[1] = l.y; w[2] = l.z; w[3] = l.w; w[4] = h.x; w[5] = h.y; w[6] = h.z; w[7] = h.w; },
+                               [&](uint32_t k, uint32_t (&w)[8]) { load_words8(w, my_fields + (size_t)k * 32); },
                                K, A, [&](const F29& v) { store_fp<Fr>(out, f29_to_fr(v)); });
     if (flag == COMMIT_ROUTED) atomicAdd(route, 1u);
   }
@@ -44,26 +42,14 @@ __global__ void __launch_bounds__(COMMIT_BLOCK) k_records_commit(char* __restric
   flags[j] = (uint8_t)flag;
 }
 
-// The table of one device: uploaded once, under the lock, and never freed; the copy is complete before the pointer is handed out.
 static int32_t commit_tables_on_device(int device, const uint32_t** out) {
-  static std::mutex mu; static std::map<int, const uint32_t*> resident;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = resident.find(device);
-  if (it == resident.end()) {
-    const serial::CommitTables& T = serial::commit_tables();
-    DevTmp buf; if (int32_t rc = buf.alloc((size_t)CK_WORDS * 4)) return rc;
-    HIPCHK(hipMemcpy(buf.p, T.words.data(), (size_t)CK_WORDS * 4, hipMemcpyHostToDevice));
-    it = resident.emplace(device, (const uint32_t*)buf.release()).first;
-  }
-  *out = it->second; return ALEO_MI355X_OK;
+  return resident_table(device, ResidentTable::COMMIT, []() -> const std::vector<uint32_t>& { return serial::commit_tables().words; }, out);
 }
-
-static size_t commit_chunk_cap() { const size_t cap = env_size("ALEO_MI355X_COMMIT_CHUNK", COMMIT_CHUNK); return cap == 0 || cap > COMMIT_CHUNK ? COMMIT_CHUNK : cap; }
 
 // k_records_commit over n records in launches of at most ALEO_MI355X_COMMIT_CHUNK lanes (read per call); *droute is zeroed first
 static int32_t launch_records_commit(hipStream_t s, char* dcm, uint8_t* dflags, uint32_t* droute, const char* fields, const uint32_t* off, const uint32_t* index, const int8_t* kind,
                                      const uint8_t* status, const char* text, const uint32_t* soff, const uint32_t* dK, const CommitArgs& A, size_t n) {
-  const size_t cap = commit_chunk_cap();
+  const size_t cap = env_cap("ALEO_MI355X_COMMIT_CHUNK", COMMIT_CHUNK);
   HIPCHK(hipMemsetAsync(droute, 0, 4, s));
   for (size_t lo = 0; lo < n; lo += cap) {
     const size_t hi = n - lo < cap ? n : lo + cap;
@@ -116,7 +102,7 @@ int32_t commit_rows_of_chunk(Ctx* c, hipStream_t s, const FoundChunk& ch, const 
   if (on_device) {
     const uint32_t* dK; if (int32_t rc = commit_tables_on_device(c->device, &dK)) return rc;
     if (int32_t rc = launch_records_commit(s, dcm, dflags, droute, ch.fields, ch.off, ch.index, ch.kind, ch.status, ch.text, ch.soff, dK, cc.args, owned)) return rc;
-    uint32_t* h_route = (uint32_t*)((char*)c->h_pinned + 6144);      // behind the flow's and the unspent stage's words
+    uint32_t* h_route = &ch.pin->routed;
     HIPCHK(hipMemcpyAsync(h_route, droute, 4, hipMemcpyDeviceToHost, s));
     if (want_host) { H.cm.resize(owned * 32); HIPCHK(hipMemcpyAsync(H.cm.data(), dcm, owned * 32, hipMemcpyDeviceToHost, s)); }
     HIPCHK(hipStreamSynchronize(s));
@@ -141,10 +127,10 @@ int32_t commit_rows_of_chunk(Ctx* c, hipStream_t s, const FoundChunk& ch, const 
 }
 
 // ---- the stand-alone call -------------------------------------------------------------------------------------------------------------------------------
-// The owned strings' text and the result's arrays go up, one launch chain runs, rows and flags come down; the routed rows are the calling thread's.
-static int32_t commitments_on_device(Ctx* c, uint8_t* cm_out, uint8_t* flags, const Found& F, const char* text, const uint64_t* offsets, const CommitCall& cc) {
+// The owned strings' text and the result's arrays go up, one launch chain runs, rows and flags come down; the routed rows are the calling thread's.  The text and
+// its offsets are declared outside the slot: they outlive the copies that read them.
+static int32_t commitments_on_device(uint8_t* cm_out, uint8_t* flags, const Found& F, const char* text, const uint64_t* offsets, const CommitCall& cc) {
   const size_t count = F.index.size(), nf = F.offsets.back();
-  const uint32_t* dK; if (int32_t rc = commit_tables_on_device(c->device, &dK)) return rc;
   std::vector<uint32_t> soff(count + 1, 0);
   size_t chars = 0;
   for (size_t k = 0; k < count; ++k) {
@@ -154,25 +140,28 @@ static int32_t commitments_on_device(Ctx* c, uint8_t* cm_out, uint8_t* flags, co
   }
   std::vector<char> owned_text(chars);
   for (size_t k = 0; k < count; ++k) std::memcpy(owned_text.data() + soff[k], text + offsets[F.index[k]], soff[k + 1] - soff[k]);
-  hipStream_t s = c->stream;
-  Carve cv;
-  const size_t o_text = cv.part(chars), o_soff = cv.part((count + 1) * 4), o_fields = cv.part(nf * 32), o_off = cv.part((count + 1) * 4), o_kind = cv.part(count), o_status = cv.part(count),
-               o_cm = cv.part(count * 32), o_fl = cv.part(count), o_route = cv.part(4);
-  if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
-  char* b = c->scalars_stage.as<char>();
-  HIPCHK(hipMemcpyAsync(b + o_text, owned_text.data(), chars, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(b + o_soff, soff.data(), (count + 1) * 4, hipMemcpyHostToDevice, s));
-  if (nf) HIPCHK(hipMemcpyAsync(b + o_fields, F.plain.data(), nf * 32, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(b + o_off, F.offsets.data(), (count + 1) * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(b + o_kind, F.kind.data(), count, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(b + o_status, F.status.data(), count, hipMemcpyHostToDevice, s));
-  int32_t rc = launch_records_commit(s, b + o_cm, (uint8_t*)(b + o_fl), (uint32_t*)(b + o_route), b + o_fields, (const uint32_t*)(b + o_off), nullptr, (const int8_t*)(b + o_kind),
-                                     (const uint8_t*)(b + o_status), b + o_text, (const uint32_t*)(b + o_soff), dK, cc.args, count);
-  if (!rc) rc = hipMemcpyAsync(cm_out, b + o_cm, count * 32, hipMemcpyDeviceToHost, s) == hipSuccess && hipMemcpyAsync(flags, b + o_fl, count, hipMemcpyDeviceToHost, s) == hipSuccess ? ALEO_MI355X_OK : ALEO_MI355X_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = ALEO_MI355X_ERR_HIP;      // the host arrays above are on their way up until here, whatever went wrong
-  if (rc) { if (rc == ALEO_MI355X_ERR_HIP) g_last_error = "records_commitments_found: a HIP call failed"; return rc; }
-  commit_rows_on_host(cm_out, flags, F.index.data(), F.offsets.data(), F.status.data(), F.plain.data(), count, text, offsets, 0, cc, true);
-  return ALEO_MI355X_OK;
+  return on_slot([&](Ctx* c) -> int32_t {
+    const uint32_t* dK; if (int32_t rc = commit_tables_on_device(c->device, &dK)) return rc;
+    hipStream_t s = c->stream;
+    Carve cv;
+    const size_t o_text = cv.part(chars), o_soff = cv.part((count + 1) * 4), o_fields = cv.part(nf * 32), o_off = cv.part((count + 1) * 4), o_kind = cv.part(count), o_status = cv.part(count),
+                 o_cm = cv.part(count * 32), o_fl = cv.part(count), o_route = cv.part(4);
+    if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
+    char* b = c->scalars_stage.as<char>();
+    HIPCHK(hipMemcpyAsync(b + o_text, owned_text.data(), chars, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b + o_soff, soff.data(), (count + 1) * 4, hipMemcpyHostToDevice, s));
+    if (nf) HIPCHK(hipMemcpyAsync(b + o_fields, F.plain.data(), nf * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b + o_off, F.offsets.data(), (count + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b + o_kind, F.kind.data(), count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b + o_status, F.status.data(), count, hipMemcpyHostToDevice, s));
+    if (int32_t rc = launch_records_commit(s, b + o_cm, (uint8_t*)(b + o_fl), (uint32_t*)(b + o_route), b + o_fields, (const uint32_t*)(b + o_off), nullptr, (const int8_t*)(b + o_kind),
+                                       (const uint8_t*)(b + o_status), b + o_text, (const uint32_t*)(b + o_soff), dK, cc.args, count)) return rc;
+    HIPCHK(hipMemcpyAsync(cm_out, b + o_cm, count * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(flags, b + o_fl, count, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    commit_rows_on_host(cm_out, flags, F.index.data(), F.offsets.data(), F.status.data(), F.plain.data(), count, text, offsets, 0, cc, true);
+    return ALEO_MI355X_OK;
+  });
 }
 
 static int32_t commitments_found(void* cm_out, uint8_t* flags, const Found* found, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name,
@@ -185,7 +174,7 @@ static int32_t commitments_found(void* cm_out, uint8_t* flags, const Found* foun
   if (int32_t rc = strings_args_ok("records_commitments_found", text, offsets, n)) return rc;
   for (size_t k = 0; k < count; ++k) if (F.index[k] >= n) return bad_arg("records_commitments_found: the result was made from more strings than there are");
   if (!count) return ALEO_MI355X_OK;
-  if (may_route && count >= aleo_mi355x_min_commitments()) { Slot sl; return sl.rc ? sl.rc : commitments_on_device(sl.c, (uint8_t*)cm_out, flags, F, text, offsets, cc); }
+  if (may_route && count >= aleo_mi355x_min_commitments()) return commitments_on_device((uint8_t*)cm_out, flags, F, text, offsets, cc);
   commit_rows_on_host((uint8_t*)cm_out, flags, F.index.data(), F.offsets.data(), F.status.data(), F.plain.data(), count, text, offsets, 0, cc, false);
   return ALEO_MI355X_OK;
 }

@@ -22,7 +22,7 @@
 namespace aleo_mi355x {
 
 static constexpr uint32_t DECRYPT_BLOCK = 256;
-static constexpr size_t DECRYPT_CHUNK_RECORDS = (size_t)1 << 20, DECRYPT_CHUNK_FIELDS = (size_t)1 << 22;      // per launch: 37 B a record and 32 B a field of slot scratch (~170 MB)
+static constexpr size_t DECRYPT_CHUNK_RECORDS = (size_t)1 << 20;      // per launch, with records_strings.h DECRYPT_CHUNK_FIELDS: 37 B a record and 32 B a field of slot scratch (~170 MB)
 static constexpr size_t DECRYPT_MAX_FIELDS = 65535;        // of one record: upstream's u16 field count
 
 // what both paths refuse before they compute; *perms: the permutations of the call, sum of ceil(m / 8)
@@ -64,19 +64,18 @@ __global__ void __launch_bounds__(DECRYPT_BLOCK) k_records_decrypt(char* __restr
   flags[i] = (uint8_t)flag;
 }
 
-// the field cap of a launch, the cut of records into launches, and the launch itself: for decrypt_on_device and for records_found.hip, whose records are on the device
+// the cut of records into launches, and the launch itself: for decrypt_on_device and for records_found.hip, whose records are on the device
 size_t decrypt_cut(const uint32_t* offsets, size_t at, size_t n, size_t record_cap, size_t field_cap) {
   size_t e = at + 1; while (e < n && e - at < record_cap && (size_t)offsets[e + 1] - offsets[at] <= field_cap) ++e; return e;
 }
-size_t decrypt_chunk_fields() { size_t cap = env_size("ALEO_MI355X_DECRYPT_CHUNK_FIELDS", DECRYPT_CHUNK_FIELDS); return cap < 1 || cap > DECRYPT_CHUNK_FIELDS ? DECRYPT_CHUNK_FIELDS : cap; }
 void launch_records_decrypt(hipStream_t s, char* io, uint8_t* dflags, const char* drvk, const uint32_t* doffsets, uint32_t base, size_t n, const uint32_t* dK) {
   hipLaunchKernelGGL(k_records_decrypt, dim3((uint32_t)((n + DECRYPT_BLOCK - 1) / DECRYPT_BLOCK)), dim3(DECRYPT_BLOCK), 0, s, io, dflags, drvk, doffsets, base, (uint32_t)n, dK);
 }
 
 // Copies, launch and synchronisation per chunk as scan_many_on_device (records_many.hip).  A chunk: as many whole records as stay within DECRYPT_CHUNK_RECORDS and the field
 // cap, and one at least.  ALEO_MI355X_DECRYPT_CHUNK_FIELDS (read per call) lowers the field cap; the bytes do not depend on it.
-static int32_t decrypt_on_device(Ctx* c, uint8_t* plain, uint8_t* flags, const uint8_t* rvk, const uint32_t* offsets, const uint8_t* fields, size_t n) {
-  const size_t cap = decrypt_chunk_fields();
+static int32_t decrypt_on_device(uint8_t* plain, uint8_t* flags, const uint8_t* rvk, const uint32_t* offsets, const uint8_t* fields, size_t n) {
+  const size_t cap = env_cap("ALEO_MI355X_DECRYPT_CHUNK_FIELDS", DECRYPT_CHUNK_FIELDS);
   std::vector<size_t> cut{0};                                 // chunk k: records cut[k] .. cut[k + 1]
   size_t max_records = 0, max_fields = 0;
   for (size_t at = 0; at < n;) {
@@ -85,26 +84,28 @@ static int32_t decrypt_on_device(Ctx* c, uint8_t* plain, uint8_t* flags, const u
     if ((size_t)offsets[e] - offsets[at] > max_fields) max_fields = offsets[e] - offsets[at];
     cut.push_back(e); at = e;
   }
-  hipStream_t s = c->stream;
-  int32_t rc;
-  const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
-  Carve cv;
-  const size_t o_io = cv.part(max_fields * 32), o_rvk = cv.part(max_records * 32), o_off = cv.part((max_records + 1) * 4), o_fl = cv.part(max_records);
-  if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
-  char* base = c->scalars_stage.as<char>();
-  char* dio = base + o_io; char* drvk = base + o_rvk; uint32_t* doff = (uint32_t*)(base + o_off); uint8_t* dfl = (uint8_t*)(base + o_fl);
-  for (size_t k = 0; k + 1 < cut.size(); ++k) {
-    const size_t at = cut[k], m = cut[k + 1] - at, first = offsets[at], nf = offsets[at + m] - first;
-    if (nf) HIPCHK(hipMemcpyAsync(dio, fields + first * 32, nf * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(drvk, rvk + at * 32, m * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff, offsets + at, (m + 1) * 4, hipMemcpyHostToDevice, s));
-    launch_records_decrypt(s, dio, dfl, drvk, doff, (uint32_t)first, m, dK);
-    HIPCHK(hipGetLastError());
-    if (nf) HIPCHK(hipMemcpyAsync(plain + first * 32, dio, nf * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
-  }
-  return ALEO_MI355X_OK;
+  return on_slot([&](Ctx* c) -> int32_t {
+    hipStream_t s = c->stream;
+    int32_t rc;
+    const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
+    Carve cv;
+    const size_t o_io = cv.part(max_fields * 32), o_rvk = cv.part(max_records * 32), o_off = cv.part((max_records + 1) * 4), o_fl = cv.part(max_records);
+    if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
+    char* base = c->scalars_stage.as<char>();
+    char* dio = base + o_io; char* drvk = base + o_rvk; uint32_t* doff = (uint32_t*)(base + o_off); uint8_t* dfl = (uint8_t*)(base + o_fl);
+    for (size_t k = 0; k + 1 < cut.size(); ++k) {
+      const size_t at = cut[k], m = cut[k + 1] - at, first = offsets[at], nf = offsets[at + m] - first;
+      if (nf) HIPCHK(hipMemcpyAsync(dio, fields + first * 32, nf * 32, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(drvk, rvk + at * 32, m * 32, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(doff, offsets + at, (m + 1) * 4, hipMemcpyHostToDevice, s));
+      launch_records_decrypt(s, dio, dfl, drvk, doff, (uint32_t)first, m, dK);
+      HIPCHK(hipGetLastError());
+      if (nf) HIPCHK(hipMemcpyAsync(plain + first * 32, dio, nf * 32, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
+    }
+    return ALEO_MI355X_OK;
+  });
 }
 
 // ---- one record, entirely on the host ---------------------------------------------------------------------------------------------------------------------
@@ -156,8 +157,7 @@ int32_t aleo_mi355x_records_decrypt_fields(void* plain_out, uint8_t* flags, cons
   return guarded([&] {
     size_t perms; if (int32_t rc = decrypt_args_ok(plain_out, flags, rvk, offsets, fields, n, &perms)) return rc;
     if (perms < aleo_mi355x_min_decrypt() || n == 0) return decrypt_on_host((uint8_t*)plain_out, flags, (const uint8_t*)rvk, offsets, (const uint8_t*)fields, n);
-    Slot sl; if (sl.rc) return sl.rc;
-    return decrypt_on_device(sl.c, (uint8_t*)plain_out, flags, (const uint8_t*)rvk, offsets, (const uint8_t*)fields, n);
+    return decrypt_on_device((uint8_t*)plain_out, flags, (const uint8_t*)rvk, offsets, (const uint8_t*)fields, n);
   });
 }
 

@@ -167,9 +167,7 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_found_microcredits(uint8_t* __r
   const uint32_t mn = c_mc_n[j];
   if (!mn) return;                                             // a public entry's value, or 0, stands
   const char* at = fields + (size_t)c_mc_at[j] * 32;
-  c_mc[j] = found_microcredits_private(mn, [&](uint32_t k, uint32_t (&w)[8]) {
-    const uint4* p = (const uint4*)(at + (size_t)k * 32); const uint4 l = p[0], h = p[1];
-    w[0] = l.x; w[1] = l.y; w[2] = l.z; w[3] = l.w; w[4] = h.x; w[5] = h.y; w[6] = h.z; w[7] = h.w; });
+  c_mc[j] = found_microcredits_private(mn, [&](uint32_t k, uint32_t (&w)[8]) { load_words8(w, at + (size_t)k * 32); });
 }
 
 void launch_found_offsets(hipStream_t s, uint32_t* blk, uint32_t* stat, uint32_t rows, uint32_t nb) {
@@ -178,9 +176,9 @@ void launch_found_offsets(hipStream_t s, uint32_t* blk, uint32_t* stat, uint32_t
 
 // ---- the device flow ----------------------------------------------------------------------------------------------------------------------------------
 // What one call holds on the device, in the slot's scalars_stage: the scan's own scratch (64 B per record, 33 B per pair), 10 B per pair for the walk (the scan's
-// flags, the pre-status, the two first-level sums), the block totals, the statistics (read through h_pinned) and the source's scratch.
+// flags, the pre-status, the two first-level sums), the block totals, the statistics (read through pin->flow) and the source's scratch.
 struct FoundCall {
-  Ctx* c; hipStream_t s; FoundStage* stage; size_t K, cap, stat_words; uint32_t W;      // cap: the fields of one decryption launch
+  Ctx* c; hipStream_t s; FoundPinned* pin; FoundStage* stage; size_t K, cap, stat_words; uint32_t W;      // cap: the fields of one decryption launch
   const uint32_t* dK; const ScanArgs* dkeys;
   char* dc0; char* dnx; char* drvk; char* dstr; uint8_t* dfl; uint8_t* dscan; uint8_t* dpre; uint32_t* dcnt; uint32_t* dpos; uint32_t* dblk; uint32_t* dstat;
   uint32_t* dsoff; int8_t* dkinds; char* dtext;
@@ -211,14 +209,14 @@ static int32_t found_count(const FoundCall& f, StringSource& src, size_t ck, std
   HIPCHK(hipGetLastError());
   launch_found_offsets(s, f.dblk, f.dstat, nb * (uint32_t)K, nb);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(f.c->h_pinned, f.dstat, f.stat_words * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(f.pin->flow, f.dstat, f.stat_words * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));                           // the one wait before the gather: the host sizes the compacted arrays
-  const uint32_t* stat = (const uint32_t*)f.c->h_pinned;
+  const uint32_t* stat = f.pin->flow;
   const size_t owned = stat[0], nf = stat[1];
   if (stat[2]) for (auto& r : R) { if (!r->unparsed) r->first_unparsed = at + (m - stat[3]); r->unparsed += stat[2]; }
-  ch.at = at; ch.owned = owned; ch.nf = nf; ch.first.assign(K + 1, 0); ch.first_f.assign(K + 1, 0);
+  ch.pin = f.pin; ch.at = at; ch.owned = owned; ch.nf = nf; ch.first.assign(K + 1, 0); ch.first_f.assign(K + 1, 0);
   if (!owned) return ALEO_MI355X_OK;
-  for (size_t j = 0; j < K; ++j) { ch.first[j] = stat[4 + j]; ch.first_f[j] = stat[4 + K + j]; }      // a stage may use h_pinned, and moves these boundaries
+  for (size_t j = 0; j < K; ++j) { ch.first[j] = stat[4 + j]; ch.first_f[j] = stat[4 + K + j]; }      // a stage moves these boundaries
   ch.first[K] = (uint32_t)owned; ch.first_f[K] = (uint32_t)nf;
   for (size_t j = 0; j < K; ++j) {
     const size_t mine = ch.first[j + 1] - ch.first[j], mine_f = ch.first_f[j + 1] - ch.first_f[j];
@@ -305,44 +303,47 @@ static int32_t found_download(const FoundCall& f, const FoundChunk& ch, Found& t
   return ALEO_MI355X_OK;
 }
 
-int32_t found_many_on_device(Ctx* c, std::vector<std::unique_ptr<Found>>& R, const char* text, const uint64_t* offsets, size_t n, const ManyKeys& k, FoundStage* stage) {
-  FoundCall f{}; f.c = c; f.s = c->stream; f.stage = stage; f.K = k.args.size(); f.cap = decrypt_chunk_fields(); f.stat_words = 4 + 2 * f.K;
-  std::vector<ScanArgs> table;                                // outlives the call's last synchronisation
-  const size_t K = f.K, chunk = scan_many_plan(n, k, &f.W, &table);
-  StringSource src{text, offsets, nullptr};
-  src.cut_chunks(n, chunk);
-  const size_t M = src.max_records, NB = (M + FOUND_BLOCK - 1) / FOUND_BLOCK, P = M * K;
-  int32_t rc;
-  if ((rc = records_constants(c, &f.dK))) return rc;
-  if ((rc = ensure_host_pinned(c, f.stat_words * 4))) return rc;
-  Carve cv;
-  const size_t o_keys = cv.part(table.size() * sizeof(ScanArgs)), o_c0 = cv.part(M * 32), o_nx = cv.part(M * 32), o_rvk = cv.part(P * 32), o_fl = cv.part(P), o_scan = cv.part(P), o_pre = cv.part(P),
-               o_cnt = cv.part(P * 4), o_pos = cv.part(P * 4), o_blk = cv.part(2 * K * NB * 4), o_stat = cv.part(f.stat_words * 4), o_str = cv.part(src.scratch_bytes());
-  if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
-  char* base = c->scalars_stage.as<char>();
-  f.dkeys = (const ScanArgs*)(base + o_keys); f.dc0 = base + o_c0; f.dnx = base + o_nx; f.drvk = base + o_rvk; f.dstr = base + o_str;
-  f.dfl = (uint8_t*)(base + o_fl); f.dscan = (uint8_t*)(base + o_scan); f.dpre = (uint8_t*)(base + o_pre);
-  f.dcnt = (uint32_t*)(base + o_cnt); f.dpos = (uint32_t*)(base + o_pos); f.dblk = (uint32_t*)(base + o_blk); f.dstat = (uint32_t*)(base + o_stat);
-  HIPCHK(hipMemcpyAsync(base + o_keys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, f.s));
-  src.parts(f.dstr, &f.dsoff, &f.dkinds, &f.dtext);
-  // Where a chunk's compacted arrays come down, all keys' one after another: staging arrays that are split into the K results — or, when there is one key and
-  // everything is its own, the tail of its result, which saves a host copy of everything owned (120 MB at 2^20 records all owned).
-  Found staged;
-  Found& to = K == 1 ? *R[0] : staged;
-  for (auto& r : R) r->first_unparsed = n;
-  for (size_t ck = 0; ck + 1 < src.cut.size(); ++ck) {
-    FoundChunk ch;
-    if ((rc = found_count(f, src, ck, R, ch))) return rc;
-    if (!ch.owned) continue;
-    const size_t put = K == 1 ? to.index.size() : 0, put_f = K == 1 ? to.offsets.back() : 0;      // `staged` starts over with every chunk
-    if ((rc = found_gather_decrypt(f, src.cut[ck + 1] - src.cut[ck], ch, to, put, put_f))) return rc;
-    if (stage) {                                               // from here on `ch` is what the stage kept
-      if ((rc = stage->filter(c, f.s, ch))) return rc;
+int32_t found_many_on_device(std::vector<std::unique_ptr<Found>>& R, const char* text, const uint64_t* offsets, size_t n, const ManyKeys& k, FoundStage* stage) {
+  FoundCall f{}; f.stage = stage; f.K = k.args.size(); f.cap = env_cap("ALEO_MI355X_DECRYPT_CHUNK_FIELDS", DECRYPT_CHUNK_FIELDS); f.stat_words = 4 + 2 * f.K;
+  // The host ends of the flow's copies are declared outside the slot, as R and the stage are: the key table, the source's offsets, and where a chunk's compacted
+  // arrays come down, all keys' one after another: staging arrays that are split into the K results — or, when there is one key and everything is its own, the
+  // tail of its result, which saves a host copy of everything owned (120 MB at 2^20 records all owned).
+  std::vector<ScanArgs> table; StringSource src{text, offsets, nullptr}; Found staged;
+  Found& to = f.K == 1 ? *R[0] : staged;
+  return on_slot([&](Ctx* c) -> int32_t {
+    f.c = c; f.s = c->stream;
+    int32_t rc;
+    if (stage && (rc = stage->begin(c, f.s))) return rc;      // its uploads run while the host cuts the chunks
+    const size_t K = f.K, chunk = scan_many_plan(n, k, &f.W, &table);
+    src.cut_chunks(n, chunk);
+    const size_t M = src.max_records, NB = (M + FOUND_BLOCK - 1) / FOUND_BLOCK, P = M * K;
+    if ((rc = records_constants(c, &f.dK))) return rc;
+    if ((rc = found_pinned(c, &f.pin))) return rc;
+    Carve cv;
+    const size_t o_keys = cv.part(table.size() * sizeof(ScanArgs)), o_c0 = cv.part(M * 32), o_nx = cv.part(M * 32), o_rvk = cv.part(P * 32), o_fl = cv.part(P), o_scan = cv.part(P), o_pre = cv.part(P),
+                 o_cnt = cv.part(P * 4), o_pos = cv.part(P * 4), o_blk = cv.part(2 * K * NB * 4), o_stat = cv.part(f.stat_words * 4), o_str = cv.part(src.scratch_bytes());
+    if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
+    char* base = c->scalars_stage.as<char>();
+    f.dkeys = (const ScanArgs*)(base + o_keys); f.dc0 = base + o_c0; f.dnx = base + o_nx; f.drvk = base + o_rvk; f.dstr = base + o_str;
+    f.dfl = (uint8_t*)(base + o_fl); f.dscan = (uint8_t*)(base + o_scan); f.dpre = (uint8_t*)(base + o_pre);
+    f.dcnt = (uint32_t*)(base + o_cnt); f.dpos = (uint32_t*)(base + o_pos); f.dblk = (uint32_t*)(base + o_blk); f.dstat = (uint32_t*)(base + o_stat);
+    HIPCHK(hipMemcpyAsync(base + o_keys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, f.s));
+    src.parts(f.dstr, &f.dsoff, &f.dkinds, &f.dtext);
+    for (auto& r : R) r->first_unparsed = n;
+    for (size_t ck = 0; ck + 1 < src.cut.size(); ++ck) {
+      FoundChunk ch;
+      if ((rc = found_count(f, src, ck, R, ch))) return rc;
       if (!ch.owned) continue;
+      const size_t put = K == 1 ? to.index.size() : 0, put_f = K == 1 ? to.offsets.back() : 0;      // `staged` starts over with every chunk
+      if ((rc = found_gather_decrypt(f, src.cut[ck + 1] - src.cut[ck], ch, to, put, put_f))) return rc;
+      if (stage) {                                               // from here on `ch` is what the stage kept
+        if ((rc = stage->filter(c, f.s, ch))) return rc;
+        if (!ch.owned) continue;
+      }
+      if ((rc = found_download(f, ch, to, put, put_f, R))) return rc;
     }
-    if ((rc = found_download(f, ch, to, put, put_f, R))) return rc;
-  }
-  return ALEO_MI355X_OK;
+    return ALEO_MI355X_OK;
+  });
 }
 
 static int32_t decrypt_strings_many(Found** out, const char* text, const uint64_t* offsets, size_t n, const void* view_keys32, const void* address_xs32, size_t n_keys, bool may_route) {
@@ -356,7 +357,7 @@ static int32_t decrypt_strings_many(Found** out, const char* text, const uint64_
   int32_t rc = ALEO_MI355X_OK;
   if (!may_route || n * n_keys < aleo_mi355x_min_records() || n == 0)      // in pairs, as records_scan_strings counts
     for (size_t j = 0; j < n_keys && !rc; ++j) rc = found_on_host(*R[j], text, offsets, n, k.args[j], k.addr[j]);
-  else { Slot sl; rc = sl.rc ? sl.rc : found_many_on_device(sl.c, R, text, offsets, n, k); }
+  else rc = found_many_on_device(R, text, offsets, n, k);
   if (rc) return rc;
   for (size_t j = 0; j < n_keys; ++j) out[j] = R[j].release();
   return ALEO_MI355X_OK;

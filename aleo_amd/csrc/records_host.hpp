@@ -1,4 +1,5 @@
-// records_host.hpp — the host side of the record ownership scan (records.hip): the constants of a scan, the recoding of the scalar, and the whole test
+// records_host.hpp — the host side of the record ownership scan (records.hip): the constants of a scan, the builder of the word tables the lanes read
+// (WordTable: the scan's own, and those of the serial-number, commitment and signature lanes on top of it), the recoding of the scalar, and the whole test
 // on the CPU from host_field.hpp and poseidon.hpp.  Plain C++ (no HIP): records.hip builds the library's entry points on it, and
 // tests/cpp/records_lane_emul.cpp runs the device lane's code (records_lane.h) against it on the host.
 #pragma once
@@ -22,15 +23,31 @@ struct RecordsConsts {
   std::vector<uint32_t> words;                               // the same for the device: records_lane.h RK_*
 };
 
-static void put29(uint32_t* dst, const HFr& mont) {         // Montgomery R = 2^256 -> the limbs of value * 2^261 mod r
-  static const HFr k32 = HFr::from_u64(32);
-  const HFr v = HFr::mul(mont, k32);
+static void put_plain29(uint32_t* dst, const uint64_t* v) {  // a number of four words -> its 29-bit limbs
   for (int i = 0; i < 9; ++i) {
     const int pos = 29 * i, j = pos >> 6, sh = pos & 63;
-    uint64_t w = v.l[j] >> sh; if (sh > 35 && j + 1 < 4) w |= v.l[j + 1] << (64 - sh);
+    uint64_t w = v[j] >> sh; if (sh > 35 && j + 1 < 4) w |= v[j + 1] << (64 - sh);
     dst[i] = (uint32_t)w & 0x1fffffffu;
   }
 }
+static void put29(uint32_t* dst, const HFr& mont) {         // Montgomery R = 2^256 -> the limbs of value * 2^261 mod r
+  static const HFr k32 = HFr::from_u64(32);
+  put_plain29(dst, HFr::mul(mont, k32).l);
+}
+
+struct EdH { HFr X, Y, Z, T; };
+
+// The words of a lane's table as the device reads them, for every host that builds one (records_consts below; serial_host.hpp, commit_host.hpp,
+// signature_host.hpp): `total` words, zero but for the RK_* prefix when there is one, then entries of nine limbs each at entry index idx.
+struct WordTable {
+  std::vector<uint32_t> words; HFr d2;
+  explicit WordTable(size_t total) : words(total, 0) {}                                          // the records constants themselves
+  WordTable(size_t total, const RecordsConsts& C) : words(total, 0), d2(C.d2) { std::memcpy(words.data(), C.words.data(), RK_WORDS * 4); }
+  void put(uint32_t idx, const HFr& v) { put29(words.data() + 9 * idx, v); }
+  void put_plain(uint32_t idx, const uint64_t* v) { put_plain29(words.data() + 9 * idx, v); }   // a number as it stands, not in Montgomery form
+  void put_cached(uint32_t idx, const EdH& p) { put(idx, HFr::sub(p.Y, p.X)); put(idx + 1, HFr::add(p.Y, p.X)); put(idx + 2, HFr::mul(p.T, d2)); }      // Z = 1: (Y - X, Y + X, T 2d)
+  void put_exponent(uint32_t word, const uint64_t* e) { for (int i = 0; i < 4; ++i) { words[word + 2 * i] = (uint32_t)e[i]; words[word + 2 * i + 1] = (uint32_t)(e[i] >> 32); } }      // at a word index
+};
 
 static const RecordsConsts& records_consts() {
   static const RecordsConsts C = [] {
@@ -51,27 +68,24 @@ static const RecordsConsts& records_consts() {
     s[1] = HFr::add(s[1], host::fr_domain_separator("AleoSymmetricEncryption0"));
     for (int i = 0; i < 9; ++i) c.s0[i] = s[i];
     // the device's copy
-    c.words.assign(RK_WORDS, 0);
-    auto put = [&](uint32_t idx, const HFr& v) { put29(c.words.data() + 9 * idx, v); };
-    put(RK_R2, HFr::pow_u64(HFr::from_u64(2), 261)); put(RK_ONE, HFr::one()); put(RK_D, c.d); put(RK_D2, c.d2);
-    for (int i = 0; i < 9; ++i) put(RK_S0 + i, c.s0[i]);
+    WordTable w(RK_WORDS);
+    w.put(RK_R2, HFr::pow_u64(HFr::from_u64(2), 261)); w.put(RK_ONE, HFr::one()); w.put(RK_D, c.d); w.put(RK_D2, c.d2);
+    for (int i = 0; i < 9; ++i) w.put(RK_S0 + i, c.s0[i]);
     constexpr int H = host::POSEIDON_FULL / 2, RP = host::POSEIDON_PARTIAL;
-    for (int r = 0; r < H; ++r) for (int i = 0; i < 9; ++i) put(RK_ARK_HEAD + 9 * r + i, P.ark[r][i]);
-    for (int i = 0; i < 9; ++i) for (int j = 0; j < 9; ++j) { put(RK_MDS + 9 * i + j, P.mds[i][j]); put(RK_PRE + 9 * i + j, P.pre[i][j]); }
+    for (int r = 0; r < H; ++r) for (int i = 0; i < 9; ++i) w.put(RK_ARK_HEAD + 9 * r + i, P.ark[r][i]);
+    for (int i = 0; i < 9; ++i) for (int j = 0; j < 9; ++j) { w.put(RK_MDS + 9 * i + j, P.mds[i][j]); w.put(RK_PRE + 9 * i + j, P.pre[i][j]); }
     for (int j = 0; j < RP; ++j) {
       const uint32_t base = RK_PART + 18 * j;
-      put(base, P.sp_c[j]); put(base + 1, P.sp_m00[j]);
-      for (int i = 0; i < 8; ++i) { put(base + 2 + i, P.sp_v[j][i]); put(base + 10 + i, P.sp_w[j][i]); }
+      w.put(base, P.sp_c[j]); w.put(base + 1, P.sp_m00[j]);
+      for (int i = 0; i < 8; ++i) { w.put(base + 2 + i, P.sp_v[j][i]); w.put(base + 10 + i, P.sp_w[j][i]); }
     }
-    for (int i = 0; i < 9; ++i) put(RK_ARK_AFTER + i, P.ark_after[i]);
-    for (int r = 0; r < 3; ++r) for (int i = 0; i < 9; ++i) put(RK_ARK_TAIL + 9 * r + i, P.ark[H + RP + 1 + r][i]);
+    for (int i = 0; i < 9; ++i) w.put(RK_ARK_AFTER + i, P.ark_after[i]);
+    for (int r = 0; r < 3; ++r) for (int i = 0; i < 9; ++i) w.put(RK_ARK_TAIL + 9 * r + i, P.ark[H + RP + 1 + r][i]);
     HFr g = c.sq.c;
-    for (int j = 0; j < RK_TWO_ADICITY; ++j) { put(RK_ROOTS + j, g); g = HFr::sqr(g); }
+    for (int j = 0; j < RK_TWO_ADICITY; ++j) { w.put(RK_ROOTS + j, g); g = HFr::sqr(g); }
     uint64_t rm2[4]; std::memcpy(rm2, host::HParams<4>::P, 32); rm2[0] -= 2;
-    for (int i = 0; i < 4; ++i) {
-      c.words[RK_EXP_SQRT + 2 * i] = (uint32_t)c.sq.e[i]; c.words[RK_EXP_SQRT + 2 * i + 1] = (uint32_t)(c.sq.e[i] >> 32);
-      c.words[RK_EXP_INV + 2 * i] = (uint32_t)rm2[i]; c.words[RK_EXP_INV + 2 * i + 1] = (uint32_t)(rm2[i] >> 32);
-    }
+    w.put_exponent(RK_EXP_SQRT, c.sq.e); w.put_exponent(RK_EXP_INV, rm2);
+    c.words = std::move(w.words);
     return c;
   }();
   return C;
@@ -95,7 +109,6 @@ static void recode_scalar(ScanArgs& a, const uint64_t* v4) {
 }
 
 // ---- the host path --------------------------------------------------------------------------------------------------------------------------------
-struct EdH { HFr X, Y, Z, T; };
 static inline void edh_dbl(EdH& p) {                         // dbl-2008-hwcd, a = -1
   const HFr A = HFr::sqr(p.X), B = HFr::sqr(p.Y), C = HFr::dbl(HFr::sqr(p.Z)), E = HFr::sub(HFr::sub(HFr::sqr(HFr::add(p.X, p.Y)), A), B);
   const HFr G = HFr::sub(B, A), F = HFr::sub(G, C), Hh = HFr::neg(HFr::add(A, B));
@@ -155,11 +168,7 @@ static const char* scan_args(ScanArgs& a, HFr& addr_mont, const void* view_key32
   if (HFr::geq_p(ax.l)) return "records_scan: the address x-coordinate is not a canonical field element";
   recode_scalar(a, v);
   addr_mont = HFr::to_mont(ax);
-  for (int i = 0; i < 9; ++i) {
-    const int pos = 29 * i, j = pos >> 6, sh = pos & 63;
-    uint64_t w = ax.l[j] >> sh; if (sh > 35 && j + 1 < 4) w |= ax.l[j + 1] << (64 - sh);
-    a.addr[i] = (uint32_t)w & 0x1fffffffu;
-  }
+  put_plain29(a.addr, ax.l);
   return nullptr;
 }
 

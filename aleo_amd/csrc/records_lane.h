@@ -44,6 +44,14 @@ __device__ __forceinline__ F29 rk_const(const uint32_t* __restrict__ K, uint32_t
   for (int i = 0; i < 9; ++i) r.v[i] = K[idx * 9 + i];
   return r; }
 
+#ifdef __HIPCC__
+// the 32 bytes at p (16-byte aligned) as eight words, by two 16-byte loads: how the kernels hand a lane a field that lies in device memory
+__device__ __forceinline__ void load_words8(uint32_t (&w)[8], const char* p) {
+  const uint4* q = (const uint4*)p; const uint4 l = q[0], h = q[1];
+  w[0] = l.x; w[1] = l.y; w[2] = l.z; w[3] = l.w; w[4] = h.x; w[5] = h.y; w[6] = h.z; w[7] = h.w;
+}
+#endif
+
 // a^e for an exponent of `bits` bits (its top bit set) held in uniform words; a normalised
 __device__ __forceinline__ F29 f29_pow(const F29& a, const uint32_t* __restrict__ e, int bits) {
   F29 acc = a;

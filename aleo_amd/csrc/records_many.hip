@@ -114,37 +114,39 @@ void launch_scan_keys(hipStream_t s, uint32_t W, uint8_t* dflags, char* drvk, co
 
 // The records of a chunk reach dc0 / dnx either as the caller's rows, by two copies, or from `strings` (records_strings.h): its text goes up and k_records_parse
 // writes the rows; its chunks are cut at the character cap as well, and k_records_resolve follows the scan kernel.
-int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings) {
+int32_t scan_many_on_device(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings) {
   const size_t n_keys = k.args.size();
-  uint32_t W; std::vector<ScanArgs> table;                    // the table is a local of this call: it outlives every chunk's synchronisation
+  uint32_t W; std::vector<ScanArgs> table;                    // the table and the source's offsets are declared outside the slot: they outlive every copy that reads them
   const size_t chunk = scan_many_plan(n, k, &W, &table);
   if (strings) strings->cut_chunks(n, chunk);
-  hipStream_t s = c->stream;
-  int32_t rc;
-  const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
-  Carve cv;
-  const size_t o_keys = cv.part(table.size() * sizeof(ScanArgs)), o_c0 = cv.part(chunk * 32), o_nx = cv.part(chunk * 32), o_rvk = cv.part(chunk * n_keys * 32), o_fl = cv.part(chunk * n_keys),
-               o_str = cv.part(strings ? strings->scratch_bytes() : 0);
-  if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
-  char* base = c->scalars_stage.as<char>();
-  char* dkeys = base + o_keys; char* dc0 = base + o_c0; char* dnx = base + o_nx; char* drvk = base + o_rvk; uint8_t* dfl = (uint8_t*)(base + o_fl); char* dstr = base + o_str;
-  HIPCHK(hipMemcpyAsync(dkeys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, s));
-  for (size_t at = 0, ck = 0, m; at < n; at += m, ++ck) {
-    m = strings ? strings->cut[ck + 1] - at : (n - at < chunk ? n - at : chunk);
-    if (strings) { if ((rc = strings->fill(s, ck, dstr, dc0, dnx))) return rc; }
-    else {
-      HIPCHK(hipMemcpyAsync(dc0, (const char*)owner_c0 + at * 32, m * 32, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(dnx, (const char*)nonce_x + at * 32, m * 32, hipMemcpyHostToDevice, s));
+  return on_slot([&](Ctx* c) -> int32_t {
+    hipStream_t s = c->stream;
+    int32_t rc;
+    const uint32_t* dK; if ((rc = records_constants(c, &dK))) return rc;
+    Carve cv;
+    const size_t o_keys = cv.part(table.size() * sizeof(ScanArgs)), o_c0 = cv.part(chunk * 32), o_nx = cv.part(chunk * 32), o_rvk = cv.part(chunk * n_keys * 32), o_fl = cv.part(chunk * n_keys),
+                 o_str = cv.part(strings ? strings->scratch_bytes() : 0);
+    if ((rc = c->scalars_stage.reserve(cv.total))) return rc;
+    char* base = c->scalars_stage.as<char>();
+    char* dkeys = base + o_keys; char* dc0 = base + o_c0; char* dnx = base + o_nx; char* drvk = base + o_rvk; uint8_t* dfl = (uint8_t*)(base + o_fl); char* dstr = base + o_str;
+    HIPCHK(hipMemcpyAsync(dkeys, table.data(), table.size() * sizeof(ScanArgs), hipMemcpyHostToDevice, s));
+    for (size_t at = 0, ck = 0, m; at < n; at += m, ++ck) {
+      m = strings ? strings->cut[ck + 1] - at : (n - at < chunk ? n - at : chunk);
+      if (strings) { if ((rc = strings->fill(s, ck, dstr, dc0, dnx))) return rc; }
+      else {
+        HIPCHK(hipMemcpyAsync(dc0, (const char*)owner_c0 + at * 32, m * 32, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dnx, (const char*)nonce_x + at * 32, m * 32, hipMemcpyHostToDevice, s));
+      }
+      launch_scan_keys(s, W, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys);
+      HIPCHK(hipGetLastError());
+      if (strings && (rc = strings->resolve(s, ck, dstr, dfl, drvk, dc0, (const ScanArgs*)dkeys, n_keys))) return rc;
+      // rows of m on the device, rows of n at the caller
+      HIPCHK(hipMemcpy2DAsync(flags + at, n, dfl, m, m, n_keys, hipMemcpyDeviceToHost, s));
+      if (rvk_out) HIPCHK(hipMemcpy2DAsync((char*)rvk_out + at * 32, n * 32, drvk, m * 32, m * 32, n_keys, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
     }
-    launch_scan_keys(s, W, dfl, drvk, dc0, dnx, m, dK, (const ScanArgs*)dkeys, n_keys);
-    HIPCHK(hipGetLastError());
-    if (strings && (rc = strings->resolve(s, ck, dstr, dfl, drvk, dc0, (const ScanArgs*)dkeys, n_keys))) return rc;
-    // rows of m on the device, rows of n at the caller
-    HIPCHK(hipMemcpy2DAsync(flags + at, n, dfl, m, m, n_keys, hipMemcpyDeviceToHost, s));
-    if (rvk_out) HIPCHK(hipMemcpy2DAsync((char*)rvk_out + at * 32, n * 32, drvk, m * 32, m * 32, n_keys, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
-  }
-  return ALEO_MI355X_OK;
+    return ALEO_MI355X_OK;
+  });
 }
 
 }  // namespace aleo_mi355x
@@ -165,8 +167,7 @@ int32_t aleo_mi355x_records_scan_many(uint8_t* flags, void* rvk_out, const void*
     ManyKeys k; if (int32_t rc = many_keys(k, view_keys32, address_xs32, n_keys)) return rc;
     if (n * n_keys < aleo_mi355x_min_records() || n == 0) return scan_many_on_host(flags, rvk_out, owner_c0, nonce_x, n, k);      // in pairs: such a call runs at width 1, one lane's chain like a single scan
     if (!flags || !owner_c0 || !nonce_x) return bad_arg("records_scan_many: null buffer");
-    Slot sl; if (sl.rc) return sl.rc;
-    return scan_many_on_device(sl.c, flags, rvk_out, owner_c0, nonce_x, n, k);
+    return scan_many_on_device(flags, rvk_out, owner_c0, nonce_x, n, k);
   });
 }
 

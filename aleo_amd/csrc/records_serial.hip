@@ -37,24 +37,13 @@ __global__ void __launch_bounds__(SERIAL_BLOCK) k_records_serial(char* __restric
   flags[rank] = (uint8_t)flag;
 }
 
-// The tables of one device: uploaded once, under the lock, and never freed; the copy is complete before the pointer is handed out.
 int32_t serial_tables_on_device(int device, const uint32_t** out) {
-  static std::mutex mu; static std::map<int, const uint32_t*> resident;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = resident.find(device);
-  if (it == resident.end()) {
-    const SerialTables& T = serial::serial_tables();
-    DevTmp buf; if (int32_t rc = buf.alloc((size_t)SK_WORDS * 4)) return rc;
-    HIPCHK(hipMemcpy(buf.p, T.words.data(), (size_t)SK_WORDS * 4, hipMemcpyHostToDevice));
-    it = resident.emplace(device, (const uint32_t*)buf.release()).first;
-  }
-  *out = it->second; return ALEO_MI355X_OK;
+  return resident_table(device, ResidentTable::SERIAL, []() -> const std::vector<uint32_t>& { return serial::serial_tables().words; }, out);
 }
 
-static size_t serial_chunk_cap() { const size_t cap = env_size("ALEO_MI355X_SERIAL_CHUNK", SERIAL_CHUNK); return cap == 0 || cap > SERIAL_CHUNK ? SERIAL_CHUNK : cap; }
-
 int32_t launch_records_serial(hipStream_t s, char* dsn, uint8_t* dflags, const char* dcm, const uint32_t* dK, const SerialArgs* dkeys, const UnspentSegs& seg) {
-  const uint32_t waves = seg.wave0[seg.n_keys], per = serial_chunk_cap() < 64 ? 1 : (uint32_t)(serial_chunk_cap() / 64);
+  const size_t cap = env_cap("ALEO_MI355X_SERIAL_CHUNK", SERIAL_CHUNK);
+  const uint32_t waves = seg.wave0[seg.n_keys], per = cap < 64 ? 1 : (uint32_t)(cap / 64);
   for (uint32_t lo = 0; lo < waves; lo += per) {
     const uint32_t hi = waves - lo < per ? waves : lo + per;
     hipLaunchKernelGGL(k_records_serial, dim3((hi - lo + SERIAL_BLOCK / 64 - 1) / (SERIAL_BLOCK / 64)), dim3(SERIAL_BLOCK), 0, s, dsn, dflags, dcm, dK, dkeys, seg, lo, hi);
@@ -63,40 +52,36 @@ int32_t launch_records_serial(hipStream_t s, char* dsn, uint8_t* dflags, const c
   return ALEO_MI355X_OK;
 }
 
-// One key: a table of one row and, per chunk, one segment over the chunk.  `a` outlives the call's last synchronisation.
-static int32_t serials_on_device(Ctx* c, void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const SerialArgs& a) {
-  const uint32_t* dK; if (int32_t rc = serial_tables_on_device(c->device, &dK)) return rc;
-  const size_t cap = serial_chunk_cap();
-  const size_t chunk = n < cap ? n : cap;
-  hipStream_t s = c->stream;
-  Carve cv;
-  const size_t o_key = cv.part(sizeof(SerialArgs)), o_cm = cv.part(chunk * 32), o_sn = cv.part(chunk * 32), o_fl = cv.part(chunk);
-  if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
-  char* base = c->scalars_stage.as<char>();
-  char* dcm = base + o_cm; char* dsn = base + o_sn; uint8_t* dfl = (uint8_t*)(base + o_fl);
-  HIPCHK(hipMemcpyAsync(base + o_key, &a, sizeof a, hipMemcpyHostToDevice, s));
-  for (size_t at = 0; at < n; at += chunk) {
-    const size_t m = n - at < chunk ? n - at : chunk;
-    UnspentSegs seg{}; seg.n_keys = 1; seg.rank0[1] = (uint32_t)m; seg.wave0[1] = (uint32_t)((m + 63) / 64);
-    HIPCHK(hipMemcpyAsync(dcm, (const char*)commitments32 + at * 32, m * 32, hipMemcpyHostToDevice, s));
-    if (int32_t rc = launch_records_serial(s, dsn, dfl, dcm, dK, (const SerialArgs*)(base + o_key), seg)) return rc;
-    HIPCHK(hipMemcpyAsync((char*)sn_out + at * 32, dsn, m * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
-  }
-  return ALEO_MI355X_OK;
+// One key: a table of one row and, per chunk, one segment over the chunk.  The row is declared outside the slot: it outlives the copy that reads it.
+static int32_t serials_on_device(void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const ScanArgs& key) {
+  const SerialArgs a = serial_args_of(key);
+  const size_t cap = env_cap("ALEO_MI355X_SERIAL_CHUNK", SERIAL_CHUNK), chunk = n < cap ? n : cap;
+  return on_slot([&](Ctx* c) -> int32_t {
+    const uint32_t* dK; if (int32_t rc = serial_tables_on_device(c->device, &dK)) return rc;
+    hipStream_t s = c->stream;
+    Carve cv;
+    const size_t o_key = cv.part(sizeof(SerialArgs)), o_cm = cv.part(chunk * 32), o_sn = cv.part(chunk * 32), o_fl = cv.part(chunk);
+    if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
+    char* base = c->scalars_stage.as<char>();
+    char* dcm = base + o_cm; char* dsn = base + o_sn; uint8_t* dfl = (uint8_t*)(base + o_fl);
+    HIPCHK(hipMemcpyAsync(base + o_key, &a, sizeof a, hipMemcpyHostToDevice, s));
+    for (size_t at = 0; at < n; at += chunk) {
+      const size_t m = n - at < chunk ? n - at : chunk;
+      UnspentSegs seg{}; seg.n_keys = 1; seg.rank0[1] = (uint32_t)m; seg.wave0[1] = (uint32_t)((m + 63) / 64);
+      HIPCHK(hipMemcpyAsync(dcm, (const char*)commitments32 + at * 32, m * 32, hipMemcpyHostToDevice, s));
+      if (int32_t rc = launch_records_serial(s, dsn, dfl, dcm, dK, (const SerialArgs*)(base + o_key), seg)) return rc;
+      HIPCHK(hipMemcpyAsync((char*)sn_out + at * 32, dsn, m * 32, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(flags + at, dfl, m, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
+    }
+    return ALEO_MI355X_OK;
+  });
 }
 
 static int32_t serial_numbers(void* sn_out, uint8_t* flags, const void* commitments32, size_t n, const void* sk_sig32, bool may_route) {
   if (!sk_sig32 || ((!sn_out || !flags || !commitments32) && n)) return bad_arg("records_serial_numbers: null buffer");
   ScanArgs key; if (!serial::serial_key(key, sk_sig32)) return bad_arg("records_serial_numbers: sk_sig is not a canonical scalar below the subgroup order");
-  if (may_route && n && n >= aleo_mi355x_min_serials()) {
-    const SerialArgs a = serial_args_of(key);
-    Slot sl; if (sl.rc) return sl.rc;
-    const int32_t rc = serials_on_device(sl.c, sn_out, flags, commitments32, n, a);
-    if (rc) (void)hipStreamSynchronize(sl.c->stream);        // the key's row may still be on its way up
-    return rc;
-  }
+  if (may_route && n && n >= aleo_mi355x_min_serials()) return serials_on_device(sn_out, flags, commitments32, n, key);
   const SerialTables& T = serial::serial_tables();
   for (size_t i = 0; i < n; ++i) flags[i] = serial::serial_one_host((uint8_t*)sn_out + 32 * i, (const uint8_t*)commitments32 + 32 * i, key, T);
   return ALEO_MI355X_OK;

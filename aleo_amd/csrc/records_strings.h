@@ -8,6 +8,11 @@
 
 namespace aleo_mi355x {
 
+// *dK: the records constants (records_lane.h RK_*) resident on the slot's device: what the scan, the decryption and the walks between them read
+inline int32_t records_constants(Ctx* c, const uint32_t** dK) {
+  return resident_table(c->device, ResidentTable::RECORDS, []() -> const std::vector<uint32_t>& { return records_consts().words; }, dK);
+}
+
 static constexpr uint32_t SCAN_MANY_KEYS = 64;               // the accounts of one call: many_keys refuses more, and the per-key tables are sized by it
 struct ManyKeys { std::vector<ScanArgs> args; std::vector<HFr> addr; };
 
@@ -52,8 +57,8 @@ int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offse
 
 // records_many.hip
 int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32, size_t n_keys);
-// the records come as rows (owner_c0, nonce_x) or, when `strings` is given, from it
-int32_t scan_many_on_device(Ctx* c, uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings = nullptr);
+// the records come as rows (owner_c0, nonce_x) or, when `strings` is given, from it; takes a slot for itself (entry.h on_slot)
+int32_t scan_many_on_device(uint8_t* flags, void* rvk_out, const void* owner_c0, const void* nonce_x, size_t n, const ManyKeys& k, StringSource* strings = nullptr);
 // the plan of a scan of k's keys over n records — the records of one launch (the pair cap, the record cap, n), *W, the keys one lane takes, and the table of the
 // keys padded with zero entries to a multiple of W — and that launch over m records already on the device (flags m x n_keys B, rvk m x n_keys x 32 B,
 // [key][record]; dkeys: the table); the caller checks hipGetLastError
@@ -61,7 +66,7 @@ size_t scan_many_plan(size_t n, const ManyKeys& k, uint32_t* W, std::vector<Scan
 void launch_scan_keys(hipStream_t s, uint32_t W, uint8_t* dflags, char* drvk, const char* dc0, const char* dnx, size_t m, const uint32_t* dK, const ScanArgs* dkeys, size_t n_keys);
 
 // records_decrypt.hip
-size_t decrypt_chunk_fields();                                // the field cap of one k_records_decrypt launch (ALEO_MI355X_DECRYPT_CHUNK_FIELDS, read per call)
+static constexpr size_t DECRYPT_CHUNK_FIELDS = (size_t)1 << 22;      // the field cap of one k_records_decrypt launch; ALEO_MI355X_DECRYPT_CHUNK_FIELDS (read per call) lowers it
 // the end of the launch that starts at record `at` of n (offsets: n + 1 field boundaries): whole records within the two caps, one at least
 size_t decrypt_cut(const uint32_t* offsets, size_t at, size_t n, size_t record_cap, size_t field_cap);
 // k_records_decrypt over n records already on the device: io the fields from offsets[0] on, in place; the caller checks hipGetLastError

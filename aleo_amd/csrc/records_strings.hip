@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(PARSE_BLOCK) k_records_resolve(uint8_t* __rest
 static inline size_t uploaded(const uint64_t* offsets, size_t i) { const uint64_t span = offsets[i + 1] - offsets[i]; return span > RS_MAX_CHARS ? 0 : (size_t)span; }
 
 void StringSource::cut_chunks(size_t n, size_t record_cap) {
-  size_t cap = env_size("ALEO_MI355X_SCAN_CHUNK_CHARS", STRINGS_CHUNK_CHARS); if (cap < 1 || cap > STRINGS_CHUNK_CHARS) cap = STRINGS_CHUNK_CHARS;
+  const size_t cap = env_cap("ALEO_MI355X_SCAN_CHUNK_CHARS", STRINGS_CHUNK_CHARS);
   cut.assign(1, 0); max_records = max_chars = 0;
   for (size_t at = 0; at < n;) {
     size_t e = at + 1, chars = uploaded(offsets, at);
@@ -168,24 +168,26 @@ void StringSource::parts(char* scratch, uint32_t** off, int8_t** kinds_, char** 
 }
 
 // parse_many on the device: the chunks of a scan over strings, the parse kernel alone, the rows copied back
-static int32_t parse_many_on_device(Ctx* c, int8_t* kinds, void* owner32, void* nonce32, const char* text, const uint64_t* offsets, size_t n) {
-  StringSource src{text, offsets, kinds};
+static int32_t parse_many_on_device(int8_t* kinds, void* owner32, void* nonce32, const char* text, const uint64_t* offsets, size_t n) {
+  StringSource src{text, offsets, kinds};                     // outside the slot: its offsets outlive the copies that read them
   src.cut_chunks(n, PARSE_CHUNK_RECORDS);
-  hipStream_t s = c->stream;
-  Carve cv;
-  const size_t o_c0 = cv.part(src.max_records * 32), o_nx = cv.part(src.max_records * 32), o_str = cv.part(src.scratch_bytes());
-  if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
-  char* base = c->scalars_stage.as<char>(); char* dc0 = base + o_c0; char* dnx = base + o_nx; char* dstr = base + o_str;
-  uint32_t* doff; int8_t* dkinds; char* dtext; src.parts(dstr, &doff, &dkinds, &dtext);
-  for (size_t k = 0; k + 1 < src.cut.size(); ++k) {
-    const size_t at = src.cut[k], m = src.cut[k + 1] - at;
-    if (int32_t rc = src.fill(s, k, dstr, dc0, dnx)) return rc;
-    HIPCHK(hipMemcpyAsync(kinds + at, dkinds, m, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync((char*)owner32 + at * 32, dc0, m * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync((char*)nonce32 + at * 32, dnx, m * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
-  }
-  return ALEO_MI355X_OK;
+  return on_slot([&](Ctx* c) -> int32_t {
+    hipStream_t s = c->stream;
+    Carve cv;
+    const size_t o_c0 = cv.part(src.max_records * 32), o_nx = cv.part(src.max_records * 32), o_str = cv.part(src.scratch_bytes());
+    if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
+    char* base = c->scalars_stage.as<char>(); char* dc0 = base + o_c0; char* dnx = base + o_nx; char* dstr = base + o_str;
+    uint32_t* doff; int8_t* dkinds; char* dtext; src.parts(dstr, &doff, &dkinds, &dtext);
+    for (size_t k = 0; k + 1 < src.cut.size(); ++k) {
+      const size_t at = src.cut[k], m = src.cut[k + 1] - at;
+      if (int32_t rc = src.fill(s, k, dstr, dc0, dnx)) return rc;
+      HIPCHK(hipMemcpyAsync(kinds + at, dkinds, m, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync((char*)owner32 + at * 32, dc0, m * 32, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync((char*)nonce32 + at * 32, dnx, m * 32, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));                         // the next chunk reuses the buffers
+    }
+    return ALEO_MI355X_OK;
+  });
 }
 
 }  // namespace aleo_mi355x
@@ -207,8 +209,7 @@ int32_t aleo_mi355x_records_parse_many(int8_t* kinds, void* owner32, void* nonce
     if ((!kinds || !owner32 || !nonce32) && n) return bad_arg("records_parse_many: null buffer");
     if (int32_t rc = strings_args_ok("records_parse_many", text, offsets, n)) return rc;
     if (n < aleo_mi355x_min_records() || n == 0) return parse_many_on_host(kinds, owner32, nonce32, text, offsets, n);
-    Slot sl; if (sl.rc) return sl.rc;
-    return parse_many_on_device(sl.c, kinds, owner32, nonce32, text, offsets, n);
+    return parse_many_on_device(kinds, owner32, nonce32, text, offsets, n);
   });
 }
 
@@ -229,9 +230,8 @@ int32_t aleo_mi355x_records_scan_strings(uint8_t* flags, int8_t* kinds, void* rv
     if (!flags && n) return bad_arg("records_scan_strings: null buffer");
     if (int32_t rc = strings_args_ok("records_scan_strings", text, offsets, n)) return rc;
     if (n * n_keys < aleo_mi355x_min_records() || n == 0) return scan_strings_on_host(flags, kinds, rvk_out, text, offsets, n, k);      // in pairs, as records_scan_many counts
-    Slot sl; if (sl.rc) return sl.rc;
     StringSource src{text, offsets, kinds};
-    return scan_many_on_device(sl.c, flags, rvk_out, nullptr, nullptr, n, k, &src);
+    return scan_many_on_device(flags, rvk_out, nullptr, nullptr, n, k, &src);
   });
 }
 

@@ -99,14 +99,14 @@ struct UnspentStage : FoundStage {
   const uint32_t* dK = nullptr; const SerialArgs* dkeys = nullptr; const uint32_t* dspent = nullptr; const uint32_t* dtable = nullptr; uint32_t cap = 0;
   std::vector<SerialArgs> table;                               // outlives the call's last synchronisation
   std::vector<uint32_t> h_index; std::vector<uint8_t> h_cm, h_sn, h_fl;
-  // unspent_named: no commitments come in; the stage computes them from the call's strings (records_commit.hip) in front of the serial numbers
-  const CommitCall* named = nullptr; const char* text = nullptr; const uint64_t* offsets = nullptr; CommitScratch H;
-  UnspentStage(const uint8_t* cm, const UnspentKeys& k, const uint8_t* sp, size_t ns) : commitments(cm), keys(k), spent(sp), n_spent(ns) {}
+  // unspent_named (named not null): no commitments come in; the stage computes them from the call's strings (records_commit.hip) in front of the serial numbers
+  const CommitCall* named; const char* text; const uint64_t* offsets; CommitScratch H;
+  UnspentStage(const uint8_t* cm, const UnspentKeys& k, const uint8_t* sp, size_t ns, const CommitCall* named_call, const char* strings, const uint64_t* string_offsets)
+      : commitments(cm), keys(k), spent(sp), n_spent(ns), named(named_call), text(strings), offsets(string_offsets) {}
 
   // once per call: the lane's tables, the keys' digits, and S with its table
-  int32_t begin(Ctx* c, hipStream_t s) {
+  int32_t begin(Ctx* c, hipStream_t s) override {
     if (int32_t rc = serial_tables_on_device(c->device, &dK)) return rc;
-    if (int32_t rc = ensure_host_pinned(c, 8192)) return rc;
     const size_t K = keys.serial.size();
     table.resize(K);
     for (size_t j = 0; j < K; ++j) table[j] = serial_args_of(keys.serial[j]);
@@ -146,7 +146,7 @@ struct UnspentStage : FoundStage {
     UnspentSegs seg{}; seg.n_keys = (uint32_t)K;
     for (size_t j = 0; j <= K; ++j) seg.rank0[j] = ch.first[j];
     for (size_t j = 0; j < K; ++j) seg.wave0[j + 1] = seg.wave0[j] + (ch.first[j + 1] - ch.first[j] + 63) / 64;
-    const size_t stat_words = 8 + 2 * (SCAN_MANY_KEYS + 1);
+    const size_t stat_words = sizeof(FoundPinned::stage) / 4;
     Carve cv;
     const size_t o_cm = cv.part(owned * 32), o_cf = cv.part(owned), o_route = cv.part(4), k_cm = cv.part(owned * 32), o_sn = cv.part(owned * 32), o_fl = cv.part(owned), o_keep = cv.part(owned), o_cnt = cv.part(owned * 4), o_pos = cv.part(owned * 4), o_blk = cv.part((size_t)2 * nb * 4),
                  o_stat = cv.part(stat_words * 4), k_fields = cv.part(nf * 32), k_index = cv.part(owned * 4), k_off = cv.part((owned + 1) * 4), k_mc = cv.part(owned * 8), k_rvk = cv.part(owned * 32),
@@ -181,7 +181,7 @@ struct UnspentStage : FoundStage {
                        (const uint32_t*)ch.index, (const int8_t*)ch.kind, (const char*)ch.rvk, (const uint32_t*)ch.off, (const uint64_t*)ch.mc, (const char*)dsn, (const char*)(b + o_cm), (const uint32_t*)dcnt,
                        (const uint32_t*)dpos, (const uint8_t*)dkeep, (const uint32_t*)dblk, seg, (uint32_t)owned);
     HIPCHK(hipGetLastError());
-    uint32_t* stat = (uint32_t*)((char*)c->h_pinned + 4096);  // behind the flow's own words; begin() made the room
+    uint32_t* stat = ch.pin->stage;
     HIPCHK(hipMemcpyAsync(stat, dstat, stat_words * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     kept.owned = stat[0]; kept.nf = stat[1];
@@ -244,12 +244,8 @@ static int32_t unspent_strings_many(Found** out, const char* text, const uint64_
     std::sort(sorted_spent.begin(), sorted_spent.end());
     for (size_t j = 0; j < n_keys && !rc; ++j) rc = unspent_on_host(*R[j], text, offsets, n, (const uint8_t*)commitments32, k, j, sorted_spent, named);
   } else {
-    Slot sl; if (sl.rc) return sl.rc;
-    UnspentStage stage((const uint8_t*)commitments32, k, (const uint8_t*)spent32, n_spent);
-    stage.named = named; stage.text = text; stage.offsets = offsets;
-    rc = stage.begin(sl.c, sl.c->stream);
-    if (!rc) rc = found_many_on_device(sl.c, R, text, offsets, n, k.scan, &stage);
-    if (rc) (void)hipStreamSynchronize(sl.c->stream);        // the stage's host buffers may still be on their way up
+    UnspentStage stage((const uint8_t*)commitments32, k, (const uint8_t*)spent32, n_spent, named, text, offsets);      // its host buffers outlive the flow's slot
+    rc = found_many_on_device(R, text, offsets, n, k.scan, &stage);
   }
   if (rc) return rc;
   for (size_t j = 0; j < n_keys; ++j) out[j] = R[j].release();

@@ -216,14 +216,6 @@ static bool elligator2(EdH& out, const HFr& r, const SerialTables& T) {
   return true;
 }
 
-static void put_plain29(uint32_t* dst, const uint64_t* v) {  // a number -> its 29-bit limbs
-  for (int i = 0; i < 9; ++i) {
-    const int pos = 29 * i, j = pos >> 6, sh = pos & 63;
-    uint64_t w = v[j] >> sh; if (sh > 35 && j + 1 < 4) w |= v[j + 1] << (64 - sh);
-    dst[i] = (uint32_t)w & 0x1fffffffu;
-  }
-}
-
 static const SerialTables& serial_tables() {
   static const SerialTables T = [] {
     SerialTables t;
@@ -252,10 +244,8 @@ static const SerialTables& serial_tables() {
       }
     }
     // the device's copy
-    t.words.assign(SK_WORDS, 0);
-    std::memcpy(t.words.data(), C.words.data(), RK_WORDS * 4);
-    auto put = [&](uint32_t idx, const HFr& v) { put29(t.words.data() + 9 * idx, v); };
-    auto put_entry = [&](uint32_t idx, const EdH& p) { put(idx, HFr::sub(p.Y, p.X)); put(idx + 1, HFr::add(p.Y, p.X)); put(idx + 2, HFr::mul(p.T, C.d2)); };      // Z = 1
+    WordTable wt(SK_WORDS, C);
+    auto put = [&](uint32_t idx, const HFr& v) { wt.put(idx, v); };
     const auto& P = host::PoseidonParams<4, 2>::get();
     for (int i = 0; i < 3; ++i) put(SK_S0 + i, t.s0[i]);
     for (int r = 0; r < host::POSEIDON_ROUNDS; ++r) for (int i = 0; i < 3; ++i) put(SK_ARK + 3 * r + i, P.ark[r][i]);
@@ -264,10 +254,11 @@ static const SerialTables& serial_tables() {
     put(SK_START, t.start.X); put(SK_START + 1, t.start.Y); put(SK_START + 2, t.start.Z); put(SK_START + 3, t.start.T);
     uint64_t half[4]; std::memcpy(half, host::HParams<4>::P, 32);
     for (int i = 0; i < 4; ++i) half[i] = (half[i] >> 1) | (i + 1 < 4 ? half[i + 1] << 63 : 0);      // (r - 1) / 2: r is odd
-    put_plain29(t.words.data() + 9 * SK_HALF, half);
-    for (int c = 0; c < SK_CHUNKS; ++c) for (int k = 0; k < 4; ++k) put_entry(SK_CHUNK + 3 * (4 * c + k), B.lookup[4 * (SK_FIRST_CHUNK + c) + k]);
-    for (size_t i = 0; i < t.rnd.size(); ++i) put_entry(SK_RND + 3 * (uint32_t)i, t.rnd[i]);
-    for (int i = 0; i < 4; ++i) { t.words[SK_EXP_LEG + 2 * i] = (uint32_t)half[i]; t.words[SK_EXP_LEG + 2 * i + 1] = (uint32_t)(half[i] >> 32); }
+    wt.put_plain(SK_HALF, half);
+    for (int c = 0; c < SK_CHUNKS; ++c) for (int k = 0; k < 4; ++k) wt.put_cached(SK_CHUNK + 3 * (4 * c + k), B.lookup[4 * (SK_FIRST_CHUNK + c) + k]);
+    for (size_t i = 0; i < t.rnd.size(); ++i) wt.put_cached(SK_RND + 3 * (uint32_t)i, t.rnd[i]);
+    wt.put_exponent(SK_EXP_LEG, half);
+    t.words = std::move(wt.words);
     return t;
   }();
   return T;

@@ -99,22 +99,19 @@ static const SigTables& sig_tables() {
     const HFr arg = HFr::mul(HFr::mul(HFr::sqr(HFr::mul(nl, dl)), du), HFr::mul(HFr::sqr(nu), nu));
     const HFr kappa = HFr::pow(arg, quart, 4);
     // the device's copy
-    t.words.assign(SG_WORDS, 0);
-    std::memcpy(t.words.data(), C.words.data(), RK_WORDS * 4);
-    auto put = [&](uint32_t idx, const HFr& v) { put29(t.words.data() + 9 * idx, v); };
+    WordTable wt(SG_WORDS, C);
+    auto put = [&](uint32_t idx, const HFr& v) { wt.put(idx, v); };
     put(SG_TWO, HFr::from_u64(2)); put(SG_V4, v4); put(SG_V4X2, HFr::dbl(v4));
     const HFr kin = HFr::from_mont(kappa), kout = HFr::from_mont(HFr::neg(kappa));
-    serial::put_plain29(t.words.data() + 9 * SG_KIN, kin.l); serial::put_plain29(t.words.data() + 9 * SG_KOUT, kout.l);
+    wt.put_plain(SG_KIN, kin.l); wt.put_plain(SG_KOUT, kout.l);
     put(SG_DOM8, host::fr_domain_separator("AleoPoseidon8"));
     const auto& P = host::PoseidonParams<4, 4>::get();
     for (int i = 0; i < 5; ++i) put(SG_S4 + i, t.s4[i]);
     for (int r = 0; r < host::POSEIDON_ROUNDS; ++r) for (int i = 0; i < 5; ++i) put(SG_ARK4 + 5 * r + i, P.ark[r][i]);
     for (int i = 0; i < 5; ++i) for (int j = 0; j < 5; ++j) put(SG_MDS4 + 5 * i + j, P.mds[i][j]);
-    for (size_t i = 0; i < t.g.size(); ++i) {
-      const EdH& p = t.g[i]; const uint32_t idx = SG_G + 3 * (uint32_t)i;      // Z = 1
-      put(idx, HFr::sub(p.Y, p.X)); put(idx + 1, HFr::add(p.Y, p.X)); put(idx + 2, HFr::mul(p.T, C.d2));
-    }
-    for (int i = 0; i < 4; ++i) { t.words[SG_EXP_QUART + 2 * i] = (uint32_t)quart[i]; t.words[SG_EXP_QUART + 2 * i + 1] = (uint32_t)(quart[i] >> 32); }
+    for (size_t i = 0; i < t.g.size(); ++i) wt.put_cached(SG_G + 3 * (uint32_t)i, t.g[i]);
+    wt.put_exponent(SG_EXP_QUART, quart);
+    t.words = std::move(wt.words);
     return t;
   }();
   return T;

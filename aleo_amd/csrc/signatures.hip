@@ -31,61 +31,46 @@ __global__ void __launch_bounds__(SIG_BLOCK) k_signatures_verify(char* base, Sig
   const uint32_t first = *(const uint32_t*)(base + (C.off + 4u * i)), len = *(const uint32_t*)(base + (C.off + 4u * i + 4u)) - first;
   const uint32_t o_msg = C.text + first;
   base[o_flag] = (char)signature_verify_lane(
-      [&](uint32_t k, uint32_t (&w)[8]) {
-        const uint4* p = (const uint4*)(base + (k < 4 ? o_mine + 32u * k : o_addr)); const uint4 l = p[0], h = p[1];
-        w[0] = l.x; w[1] = l.y; w[2] = l.z; w[3] = l.w; w[4] = h.x; w[5] = h.y; w[6] = h.z; w[7] = h.w; },
+      [&](uint32_t k, uint32_t (&w)[8]) { load_words8(w, base + (k < 4 ? o_mine + 32u * k : o_addr)); },
       len, [&](uint32_t q) { return (uint8_t)base[o_msg + q]; }, K, [&] { base[o_flag] = (char)SIG_MALFORMED; });      // provisional: signature_lane.h phase()
 }
 
-// The table of one device: uploaded once, under the lock, and never freed; the copy is complete before the pointer is handed out.
-static int32_t sig_tables_on_device(int device, const uint32_t** out) {
-  static std::mutex mu; static std::map<int, const uint32_t*> resident;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = resident.find(device);
-  if (it == resident.end()) {
-    const sig::SigTables& T = sig::sig_tables();
-    DevTmp buf; if (int32_t rc = buf.alloc((size_t)SG_WORDS * 4)) return rc;
-    HIPCHK(hipMemcpy(buf.p, T.words.data(), (size_t)SG_WORDS * 4, hipMemcpyHostToDevice));
-    it = resident.emplace(device, (const uint32_t*)buf.release()).first;
-  }
-  *out = it->second; return ALEO_MI355X_OK;
-}
-
-static size_t sig_chunk_cap() { const size_t cap = env_size("ALEO_MI355X_SIGNATURES_CHUNK", SIG_CHUNK); return cap == 0 || cap > SIG_CHUNK ? SIG_CHUNK : cap; }
-
 // Chunk by chunk: the signatures, addresses and messages go up, one launch runs, the flags come down.  A message over the cap does not travel: its lane gets
-// no bytes and the flag is set here.
-static int32_t verify_on_device(Ctx* c, uint8_t* flags, const uint8_t* sigs, const uint8_t* addresses, size_t address_stride, const uint8_t* messages, const uint64_t* offsets, size_t n) {
-  const uint32_t* dK; if (int32_t rc = sig_tables_on_device(c->device, &dK)) return rc;
-  const size_t cap = sig_chunk_cap();
-  hipStream_t s = c->stream;
+// no bytes and the flag is set here.  The chunk's offsets and messages are declared outside the slot: they outlive the copies that read them.
+static int32_t verify_on_device(uint8_t* flags, const uint8_t* sigs, const uint8_t* addresses, size_t address_stride, const uint8_t* messages, const uint64_t* offsets, size_t n) {
+  const size_t cap = env_cap("ALEO_MI355X_SIGNATURES_CHUNK", SIG_CHUNK);
   std::vector<uint32_t> off; std::vector<uint8_t> text;
-  for (size_t lo = 0; lo < n;) {
-    off.assign(1, 0); text.clear();
-    size_t hi = lo;
-    for (; hi < n && hi - lo < cap && text.size() < SIG_CHUNK_BYTES; ++hi) {
-      const uint64_t len = offsets[hi + 1] - offsets[hi];
-      if (len <= SIG_MAX_BYTES) text.insert(text.end(), messages + offsets[hi], messages + offsets[hi + 1]);
-      off.push_back((uint32_t)text.size());
+  return on_slot([&](Ctx* c) -> int32_t {
+    const uint32_t* dK;
+    if (int32_t rc = resident_table(c->device, ResidentTable::SIGNATURE, []() -> const std::vector<uint32_t>& { return sig::sig_tables().words; }, &dK)) return rc;
+    hipStream_t s = c->stream;
+    for (size_t lo = 0; lo < n;) {
+      off.assign(1, 0); text.clear();
+      size_t hi = lo;
+      for (; hi < n && hi - lo < cap && text.size() < SIG_CHUNK_BYTES; ++hi) {
+        const uint64_t len = offsets[hi + 1] - offsets[hi];
+        if (len <= SIG_MAX_BYTES) text.insert(text.end(), messages + offsets[hi], messages + offsets[hi + 1]);
+        off.push_back((uint32_t)text.size());
+      }
+      const size_t m = hi - lo, rows = address_stride ? m : 1;
+      Carve cv;
+      const size_t o_sig = cv.part(m * 128), o_addr = cv.part(rows * 32), o_text = cv.part(text.size()), o_off = cv.part((m + 1) * 4), o_fl = cv.part(m);
+      if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
+      char* b = c->scalars_stage.as<char>();
+      HIPCHK(hipMemcpyAsync(b + o_sig, sigs + lo * 128, m * 128, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(b + o_addr, addresses + (address_stride ? lo * 32 : 0), rows * 32, hipMemcpyHostToDevice, s));
+      if (!text.empty()) HIPCHK(hipMemcpyAsync(b + o_text, text.data(), text.size(), hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(b + o_off, off.data(), (m + 1) * 4, hipMemcpyHostToDevice, s));
+      const SigChunk C{(uint32_t)o_fl, (uint32_t)o_sig, (uint32_t)o_addr, address_stride ? 32u : 0u, (uint32_t)o_text, (uint32_t)o_off, (uint32_t)m};
+      hipLaunchKernelGGL(k_signatures_verify, dim3((uint32_t)((m + SIG_BLOCK - 1) / SIG_BLOCK)), dim3(SIG_BLOCK), 0, s, b, C, dK);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(flags + lo, b + o_fl, m, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers, and the host arrays above
+      for (size_t i = lo; i < hi; ++i) if (offsets[i + 1] - offsets[i] > SIG_MAX_BYTES) flags[i] = (uint8_t)SIG_MALFORMED;
+      lo = hi;
     }
-    const size_t m = hi - lo, rows = address_stride ? m : 1;
-    Carve cv;
-    const size_t o_sig = cv.part(m * 128), o_addr = cv.part(rows * 32), o_text = cv.part(text.size()), o_off = cv.part((m + 1) * 4), o_fl = cv.part(m);
-    if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
-    char* b = c->scalars_stage.as<char>();
-    HIPCHK(hipMemcpyAsync(b + o_sig, sigs + lo * 128, m * 128, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(b + o_addr, addresses + (address_stride ? lo * 32 : 0), rows * 32, hipMemcpyHostToDevice, s));
-    if (!text.empty()) HIPCHK(hipMemcpyAsync(b + o_text, text.data(), text.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(b + o_off, off.data(), (m + 1) * 4, hipMemcpyHostToDevice, s));
-    const SigChunk C{(uint32_t)o_fl, (uint32_t)o_sig, (uint32_t)o_addr, address_stride ? 32u : 0u, (uint32_t)o_text, (uint32_t)o_off, (uint32_t)m};
-    hipLaunchKernelGGL(k_signatures_verify, dim3((uint32_t)((m + SIG_BLOCK - 1) / SIG_BLOCK)), dim3(SIG_BLOCK), 0, s, b, C, dK);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(flags + lo, b + o_fl, m, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffers, and the host arrays above
-    for (size_t i = lo; i < hi; ++i) if (offsets[i + 1] - offsets[i] > SIG_MAX_BYTES) flags[i] = (uint8_t)SIG_MALFORMED;
-    lo = hi;
-  }
-  return ALEO_MI355X_OK;
+    return ALEO_MI355X_OK;
+  });
 }
 
 static int32_t signatures_verify(uint8_t* flags, const void* sigs128, const void* addresses_x32, size_t address_stride, const void* messages, const uint64_t* offsets, size_t n, bool may_route) {
@@ -97,12 +82,7 @@ static int32_t signatures_verify(uint8_t* flags, const void* sigs128, const void
   for (size_t i = 0; i < n; ++i) if (offsets[i + 1] < offsets[i]) return bad_arg("signatures_verify: offsets decrease");
   if (offsets[n] && !messages) return bad_arg("signatures_verify: null buffer");
   const uint8_t* sg = (const uint8_t*)sigs128; const uint8_t* ad = (const uint8_t*)addresses_x32; const uint8_t* ms = (const uint8_t*)messages;
-  if (may_route && n >= aleo_mi355x_min_signatures()) {
-    Slot sl; if (sl.rc) return sl.rc;
-    const int32_t rc = verify_on_device(sl.c, flags, sg, ad, address_stride, ms, offsets, n);
-    if (rc) (void)hipStreamSynchronize(sl.c->stream);        // a chunk's arrays may still be on their way up
-    return rc;
-  }
+  if (may_route && n >= aleo_mi355x_min_signatures()) return verify_on_device(flags, sg, ad, address_stride, ms, offsets, n);
   for (size_t i = 0; i < n; ++i) flags[i] = sig::verify_one_host(sg + 128 * i, ad + address_stride * i, ms + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
   return ALEO_MI355X_OK;
 }

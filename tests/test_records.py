@@ -199,17 +199,11 @@ def test_routing_threshold_and_its_environment_override():
 # ---- 6: the kernel's code object, and its lane code on the host ------------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_scan_kernel_code_object_is_gfx950_and_has_no_scratch():
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, 'records_many.s')                     # the one-account scan runs the K-account kernel at one key per lane
-        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, os.path.join(CSRC, 'records_many.hip'), '-o', out],
-                       check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    meta = [m for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S) if 'k_records_scan_manyILi1E' in m.group(0)]
-    assert len(meta) == 1, 'the scan kernel is not in the code object'
-    field = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0].group(0)).group(1))
-    print('k_records_scan_many<1>: vgpr_count %d, agpr_count %d, sgpr_count %d, private_segment_fixed_size %d' % (field('vgpr_count'), field('agpr_count'), field('sgpr_count'), field('private_segment_fixed_size')))
-    assert field('private_segment_fixed_size') == 0 and field('vgpr_spill_count') == 0
+    import code_object as co
+    asm, blocks = co.compile_unit('records_many')                         # the one-account scan runs the K-account kernel at one key per lane
+    meta = co.block_of(blocks, 'k_records_scan_manyILi1E')
+    print(co.registers('k_records_scan_many<1>', meta))
+    assert co.field(meta, 'private_segment_fixed_size') == 0 and co.field(meta, 'vgpr_spill_count') == 0
     start = re.search(r'^_Z\w*k_records_scan_manyILi1E\w*:', asm, flags=re.M).start()
     body = asm[start:asm.index('.Lfunc_end', start)]
     code = [l.split(';')[0].strip() for l in body.split('\n')]

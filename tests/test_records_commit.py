@@ -266,17 +266,12 @@ def test_routing_threshold_and_its_environment_override():
 
 # ---- 5: the code object -------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
-def test_commit_kernel_code_object_is_gfx950_and_has_no_scratch(tmp_path):
-    out = os.path.join(str(tmp_path), 'records_commit.s')
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, '-I' + os.path.join(ROOT, 'include'), os.path.join(CSRC, 'records_commit.hip'), '-o', out],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    blocks = re.findall(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S)
+def test_commit_kernel_code_object_is_gfx950_and_has_no_scratch():
+    import code_object as co
+    asm, blocks = co.compile_unit('records_commit')
     assert len(blocks) == 1 and 'k_records_commit' in blocks[0]                                  # this one and no other
-    get = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, blocks[0]).group(1))
-    print('k_records_commit: vgpr_count %d, agpr_count %d, sgpr_count %d, private_segment_fixed_size %d' % (get('vgpr_count'), get('agpr_count'), get('sgpr_count'), get('private_segment_fixed_size')))
-    assert get('private_segment_fixed_size') == 0 and get('vgpr_spill_count') == 0 and get('sgpr_spill_count') == 0
+    print(co.registers('k_records_commit', blocks[0]))
+    assert co.field(blocks[0], 'private_segment_fixed_size') == 0 and co.field(blocks[0], 'vgpr_spill_count') == 0 and co.field(blocks[0], 'sgpr_spill_count') == 0
 
 
 # ---- 6: the C++ mirror ----------------------------------------------------------------------------------------------------------------------------------
@@ -406,4 +401,14 @@ def test_two_threads_at_once_get_the_host_path_s_bytes(on_kernel):
     """tests/helpers/commit_two_threads.py, a process of its own: there the two calls are the first of the process, so the one-time table builds run under both."""
     env = dict(os.environ, PYTHONPATH=ROOT, ALEO_MI355X_MIN_SERIALS='0', ALEO_MI355X_MIN_RECORDS='0', ALEO_MI355X_MIN_DECRYPT='0', ALEO_MI355X_MIN_COMMITMENTS='0')
     r = subprocess.run([sys.executable, os.path.join(HERE, 'helpers', 'commit_two_threads.py')], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.split() == ['ok'], r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+def test_first_calls_of_a_process_in_an_unusual_order_get_the_host_path_s_bytes():
+    """tests/helpers/records_first_calls.py, a process of its own: signatures_verify, unspent_named_many (K = 3), serial_numbers and decrypt_strings are its first
+    device calls, in that order, so the resident tables are uploaded and the slot's pinned words first used in an order no other test has."""
+    env = dict(os.environ, PYTHONPATH=ROOT, ALEO_MI355X_MIN_SERIALS='0', ALEO_MI355X_MIN_RECORDS='0', ALEO_MI355X_MIN_DECRYPT='0', ALEO_MI355X_MIN_COMMITMENTS='0',
+               ALEO_MI355X_MIN_SIGNATURES='0')
+    r = subprocess.run([sys.executable, os.path.join(HERE, 'helpers', 'records_first_calls.py')], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.split() == ['ok'], r.stdout + r.stderr

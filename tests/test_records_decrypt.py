@@ -313,17 +313,11 @@ def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_decrypt_kernel_code_object_is_gfx950_and_has_no_scratch():
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, 'records_decrypt.s')
-        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, os.path.join(CSRC, 'records_decrypt.hip'), '-o', out],
-                       check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    meta = [m for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S) if 'k_records_decrypt' in m.group(0)]
-    assert len(meta) == 1, 'the decrypt kernel is not in the code object'
-    field = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0].group(0)).group(1))
-    print('k_records_decrypt: vgpr_count %d, agpr_count %d, sgpr_count %d, private_segment_fixed_size %d' % (field('vgpr_count'), field('agpr_count'), field('sgpr_count'), field('private_segment_fixed_size')))
-    assert field('private_segment_fixed_size') == 0 and field('vgpr_spill_count') == 0
+    import code_object as co
+    asm, blocks = co.compile_unit('records_decrypt')
+    meta = co.block_of(blocks, 'k_records_decrypt')
+    print(co.registers('k_records_decrypt', meta))
+    assert co.field(meta, 'private_segment_fixed_size') == 0 and co.field(meta, 'vgpr_spill_count') == 0
 
 
 # ---- on the GPU -----------------------------------------------------------------------------------------------------------------------------------------

@@ -295,21 +295,13 @@ NEW_KERNELS = ('k_found_count', 'k_found_offsets', 'k_found_gather', 'k_found_mi
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_found_kernels_are_gfx950_and_have_no_scratch():
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, 'records_found.s')
-        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, '-I' + os.path.join(ROOT, 'include'), os.path.join(CSRC, 'records_found.hip'), '-o', out],
-                       check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    metas = re.findall(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S)
-    assert len(metas) == len(NEW_KERNELS)                                                                           # these four and no other
+    import code_object as co
+    asm, blocks = co.compile_unit('records_found')
+    assert len(blocks) == len(NEW_KERNELS)                                                                          # these four and no other
     for kernel in NEW_KERNELS:
-        meta = [m for m in metas if kernel in m]
-        assert len(meta) == 1, kernel + ' is not in the code object'
-        field = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0]).group(1))
-        print('%s: vgpr_count %d, agpr_count %d, sgpr_count %d, group_segment_fixed_size %d, private_segment_fixed_size %d' % (
-            kernel, field('vgpr_count'), field('agpr_count'), field('sgpr_count'), field('group_segment_fixed_size'), field('private_segment_fixed_size')))
-        assert field('private_segment_fixed_size') == 0 and field('vgpr_spill_count') == 0 and field('sgpr_spill_count') == 0
+        meta = co.block_of(blocks, kernel)
+        print(co.registers(kernel, meta, ('vgpr_count', 'agpr_count', 'sgpr_count', 'group_segment_fixed_size', 'private_segment_fixed_size')))
+        assert co.field(meta, 'private_segment_fixed_size') == 0 and co.field(meta, 'vgpr_spill_count') == 0 and co.field(meta, 'sgpr_spill_count') == 0
 
 
 # ---- on the GPU -------------------------------------------------------------------------------------------------------------------------------------

@@ -104,22 +104,16 @@ def test_grouped_lane_emulated_on_the_host_matches_the_host_path(tmp_path):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_grouped_kernels_are_gfx950_and_have_no_scratch_at_any_width():
     """The kernels of records_many.hip; the figures of W = 1, which is the one-account scan's kernel too, are asserted by tests/test_records.py as well."""
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, 'records_many.s')
-        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, os.path.join(CSRC, 'records_many.hip'), '-o', out],
-                       check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    meta = [m.group(0) for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S) if 'k_records_scan_many' in m.group(0)]
-    built = {}
-    for m in meta:
-        field = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, m).group(1))
+    import code_object as co
+    asm, blocks = co.compile_unit('records_many')
+    built = set()
+    for m in (b for b in blocks if 'k_records_scan_many' in b):
         w = int(re.search(r'k_records_scan_manyILi(\d+)E', m).group(1))
-        built[w] = field
+        built.add(w)
         print('k_records_scan_many<%d>: vgpr_count %d, agpr_count %d, sgpr_count %d, group_segment_fixed_size (LDS) %d, private_segment_fixed_size %d'
-              % (w, field('vgpr_count'), field('agpr_count'), field('sgpr_count'), field('group_segment_fixed_size'), field('private_segment_fixed_size')))
-        assert field('private_segment_fixed_size') == 0 and field('vgpr_spill_count') == 0, w
-        assert field('group_segment_fixed_size') == (0 if w == 1 else w * 9 * 256 * 4) <= 160 * 1024       # the parked x of W keys, 9 words a lane
+              % (w, co.field(m, 'vgpr_count'), co.field(m, 'agpr_count'), co.field(m, 'sgpr_count'), co.field(m, 'group_segment_fixed_size'), co.field(m, 'private_segment_fixed_size')))
+        assert co.field(m, 'private_segment_fixed_size') == 0 and co.field(m, 'vgpr_spill_count') == 0, w
+        assert co.field(m, 'group_segment_fixed_size') == (0 if w == 1 else w * 9 * 256 * 4) <= 160 * 1024       # the parked x of W keys, 9 words a lane
     assert sorted(built) == list(WIDTHS)
     src = open(os.path.join(CSRC, 'records_many.hip')).read()
     for w in WIDTHS: assert 'launch_many<%d>' % w in src                                                     # every width the rule or the switch can ask for is built

@@ -218,18 +218,12 @@ def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
-def test_serial_kernel_code_object_is_gfx950_and_has_no_scratch(tmp_path):
-    import re
-    out = os.path.join(str(tmp_path), 'records_serial.s')
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, os.path.join(CSRC, 'records_serial.hip'), '-o', out],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    meta = [m for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S) if 'k_records_serial' in m.group(0)]
-    assert len(meta) == 1, 'the serial-number kernel is not in the code object'
-    get = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0].group(0)).group(1))
-    print('k_records_serial: vgpr_count %d, agpr_count %d, sgpr_count %d, private_segment_fixed_size %d' % (get('vgpr_count'), get('agpr_count'), get('sgpr_count'), get('private_segment_fixed_size')))
-    assert get('private_segment_fixed_size') == 0 and get('vgpr_spill_count') == 0
+def test_serial_kernel_code_object_is_gfx950_and_has_no_scratch():
+    import code_object as co
+    asm, blocks = co.compile_unit('records_serial')
+    meta = co.block_of(blocks, 'k_records_serial')
+    print(co.registers('k_records_serial', meta))
+    assert co.field(meta, 'private_segment_fixed_size') == 0 and co.field(meta, 'vgpr_spill_count') == 0
 
 
 # ---- on the GPU ------------------------------------------------------------------------------------------------------------------------------------------------

@@ -332,19 +332,12 @@ def test_a_bad_string_raises_from_strings_what_it_raises_from_the_loop(on_host, 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_parse_and_resolve_kernels_are_gfx950_and_have_no_scratch():
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, 'records_strings.s')
-        subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, '-I' + os.path.join(ROOT, 'include'), os.path.join(CSRC, 'records_strings.hip'), '-o', out],
-                       check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
+    import code_object as co
+    asm, blocks = co.compile_unit('records_strings')
     for kernel in ('k_records_parse', 'k_records_resolve'):
-        meta = [m for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S) if kernel in m.group(0)]
-        assert len(meta) == 1, kernel + ' is not in the code object'
-        field = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0].group(0)).group(1))
-        print('%s: vgpr_count %d, agpr_count %d, sgpr_count %d, group_segment_fixed_size %d, private_segment_fixed_size %d, max_flat_workgroup_size %d' % (
-            kernel, field('vgpr_count'), field('agpr_count'), field('sgpr_count'), field('group_segment_fixed_size'), field('private_segment_fixed_size'), field('max_flat_workgroup_size')))
-        assert field('private_segment_fixed_size') == 0 and field('vgpr_spill_count') == 0
+        meta = co.block_of(blocks, kernel)
+        print(co.registers(kernel, meta, ('vgpr_count', 'agpr_count', 'sgpr_count', 'group_segment_fixed_size', 'private_segment_fixed_size', 'max_flat_workgroup_size')))
+        assert co.field(meta, 'private_segment_fixed_size') == 0 and co.field(meta, 'vgpr_spill_count') == 0
 
 
 def test_device_lane_code_run_on_the_host_equals_the_one_record_parser(tmp_path):

@@ -206,19 +206,13 @@ def test_spent_lane_emulated_on_the_host_matches_std_set(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
-def test_new_kernels_code_objects_are_gfx950_and_have_no_scratch(tmp_path):
-    out = os.path.join(str(tmp_path), 'records_unspent.s')
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, os.path.join(CSRC, 'records_unspent.hip'), '-o', out],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    blocks = re.findall(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S)
+def test_new_kernels_code_objects_are_gfx950_and_have_no_scratch():
+    import code_object as co
+    asm, blocks = co.compile_unit('records_unspent')
     for kernel in ('k_spent_insert', 'k_unspent_keep', 'k_unspent_scatter'):      # the serial-number kernel is records_serial.hip's: tests/test_records_serial.py
-        meta = [m for m in blocks if kernel in m]
-        assert len(meta) == 1, '%s is not in the code object' % kernel
-        get = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, meta[0]).group(1))
-        print('%s: vgpr_count %d, agpr_count %d, sgpr_count %d, private_segment_fixed_size %d' % (kernel, get('vgpr_count'), get('agpr_count'), get('sgpr_count'), get('private_segment_fixed_size')))
-        assert get('private_segment_fixed_size') == 0 and get('vgpr_spill_count') == 0, kernel
+        meta = co.block_of(blocks, kernel)
+        print(co.registers(kernel, meta))
+        assert co.field(meta, 'private_segment_fixed_size') == 0 and co.field(meta, 'vgpr_spill_count') == 0, kernel
 
 
 def test_cpp_mirror_on_the_host_path(tmp_path):

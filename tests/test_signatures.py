@@ -365,17 +365,12 @@ def test_routing_threshold_and_its_environment_override():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
-def test_signature_kernel_code_object_is_gfx950_and_has_no_scratch(tmp_path):
-    out = os.path.join(str(tmp_path), 'signatures.s')
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S', '-I' + CSRC, '-I' + os.path.join(ROOT, 'include'), os.path.join(CSRC, 'signatures.hip'), '-o', out],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    assert '.amdgcn_target "amdgcn-amd-amdhsa--gfx950"' in asm
-    blocks = re.findall(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', asm, flags=re.S)
+def test_signature_kernel_code_object_is_gfx950_and_has_no_scratch():
+    import code_object as co
+    asm, blocks = co.compile_unit('signatures')
     assert len(blocks) == 1 and 'k_signatures_verify' in blocks[0]                               # this one and no other
-    get = lambda name: int(re.search(r'\.%s:\s*(\d+)' % name, blocks[0]).group(1))
-    print('k_signatures_verify: vgpr_count %d, agpr_count %d, sgpr_count %d, private_segment_fixed_size %d' % (get('vgpr_count'), get('agpr_count'), get('sgpr_count'), get('private_segment_fixed_size')))
-    assert get('private_segment_fixed_size') == 0 and get('vgpr_spill_count') == 0 and get('sgpr_spill_count') == 0
+    print(co.registers('k_signatures_verify', blocks[0]))
+    assert co.field(blocks[0], 'private_segment_fixed_size') == 0 and co.field(blocks[0], 'vgpr_spill_count') == 0 and co.field(blocks[0], 'sgpr_spill_count') == 0
 
 
 def run_cpp_mirror(tmp_path, env, n):
