@@ -692,6 +692,28 @@ def test_ntt_batch_and_grid_scale_match_oracle():
             assert (t.cpu() == e).all(), (mode, direction)
 
 
+def test_ntt_limb_forms_keep_their_own_tables():
+    """One kernel pair serves both limb forms, each with its own tables (Montgomery forms of R = 2^256 and R = 2^261) of the same (size, direction).
+    At 2^12, in this order: one transform runs the latency form (32-bit limbs) and builds its n-entry inter-pass table; 256 transforms are 2^20 elements,
+    so they run the 2048-element tiles on 29-bit limbs in two passes and build that form's table for the same size and split; one transform again.
+    At 2^10: 512 transforms still take the latency form, 513 the 29-bit form in one pass.  Rows 0, 1 and the last against the restatement."""
+    import torch
+    from aleo_amd import dist as adist
+    ops = adist.HipLocalOps()
+    x = c.fr_to_mont(util.uniform_scalars(1 << 20, 8300))
+    expected = {}
+    for lg, batches in ((12, (1, 256, 1)), (10, (512, 513))):
+        n = 1 << lg
+        for direction in (0, 1):
+            for batch in batches:
+                t = torch.from_numpy(x[:batch * n].view(np.int64).copy()).cuda()
+                ops.batch_ntt(t, lg, batch, direction); torch.cuda.synchronize()
+                got = t.cpu().numpy().view(np.uint64).reshape(batch, n, 4)
+                for b in sorted({0, min(1, batch - 1), batch - 1}):
+                    if (lg, b, direction) not in expected: expected[lg, b, direction] = c.ntt_fr(x[b * n:(b + 1) * n], 0, direction, 0)
+                    assert (got[b] == expected[lg, b, direction]).all(), (lg, batch, b, direction)
+
+
 @pytest.mark.parametrize('lg_n,world', [(10, 4), (16, 2), (20, 4)])
 def test_sharded_ntt_ranks_on_one_gpu(lg_n, world):
     """The 4-step transform of aleo_amd.dist.ShardedDomain with the HIP local steps; the `world` ranks run as threads of this
