@@ -1,6 +1,7 @@
 // api.hip — the C ABI of libaleo_mi355x.so (include/aleo_mi355x.h): argument checking, host<->HBM staging and the host-side tails of the MSM, KZG,
-// field, transform, prover and self-test entry points.  Devices and slots: device.hip; base sets: bases.hip; several devices: sharded.hip.  Kernels live in msm_sort.hip / msm.hip / g1_setup.hip / ntt.hip / frops.hip.
+// field, transform, prover and self-test entry points.  Devices and slots: device.hip; base sets: bases.hip; several devices: sharded.hip.  Kernels live in msm_sort.hip / msm.hip / g1_setup.hip / ntt.hip / frops.hip / fr_spmv.hip / fr_divide.hip / ahp_kernels.hip.
 #include "entry.h"
+#include "frops.h"
 #include "host_field.hpp"
 #include <cstdlib>
 #include <chrono>

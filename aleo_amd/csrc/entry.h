@@ -1,6 +1,6 @@
 // entry.h — what the units with entry points of the C ABI share (device.hip, bases.hip, sharded.hip, api.hip): the guard at the C boundary, the slot a call runs
 // on (and on_slot, the form the records and signature units take it in), its stream, handle lookup, sizes and caps from the environment, the tables resident on a
-// device, and the functions that cross between those four files.  (Kernels and their hosts: ctx.h.)
+// device, and the functions that cross between those four files.  (Kernels and their hosts: ctx.h, frops.h.)
 #pragma once
 #include "ctx.h"
 #include <cstdlib>

@@ -552,28 +552,29 @@ static int32_t ntt_run_chunk(Ctx* c, void* d_inout, uint32_t lg_n, uint32_t batc
   int32_t rc;
   NttTables* t = nullptr;
   if ((rc = get_tables(c, lg_n, direction, &t))) return rc;
-  if ((rc = scratch_acquire(c, c->ntt_tmp, bytes, s))) return rc;      // ordered after the slot's previous asynchronous user
-  char* buf = (char*)d_inout; char* tmp = c->ntt_tmp.as<char>();
-  const bool in_rev = (order == ALEO_NTT_ORDER_RN || order == ALEO_NTT_ORDER_RR), out_rev = (order == ALEO_NTT_ORDER_NR || order == ALEO_NTT_ORDER_RR);
-  const dim3 gperm((uint32_t)((n + 255) / 256), batch);
-  if (in_rev) {
-    hipLaunchKernelGGL(k_bitrev_copy, gperm, dim3(256), 0, s, buf, tmp, lg_n);
-    HIPCHK(hipMemcpyAsync(buf, tmp, bytes, hipMemcpyDeviceToDevice, s));
-  }
-  const int coset = (type == ALEO_NTT_COSET), inv = (direction == ALEO_NTT_INVERSE);
-  const int pre_coset = coset && !inv, post_coset = coset && inv, do_scale = inv && !coset;   // cs_lo carries n^-1 for coset_ifft
-  switch (choose_form(lg_n, batch)) {
-    case NttForm::Latency512: rc = run_passes<Limbs32, 512, 256, 1>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext); break;
-    case NttForm::Tile4096: rc = run_passes<Limbs29, 4096, 512, 3>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext); break;
-    case NttForm::Tile2048: rc = run_passes<Limbs29, 2048, 256, 3>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext); break;
-  }
-  if (rc) return rc;
-  if (out_rev) {
-    hipLaunchKernelGGL(k_bitrev_copy, gperm, dim3(256), 0, s, buf, tmp, lg_n);
-    HIPCHK(hipMemcpyAsync(buf, tmp, bytes, hipMemcpyDeviceToDevice, s));
-  }
-  HIPCHK(hipGetLastError());
-  return scratch_release(c, s);
+  return with_scratch(c, c->ntt_tmp, bytes, s, [&]() -> int32_t {      // ordered after the slot's previous asynchronous user
+    char* buf = (char*)d_inout; char* tmp = c->ntt_tmp.as<char>();
+    const bool in_rev = (order == ALEO_NTT_ORDER_RN || order == ALEO_NTT_ORDER_RR), out_rev = (order == ALEO_NTT_ORDER_NR || order == ALEO_NTT_ORDER_RR);
+    const dim3 gperm((uint32_t)((n + 255) / 256), batch);
+    if (in_rev) {
+      hipLaunchKernelGGL(k_bitrev_copy, gperm, dim3(256), 0, s, buf, tmp, lg_n);
+      HIPCHK(hipMemcpyAsync(buf, tmp, bytes, hipMemcpyDeviceToDevice, s));
+    }
+    const int coset = (type == ALEO_NTT_COSET), inv = (direction == ALEO_NTT_INVERSE);
+    const int pre_coset = coset && !inv, post_coset = coset && inv, do_scale = inv && !coset;   // cs_lo carries n^-1 for coset_ifft
+    switch (choose_form(lg_n, batch)) {
+      case NttForm::Latency512: rc = run_passes<Limbs32, 512, 256, 1>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext); break;
+      case NttForm::Tile4096: rc = run_passes<Limbs29, 4096, 512, 3>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext); break;
+      case NttForm::Tile2048: rc = run_passes<Limbs29, 2048, 256, 3>(c, buf, tmp, lg_n, batch, t, pre_coset, post_coset, do_scale, s, ext); break;
+    }
+    if (rc) return rc;
+    if (out_rev) {
+      hipLaunchKernelGGL(k_bitrev_copy, gperm, dim3(256), 0, s, buf, tmp, lg_n);
+      HIPCHK(hipMemcpyAsync(buf, tmp, bytes, hipMemcpyDeviceToDevice, s));
+    }
+    HIPCHK(hipGetLastError());
+    return ALEO_MI355X_OK;
+  });
 }
 
 }  // namespace aleo_mi355x

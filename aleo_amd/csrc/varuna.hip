@@ -6,7 +6,7 @@
 //   algorithms/src/snark/varuna/varuna.rs                      Varuna::prove_batch
 //   algorithms/src/snark/varuna/ahp/prover/round_functions/*   AHPForR1CS::prover_{first,second,third,fourth}_round   [UPSTREAM-RECALL]
 // reached from the reference's rust/src/program/execute.rs:74 (`trace.prove_execution`) and transfer.rs:99.
-// Every circuit-sized step is a kernel of msm_sort.hip / msm.hip / ntt.hip / frops.hip queued on the calling slot's stream; these files keep what
+// Every circuit-sized step is a kernel of msm_sort.hip / msm.hip / ntt.hip / frops.hip / fr_spmv.hip / fr_divide.hip / ahp_kernels.hip queued on the calling slot's stream; these files keep what
 // upstream keeps on the CPU between them: the Fiat-Shamir transcript (upstream's Poseidon sponge over Fq, poseidon.hpp), the
 // challenge-dependent constants (host Fr arithmetic, host_field.hpp), the blinding scalars (ChaCha20 under the proof's 32-byte seed, chacha.h)
 // and the O(|X|) public-input polynomial.  aleo_amd/varuna.py is the same sequence written against the public entry points; both

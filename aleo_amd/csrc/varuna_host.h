@@ -2,6 +2,7 @@
 // term lists) and the declarations of what crosses its files — the state of a proof (Shared, Prover, Batch) and the routed transforms / commitments.
 #pragma once
 #include "ctx.h"
+#include "frops.h"
 #include "host_field.hpp"
 #include "poseidon.hpp"
 #include "chacha.h"

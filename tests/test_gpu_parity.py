@@ -1210,12 +1210,22 @@ def test_config2_full_size_chain_known_polynomial():
 
 
 # ---- KZG10 opening: witness polynomial on the device -------------------------------------------------------------------------
-@pytest.mark.parametrize('n', [1, 2, 15, 16, 17, 4095, 4096, 4097, 100003, (1 << 20) + 5, 1 << 22])
+@pytest.mark.parametrize('n', [0, 1, 2, 15, 16, 17, 4095, 4096, 4097, 100003, (1 << 20) + 5, 1 << 22])
 def test_divide_by_linear_matches_oracle(n):
     """(p(X) - p(z)) / (X - z) by the three-level suffix scan against the oracle's serial synthetic division: every quotient
-    coefficient and p(z), bit for bit; chunk / block boundaries (16, 4096) on both sides; z in {random, 0, 1}."""
+    coefficient and p(z), bit for bit; chunk / block boundaries (16, 4096) on both sides; z in {random, 0, 1}.  The empty polynomial
+    (n = 0: no block runs) has the value 0 and no quotient: p(z) reads back as 32 zero bytes, the quotient buffer keeps what it held."""
     import torch
     from aleo_amd import poly
+    if n == 0:
+        pattern = np.arange(1, 9, dtype=np.int64).reshape(2, 4) * 0x0101010101010101
+        q = torch.from_numpy(pattern.copy()).cuda(); ev = torch.from_numpy(pattern[0].copy()).cuda(); d = torch.zeros(4, dtype=torch.int64, device='cuda')
+        torch.cuda.synchronize()
+        poly.divide_by_linear_device(q.data_ptr(), ev.data_ptr(), d.data_ptr(), 0, c.fr_to_mont(util.uniform_scalars(1, 14500))[0])      # raises unless the entry point returns OK
+        torch.cuda.synchronize()
+        assert ev.cpu().numpy().tobytes() == bytes(32)
+        assert (q.cpu().numpy() == pattern).all()
+        return
     f = c.fr_to_mont(util.uniform_scalars(n, 14000 + n % 1000))
     d = torch.from_numpy(f.view(np.int64).copy()).cuda()
     q = torch.zeros((max(n - 1, 1), 4), dtype=torch.int64, device='cuda'); ev = torch.zeros(4, dtype=torch.int64, device='cuda')
