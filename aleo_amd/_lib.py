@@ -41,6 +41,8 @@ EXPORTS = [
     'aleo_mi355x_signatures_verify_host', 'aleo_mi355x_min_signatures',
     'aleo_mi355x_records_unspent_named', 'aleo_mi355x_records_unspent_named_host', 'aleo_mi355x_records_unspent_named_many', 'aleo_mi355x_records_unspent_named_many_host',
     'aleo_mi355x_found_commitments',
+    'aleo_mi355x_accounts_derive', 'aleo_mi355x_accounts_derive_host', 'aleo_mi355x_accounts_search', 'aleo_mi355x_accounts_search_host', 'aleo_mi355x_min_accounts',
+    'aleo_mi355x_private_key_from_seed', 'aleo_mi355x_private_key_seed', 'aleo_mi355x_seed_from_bytes', 'aleo_mi355x_view_key_to_string',
 ]
 
 
@@ -224,6 +226,15 @@ def lib():
         'aleo_mi355x_records_unspent_named_host': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, vp, sz], i32),
         'aleo_mi355x_records_unspent_named_many': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, sz, vp, sz], i32),
         'aleo_mi355x_records_unspent_named_many_host': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, sz, vp, sz], i32),
+        'aleo_mi355x_accounts_derive': ([vp, sz, vp, vp, vp, vp, vp], i32),
+        'aleo_mi355x_accounts_derive_host': ([vp, sz, vp, vp, vp, vp, vp], i32),
+        'aleo_mi355x_accounts_search': ([vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64)], i32),
+        'aleo_mi355x_accounts_search_host': ([vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64)], i32),
+        'aleo_mi355x_min_accounts': ([], sz),
+        'aleo_mi355x_private_key_from_seed': ([vp, sz, vp], i32),
+        'aleo_mi355x_private_key_seed': ([vp, ctypes.c_char_p], i32),
+        'aleo_mi355x_seed_from_bytes': ([vp, vp], i32),
+        'aleo_mi355x_view_key_to_string': ([vp, sz, vp], i32),
         'aleo_mi355x_found_free': ([vp], None),
         **{'aleo_mi355x_found_' + name: ([vp], sz) for name in ('count', 'fields', 'unparsed', 'first_unparsed', 'owned')},
         **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits', 'serials', 'commitments')},

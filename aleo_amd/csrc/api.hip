@@ -661,6 +661,7 @@ const char* aleo_mi355x_strerror(int32_t status) {
     case ALEO_MI355X_ERR_OOM: return "out of device memory";
     case ALEO_MI355X_ERR_UNSATISFIED: return "assignment does not satisfy the circuit";
     case ALEO_MI355X_ERR_NOT_OWNER: return "the record's owner is not the given address";
+    case ALEO_MI355X_ERR_INTERNAL: return "the device and the host path disagree";
     default: return "unknown status";
   }
 }

@@ -17,6 +17,7 @@
 #pragma once
 #include "records_plaintext.hpp"
 #include "serial_host.hpp"
+#include "account_host.hpp"
 
 namespace aleo_mi355x { namespace serial {
 
@@ -109,58 +110,23 @@ static bool program_id_ok(const char* s, size_t* dot) {
 
 static void store_canonical(void* out32, const HFr& mont) { const HFr c = HFr::from_mont(mont); std::memcpy(out32, c.l, 32); }
 
-// ---- the account of a private key ----------------------------------------------------------------------------------------------------------------------------------
-static bool base58_decode(std::vector<uint8_t>& out, const char* s, size_t want) {      // exactly `want` bytes, big-endian
-  static const char* B58 = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
-  out.assign(want, 0);
-  for (; *s; ++s) {
-    const char* d = std::strchr(B58, *s);
-    if (!d) return false;
-    unsigned carry = (unsigned)(d - B58);
-    for (size_t i = want; i-- > 0;) { carry += 58u * out[i]; out[i] = (uint8_t)carry; carry >>= 8; }
-    if (carry) return false;
-  }
-  return true;
-}
-static HFr domain_separator_mod_order(const char* text) {      // Field::new_domain_separator for a text of any length: its bytes, little-endian, mod r; Montgomery form
-  const HFr k = HFr::from_u64(256); HFr acc = HFr::zero();
-  for (size_t i = std::strlen(text); i-- > 0;) acc = HFr::add(HFr::mul(acc, k), HFr::from_u64((uint8_t)text[i]));
-  return acc;
-}
-static EdA account_mul_g(const uint64_t* k) {                // k G for a scalar below l
-  ScanArgs a; std::memset(&a, 0, sizeof a); recode_scalar(a, k);
-  return edh_affine(edh_mul_naf(edh_of(account_generator()), a));
-}
-static void hash_to_scalar(uint64_t* out4, int rate, const HFr* in, size_t n) {      // the low 250 bits of the hash
-  HFr h;
-  if (rate == 2) host::poseidon_hash_many_fr<2>(in, n, &h, 1); else host::poseidon_hash_many_fr<4>(in, n, &h, 1);
-  h = HFr::from_mont(h); h.l[3] &= (1ull << (SK_NONCE_BITS - 192)) - 1;
-  std::memcpy(out4, h.l, 32);
+// ---- the account of a private key: the string, then account_host.hpp's derivation from its seed ------------------------------------------------------------------
+// The 32 seed bytes of an "APrivateKey1…" string; refused: what is no such string, a seed that is no canonical field element
+static int32_t private_key_seed(void* seed32, const char* private_key) {
+  if (const char* why = private_key_seed_or_why(seed32, private_key)) { g_last_error = std::string("account_from_private_key: ") + why; return ALEO_MI355X_ERR_BAD_ARG; }
+  return ALEO_MI355X_OK;
 }
 // the three scalars of a private key's account: sk_sig, r_sig and sk_prf (each below 2^250)
 static int32_t account_scalars(const char* private_key, uint64_t* sk, uint64_t* rs, uint64_t* prf) {
-  static const uint8_t PREFIX[11] = {127, 134, 189, 116, 210, 221, 210, 137, 145, 18, 253};      // "APrivateKey1"
-  auto refuse = [&](const char* why) { g_last_error = why; return ALEO_MI355X_ERR_BAD_ARG; };
-  std::vector<uint8_t> raw;
-  if (!private_key || !base58_decode(raw, private_key, 43) || std::memcmp(raw.data(), PREFIX, 11)) return refuse("account_from_private_key: not an Aleo private key");
-  HFr seed; std::memcpy(seed.l, raw.data() + 11, 32);
-  if (HFr::geq_p(seed.l)) return refuse("account_from_private_key: the seed is not a canonical field element");
-  const HFr in_sk[2] = {host::fr_domain_separator("AleoAccountSignatureSecretKey0"), HFr::to_mont(seed)};
-  const HFr in_r[2] = {domain_separator_mod_order("AleoAccountSignatureRandomizer0.0"), in_sk[1]};
-  hash_to_scalar(sk, 2, in_sk, 2); hash_to_scalar(rs, 2, in_r, 2);
-  const HFr in_prf[2] = {account_mul_g(sk).x, account_mul_g(rs).x};
-  hash_to_scalar(prf, 4, in_prf, 2);
+  uint8_t seed[32];
+  if (int32_t rc = private_key_seed(seed, private_key)) return rc;
+  account_scalars_of_seed(seed, sk, rs, prf);
   return ALEO_MI355X_OK;
 }
 static int32_t account_from_private_key(const char* private_key, void* sk_sig32, void* view_key32, void* address_x32) {
-  uint64_t sk[4], rs[4], prf[4];
-  if (int32_t rc = account_scalars(private_key, sk, rs, prf)) return rc;
-  uint64_t view[5] = {0, 0, 0, 0, 0};                        // three scalars below 2^250: the sum is below 3 l
-  for (const uint64_t* t : {sk, rs, prf}) { unsigned __int128 cy = 0; for (int i = 0; i < 4; ++i) { cy += (unsigned __int128)view[i] + t[i]; view[i] = (uint64_t)cy; cy >>= 64; } }
-  while (!scalar_below_order(view)) { unsigned __int128 br = 0; for (int i = 0; i < 4; ++i) { const unsigned __int128 d = (unsigned __int128)view[i] - ED_ORDER[i] - (uint64_t)br; view[i] = (uint64_t)d; br = (d >> 64) & 1; } }
-  if (sk_sig32) std::memcpy(sk_sig32, sk, 32);
-  if (view_key32) std::memcpy(view_key32, view, 32);
-  if (address_x32) store_canonical(address_x32, account_mul_g(view).x);
+  uint8_t seed[32];
+  if (int32_t rc = private_key_seed(seed, private_key)) return rc;
+  account_from_seed(seed, sk_sig32, view_key32, address_x32);
   return ALEO_MI355X_OK;
 }
 

@@ -62,22 +62,23 @@ __device__ __forceinline__ bool f29_is_zero_limbs(const F29& a) { uint32_t o = 0
 __device__ __forceinline__ F29 f29_neg_tidy(const F29& a) { F29 r = f29_sub_pad(f29_zero(), a); f29_tidy(r); return r; }      // a tidied
 __device__ __forceinline__ bool f29_bit(const F29& canonical, int i) { return (canonical.v[i / 29] >> (i % 29)) & 1u; }
 
-// One width-3 permutation, plain form: 4 full rounds, 31 partial, 4 full; every element of the result tidied.
-__device__ __forceinline__ void psd2_permute(F29 (&s)[3], const uint32_t* __restrict__ K) {
+// One width-3 permutation, plain form: 4 full rounds, 31 partial, 4 full; every element of the result tidied.  ark, mds: where the table holds the 39 x 3 round
+// constants and the 3 x 3 matrix (the account lane's table has them elsewhere: account_lane.h).
+__device__ __forceinline__ void psd2_permute(F29 (&s)[3], const uint32_t* __restrict__ K, const uint32_t ark = SK_ARK, const uint32_t mds = SK_MDS) {
   for (int r = 0; r < 39; ++r) {
     const bool full = r < 4 || r >= 35;
     F29 t[3];
-    t[0] = psd_pow17(f29_add(s[0], rk_const(K, SK_ARK + 3 * r)));
+    t[0] = psd_pow17(f29_add(s[0], rk_const(K, ark + 3 * r)));
 #pragma unroll
     for (int i = 1; i < 3; ++i) {
-      t[i] = f29_add(s[i], rk_const(K, SK_ARK + 3 * r + i));
+      t[i] = f29_add(s[i], rk_const(K, ark + 3 * r + i));
       if (full) t[i] = psd_pow17(t[i]);
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      F29 acc = f29_mul(t[0], rk_const(K, SK_MDS + 3 * i));
-      acc = f29_add(acc, f29_mul(t[1], rk_const(K, SK_MDS + 3 * i + 1)));
-      acc = f29_add(acc, f29_mul(t[2], rk_const(K, SK_MDS + 3 * i + 2)));
+      F29 acc = f29_mul(t[0], rk_const(K, mds + 3 * i));
+      acc = f29_add(acc, f29_mul(t[1], rk_const(K, mds + 3 * i + 1)));
+      acc = f29_add(acc, f29_mul(t[2], rk_const(K, mds + 3 * i + 2)));
       f29_tidy(acc);
       s[i] = acc;
     }

@@ -534,6 +534,12 @@ class Account:
         check(lib().aleo_mi355x_account_from_private_key(private_key.encode(), _p(sk), _p(vk), _p(ax)), 'account_from_private_key')
         return cls(private_key, sk.tobytes(), vk.tobytes(), ax.tobytes())
 
+    @classmethod
+    def from_seed(cls, seed: bytes) -> 'Account':
+        """`new Account({seed})` of the reference's SDK (sdk/src/account.ts:82): aleo_amd.account.account_from_seed."""
+        from . import account
+        return account.account_from_seed(seed)
+
     @property
     def view_key_string(self) -> str:
         v = int.from_bytes(_VIEW_KEY_PREFIX + self.view_key, 'big'); out = ''

@@ -58,6 +58,7 @@ extern "C" {
 #define ALEO_MI355X_ERR_OOM 5
 #define ALEO_MI355X_ERR_UNSATISFIED 6  /* varuna_prove*: an assignment does not satisfy its circuit (upstream: the synthesiser's is_satisfied check) */
 #define ALEO_MI355X_ERR_NOT_OWNER 7    /* record_plaintext, record_decrypt: the decrypted (or public) owner is not the given address (upstream: "Decryption failed - view key did not match record") */
+#define ALEO_MI355X_ERR_INTERNAL 8     /* accounts_search: the host path does not confirm what the kernel found; nothing is handed out */
 
 /* NTT enums: mirror snarkvm_algorithms_cuda::{NTTInputOutputOrder, NTTDirection, NTTType} */
 #define ALEO_NTT_ORDER_NN 0   /* natural in, natural out (what fft_in_place exposes) */
@@ -828,6 +829,44 @@ int32_t aleo_mi355x_signature_from_string(void* out128, const char* s);
 int32_t aleo_mi355x_signatures_verify(uint8_t* flags, const void* sigs128, const void* addresses_x32, size_t address_stride, const void* messages, const uint64_t* offsets, size_t n);
 int32_t aleo_mi355x_signatures_verify_host(uint8_t* flags, const void* sigs128, const void* addresses_x32, size_t address_stride, const void* messages, const uint64_t* offsets, size_t n);
 size_t aleo_mi355x_min_signatures(void);
+
+/* ---- accounts in batches: keys and addresses of many seeds in one call, and the search for an address with a chosen prefix ---------------------------------------
+ * The first step of every record and signature call above: an account's sk_sig, view key and address, from the 32-byte seed of its private key — the reference's
+ * account module (wasm/src/account/private_key.rs:38-86 PrivateKey::new, from_seed_unchecked, to_view_key, to_address; sdk/src/account.ts:82) — snarkVM 0.14.5
+ * console/account [UPSTREAM-RECALL].  Pinned by data the reference holds: the derivation by the three accounts of tests/golden/reference_account.json, the private
+ * key string of a seed by sdk/tests/data/account-data.ts:4,8 (tests/golden/reference_seed.json).  UNPINNED: seed_from_bytes for a value not below r (the reference's
+ * one seed is below r).  A seed is the 32 bytes an "APrivateKey1…" string holds: a canonical little-endian field element.
+ *   accounts_derive   n seeds of 32 bytes -> rows of 32 canonical little-endian bytes (sk_sig32, view_key32, address_x32), rows of the 63 ASCII characters "aleo1…"
+ *                  with no terminator (address63), and flags: 0 derived; 3 the seed is not a canonical field element (its rows are zero).  Every output may be NULL.
+ *                  n below min_accounts runs the host code inside the call and needs no device; else one kernel launch per 2^20 accounts (ALEO_MI355X_ACCOUNTS_CHUNK
+ *                  caps it lower), one account per lane, the copies inside the call.  Thread-safe (one slot per call).
+ *   accounts_derive_host   the same bytes, computed by the calling thread (aleo_mi355x_account_from_private_key's code); touches no device.  The definition.
+ *   accounts_search   candidate i of [first, first + count) has the private-key seed "element i of the ChaCha20 stream under master32" (the prover's stream: counter i,
+ *                  64 bits wide, rejection sampling below r — uniform over the field, as PrivateKey::new(rng) draws its seed); it matches when the characters after
+ *                  "aleo1" of its address begin with `prefix`: 0 to 12 characters of qpzry9x8gf2tvdw0s3jn54khce6mua7l, anything else is ERR_BAD_ARG.  hit_index: the
+ *                  first max_hits matching indices, ascending; hit_seed32 (may be NULL): their seeds; *n_hits; *next: the index after the last hit when
+ *                  *n_hits == max_hits (first when max_hits is 0), first + count otherwise — a caller resumes from *next without seeing a candidate twice or skipping
+ *                  one.  count below min_accounts runs on the host; else launches of at most 2^20 candidates (ALEO_MI355X_ACCOUNTS_CHUNK) until max_hits are found,
+ *                  only the hits' indices come down, and every hit is derived again on the host before it is returned: one the host path does not confirm fails the
+ *                  call with ERR_INTERNAL.  The result does not depend on scheduling or on the launch size.
+ *   accounts_search_host   the same result, computed by the calling thread.  The definition.
+ *   min_accounts   the batch size from which accounts_derive and accounts_search take the GPU: 16, the smallest power of two at which the GPU call beats the host
+ *                  loop on one thread in both of two timings (profiles/accounts_derive.txt: a call costs 2.2-3.0 ms for any batch up to 2^12; the host loop 1.37 ms
+ *                  at 2^3, 0.55x and 0.54x, 2.77 ms at 2^4, 1.10x and 1.14x, 5.57 ms at 2^5, 2.16x and 2.23x; with the strings asked for 2^4 is 0.93x);
+ *                  ALEO_MI355X_MIN_ACCOUNTS overrides it, read per call (a bad value: the default).
+ *   private_key_from_seed / private_key_seed   32 bytes <-> "APrivateKey1…" (base58 of 11 prefix bytes and the seed; cap: 60 bytes hold it).  Both refuse a seed that
+ *                  is not a canonical field element; private_key_seed what account_from_private_key refuses.
+ *   seed_from_bytes   32 arbitrary bytes, little-endian, reduced mod r: from_seed_unchecked (private_key.rs:47-55) [UPSTREAM-RECALL, UNPINNED above r].
+ *   view_key_to_string   32 bytes -> "AViewKey1…" (cap: 54 bytes hold it). */
+int32_t aleo_mi355x_accounts_derive(const void* seeds32, size_t n, void* sk_sig32, void* view_key32, void* address_x32, char* address63, uint8_t* flags);
+int32_t aleo_mi355x_accounts_derive_host(const void* seeds32, size_t n, void* sk_sig32, void* view_key32, void* address_x32, char* address63, uint8_t* flags);
+int32_t aleo_mi355x_accounts_search(const void* master32, uint64_t first, uint64_t count, const char* prefix, size_t max_hits, uint64_t* hit_index, void* hit_seed32, size_t* n_hits, uint64_t* next);
+int32_t aleo_mi355x_accounts_search_host(const void* master32, uint64_t first, uint64_t count, const char* prefix, size_t max_hits, uint64_t* hit_index, void* hit_seed32, size_t* n_hits, uint64_t* next);
+size_t aleo_mi355x_min_accounts(void);
+int32_t aleo_mi355x_private_key_from_seed(char* out, size_t cap, const void* seed32);
+int32_t aleo_mi355x_private_key_seed(void* seed32, const char* private_key);
+int32_t aleo_mi355x_seed_from_bytes(void* seed32, const void* bytes32);
+int32_t aleo_mi355x_view_key_to_string(char* out, size_t cap, const void* view_key32);
 
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */

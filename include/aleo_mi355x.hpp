@@ -818,6 +818,74 @@ inline Result<PrivateAccount> account_from_private_key(const std::string& privat
   if (rc) return {std::nullopt, Error{rc}};
   return {a, Error{0}};
 }
+
+// ---- accounts in batches (aleo_mi355x_accounts_derive, _accounts_search): wasm/src/account/private_key.rs:38-86, sdk/src/account.ts:82 ------------------------------
+// A seed is the 32 bytes an "APrivateKey1…" string holds: a canonical little-endian field element.
+using KeySeed = std::array<uint8_t, 32>;
+inline Result<std::string> private_key_from_seed(const KeySeed& seed) {
+  char out[64];
+  int32_t rc = aleo_mi355x_private_key_from_seed(out, sizeof out, seed.data());
+  if (rc) return {std::nullopt, Error{rc}};
+  return {std::string(out), Error{0}};
+}
+inline Result<KeySeed> private_key_seed(const std::string& private_key) {
+  KeySeed s;
+  int32_t rc = aleo_mi355x_private_key_seed(s.data(), private_key.c_str());
+  if (rc) return {std::nullopt, Error{rc}};
+  return {s, Error{0}};
+}
+// from_seed_unchecked's reduction of 32 arbitrary bytes mod r (UNPINNED for a value not below r)
+inline KeySeed seed_from_bytes(const uint8_t* bytes32) { KeySeed s; (void)aleo_mi355x_seed_from_bytes(s.data(), bytes32); return s; }
+inline std::string view_key_to_string(const ViewKey& v) { char out[64] = {0}; (void)aleo_mi355x_view_key_to_string(out, sizeof out, v.scalar); return out; }
+// The accounts of n seeds in one call (host: on the calling thread), with their private key strings; a seed that is not a canonical field element fails the call.
+// addresses (optional): the n "aleo1…" strings, made where the accounts are.
+inline Result<std::vector<PrivateAccount>> derive_accounts(const std::vector<KeySeed>& seeds, bool host = false, std::vector<std::string>* addresses = nullptr) {
+  const size_t n = seeds.size();
+  std::vector<uint8_t> in(32 * n), sk(32 * n), vk(32 * n), ax(32 * n), flags(n); std::vector<char> text(addresses ? 63 * n : 0);
+  for (size_t i = 0; i < n; ++i) std::memcpy(in.data() + 32 * i, seeds[i].data(), 32);
+  int32_t rc = (host ? aleo_mi355x_accounts_derive_host : aleo_mi355x_accounts_derive)(in.data(), n, sk.data(), vk.data(), ax.data(), addresses ? text.data() : nullptr, flags.data());
+  if (rc) return {std::nullopt, Error{rc}};
+  std::vector<PrivateAccount> out(n);
+  if (addresses) addresses->clear();
+  for (size_t i = 0; i < n; ++i) {
+    if (flags[i]) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+    std::memcpy(out[i].sk_sig, sk.data() + 32 * i, 32); std::memcpy(out[i].view_key.scalar, vk.data() + 32 * i, 32); std::memcpy(out[i].address.x, ax.data() + 32 * i, 32);
+    auto key = private_key_from_seed(seeds[i]);
+    if (!key.is_ok()) return {std::nullopt, key.error};
+    out[i].private_key = *key.value;
+    if (addresses) addresses->emplace_back(text.data() + 63 * i, 63);
+  }
+  return {std::move(out), Error{0}};
+}
+// ... of n "APrivateKey1…" strings: decoded on the host, derived in one call
+inline Result<std::vector<PrivateAccount>> accounts_from_private_keys(const std::vector<std::string>& keys, bool host = false) {
+  std::vector<KeySeed> seeds;
+  for (const auto& k : keys) { auto s = private_key_seed(k); if (!s.is_ok()) return {std::nullopt, s.error}; seeds.push_back(*s.value); }
+  return derive_accounts(seeds, host);
+}
+// `new Account({seed})` of the reference's SDK: the 32 bytes reduced mod r, then the account, on the calling thread
+inline Result<PrivateAccount> account_from_seed(const uint8_t* bytes32) {
+  auto r = derive_accounts({seed_from_bytes(bytes32)}, true);
+  if (!r.is_ok()) return {std::nullopt, r.error};
+  return {(*r.value)[0], Error{0}};
+}
+// The first max_hits candidates of [first, first + count) under a 32-byte master seed whose address begins with "aleo1" + prefix (0 to 12 characters of the
+// bech32 alphabet), as accounts with their private key strings; index: their positions; next: where to resume.  Candidate i's private-key seed is element i of the
+// ChaCha20 stream under the master seed, which regenerates every key found: keep it secret.
+struct AccountSearch { std::vector<PrivateAccount> accounts; std::vector<uint64_t> index; uint64_t next = 0; };
+inline Result<AccountSearch> search_accounts(const uint8_t* master32, const std::string& prefix, uint64_t first, uint64_t count, size_t max_hits = 1, bool host = false) {
+  AccountSearch out; out.index.resize(max_hits ? max_hits : 1);
+  std::vector<uint8_t> seeds(32 * out.index.size()); size_t n = 0;
+  int32_t rc = (host ? aleo_mi355x_accounts_search_host : aleo_mi355x_accounts_search)(master32, first, count, prefix.c_str(), max_hits, out.index.data(), seeds.data(), &n, &out.next);
+  if (rc) return {std::nullopt, Error{rc}};
+  out.index.resize(n);
+  std::vector<KeySeed> found(n);
+  for (size_t i = 0; i < n; ++i) std::memcpy(found[i].data(), seeds.data() + 32 * i, 32);
+  auto accts = derive_accounts(found, true);
+  if (!accts.is_ok()) return {std::nullopt, accts.error};
+  out.accounts = std::move(*accts.value);
+  return {std::move(out), Error{0}};
+}
 // n serial numbers (32 canonical little-endian bytes each) and flags (0 computed, 2 refused: a zero row, the record is dropped as upstream's `.ok()?` drops it) of n
 // commitments under one sk_sig
 struct SerialNumbers { std::vector<uint8_t> rows, flags; const uint8_t* row(size_t i) const { return rows.data() + 32 * i; } size_t size() const { return flags.size(); } };
