@@ -2,6 +2,7 @@
 // field, transform, prover and self-test entry points.  Devices and slots: device.hip; base sets: bases.hip; several devices: sharded.hip.  Kernels live in msm_sort.hip / msm.hip / g1_setup.hip / ntt.hip / frops.hip / fr_spmv.hip / fr_divide.hip / ahp_kernels.hip.
 #include "entry.h"
 #include "frops.h"
+#include "g2.h"
 #include "host_field.hpp"
 #include <cstdlib>
 #include <chrono>

@@ -1,6 +1,7 @@
 // bases.hip — base sets of libaleo_mi355x.so: staging point rows into HBM (pinned sets that own their buffers, the cold one-shot call's copy in the slot's),
 // the G1 and G2 handle tables, fixed-base tables built once per set, the SRS cache, host-scalar MSMs against a set, and the bases_* entry points.
 #include "entry.h"
+#include "g2.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -11,7 +12,7 @@ namespace aleo_mi355x {
 // into packed ones plus one flag byte per row, and leaves the number of set flags in a uint32 behind the flags, at the next multiple of 4.
 struct RowFormat { size_t packed, strided; int32_t (*unpack)(Ctx* c, const void* d_rows, void* d_xy, void* d_flags, size_t n, hipStream_t s); };
 static int32_t unpack_g2_200(Ctx* c, const void* d_rows, void* d_xy, void* d_flags, size_t n, hipStream_t s) {
-  return g2_unpack200(c, d_rows, d_xy, d_flags, (uint32_t*)((char*)d_flags + ((n + 3) & ~(size_t)3)), n, s);
+  return g2_unpack200(d_rows, d_xy, d_flags, (uint32_t*)((char*)d_flags + ((n + 3) & ~(size_t)3)), n, s);
 }
 static constexpr RowFormat G1_ROWS = {96, 104, unpack_affine104}, G2_ROWS = {192, 200, unpack_g2_200};
 

@@ -246,12 +246,6 @@ int32_t commit_sharded(Ctx* c, uint64_t sharded_handle, const MsmSeg* segs, uint
 // sharded.hip: one transform of 2^lg_n elements resident at d_inout on the caller's device, computed over the listed devices (4-step, peer copies, no host buffer); blocking
 int32_t ntt_sharded_device(Ctx* c, void* d_inout, uint32_t lg_n, int32_t direction, int32_t type, const int* devices, size_t n_devices, hipStream_t s);
 int32_t sharded_devices(uint64_t sharded_handle, std::vector<int>* out);      // the device list of a sharded base set
-// g2.hip
-int32_t msm_g2_run(Ctx* c, uint64_t* out_jac36, const void* d_xy, const uint8_t* d_inf, const void* d_scalars, size_t n, hipStream_t s, const void* d_rows28 = nullptr);      // d_rows28: the set's resident 28-bit rows (a pinned G2 set), else built per call
-int32_t g2_rows_to28(const void* d_xy192, void* d_dst224, size_t n, hipStream_t s);
-int32_t g2_sum_host(uint64_t* out36, const uint64_t* pts36, size_t count);
-int32_t selftest_g2pair(Ctx* c, const void* aff192_host, uint32_t n, uint32_t npairs, uint32_t* failures2);      // [0] pairs that disagreed, [1] OR of the failing steps
-int32_t g2_unpack200(Ctx* c, const void* d_rows200, void* d_xy192, void* d_flags, uint32_t* d_count, size_t n, hipStream_t s);      // 200-byte G2Affine rows -> 192-byte rows + flag bytes + their count
 // varuna.hip; the index: varuna_index.hip (jacobian_rows_to_affine104: api.hip)
 // one request of a lockstep call (varuna_prove_many): the circuits of ONE proof, its assignments, seed and output; status / error come back per request
 struct ProveRequest { std::vector<const aleo_mi355x_varuna_index*> ixs; const void* const* assignments = nullptr; const size_t* ks = nullptr; const uint8_t* seed32 = nullptr;

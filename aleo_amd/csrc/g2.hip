@@ -4,33 +4,39 @@
 // every curve but BLS12-377 G1 to the standard Pippenger] over snarkvm-curves bls12_377/{fq2,g2}.rs (pin: /root/reference/Cargo.lock:2637).
 // The prover never runs a G2 MSM (G2 appears in the verifying key and in SRS setup), so this path is built for
 // parity and reach, not for the last percent: it shares the whole scalar side with G1 — signed-digit windows, the two-level
-// counting sort, slice sizing and ordering (msm_sort.hip msm_sort_phase: none of it depends on the group) — and swaps the group law:
+// counting sort, slice sizing and ordering (msm_sort.hip msm_sort_phase: none of it depends on the group) — and, behind its own accumulation, the plain
+// path's slice trees, reduction kernels and host back end (msm_reduce.h, msm_front_finish), instantiated for its point format — and swaps the group law:
 // extended Jacobian (XYZZ) over Fq2 on the 32-bit-limb Montgomery blocks of fp.h, one lane per addition, out-of-line field
 // calls (a 2 x 12-limb product inlined ten times per addition would not fit the register file).
 //
 // Layouts at the boundary (snarkVM in-memory): G2Affine {x: Fq2 (c0, c1), y: Fq2, infinity: bool} = 4 x 48 bytes Montgomery +
 // flag byte at 192, stride 200 (or 192 without the flag); result G2Projective (Jacobian) {x, y, z: Fq2} = 288 bytes,
 // returned affine-normalised (x, y, 1) or (1, 1, 0) for the identity.  HBM: bases n x 192 B (+ 224 B 28-bit rows); partial sums 448 B per slice.
-#include "ctx.h"
-#include "ec.h"
-#include "fp28.h"
-#include "host_field.hpp"
-#include "msm_common.h"
-#include <vector>
+#include "g2.h"
+#include "msm_reduce.h"
 
 namespace aleo_mi355x {
 
-// ---- Fq2 on the device: components stay below 2q between operations ----------------------------------------------------
-struct Fq2 { Fq a, b; };                       // a + b u,  u^2 = -5
-struct G2Affine { Fq2 x, y; };                 // 192 bytes
-struct XYZZ2 { Fq2 X, Y, ZZ, ZZZ; };           // 384 bytes; infinity <=> ZZ stored as raw zero
-
+// ---- Fq2 on the device: components stay below 2q between operations, so the one XYZZ law of xyzz_law.h runs over it as it does over the host's fields ---
+struct Fq2;
+__device__ void fq2_mul_ni(Fq2* r, const Fq2* px, const Fq2* py);
+__device__ void fq2_sqr_ni(Fq2* r, const Fq2* px);
 __device__ __forceinline__ Fq lt2q(const Fq& x) { return Fq::cond_sub<2>(x); }                       // < 4q -> < 2q
-__device__ __forceinline__ Fq2 fq2_zero() { Fq2 r; r.a = Fq::zero(); r.b = Fq::zero(); return r; }
-__device__ __forceinline__ Fq2 fq2_one() { Fq2 r; r.a = Fq::one(); r.b = Fq::zero(); return r; }
-__device__ __forceinline__ Fq2 fq2_add(const Fq2& x, const Fq2& y) { Fq2 r; r.a = lt2q(Fq::add(x.a, y.a)); r.b = lt2q(Fq::add(x.b, y.b)); return r; }
-__device__ __forceinline__ Fq2 fq2_sub(const Fq2& x, const Fq2& y) { Fq2 r; r.a = lt2q(Fq::sub<2>(x.a, y.a)); r.b = lt2q(Fq::sub<2>(x.b, y.b)); return r; }
-__device__ __forceinline__ Fq2 fq2_dbl(const Fq2& x) { return fq2_add(x, x); }
+struct Fq2 {                                   // a + b u,  u^2 = -5
+  Fq a, b;
+  static __device__ __forceinline__ Fq2 zero() { Fq2 r; r.a = Fq::zero(); r.b = Fq::zero(); return r; }
+  static __device__ __forceinline__ Fq2 one() { Fq2 r; r.a = Fq::one(); r.b = Fq::zero(); return r; }
+  static __device__ __forceinline__ Fq2 add(const Fq2& x, const Fq2& y) { Fq2 r; r.a = lt2q(Fq::add(x.a, y.a)); r.b = lt2q(Fq::add(x.b, y.b)); return r; }
+  static __device__ __forceinline__ Fq2 sub(const Fq2& x, const Fq2& y) { Fq2 r; r.a = lt2q(Fq::sub<2>(x.a, y.a)); r.b = lt2q(Fq::sub<2>(x.b, y.b)); return r; }
+  static __device__ __forceinline__ Fq2 dbl(const Fq2& x) { return add(x, x); }
+  static __device__ __forceinline__ Fq2 mul(const Fq2& x, const Fq2& y) { Fq2 r; fq2_mul_ni(&r, &x, &y); return r; }      // out of line: a 2 x 12-limb product inlined ten times per addition would not fit the register file
+  static __device__ __forceinline__ Fq2 sqr(const Fq2& x) { Fq2 r; fq2_sqr_ni(&r, &x); return r; }
+  __device__ __forceinline__ bool is_zero() const { return a.is_zero_mod_lt2p() && b.is_zero_mod_lt2p(); }
+  __device__ __forceinline__ bool is_zero_raw() const { return a.is_zero_raw() && b.is_zero_raw(); }
+};
+struct G2Affine { Fq2 x, y; };                 // 192 bytes
+using XYZZ2 = XYZZOf<Fq2>;                     // 384 bytes; infinity <=> ZZ stored as raw zero
+
 __device__ __forceinline__ Fq fq_times5_canonical(const Fq& v) {      // 5 v mod q, v < 2q
   Fq d2 = Fq::dbl(v), d4 = Fq::dbl(d2);                               // < 4q, < 8q
   return Fq::reduce(Fq::add(d4, v));                                  // < 10q -> canonical
@@ -55,70 +61,27 @@ __device__ __noinline__ void fq2_sqr_ni(Fq2* r, const Fq2* px) {
   o.a = Fq::reduce(Fq::add(w, Fq::dbl(Fq::dbl(m))));                  // < 10q -> canonical
   *r = o;
 }
-__device__ __forceinline__ Fq2 fq2_mul(const Fq2& x, const Fq2& y) { Fq2 r; fq2_mul_ni(&r, &x, &y); return r; }
-__device__ __forceinline__ Fq2 fq2_sqr(const Fq2& x) { Fq2 r; fq2_sqr_ni(&r, &x); return r; }
-__device__ __forceinline__ bool fq2_is_zero(const Fq2& x) { return x.a.is_zero_mod_lt2p() && x.b.is_zero_mod_lt2p(); }
-__device__ __forceinline__ bool fq2_is_zero_raw(const Fq2& x) { return x.a.is_zero_raw() && x.b.is_zero_raw(); }
-
 __device__ __forceinline__ Fq2 load_fq2(const void* p) { Fq2 r; r.a = load_fp<Fq>(p); r.b = load_fp<Fq>((const char*)p + 48); return r; }
-__device__ __forceinline__ void store_fq2(void* p, const Fq2& x) { store_fp<Fq>(p, x.a); store_fp<Fq>((char*)p + 48, x.b); }
-__device__ __forceinline__ XYZZ2 g2_infinity() { XYZZ2 r; r.X = fq2_zero(); r.Y = r.X; r.ZZ = r.X; r.ZZZ = r.X; return r; }
-__device__ __forceinline__ bool g2_is_inf(const XYZZ2& p) { return fq2_is_zero_raw(p.ZZ); }
-__device__ __forceinline__ XYZZ2 load_xyzz2(const void* p) {
-  const char* c = (const char*)p; XYZZ2 r; r.X = load_fq2(c); r.Y = load_fq2(c + 96); r.ZZ = load_fq2(c + 192); r.ZZZ = load_fq2(c + 288); return r;
-}
-__device__ __forceinline__ void store_xyzz2(void* p, const XYZZ2& a) {
-  char* c = (char*)p; store_fq2(c, a.X); store_fq2(c + 96, a.Y); store_fq2(c + 192, a.ZZ); store_fq2(c + 288, a.ZZZ);
-}
 
-// 2P (EFD dbl-2008-s-1, a = 0)
-__device__ __noinline__ void g2_double_ni(XYZZ2* io) {
-  const XYZZ2 p = *io;
-  if (g2_is_inf(p)) return;
-  Fq2 U = fq2_dbl(p.Y), V = fq2_sqr(U), W = fq2_mul(U, V), S = fq2_mul(p.X, V);
-  Fq2 xx = fq2_sqr(p.X), M = fq2_add(fq2_dbl(xx), xx);
-  XYZZ2 r;
-  r.X = fq2_sub(fq2_sqr(M), fq2_dbl(S));
-  r.Y = fq2_sub(fq2_mul(M, fq2_sub(S, r.X)), fq2_mul(W, p.Y));
-  r.ZZ = fq2_mul(V, p.ZZ); r.ZZZ = fq2_mul(W, p.ZZZ);
-  if (fq2_is_zero(r.ZZ)) r = g2_infinity();                           // y == 0: a 2-torsion point
-  *io = r;
-}
-// acc += b, both XYZZ (EFD add-2008-s); handles the identity, doubling and cancellation
-__device__ __noinline__ void g2_add_ni(XYZZ2* pa, const XYZZ2* pb) {
-  const XYZZ2 a = *pa, b = *pb;
-  if (g2_is_inf(b)) return;
-  if (g2_is_inf(a)) { *pa = b; return; }
-  Fq2 U1 = fq2_mul(a.X, b.ZZ), U2 = fq2_mul(b.X, a.ZZ), S1 = fq2_mul(a.Y, b.ZZZ), S2 = fq2_mul(b.Y, a.ZZZ);
-  Fq2 P = fq2_sub(U2, U1), R = fq2_sub(S2, S1);
-  if (fq2_is_zero(P)) {
-    if (fq2_is_zero(R)) { XYZZ2 d = a; g2_double_ni(&d); *pa = d; } else *pa = g2_infinity();
-    return;
-  }
-  Fq2 PP = fq2_sqr(P), PPP = fq2_mul(P, PP), Q = fq2_mul(U1, PP);
-  XYZZ2 r;
-  r.X = fq2_sub(fq2_sub(fq2_sqr(R), PPP), fq2_dbl(Q));
-  r.Y = fq2_sub(fq2_mul(R, fq2_sub(Q, r.X)), fq2_mul(S1, PPP));
-  r.ZZ = fq2_mul(fq2_mul(a.ZZ, b.ZZ), PP);
-  r.ZZZ = fq2_mul(fq2_mul(a.ZZZ, b.ZZZ), PPP);
-  *pa = r;
-}
-// acc += (x, y) affine (EFD madd-2008-s)
+// 2P and acc += b: the law of xyzz_law.h, out of line (the identity, doubling and cancellation included)
+__device__ __noinline__ void g2_double_ni(XYZZ2* io) { *io = law_double(*io); }
+__device__ __noinline__ void g2_add_ni(XYZZ2* pa, const XYZZ2* pb) { const XYZZ2 a = *pa, b = *pb; *pa = law_add(a, b); }
+// acc += (x, y) affine (EFD madd-2008-s): the repeated-base path's own formula (an addition with ZZ = ZZZ = 1 would spend four products on the ones)
 __device__ __noinline__ void g2_madd_ni(XYZZ2* pa, const G2Affine* pp) {
   const XYZZ2 a = *pa; const G2Affine q = *pp;
-  if (g2_is_inf(a)) { XYZZ2 r; r.X = q.x; r.Y = q.y; r.ZZ = fq2_one(); r.ZZZ = fq2_one(); *pa = r; return; }
-  Fq2 U2 = fq2_mul(q.x, a.ZZ), S2 = fq2_mul(q.y, a.ZZZ);
-  Fq2 P = fq2_sub(U2, a.X), R = fq2_sub(S2, a.Y);
-  if (fq2_is_zero(P)) {
-    if (fq2_is_zero(R)) { XYZZ2 d; d.X = q.x; d.Y = q.y; d.ZZ = fq2_one(); d.ZZZ = fq2_one(); g2_double_ni(&d); *pa = d; } else *pa = g2_infinity();
+  if (a.is_inf()) { XYZZ2 r; r.X = q.x; r.Y = q.y; r.ZZ = Fq2::one(); r.ZZZ = Fq2::one(); *pa = r; return; }
+  Fq2 U2 = Fq2::mul(q.x, a.ZZ), S2 = Fq2::mul(q.y, a.ZZZ);
+  Fq2 P = Fq2::sub(U2, a.X), R = Fq2::sub(S2, a.Y);
+  if (P.is_zero()) {
+    if (R.is_zero()) { XYZZ2 d; d.X = q.x; d.Y = q.y; d.ZZ = Fq2::one(); d.ZZZ = Fq2::one(); g2_double_ni(&d); *pa = d; } else *pa = XYZZ2::infinity();
     return;
   }
-  Fq2 PP = fq2_sqr(P), PPP = fq2_mul(P, PP), Q = fq2_mul(a.X, PP);
+  Fq2 PP = Fq2::sqr(P), PPP = Fq2::mul(P, PP), Q = Fq2::mul(a.X, PP);
   XYZZ2 r;
-  r.X = fq2_sub(fq2_sub(fq2_sqr(R), PPP), fq2_dbl(Q));
-  r.Y = fq2_sub(fq2_mul(R, fq2_sub(Q, r.X)), fq2_mul(a.Y, PPP));
-  r.ZZ = fq2_mul(a.ZZ, PP);
-  r.ZZZ = fq2_mul(a.ZZZ, PPP);
+  r.X = Fq2::sub(Fq2::sub(Fq2::sqr(R), PPP), Fq2::dbl(Q));
+  r.Y = Fq2::sub(Fq2::mul(R, Fq2::sub(Q, r.X)), Fq2::mul(a.Y, PPP));
+  r.ZZ = Fq2::mul(a.ZZ, PP);
+  r.ZZZ = Fq2::mul(a.ZZZ, PPP);
   *pa = r;
 }
 
@@ -147,8 +110,8 @@ template <uint32_t KY> __device__ __forceinline__ F28 fq2p_mul(const F28& x, con
   const F28 b2 = f28_sel(odd, f28_neg5<KY>(oy), y);        // even: x.b * (-5 y.b)   odd: x.a * y.b
   return f28_muladd(x, b1, ox, b2);
 }
-// both lanes exchange their flags FIRST, then decide: `z && shfl(z)` would skip the exchange on the lane whose flag is false and leave its partner reading an inactive lane
-__device__ __forceinline__ bool g2p_zero_mod_early(const F28& v_lt2q_exact) { const bool z = f28_is_zero_mod_lt2q(v_lt2q_exact), zo = (bool)__shfl_xor((int)z, 1); return z && zo; }
+__device__ __forceinline__ bool pair_and(bool v) { const bool o = (bool)__shfl_xor((int)v, 1); return v && o; }      // the exchange first, by BOTH lanes: `v && shfl(..)` would skip it on the lane whose v is false and leave its partner reading an inactive lane
+__device__ __forceinline__ bool g2p_zero_mod(const F28& v_lt2q_exact) { return pair_and(f28_is_zero_mod_lt2q(v_lt2q_exact)); }      // an Fq2 value is 0 iff both components are
 struct XYZZ2P { F28 X, Y, ZZ, ZZZ; };                      // my components of an XYZZ point over Fq2
 // acc += (x2, y2).  In: acc.X exact < 12q, acc.Y exact < 6q, acc.ZZ / ZZZ exact < 2q; x2, y2 exact < 2q.  Out: the same.  false (acc untouched): P == +-acc.
 __device__ __forceinline__ bool g2p_madd_fast(XYZZ2P& acc, const F28& x2, const F28& y2, bool odd) {
@@ -159,7 +122,7 @@ __device__ __forceinline__ bool g2p_madd_fast(XYZZ2P& acc, const F28& x2, const 
   const F28 PP = fq2p_mul<96>(P, P, odd);                                          // (18*18 + 18*96) / 38000 + 1 -> < 2q
   const F28 ZZ3 = fq2p_mul<16>(acc.ZZ, PP, odd);                                   // < 2q
   {
-    if (__builtin_expect(g2p_zero_mod_early(ZZ3), 0)) return false;
+    if (__builtin_expect(g2p_zero_mod(ZZ3), 0)) return false;
   }
   const F28 PPP = fq2p_mul<16>(P, PP, odd);                                        // (18*2 + 18*16) / 38000 + 1 -> < 2q
   const F28 Q = fq2p_mul<16>(acc.X, PP, odd);                                      // (12*2 + 12*16) / 38000 + 1 -> < 2q
@@ -178,7 +141,7 @@ __device__ __forceinline__ bool g2p_madd_fast(XYZZ2P& acc, const F28& x2, const 
 // ---- stored points of the pair form: 448 bytes = X.a | X.b | Y.a | Y.b | ZZ.a | ZZ.b | ZZZ.a | ZZZ.b, 14 x 28-bit limbs each --------------------------------
 // Stored invariant (what g2p_madd_fast keeps for its accumulator): X exact digits < 12q, Y exact < 6q, ZZ / ZZZ exact < 2q; the identity = all zero.
 // Everything below is pair-cooperative: both lanes of a pair call with the same pointers, each moves and computes its own component.
-static constexpr uint32_t P2B = 448;
+static constexpr uint32_t P2B = 448, ROW2 = 224;      // a stored point; a base's 28-bit row
 __device__ __forceinline__ XYZZ2P g2p_load(const char* p, bool odd) {
   const char* c = p + (odd ? 56 : 0); XYZZ2P r; r.X = load_f28(c); r.Y = load_f28(c + 112); r.ZZ = load_f28(c + 224); r.ZZZ = load_f28(c + 336); return r;
 }
@@ -186,9 +149,7 @@ __device__ __forceinline__ void g2p_store(char* p, bool odd, const XYZZ2P& a) {
   char* c = p + (odd ? 56 : 0); store_f28(c, a.X); store_f28(c + 112, a.Y); store_f28(c + 224, a.ZZ); store_f28(c + 336, a.ZZZ);
 }
 __device__ __forceinline__ void g2p_store_inf(char* p, bool odd) { XYZZ2P z; z.X = f28_const(Limbs14{}); z.Y = z.X; z.ZZ = z.X; z.ZZZ = z.X; g2p_store(p, odd, z); }
-__device__ __forceinline__ bool pair_and(bool v) { const bool o = (bool)__shfl_xor((int)v, 1); return v && o; }      // the exchange first, by BOTH lanes: `v && shfl(..)` would skip it on the lane whose v is false and leave its partner reading an inactive lane
 __device__ __forceinline__ bool g2p_is_inf(const XYZZ2P& a) { return pair_and(f28_is_zero_raw(a.ZZ)); }
-__device__ __forceinline__ bool g2p_zero_mod(const F28& v_lt2q_exact) { return pair_and(f28_is_zero_mod_lt2q(v_lt2q_exact)); }      // an Fq2 value is 0 iff both components are
 // 2a (EFD dbl-2008-s-1, a = 0); a not the identity
 __device__ __forceinline__ XYZZ2P g2p_double(const XYZZ2P& a, bool odd, bool* is_inf) {
   const F28 U = f28_normalise(f28_add(a.Y, a.Y));                                  // < 12q
@@ -259,14 +220,14 @@ __device__ __noinline__ void g2p_double_any(const char* pa, char* out) {
 // conversions between the pair form and the 32-bit XYZZ2 the slow path of the accumulation works in (one lane does the whole point)
 __device__ __noinline__ void g2_p2_to_xyzz2(const char* p, XYZZ2* out) {
   XYZZ2 r;
-  if (f28_is_zero_raw(load_f28(p + 224)) && f28_is_zero_raw(load_f28(p + 280))) { *out = g2_infinity(); return; }
+  if (f28_is_zero_raw(load_f28(p + 224)) && f28_is_zero_raw(load_f28(p + 280))) { *out = XYZZ2::infinity(); return; }
   r.X.a = f28_to_fq(load_f28(p)); r.X.b = f28_to_fq(load_f28(p + 56)); r.Y.a = f28_to_fq(load_f28(p + 112)); r.Y.b = f28_to_fq(load_f28(p + 168));
   r.ZZ.a = f28_to_fq(load_f28(p + 224)); r.ZZ.b = f28_to_fq(load_f28(p + 280)); r.ZZZ.a = f28_to_fq(load_f28(p + 336)); r.ZZZ.b = f28_to_fq(load_f28(p + 392));
   *out = r;
 }
 __device__ __noinline__ void g2_xyzz2_to_p2(const XYZZ2* in, char* p) {
   const XYZZ2 a = *in;
-  if (g2_is_inf(a) || fq2_is_zero(a.ZZ)) { for (int i = 0; i < 8; ++i) store_f28(p + 56 * i, f28_const(Limbs14{})); return; }
+  if (a.is_inf() || a.ZZ.is_zero()) { for (int i = 0; i < 8; ++i) store_f28(p + 56 * i, f28_const(Limbs14{})); return; }
   store_f28(p, f28_from_fq(a.X.a)); store_f28(p + 56, f28_from_fq(a.X.b)); store_f28(p + 112, f28_from_fq(a.Y.a)); store_f28(p + 168, f28_from_fq(a.Y.b));
   store_f28(p + 224, f28_from_fq(a.ZZ.a)); store_f28(p + 280, f28_from_fq(a.ZZ.b)); store_f28(p + 336, f28_from_fq(a.ZZZ.a)); store_f28(p + 392, f28_from_fq(a.ZZZ.b));
 }
@@ -274,7 +235,7 @@ __device__ __noinline__ void g2_xyzz2_to_p2(const XYZZ2* in, char* p) {
 // 192-byte rows (x.a | x.b | y.a | y.b, 32-bit Montgomery) -> 224-byte rows [x.a | y.a | x.b | y.b] in the 28-bit form: each lane of a pair reads 112 contiguous bytes
 __global__ void __launch_bounds__(256) k_g2_rows_to28(const char* __restrict__ src192, char* __restrict__ dst224, uint32_t n) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
-  const char* r = src192 + (size_t)i * 192; char* o = dst224 + (size_t)i * 224;
+  const char* r = src192 + (size_t)i * 192; char* o = dst224 + (size_t)i * ROW2;
   store_affine28(o, f28_from_fq(load_fp<Fq>(r)), f28_from_fq(load_fp<Fq>(r + 96)));
   store_affine28(o + 112, f28_from_fq(load_fp<Fq>(r + 48)), f28_from_fq(load_fp<Fq>(r + 144)));
 }
@@ -289,8 +250,7 @@ __global__ void __launch_bounds__(256) k_g2_unpack200(const char* __restrict__ r
   flags[i] = f;
   if (f) atomicAdd(n_inf, 1u);
 }
-int32_t g2_unpack200(Ctx* c, const void* d_rows200, void* d_xy192, void* d_flags, uint32_t* d_count, size_t n, hipStream_t s) {
-  (void)c;
+int32_t g2_unpack200(const void* d_rows200, void* d_xy192, void* d_flags, uint32_t* d_count, size_t n, hipStream_t s) {
   HIPCHK(hipMemsetAsync(d_count, 0, 4, s));
   if (n) hipLaunchKernelGGL(k_g2_unpack200, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const char*)d_rows200, (char*)d_xy192, (uint8_t*)d_flags, d_count, (uint32_t)n);
   HIPCHK(hipGetLastError());
@@ -324,7 +284,7 @@ __global__ void __launch_bounds__(256, 2) k_g2_accum28(const char* __restrict__ 
   const uint32_t* run = sorted + st.x;
   char* slot = partial + (size_t)sid * P2B;
   auto fetch = [&](uint32_t e, F28& x, F28& y) {
-    load_affine28(rows28 + (size_t)(e & 0x7fffffffu) * 224 + (odd ? 112 : 0), x, y);
+    load_affine28(rows28 + (size_t)(e & 0x7fffffffu) * ROW2 + (odd ? 112 : 0), x, y);
     if (e >> 31) y = f28_normalise(f28_sub<2, 1>(f28_const(Limbs14{}), y));      // 2q - y (canonical rows): exact digits, <= 2q
   };
   XYZZ2P acc; uint32_t j = j0; bool ok = true;
@@ -349,24 +309,11 @@ __global__ void __launch_bounds__(256, 2) k_g2_accum28(const char* __restrict__ 
     if (!odd) g2_slice_slow_path(bases192, run, j, j1, slot);
   }
 }
-// ---- the reduction in the pair form (round 4): the bookkeeping of msm.hip, one lane pair per operation, points of 448 bytes ------
-__global__ void __launch_bounds__(256) k_g2p_tree_pass(char* __restrict__ partial, const uint32_t* __restrict__ list, const uint2* __restrict__ scan_local,
-                                                       const uint2* __restrict__ scan_blk, uint32_t M, const uint32_t* __restrict__ meta, uint32_t pass, uint32_t max_pairs,
-                                                       uint32_t list_len) {
-  const uint32_t op = (blockIdx.x * 256 + threadIdx.x) >> 1;
-  uint32_t h = op / max_pairs, i = op % max_pairs;
-  if (h >= list_len) return;
-  uint32_t g = list[h];
-  uint32_t ft = scan_at(scan_local, scan_blk, g).y;
-  uint32_t fn = (g + 1 < M) ? scan_at(scan_local, scan_blk, g + 1).y : meta[0];
-  uint32_t L = fn - ft;
-  for (uint32_t p = 0; p < pass; ++p) L = (L + 1) >> 1;
-  if (L <= 1) return;
-  uint32_t half = (L + 1) >> 1;
-  if (i >= L - half) return;
-  char* pa = partial + (size_t)(ft + i) * P2B;
-  g2p_add_any(pa, pa + (size_t)half * P2B, pa);
-}
+// ---- the reduction in the pair form: the plain path's kernels and back end (msm_reduce.h) over this point format, one lane pair per addition ------
+struct PtG2 {
+  static constexpr uint32_t BYTES = P2B;
+  template <uint32_t LANES> static __device__ __forceinline__ void add(const char* pa, const char* pb, char* out) { static_assert(LANES == 2, "the pair form"); g2p_add_any(pa, pb, out); }
+};
 // one lane pair per chunk of S consecutive buckets: run / acc / the double-and-add register live in a per-pair work area between the cooperative operations
 __global__ void __launch_bounds__(128) k_g2p_bucket_chunks(const char* __restrict__ partial, const uint32_t* __restrict__ hist, const uint2* __restrict__ scan_local,
                                                            const uint2* __restrict__ scan_blk, uint32_t B, uint32_t S, uint32_t nchunks_total, char* __restrict__ V,
@@ -388,20 +335,6 @@ __global__ void __launch_bounds__(128) k_g2p_bucket_chunks(const char* __restric
   }
   const XYZZ2P v = g2p_load(acc, odd); g2p_store(V + (size_t)t * P2B, odd, v);
 }
-__global__ void __launch_bounds__(256) k_g2p_seg_tree_pass(char* __restrict__ V, uint32_t seg_len, uint32_t nseg, uint32_t L) {
-  const uint32_t half = (L + 1) >> 1, pairs = L - half;
-  const uint32_t op = (blockIdx.x * 256 + threadIdx.x) >> 1;
-  if (op >= pairs * nseg) return;
-  const uint32_t seg = op / pairs, i = op % pairs;
-  char* pa = V + ((size_t)seg * seg_len + i) * P2B;
-  g2p_add_any(pa, pa + (size_t)half * P2B, pa);
-}
-__global__ void k_g2p_gather_windows(const char* __restrict__ V, uint32_t seg_len, uint32_t W, char* __restrict__ out) {
-  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= W * 28) return;
-  uint32_t w = t / 28, q = t % 28;
-  ((uint4*)out)[t] = ((const uint4*)(V + (size_t)w * seg_len * P2B))[q];
-}
 
 // Test hook: the pair-form addition / doubling against the one-lane 32-bit code on chains of real curve points (aleo_mi355x_selftest_g2pair).
 // Pair t takes the affine points i = t, t + 1, t + 2 (mod n): s = (P_i + P_j) + P_k, u = s + (P_i + P_j), d = 2u, e = u + u (the same-point case),
@@ -410,7 +343,7 @@ __global__ void __launch_bounds__(128) k_g2p_selftest(const char* __restrict__ a
   const uint32_t t = (blockIdx.x * 128 + threadIdx.x) >> 1; const bool odd = threadIdx.x & 1;
   if (t >= npairs) return;
   char* sl = scratch + (size_t)t * 9 * P2B;                  // nine pair-form slots per pair
-  auto aff = [&](uint32_t i) { XYZZ2 r; const char* row = aff192 + (size_t)(i % n) * 192; r.X = load_fq2(row); r.Y = load_fq2(row + 96); r.ZZ = fq2_one(); r.ZZZ = fq2_one(); return r; };
+  auto aff = [&](uint32_t i) { XYZZ2 r; const char* row = aff192 + (size_t)(i % n) * 192; r.X = load_fq2(row); r.Y = load_fq2(row + 96); r.ZZ = Fq2::one(); r.ZZZ = r.ZZ; return r; };
   XYZZ2 Pi = aff(t), Pj = aff(t + 1), Pk = aff(t + 2);
   if (!odd) { g2_xyzz2_to_p2(&Pi, sl); g2_xyzz2_to_p2(&Pj, sl + P2B); g2_xyzz2_to_p2(&Pk, sl + 2 * P2B); }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -430,7 +363,7 @@ __global__ void __launch_bounds__(128) k_g2p_selftest(const char* __restrict__ a
     XYZZ2 got; g2_p2_to_xyzz2(slot, &got);
     XYZZ2 neg = want; neg.Y.a = lt2q(Fq::sub<2>(Fq::zero(), neg.Y.a)); neg.Y.b = lt2q(Fq::sub<2>(Fq::zero(), neg.Y.b));
     g2_add_ni(&got, &neg);
-    return !(g2_is_inf(got) || fq2_is_zero(got.ZZ));
+    return !(got.is_inf() || got.ZZ.is_zero());
   };
   uint32_t bad = 0;
   if (differs(sl + 8 * P2B, a)) bad |= 64;                  // g2p_madd_fast
@@ -454,74 +387,6 @@ int32_t selftest_g2pair(Ctx* c, const void* aff192_host, uint32_t n, uint32_t np
   return ALEO_MI355X_OK;
 }
 
-// ---- host tail: Fq2 and G2 on the host -----------------------------------------------------------------------------------------
-namespace host {
-struct HFq2 {
-  HFq a, b;
-  static HFq2 zero() { HFq2 r; r.a = HFq::zero(); r.b = HFq::zero(); return r; }
-  static HFq2 one() { HFq2 r; r.a = HFq::one(); r.b = HFq::zero(); return r; }
-  bool is_zero() const { return a.is_zero() && b.is_zero(); }
-  static HFq2 add(const HFq2& x, const HFq2& y) { HFq2 r; r.a = HFq::add(x.a, y.a); r.b = HFq::add(x.b, y.b); return r; }
-  static HFq2 sub(const HFq2& x, const HFq2& y) { HFq2 r; r.a = HFq::sub(x.a, y.a); r.b = HFq::sub(x.b, y.b); return r; }
-  static HFq2 dbl(const HFq2& x) { return add(x, x); }
-  static HFq times5(const HFq& v) { HFq d = HFq::dbl(HFq::dbl(v)); return HFq::add(d, v); }
-  static HFq2 mul(const HFq2& x, const HFq2& y) {
-    HFq v0 = HFq::mul(x.a, y.a), v1 = HFq::mul(x.b, y.b);
-    HFq2 r; r.a = HFq::sub(v0, times5(v1)); r.b = HFq::sub(HFq::sub(HFq::mul(HFq::add(x.a, x.b), HFq::add(y.a, y.b)), v0), v1); return r;
-  }
-  static HFq2 sqr(const HFq2& x) { return mul(x, x); }
-  static HFq2 inv(const HFq2& x) {                     // (a - b u) / (a^2 + 5 b^2)
-    HFq n = HFq::inv(HFq::add(HFq::sqr(x.a), times5(HFq::sqr(x.b))));
-    HFq2 r; r.a = HFq::mul(x.a, n); r.b = HFq::neg(HFq::mul(x.b, n)); return r;
-  }
-};
-struct HXYZZ2 {
-  HFq2 X, Y, ZZ, ZZZ;
-  static HXYZZ2 infinity() { HXYZZ2 r; r.X = HFq2::zero(); r.Y = r.X; r.ZZ = r.X; r.ZZZ = r.X; return r; }
-  bool is_inf() const { return ZZ.is_zero(); }
-};
-static HXYZZ2 h2double(const HXYZZ2& p) {
-  if (p.is_inf()) return p;
-  HFq2 U = HFq2::dbl(p.Y), V = HFq2::sqr(U), W = HFq2::mul(U, V), S = HFq2::mul(p.X, V);
-  HFq2 xx = HFq2::sqr(p.X), M = HFq2::add(HFq2::dbl(xx), xx);
-  HXYZZ2 r;
-  r.X = HFq2::sub(HFq2::sqr(M), HFq2::dbl(S));
-  r.Y = HFq2::sub(HFq2::mul(M, HFq2::sub(S, r.X)), HFq2::mul(W, p.Y));
-  r.ZZ = HFq2::mul(V, p.ZZ); r.ZZZ = HFq2::mul(W, p.ZZZ);
-  if (r.ZZ.is_zero()) return HXYZZ2::infinity();
-  return r;
-}
-static HXYZZ2 h2add(const HXYZZ2& a, const HXYZZ2& b) {
-  if (a.is_inf()) return b;
-  if (b.is_inf()) return a;
-  HFq2 U1 = HFq2::mul(a.X, b.ZZ), U2 = HFq2::mul(b.X, a.ZZ), S1 = HFq2::mul(a.Y, b.ZZZ), S2 = HFq2::mul(b.Y, a.ZZZ);
-  HFq2 P = HFq2::sub(U2, U1), R = HFq2::sub(S2, S1);
-  if (P.is_zero()) { if (R.is_zero()) return h2double(a); return HXYZZ2::infinity(); }
-  HFq2 PP = HFq2::sqr(P), PPP = HFq2::mul(P, PP), Q = HFq2::mul(U1, PP);
-  HXYZZ2 r;
-  r.X = HFq2::sub(HFq2::sub(HFq2::sqr(R), PPP), HFq2::dbl(Q));
-  r.Y = HFq2::sub(HFq2::mul(R, HFq2::sub(Q, r.X)), HFq2::mul(S1, PPP));
-  r.ZZ = HFq2::mul(HFq2::mul(a.ZZ, b.ZZ), PP);
-  r.ZZZ = HFq2::mul(HFq2::mul(a.ZZZ, b.ZZZ), PPP);
-  return r;
-}
-static HFq2 h2load(const uint64_t* p) { HFq2 r; std::memcpy(r.a.l, p, 48); std::memcpy(r.b.l, p + 6, 48); return r; }
-static void h2store(uint64_t* p, const HFq2& x) { std::memcpy(p, x.a.l, 48); std::memcpy(p + 6, x.b.l, 48); }
-static HXYZZ2 h2from_jacobian(const uint64_t* j36) {
-  HXYZZ2 r; r.X = h2load(j36); r.Y = h2load(j36 + 12); HFq2 Z = h2load(j36 + 24);
-  if (Z.is_zero()) return HXYZZ2::infinity();
-  r.ZZ = HFq2::sqr(Z); r.ZZZ = HFq2::mul(r.ZZ, Z); return r;
-}
-// affine-normalised Jacobian (x, y, 1); the identity as snarkVM's Projective::zero() = (1, 1, 0)
-static void h2store_jacobian_normalized(uint64_t* j36, const HXYZZ2& p) {
-  const HFq2 one = HFq2::one();
-  if (p.is_inf()) { h2store(j36, one); h2store(j36 + 12, one); h2store(j36 + 24, HFq2::zero()); return; }
-  HFq2 zi3 = HFq2::inv(p.ZZZ), zi2 = HFq2::sqr(HFq2::mul(zi3, p.ZZ));
-  h2store(j36, HFq2::mul(p.X, zi2)); h2store(j36 + 12, HFq2::mul(p.Y, zi3)); h2store(j36 + 24, one);
-}
-}  // namespace host
-
-// One G2 MSM: bases d_xy (n x 192 B, device) with optional infinity flags, scalars on the device.  Plain schedule (no table).
 // the 28-bit rows of n affine points (192-byte x | y rows on the device) into dst224: what a pinned G2 set keeps beside its rows
 int32_t g2_rows_to28(const void* d_xy192, void* d_dst224, size_t n, hipStream_t s) {
   if (n == 0) return ALEO_MI355X_OK;
@@ -529,76 +394,44 @@ int32_t g2_rows_to28(const void* d_xy192, void* d_dst224, size_t n, hipStream_t 
   HIPCHK(hipGetLastError());
   return ALEO_MI355X_OK;
 }
+// G2 on the plain back end (msm_reduce.h): pair-form partial sums, a lane pair per chunk; no phase times (a G2 call leaves g_last_msm alone)
+struct G2Plain {
+  using PT = PtG2; using HF = host::HFq2; static constexpr bool TIMED = false;
+  static host::HXYZZ2 read(const char* p) { return law_point28<HF>(p); }
+  static void launch_chunks(Ctx* c, const Front& f, hipStream_t s, char* V, char* work) {      // work: three points per chunk
+    hipLaunchKernelGGL(k_g2p_bucket_chunks, dim3((f.nchunks + 63) / 64), dim3(128), 0, s, c->partial.as<char>(), f.sp.hist, f.sp.scan_local, f.sp.scan_blk, f.P.B, f.P.S, f.nchunks, V, work);
+  }
+};
+// One G2 MSM: bases d_xy (n x 192 B, device) with optional infinity flags, scalars on the device.  Plain schedule (no table): the scalar side of
+// msm_sort.hip, this unit's accumulation, then the slice trees and the back end G1's plain path runs (msm_front_finish, msm_back_plain).
 int32_t msm_g2_run(Ctx* c, uint64_t* out_jac36, const void* d_xy, const uint8_t* d_inf, const void* d_scalars, size_t n, hipStream_t s, const void* d_rows28) {
-  using namespace host;
-  if (n == 0) { h2store_jacobian_normalized(out_jac36, HXYZZ2::infinity()); return ALEO_MI355X_OK; }
+  if (n == 0) { law_store_jacobian_normalized(out_jac36, host::HXYZZ2::infinity()); return ALEO_MI355X_OK; }
   if (n >= (1ull << 31)) { g_last_error = "msm_g2: n exceeds 2^31"; return ALEO_MI355X_ERR_BAD_ARG; }
-  MsmPlan P = make_plan(n, 0);
+  Front f; f.lean = true; f.plain_tree = k_tree_pass<PtG2, 2>;      // lean: no phase-timing events behind the sort's
+  MsmPlan& P = f.P; P = make_plan(n, 0);
   SegArgs segs{}; segs.nseg = 1; segs.ptr[0] = (const char*)d_scalars; segs.n[0] = (uint32_t)n;
   int32_t rc;
-  if ((rc = ensure_host_pinned(c, 64 + (size_t)P.W * 448))) return rc;
-  SortPhase sp;
+  if ((rc = ensure_host_pinned(c, 64 + (size_t)P.W * P2B))) return rc;
+  SortPhase& sp = f.sp;
   if ((rc = msm_sort_phase(c, segs, n, false, d_inf, (uint32_t)n, P, false, s, &sp))) return rc;
-  const uint32_t M = sp.M, cpw = P.B / P.S, nchunks = cpw * P.W;
-  if ((rc = c->partial.reserve(sp.slices_max * 448))) return rc;
-  if ((rc = c->vbuf.reserve(((size_t)nchunks * 4 + P.W) * 448))) return rc;      // chunk sums | window sums | three working points per chunk (pair form)
-  char* partial = c->partial.as<char>(); char* V = c->vbuf.as<char>(); char* Vout = V + (size_t)nchunks * 448;
+  f.cpw = P.B / P.S; f.nchunks = f.cpw * P.W;
+  if ((rc = c->partial.reserve(sp.slices_max * P2B))) return rc;
+  if ((rc = c->vbuf.reserve(((size_t)f.nchunks * 4 + P.W) * P2B))) return rc;      // chunk sums | window sums | three working points per chunk (pair form)
   const bool resident = d_rows28 != nullptr;                // a pinned set (aleo_mi355x_bases_g2_pin) keeps its 28-bit rows
-  if ((rc = c->out_stage.reserve((resident ? 0 : n * 224) + 256))) return rc;      // the bases in the 28-bit form (per call for the one-shot entry point)
-  if (!resident) hipLaunchKernelGGL(k_g2_rows_to28, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const char*)d_xy, c->out_stage.as<char>(), (uint32_t)n);
+  if ((rc = c->out_stage.reserve((resident ? 0 : n * ROW2) + 256))) return rc;      // the bases in the 28-bit form (per call for the one-shot entry point)
+  if (!resident && (rc = g2_rows_to28(d_xy, c->out_stage.p, n, s))) return rc;
   hipLaunchKernelGGL(k_g2_accum28, dim3(2 * sp.slice_blocks), dim3(256), 0, s, resident ? (const char*)d_rows28 : c->out_stage.as<const char>(), (const char*)d_xy, sp.sorted, sp.hist, sp.scan_local, sp.scan_blk,
-                     sp.total_pairs, M, sp.meta, sp.order, sp.task_g, partial);
+                     sp.total_pairs, sp.M, sp.meta, sp.order, sp.task_g, c->partial.as<char>());
   HIPCHK(hipGetLastError());
-  SliceMeta sm;
-  if ((rc = msm_wait_meta(c, sp, s, &sm))) return rc;
-  for (uint32_t pass = 0, L = sm.max_m; L > 1; ++pass, L = (L + 1) >> 1) {
-    const uint32_t Lc = sm.super_overflow ? L : (L < 16u ? L : (16u >> (pass < 4 ? pass : 4)));
-    if (sm.n_heavy && Lc > 1) {
-      uint32_t mp = Lc >> 1; uint64_t threads = (uint64_t)sm.n_heavy * mp;
-      hipLaunchKernelGGL(k_g2p_tree_pass, dim3((uint32_t)((2 * threads + 255) / 256)), dim3(256), 0, s, partial, sp.heavy, sp.scan_local, sp.scan_blk, M, sp.meta, pass, mp, sm.n_heavy);
-    }
-    if (sm.n_super) {
-      uint32_t mp = L >> 1; uint64_t threads = (uint64_t)sm.n_super * mp;
-      hipLaunchKernelGGL(k_g2p_tree_pass, dim3((uint32_t)((2 * threads + 255) / 256)), dim3(256), 0, s, partial, sp.super_list, sp.scan_local, sp.scan_blk, M, sp.meta, pass, mp, sm.n_super);
-    }
-  }
-  hipLaunchKernelGGL(k_g2p_bucket_chunks, dim3((nchunks + 63) / 64), dim3(128), 0, s, partial, sp.hist, sp.scan_local, sp.scan_blk, P.B, P.S, nchunks, V, Vout + (size_t)P.W * 448);
-  for (uint32_t L = cpw; L > 1; L = (L + 1) >> 1) {
-    uint32_t pairs = (L - ((L + 1) >> 1)) * P.W;
-    hipLaunchKernelGGL(k_g2p_seg_tree_pass, dim3((2 * pairs + 255) / 256), dim3(256), 0, s, V, cpw, P.W, L);
-  }
-  hipLaunchKernelGGL(k_g2p_gather_windows, dim3((P.W * 28 + 255) / 256), dim3(256), 0, s, V, cpw, P.W, Vout);
-  char* h_win = (char*)c->h_pinned + 64;
-  HIPCHK(hipMemcpyAsync(h_win, Vout, (size_t)P.W * 448, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  // host tail: total = sum_w 2^(c w) * S_w (Horner from the top window)
-  // (a 56-byte component of the pair form: host_field.hpp hfq_from28)
-  auto point28 = [&](const char* p) {
-    HXYZZ2 v; HFq2* f[4] = {&v.X, &v.Y, &v.ZZ, &v.ZZZ};
-    for (int i = 0; i < 4; ++i) { f[i]->a = hfq_from28((const uint32_t*)(p + 112 * i)); f[i]->b = hfq_from28((const uint32_t*)(p + 112 * i + 56)); }
-    if (v.ZZ.is_zero()) return HXYZZ2::infinity();
-    return v;
-  };
-  HXYZZ2 total = HXYZZ2::infinity();
-  for (int w = (int)P.W - 1; w >= 0; --w) {
-    for (int d = 0; d < win_width((int)P.c, w); ++d) total = h2double(total);
-    total = h2add(total, point28(h_win + (size_t)w * 448));
-  }
-  h2store_jacobian_normalized(out_jac36, total);
-  return ALEO_MI355X_OK;
+  if ((rc = msm_front_finish(c, s, f, false))) return rc;
+  return msm_back_plain<G2Plain>(c, out_jac36, f, s);
 }
-
-}  // namespace aleo_mi355x
-
-using namespace aleo_mi355x;
-
-// Slot acquisition lives in device.hip; the two entry points are defined in api.hip around msm_g2_run / the host group law:
-namespace aleo_mi355x {
+// Slot acquisition lives in device.hip; the entry points are defined in api.hip around msm_g2_run and this sum of Jacobian points on the host:
 int32_t g2_sum_host(uint64_t* out36, const uint64_t* pts36, size_t count) {
   host::HXYZZ2 t = host::HXYZZ2::infinity();
-  for (size_t i = 0; i < count; ++i) t = host::h2add(t, host::h2from_jacobian(pts36 + 36 * i));
-  host::h2store_jacobian_normalized(out36, t);
+  for (size_t i = 0; i < count; ++i) t = law_add(t, law_from_jacobian<host::HFq2>(pts36 + 36 * i));
+  law_store_jacobian_normalized(out36, t);
   return ALEO_MI355X_OK;
 }
+
 }  // namespace aleo_mi355x

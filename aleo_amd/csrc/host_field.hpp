@@ -11,6 +11,7 @@
 #include <cstring>
 #include <immintrin.h>
 #include "host_modinv.hpp"
+#include "xyzz_law.h"
 
 namespace aleo_mi355x { namespace host {
 
@@ -40,6 +41,11 @@ template <int N> struct HFp {
   static HFp one() { HFp r; std::memcpy(r.l, Pm::ONE, sizeof r.l); return r; }
   static HFp from_u64(uint64_t v) { HFp t = zero(); t.l[0] = v; HFp r2; std::memcpy(r2.l, Pm::R2, sizeof r2.l); return mul(t, r2); }
   bool is_zero() const { uint64_t o = 0; for (int i = 0; i < N; ++i) o |= l[i]; return o == 0; }
+  bool is_zero_raw() const { return is_zero(); }          // fully reduced: zero has one representation
+  static constexpr int LIMBS = N, WORDS28 = 14;
+  static HFp load(const uint64_t* p) { HFp r; std::memcpy(r.l, p, sizeof r.l); return r; }
+  static void store(uint64_t* p, const HFp& x) { std::memcpy(p, x.l, sizeof x.l); }
+  static inline HFp from28(const uint32_t* w);            // Fq: a 56-byte coordinate of the 28-bit forms (below)
   bool operator==(const HFp& b) const { uint64_t o = 0; for (int i = 0; i < N; ++i) o |= l[i] ^ b.l[i]; return o == 0; }
 
   static bool geq_p(const uint64_t* a) {
@@ -192,72 +198,9 @@ template <int N> inline HFp<N> HFp<N>::sqr(const HFp<N>& a) { return fsqr<N>(a);
 
 using HFr = HFp<4>;
 using HFq = HFp<6>;
-
-// Fr constants of the evaluation domain (snarkvm-curves bls12_377/fr.rs; SURVEY.md §0 fact 5)
-static constexpr uint64_t FR_TWO_ADIC_ROOT_CANON[4] = {0x476ef4a4ec2a895eULL, 0x9b506ee363e3f04aULL, 0x60c69477d1a8a12fULL, 0x11d4b7f60cb92cc1ULL};
-static constexpr int FR_TWO_ADICITY = 47;
-static constexpr uint64_t FR_GENERATOR = 22;
-
-// ---- G1 on the host: extended Jacobian (X, Y, ZZ, ZZZ), fully reduced coordinates -------------
-struct HXYZZ {
-  HFq X, Y, ZZ, ZZZ;
-  static HXYZZ infinity() { HXYZZ r; r.X = HFq::zero(); r.Y = HFq::zero(); r.ZZ = HFq::zero(); r.ZZZ = HFq::zero(); return r; }
-  bool is_inf() const { return ZZ.is_zero(); }
-};
-
-inline HXYZZ hdouble(const HXYZZ& p) {  // dbl-2008-s-1, a = 0
-  if (p.is_inf()) return p;
-  HXYZZ r;
-  HFq U = HFq::dbl(p.Y), V = HFq::sqr(U), W = HFq::mul(U, V), S = HFq::mul(p.X, V);
-  HFq xx = HFq::sqr(p.X), M = HFq::add(HFq::dbl(xx), xx);
-  r.X = HFq::sub(HFq::sqr(M), HFq::dbl(S));
-  r.Y = HFq::sub(HFq::mul(M, HFq::sub(S, r.X)), HFq::mul(W, p.Y));
-  r.ZZ = HFq::mul(V, p.ZZ); r.ZZZ = HFq::mul(W, p.ZZZ);
-  if (r.ZZ.is_zero()) return HXYZZ::infinity();
-  return r;
-}
-
-inline HXYZZ hadd(const HXYZZ& a, const HXYZZ& b) {  // add-2008-s
-  if (a.is_inf()) return b;
-  if (b.is_inf()) return a;
-  HFq U1 = HFq::mul(a.X, b.ZZ), U2 = HFq::mul(b.X, a.ZZ), S1 = HFq::mul(a.Y, b.ZZZ), S2 = HFq::mul(b.Y, a.ZZZ);
-  HFq P = HFq::sub(U2, U1), R = HFq::sub(S2, S1);
-  if (P.is_zero()) { if (R.is_zero()) return hdouble(a); return HXYZZ::infinity(); }
-  HFq PP = HFq::sqr(P), PPP = HFq::mul(P, PP), Q = HFq::mul(U1, PP);
-  HXYZZ r;
-  r.X = HFq::sub(HFq::sub(HFq::sqr(R), PPP), HFq::dbl(Q));
-  r.Y = HFq::sub(HFq::mul(R, HFq::sub(Q, r.X)), HFq::mul(S1, PPP));
-  r.ZZ = HFq::mul(HFq::mul(a.ZZ, b.ZZ), PP);
-  r.ZZZ = HFq::mul(HFq::mul(a.ZZZ, b.ZZZ), PPP);
-  return r;
-}
-
-// (x, y) affine of an XYZZ point; returns false for infinity
-inline bool hto_affine(const HXYZZ& p, HFq& x, HFq& y) {
-  if (p.is_inf()) return false;
-  HFq zi3 = HFq::inv(p.ZZZ);                 // 1/Z^3
-  HFq zi2 = HFq::sqr(HFq::mul(zi3, p.ZZ));    // (Z^2/Z^3)^2 = 1/Z^2
-  x = HFq::mul(p.X, zi2); y = HFq::mul(p.Y, zi3);
-  return true;
-}
-
-// Jacobian (X, Y, Z) as snarkVM's Projective stores it (144 bytes) <-> XYZZ
-inline HXYZZ hfrom_jacobian(const uint64_t* j18) {
-  HXYZZ r; HFq Z;
-  std::memcpy(r.X.l, j18, 48); std::memcpy(r.Y.l, j18 + 6, 48); std::memcpy(Z.l, j18 + 12, 48);
-  if (Z.is_zero()) return HXYZZ::infinity();
-  r.ZZ = HFq::sqr(Z); r.ZZZ = HFq::mul(r.ZZ, Z);
-  return r;
-}
-// Points as the device leaves them.  A 192-byte point of the plain path: four coordinates of 12 x 32-bit Montgomery limbs, < 2q or looser.
-static inline HXYZZ lazy_point(const char* p) {
-  const uint64_t* src = (const uint64_t*)p;
-  HXYZZ v; v.X = HFq::reduce_lazy(src); v.Y = HFq::reduce_lazy(src + 6); v.ZZ = HFq::reduce_lazy(src + 12); v.ZZZ = HFq::reduce_lazy(src + 18);
-  return v;
-}
 // A 56-byte coordinate of the 28-bit forms (fp28.h; G1's table path, G2's pair form): value * 2^392 mod q (+ a few q) as 14 x 28-bit limbs (possibly
 // loose); * 2^376 under the 2^-384 of the host Montgomery product gives value * 2^384, the HFq form.
-static inline HFq hfq_from28(const uint32_t* w) {
+template <> inline HFq HFq::from28(const uint32_t* w) {
   uint64_t big[8] = {0, 0, 0, 0, 0, 0, 0, 0};           // sum_i w_i * 2^(28 i), limbs may exceed 28 bits
   for (int i = 0; i < 14; ++i) {
     const int pos = 28 * i, j = pos >> 6, sh = pos & 63;
@@ -270,22 +213,51 @@ static inline HFq hfq_from28(const uint32_t* w) {
   HFq c376 = HFq::zero(); c376.l[5] = 1ull << 56;
   return HFq::mul(HFq::reduce_lazy(big), c376);        // value < 64q < 2^384: six limbs hold it
 }
-// a 224-byte point of G1's table path (X | Y | ZZ | ZZZ); ZZ = 0 is the identity
-static inline HXYZZ lazy_point28(const char* p) {
-  const uint32_t* w = (const uint32_t*)p;
-  HXYZZ v; v.X = hfq_from28(w); v.Y = hfq_from28(w + 14); v.ZZ = hfq_from28(w + 28); v.ZZZ = hfq_from28(w + 42);
-  if (v.ZZ.is_zero()) return HXYZZ::infinity();
-  return v;
-}
 
-// Writes the affine-normalised point as Jacobian (x, y, 1); infinity as snarkVM's Projective::zero() = (1, 1, 0).
-inline void hstore_jacobian_normalized(uint64_t* j18, const HXYZZ& p) {
-  HFq x, y;
-  if (!hto_affine(p, x, y)) {
-    HFq o = HFq::one(); std::memcpy(j18, o.l, 48); std::memcpy(j18 + 6, o.l, 48); std::memset(j18 + 12, 0, 48); return;
+// Fr constants of the evaluation domain (snarkvm-curves bls12_377/fr.rs; SURVEY.md §0 fact 5)
+static constexpr uint64_t FR_TWO_ADIC_ROOT_CANON[4] = {0x476ef4a4ec2a895eULL, 0x9b506ee363e3f04aULL, 0x60c69477d1a8a12fULL, 0x11d4b7f60cb92cc1ULL};
+static constexpr int FR_TWO_ADICITY = 47;
+static constexpr uint64_t FR_GENERATOR = 22;
+
+// ---- G1 and G2 on the host: the one XYZZ law of xyzz_law.h over HFq and HFq2 = HFq[u] / (u^2 + 5) -------------
+struct HFq2 {
+  HFq a, b;
+  static constexpr int LIMBS = 12, WORDS28 = 28;
+  static HFq2 zero() { HFq2 r; r.a = HFq::zero(); r.b = HFq::zero(); return r; }
+  static HFq2 one() { HFq2 r; r.a = HFq::one(); r.b = HFq::zero(); return r; }
+  bool is_zero() const { return a.is_zero() && b.is_zero(); }
+  bool is_zero_raw() const { return is_zero(); }
+  static HFq2 load(const uint64_t* p) { HFq2 r; r.a = HFq::load(p); r.b = HFq::load(p + 6); return r; }
+  static void store(uint64_t* p, const HFq2& x) { HFq::store(p, x.a); HFq::store(p + 6, x.b); }
+  static HFq2 from28(const uint32_t* w) { HFq2 r; r.a = HFq::from28(w); r.b = HFq::from28(w + 14); return r; }
+  static HFq2 add(const HFq2& x, const HFq2& y) { HFq2 r; r.a = HFq::add(x.a, y.a); r.b = HFq::add(x.b, y.b); return r; }
+  static HFq2 sub(const HFq2& x, const HFq2& y) { HFq2 r; r.a = HFq::sub(x.a, y.a); r.b = HFq::sub(x.b, y.b); return r; }
+  static HFq2 dbl(const HFq2& x) { return add(x, x); }
+  static HFq times5(const HFq& v) { HFq d = HFq::dbl(HFq::dbl(v)); return HFq::add(d, v); }
+  static HFq2 mul(const HFq2& x, const HFq2& y) {
+    HFq v0 = HFq::mul(x.a, y.a), v1 = HFq::mul(x.b, y.b);
+    HFq2 r; r.a = HFq::sub(v0, times5(v1)); r.b = HFq::sub(HFq::sub(HFq::mul(HFq::add(x.a, x.b), HFq::add(y.a, y.b)), v0), v1); return r;
   }
-  HFq o = HFq::one();
-  std::memcpy(j18, x.l, 48); std::memcpy(j18 + 6, y.l, 48); std::memcpy(j18 + 12, o.l, 48);
+  static HFq2 sqr(const HFq2& x) { return mul(x, x); }
+  static HFq2 inv(const HFq2& x) {                     // (a - b u) / (a^2 + 5 b^2)
+    HFq n = HFq::inv(HFq::add(HFq::sqr(x.a), times5(HFq::sqr(x.b))));
+    HFq2 r; r.a = HFq::mul(x.a, n); r.b = HFq::neg(HFq::mul(x.b, n)); return r;
+  }
+};
+using HXYZZ = XYZZOf<HFq>;      // fully reduced coordinates; the identity: ZZ = 0
+using HXYZZ2 = XYZZOf<HFq2>;
+inline HXYZZ hdouble(const HXYZZ& p) { return law_double(p); }
+inline HXYZZ hadd(const HXYZZ& a, const HXYZZ& b) { return law_add(a, b); }
+inline bool hto_affine(const HXYZZ& p, HFq& x, HFq& y) { return law_to_affine(p, x, y); }
+inline HXYZZ hfrom_jacobian(const uint64_t* j18) { return law_from_jacobian<HFq>(j18); }                      // snarkVM's Projective, 144 bytes
+inline void hstore_jacobian_normalized(uint64_t* j18, const HXYZZ& p) { law_store_jacobian_normalized(j18, p); }
+inline HFq hfq_from28(const uint32_t* w) { return HFq::from28(w); }
+static inline HXYZZ lazy_point28(const char* p) { return law_point28<HFq>(p); }      // a 224-byte point of G1's table path
+// Points as the device leaves them.  A 192-byte point of the plain path: four coordinates of 12 x 32-bit Montgomery limbs, < 2q or looser.
+static inline HXYZZ lazy_point(const char* p) {
+  const uint64_t* src = (const uint64_t*)p;
+  HXYZZ v; v.X = HFq::reduce_lazy(src); v.Y = HFq::reduce_lazy(src + 6); v.ZZ = HFq::reduce_lazy(src + 12); v.ZZZ = HFq::reduce_lazy(src + 18);
+  return v;
 }
 
 // Affine normalisation of `count` results with ONE field inversion (Montgomery's trick over the ZZZ coordinates): the tail

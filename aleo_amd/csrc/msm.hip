@@ -3,7 +3,8 @@
 // `VariableBase::msm(bases, scalars)` [UPSTREAM-RECALL; pin /root/reference/Cargo.lock:2200], reached from
 // /root/reference/rust/src/program/execute.rs:74,177 and transfer.rs:99 through Varuna's KZG commitments.
 // Same mathematical function (sum_i s_i * P_i); the schedule is GPU-first, not a translation.  The scalar side (digits, sort, slices) is
-// msm_sort.hip; which chains a request becomes and where they run is msm_request.hip; tables and base sets are built by g1_setup.hip.
+// msm_sort.hip; which chains a request becomes and where they run is msm_request.hip; tables and base sets are built by g1_setup.hip; the slice-tree
+// kernel, the plain path's reduction kernels and its host back end are msm_reduce.h, which g2.hip instantiates for G2.
 //
 //   tiers     a pinned set's fixed-base tables (rows 2^win_offset(w) * P_i): c = 20 / 17 for the whole set, c = 16 for its first 2^17 points, c = 13 for its
 //             first 2^15, optionally a range table over a sub-range.  All windows of a result feed ONE set of 2^(c-1) buckets; a chain carries several results.
@@ -16,11 +17,7 @@
 //             window sums go to the host for the 2^c Horner chain (~250 dependent doublings are ~0.1 ms on a host core, ~4 ms on one GPU lane).
 // HBM layout: bases n x 96 B (x|y Montgomery, AoS so a gathered point is 1-2 cache lines), their 28-bit rows and the tables' W x n x 128 B; sorted stream n*W x 4 B; partial sums
 // #slices x 192 B (XYZZ) or 224 B (28-bit XYZZ).  Algorithmic bytes per point: 32 (scalar) + 96 (base).
-#include "ec.h"
-#include "fp28.h"
-#include "host_field.hpp"
-#include "msm_chain.h"
-#include <chrono>
+#include "msm_reduce.h"
 
 namespace aleo_mi355x {
 
@@ -102,22 +99,7 @@ __global__ void __launch_bounds__(256) k_accum28(const char* __restrict__ bases,
 // Every kernel from here to the host tail is a chain of full XYZZ additions with little parallelism, so each addition
 // is shared by a lane pair (ec.h xyzz_add_pair: same work, half the latency).  "op" below = pair index = thread / 2.
 __device__ __forceinline__ void pair_fence() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
-// Point formats of the partial sums: 32-bit XYZZ (192 B, ec.h) on the plain path, 28-bit XYZZ (224 B, fp28.h) on the table path,
-// where everything after the accumulation kernel — slice tree, chunk running sums, masked sums, segment folds — stays in the
-// representation that kernel computes in (its products are ~14 % cheaper and nothing is converted on the device); the host
-// tail turns the lg(N) + 4 final points into its 64-bit-limb Montgomery form.
-template <bool F28> struct PtFmt { static constexpr uint32_t BYTES = F28 ? 224u : 192u, WORDS = BYTES / 4; };
-template <bool F28> __device__ __forceinline__ void pt_add_pair(const char* pa, const char* pb, char* out) {
-  if constexpr (F28) xyzz28_add_pair(pa, pb, out); else xyzz_add_pair(pa, pb, out);
-}
-// The same chains with FOUR lanes per addition (fp28.h xyzz28_add_quad: four product levels instead of seven, 28-bit points only): taken while a
-// launch leaves the chip latency-bound (grp_lanes below), the pair form where the additions of a level already fill it (14 of a quad's 16 product slots work).
-template <uint32_t LANES> __device__ __forceinline__ void pt28_add(const char* pa, const char* pb, char* out) {
-  if constexpr (LANES == 4) xyzz28_add_quad(pa, pb, out); else xyzz28_add_pair(pa, pb, out);
-}
-template <uint32_t LANES, bool F28> __device__ __forceinline__ void pt_add_grp(const char* pa, const char* pb, char* out) {
-  if constexpr (LANES == 4) { static_assert(F28, "quad additions work on 28-bit points"); xyzz28_add_quad(pa, pb, out); } else pt_add_pair<F28>(pa, pb, out);
-}
+template <bool F28> using PtFmt = std::conditional_t<F28, Pt28, Pt32>;      // the formats: msm_reduce.h
 template <uint32_t LANES, uint32_t BYTES> __device__ __forceinline__ void grp_copy(const char* src, char* dst) {      // BYTES / LANES per lane
   const uint32_t o = (threadIdx.x & (LANES - 1)) * (BYTES / LANES);
   const uint2* s2 = (const uint2*)(src + o); uint2* d2 = (uint2*)(dst + o);
@@ -129,7 +111,6 @@ template <uint32_t LANES, uint32_t BYTES> __device__ __forceinline__ void grp_ze
 #pragma unroll
   for (int i = 0; i < (int)(BYTES / LANES / 8); ++i) d2[i] = make_uint2(0, 0);
 }
-constexpr uint32_t lg_lanes(uint32_t lanes) { return lanes == 4 ? 2u : 1u; }
 // lanes per addition for a launch of `ops` independent additions: quads up to two waves per SIMD (2^17 lanes), pairs beyond.  Measured: k_seg_fold 90 -> 57 us,
 // k_tree_pass 15 -> 11 us, a 2^15-constraint proof 6.9 -> 6.6 ms; with the cut at 2^16 lanes the proof is at 6.8 ms.  (The 2^15-chunk kernel of the
 // widest window is the exception: 2^17 quad lanes take what 2^16 pair lanes take, 330 against 321 us — it keeps the pair form.)
@@ -141,56 +122,30 @@ template <class... KA, class... A>
 static void launch_grp(uint32_t lanes, void (*k4)(KA...), void (*k2)(KA...), uint64_t ops, hipStream_t s, A... args) {
   hipLaunchKernelGGL(lanes == 4 ? k4 : k2, dim3((uint32_t)((lanes * ops + 255) / 256)), dim3(256), 0, s, args...);
 }
-// partial[ft + i] += partial[ft + i + half] inside every multi-slice bucket: one launch per level serves both lists of the scan —
-// the common one (buckets of <= 16 slices, `pairs_a` lane pairs each) and the super-heavy one (`pairs_b` each; skewed scalars).
-template <bool F28, uint32_t LANES = 2>
-__global__ void __launch_bounds__(256) k_tree_pass(char* __restrict__ partial, const uint32_t* __restrict__ list_a, uint32_t len_a, uint32_t pairs_a,
-                                                   const uint32_t* __restrict__ list_b, uint32_t len_b, uint32_t pairs_b, const uint2* __restrict__ scan_local,
-                                                   const uint2* __restrict__ scan_blk, uint32_t M, const uint32_t* __restrict__ meta, uint32_t pass, uint32_t skip_b) {
-  constexpr uint32_t PB = PtFmt<F28>::BYTES;
-  uint32_t op = (blockIdx.x * 256 + threadIdx.x) >> lg_lanes(LANES);
-  const uint32_t ops_a = len_a * pairs_a;
-  const uint32_t* list = list_a; uint32_t max_pairs = pairs_a, list_len = len_a, skip = 0;
-  if (op >= ops_a) { op -= ops_a; list = list_b; max_pairs = pairs_b; list_len = len_b; skip = skip_b; }
-  if (max_pairs == 0) return;
-  uint32_t h = op / max_pairs, i = op % max_pairs;
-  if (h >= list_len) return;
-  uint32_t g = list[h];
-  uint32_t ft = scan_at(scan_local, scan_blk, g).y + skip;      // skip_b = 1: the tree of slices 1.. of a super-heavy bucket (slice 0 stays the bucket's sum for the reduction; msm_run "aside")
-  uint32_t fn = (g + 1 < M) ? scan_at(scan_local, scan_blk, g + 1).y : meta[0];
-  uint32_t L = fn - ft;
-  for (uint32_t p = 0; p < pass; ++p) L = (L + 1) >> 1;
-  if (L <= 1) return;
-  uint32_t half = (L + 1) >> 1;
-  if (i >= L - half) return;
-  char* pa = partial + (size_t)(ft + i) * PB;
-  pt_add_grp<LANES, F28>(pa, pa + (size_t)half * PB, pa);
-}
-
 // What is left of the common list's trees after the first level (at most 4 partial sums per bucket when no bucket had more than 8 slices) folded by ONE launch:
 // a lane quad per multi-slice bucket adds its partials 1.. into partial 0 one after the other.  Two or three dependent additions of ~7 us inside one launch
 // instead of two launches of one level each (~10 us of launch floor + its addition per level): the chains of real-circuit-sized proofs are made of such steps.
 template <uint32_t LANES>
 __global__ void __launch_bounds__(256) k_tree_rest(char* __restrict__ partial, const uint32_t* __restrict__ list, uint32_t list_len, const uint2* __restrict__ scan_local,
                                                    const uint2* __restrict__ scan_blk, uint32_t M, const uint32_t* __restrict__ meta) {
-  constexpr uint32_t PB = PtFmt<true>::BYTES;
+  constexpr uint32_t PB = Pt28::BYTES;
   const uint32_t h = (blockIdx.x * 256 + threadIdx.x) >> lg_lanes(LANES);
   if (h >= list_len) return;
   const uint32_t g = list[h];
   const uint32_t ft = scan_at(scan_local, scan_blk, g).y, fn = (g + 1 < M) ? scan_at(scan_local, scan_blk, g + 1).y : meta[0];
   const uint32_t L1 = (fn - ft + 1) >> 1;                   // partial sums the first level left at ft .. ft + L1 - 1
   char* pa = partial + (size_t)ft * PB;
-  for (uint32_t i = 1; i < L1; ++i) pt_add_grp<LANES, true>(pa, pa + (size_t)i * PB, pa);
+  for (uint32_t i = 1; i < L1; ++i) Pt28::add<LANES>(pa, pa + (size_t)i * PB, pa);
 }
 
 // The sums of slices 1.. of the super-heavy buckets (k_tree_pass with skip_b = 1 left them in slice 1) and the buckets' numbers, to the host.
 __global__ void k_gather_super(const char* __restrict__ partial, const uint32_t* __restrict__ list, uint32_t len, const uint2* __restrict__ scan_local,
                                const uint2* __restrict__ scan_blk, uint32_t* __restrict__ dst) {
-  constexpr uint32_t PW = PtFmt<true>::WORDS;
+  constexpr uint32_t PW = Pt28::WORDS;
   const uint32_t t = blockIdx.x * 256 + threadIdx.x, h = t / (PW + 1), w = t % (PW + 1);
   if (h >= len) return;
   const uint32_t g = list[h];
-  dst[h * (PW + 1) + w] = w == PW ? g : ((const uint32_t*)(partial + (size_t)(scan_at(scan_local, scan_blk, g).y + 1) * PtFmt<true>::BYTES))[w];
+  dst[h * (PW + 1) + w] = w == PW ? g : ((const uint32_t*)(partial + (size_t)(scan_at(scan_local, scan_blk, g).y + 1) * Pt28::BYTES))[w];
 }
 
 // ---- bucket reduction -----------------------------------------------------------------------------
@@ -225,7 +180,7 @@ __global__ void __launch_bounds__(256) k_bucket_chunks(const char* __restrict__ 
     const char* add = k < S ? nxt : zero;
     nxt = (!sp && k + 1 < S) ? sum_of(g0 + S - 2 - k) : zero;
     const char* pa = sp ? acc : rprev; const char* pb = sp ? rprev : add; char* out = sp ? acc : rnext;
-    pt_add_grp<LANES, F28>(pa, pb, out);
+    PtFmt<F28>::template add<LANES>(pa, pb, out);
     pair_fence();
   }
   // after step S: buf[S & 1] holds run_{S-1} again (step S copied it forward), acc holds sum_k run_k
@@ -265,16 +220,6 @@ __global__ void __launch_bounds__(256) k_bucket_chunks_plain(const char* __restr
   store_xyzz(V + (size_t)t * 192, acc);
 }
 
-// V[seg*seg_len + i] += V[seg*seg_len + i + half] for i < L - half, L = current length of every segment
-__global__ void __launch_bounds__(256) k_seg_tree_pass(char* __restrict__ V, uint32_t seg_len, uint32_t nseg, uint32_t L) {
-  const uint32_t half = (L + 1) >> 1, pairs = L - half;
-  const uint32_t op = (blockIdx.x * 256 + threadIdx.x) >> 1;
-  if (op >= pairs * nseg) return;
-  const uint32_t seg = op / pairs, i = op % pairs;
-  char* pa = V + ((size_t)seg * seg_len + i) * 192;
-  xyzz_add_pair(pa, pa + (size_t)half * 192, pa);
-}
-
 // Fixed-base path: sum_j j * run_j = sum_l 2^l * T_l with T_l = sum of run_j over the j that have bit l set.  This
 // kernel does the first pairwise level of all lg(N) masked sums at once: T_l[k] = run[ins_l(2k)] + run[ins_l(2k+1)],
 // ins_l(x) = x with a 1 inserted at bit l.  The remaining levels are k_seg_pair_pass / k_seg_fold; the 2^l Horner runs
@@ -291,7 +236,7 @@ __global__ void __launch_bounds__(256) k_masked_pairs(const char* __restrict__ V
   const uint32_t q = op / (seg_len * lgN), r = op % (seg_len * lgN), l = r / seg_len, k = r % seg_len;
   auto ins = [&](uint32_t x) { return ((x >> l) << (l + 1)) | (1u << l) | (x & ((1u << l) - 1u)); };
   const char* run = Vrun + ((size_t)q << lgN) * PB28;
-  pt28_add<LANES>(run + (size_t)ins(2 * k) * PB28, run + (size_t)ins(2 * k + 1) * PB28, V + ((size_t)q * v_set_stride + (1u << lgN) + r) * PB28);
+  Pt28::add<LANES>(run + (size_t)ins(2 * k) * PB28, run + (size_t)ins(2 * k + 1) * PB28, V + ((size_t)q * v_set_stride + (1u << lgN) + r) * PB28);
 }
 // One block folds up to 256 consecutive points of one segment into a single point: 8 tree levels through two LDS
 // buffers, 128 lane pairs — the latency floor of the chain with no launch gaps.
@@ -307,14 +252,14 @@ __global__ void __launch_bounds__(128 * LANES) k_seg_fold(const char* __restrict
     const uint32_t e0 = blk * FOLD + 2 * pr;
     const char* src = in + ((size_t)seg * in_stride + e0) * PB28;
     char* dst = (char*)(lds[0] + pr * PW28);
-    if (e0 + 1 < L) pt28_add<LANES>(src, src + PB28, dst);
+    if (e0 + 1 < L) Pt28::add<LANES>(src, src + PB28, dst);
     else if (e0 < L) grp_copy<LANES, PB28>(src, dst);
     else grp_zero<LANES, PB28>(dst);
   }
   uint32_t cur = 0;
   for (uint32_t n = FOLD / 2; n > 1; n >>= 1) {
     __syncthreads();
-    if (pr < (n >> 1)) pt28_add<LANES>((const char*)(lds[cur] + (2 * pr) * PW28), (const char*)(lds[cur] + (2 * pr + 1) * PW28), (char*)(lds[cur ^ 1] + pr * PW28));
+    if (pr < (n >> 1)) Pt28::add<LANES>((const char*)(lds[cur] + (2 * pr) * PW28), (const char*)(lds[cur] + (2 * pr + 1) * PW28), (char*)(lds[cur ^ 1] + pr * PW28));
     cur ^= 1;
   }
   __syncthreads();
@@ -330,7 +275,7 @@ __global__ void __launch_bounds__(256) k_seg_pair_pass(const char* __restrict__ 
   const uint32_t seg = op / half, i = op % half;
   const char* src = in + ((size_t)seg * in_stride + 2 * i) * PB28;
   char* dst = out + ((size_t)seg * out_stride + i) * PB28;
-  if (2 * i + 1 < L) pt28_add<LANES>(src, src + PB28, dst); else grp_copy<LANES, PB28>(src, dst);
+  if (2 * i + 1 < L) Pt28::add<LANES>(src, src + PB28, dst); else grp_copy<LANES, PB28>(src, dst);
 }
 // ---- the chunk weights by ONE sum tree (wide tables, round 3) -------------------------------------------------------------------------------------
 // sum_j j * run_j = sum_l 2^l T_l, T_l = the sum of run_j over the j with bit l set.  k_masked_pairs builds every T_l as its own tree over half of
@@ -351,7 +296,7 @@ __global__ void __launch_bounds__(256) k_prog_pass(const char* __restrict__ node
                   : g == 1 ? A + ((size_t)q * a_set_stride + 2 * i) * PB28
                            : T + ((size_t)q * t_set_stride + (size_t)(g - 2) * L + 2 * i) * PB28;
   char* dst = out + ((size_t)q * out_set_stride + (size_t)g * half + i) * PB28;
-  pt28_add<LANES>(src, src + PB28, dst);
+  Pt28::add<LANES>(src, src + PB28, dst);
   if (g == 0) grp_copy<LANES, PB28>(src + PB28, out + ((size_t)q * out_set_stride + (size_t)(2 + nT) * half + i) * PB28);      // T_s is born: the right children of this level
 }
 // TWO levels in one launch while the passes are latency-bound (lane quads): an octet of lanes per four consecutive points of a segment.  Step 1: quad 0 adds points
@@ -375,14 +320,14 @@ __global__ void __launch_bounds__(256) k_prog_pass2(const char* __restrict__ nod
                   : g == 1 ? A + ((size_t)q * a_set_stride + 4 * i) * PB28
                            : T + ((size_t)q * t_set_stride + (size_t)(g - 2) * L + 4 * i) * PB28;
   char* slot = (char*)(lds + (2 * oct) * PW28);
-  pt28_add<4>(src + (size_t)(2 * y) * PB28, src + (size_t)(2 * y + 1) * PB28, slot + y * PB28);
+  Pt28::add<4>(src + (size_t)(2 * y) * PB28, src + (size_t)(2 * y + 1) * PB28, slot + y * PB28);
   pair_fence();
   char* base = out + (size_t)q * out_set_stride * PB28;
   const bool born = y && g == 0;
   const char* pa = y ? (born ? src + PB28 : zero) : slot;
   const char* pb = y ? (born ? src + 3 * PB28 : zero) : slot + PB28;
   char* dst = y ? (born ? base + ((size_t)(2 + nT) * quarter + i) * PB28 : zero) : base + ((size_t)g * quarter + i) * PB28;      // (an idle quad: 0 + 0 onto the zero point, nothing is written)
-  pt28_add<4>(pa, pb, dst);
+  Pt28::add<4>(pa, pb, dst);
   if (born) grp_copy<4, PB28>(slot + PB28, base + ((size_t)(3 + nT) * quarter + i) * PB28);
 }
 // The last levels, one block per result point: A and every T_l already born are plain folds of their (<= 256-point) segments; the weights of the
@@ -399,13 +344,13 @@ __global__ void __launch_bounds__(128 * LANES) k_prog_final(const char* __restri
     char* dst = (char*)(lds[0] + pr * PW28);
     if (o <= nT) {                                         // plain fold of segment 1 (A) or 2 + (o - 1) (T_{o-1})
       const char* seg = set + (size_t)(o == 0 ? 1 : 1 + o) * L * PB28; const uint32_t e0 = 2 * pr;
-      if (e0 + 1 < L) pt28_add<LANES>(seg + (size_t)e0 * PB28, seg + (size_t)(e0 + 1) * PB28, dst);
+      if (e0 + 1 < L) Pt28::add<LANES>(seg + (size_t)e0 * PB28, seg + (size_t)(e0 + 1) * PB28, dst);
       else if (e0 < L) grp_copy<LANES, PB28>(seg + (size_t)e0 * PB28, dst);
       else grp_zero<LANES, PB28>(dst);
     } else {                                               // bit b of the node index: the L / 2 nodes that have it set, in pairs
       const uint32_t b = o - 1 - nT;
       auto ins = [&](uint32_t x) { return ((x >> b) << (b + 1)) | (1u << b) | (x & ((1u << b) - 1u)); };
-      if (L >= 4 && 4 * pr + 3 < L) pt28_add<LANES>(set + (size_t)ins(2 * pr) * PB28, set + (size_t)ins(2 * pr + 1) * PB28, dst);
+      if (L >= 4 && 4 * pr + 3 < L) Pt28::add<LANES>(set + (size_t)ins(2 * pr) * PB28, set + (size_t)ins(2 * pr + 1) * PB28, dst);
       else if (L == 2 && pr == 0) grp_copy<LANES, PB28>(set + PB28, dst);
       else grp_zero<LANES, PB28>(dst);
     }
@@ -413,7 +358,7 @@ __global__ void __launch_bounds__(128 * LANES) k_prog_final(const char* __restri
   uint32_t cur = 0;
   for (uint32_t n = FOLD / 2; n > 1; n >>= 1) {
     __syncthreads();
-    if (pr < (n >> 1)) pt28_add<LANES>((const char*)(lds[cur] + (2 * pr) * PW28), (const char*)(lds[cur] + (2 * pr + 1) * PW28), (char*)(lds[cur ^ 1] + pr * PW28));
+    if (pr < (n >> 1)) Pt28::add<LANES>((const char*)(lds[cur] + (2 * pr) * PW28), (const char*)(lds[cur] + (2 * pr + 1) * PW28), (char*)(lds[cur ^ 1] + pr * PW28));
     cur ^= 1;
   }
   __syncthreads();
@@ -424,14 +369,6 @@ __global__ void k_gather_strided(const char* __restrict__ V, uint32_t stride, ui
   if (t >= count * 14) return;
   uint32_t w = t / 14, q = t % 14;
   ((uint4*)out)[t] = ((const uint4*)(V + (size_t)w * stride * PB28))[q];
-}
-
-// gathers V[w*seg_len] (the window sums) into a dense array for one D2H copy
-__global__ void k_gather_windows(const char* __restrict__ V, uint32_t seg_len, uint32_t W, char* __restrict__ out) {
-  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= W * 12) return;
-  uint32_t w = t / 12, q = t % 12;
-  ((uint4*)out)[t] = ((const uint4*)(V + (size_t)w * seg_len * 192))[q];
 }
 
 int32_t msm_front_sort(Ctx* c, const PinnedBases& pb, const MsmJob& job, hipStream_t s, Front& f) {
@@ -466,6 +403,7 @@ int32_t msm_front_sort(Ctx* c, const PinnedBases& pb, const MsmJob& job, hipStre
   if (pre) { P.W = K; P.M = K * P.B; }                       // after the sort a set is "a window with its own buckets"
   if (!pre && !pb.d_xy28) { g_last_error = "msm: pinned set without 28-bit rows"; return ALEO_MI355X_ERR_HIP; }
   f.bases = (const char*)(pre ? T->d : pb.d_xy28);          // 112-byte rows either way
+  f.plain_tree = k_tree_pass<Pt32, 2>;
   const uint32_t cpw = f.cpw = P.B / P.S, nchunks = f.nchunks = cpw * P.W;
   uint32_t lgN = 0; while ((1u << lgN) < cpw) ++lgN;
   f.lgN = lgN;
@@ -519,7 +457,7 @@ int32_t msm_front_finish(Ctx* c, hipStream_t s, Front& f, bool allow_aside) {
     HIPCHK(hipStreamWaitEvent(c->side, c->ev[5], 0));
     for (uint32_t pass = 0, L = sm.max_m - 1; L > 1; ++pass, L = (L + 1) >> 1) {
       const uint64_t ops = (uint64_t)sm.n_super * (L >> 1);
-      launch_grp(grp_lanes(ops), k_tree_pass<true, 4>, k_tree_pass<true, 2>, ops, c->side, partial, heavy, 0u, 0u, sp.super_list, sm.n_super, L >> 1, scan_local, scan_blk, M, meta, pass, 1u);
+      launch_grp(grp_lanes(ops), k_tree_pass<Pt28, 4>, k_tree_pass<Pt28, 2>, ops, c->side, partial, heavy, 0u, 0u, sp.super_list, sm.n_super, L >> 1, scan_local, scan_blk, M, meta, pass, 1u);
     }
     uint32_t* dst = nullptr;
     HIPCHK(hipHostGetDevicePointer((void**)&dst, h_aside, 0));
@@ -542,7 +480,7 @@ int32_t msm_front_finish(Ctx* c, hipStream_t s, Front& f, bool allow_aside) {
       const uint64_t threads = lanes * ops;
       if (!threads) continue;
       if (threads >= (1ull << 32)) { (void)hipStreamSynchronize(s); g_last_error = "msm: slice tree too wide"; return ALEO_MI355X_ERR_HIP; }
-      launch_grp(lanes, k_tree_pass<true, 4>, pre ? k_tree_pass<true, 2> : k_tree_pass<false, 2>, ops, s, partial, heavy, len_a, pairs_a, sp.super_list, len_b, pairs_b, scan_local, scan_blk, M, meta, pass, 0u);
+      launch_grp(lanes, k_tree_pass<Pt28, 4>, pre ? k_tree_pass<Pt28, 2> : f.plain_tree, ops, s, partial, heavy, len_a, pairs_a, sp.super_list, len_b, pairs_b, scan_local, scan_blk, M, meta, pass, 0u);
     }
   }
   if (!f.lean) HIPCHK(hipEventRecord(c->ev[2], s));
@@ -620,9 +558,7 @@ int32_t msm_reduce_queue(Ctx* c, Front& f, hipStream_t s, const FrontChain& olde
   return ALEO_MI355X_OK;
 }
 
-// phase times: HIP events on the launch stream up to the result's arrival (ev[3], already complete: the host has waited for it),
-// the host tail by the host clock — no further event round trip on the critical path of a small MSM
-static int32_t phase_times(Ctx* c, const Front& f, std::chrono::steady_clock::time_point t_host0) {
+int32_t phase_times(Ctx* c, const Front& f, std::chrono::steady_clock::time_point t_host0) {
   const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
   float ms; MsmTiming tm;
   if (f.lean) { tm.host = host_ms; tm.total = host_ms; c->last_msm = tm; g_last_msm = tm; return ALEO_MI355X_OK; }      // no phase events were recorded
@@ -681,34 +617,17 @@ int32_t msm_collect(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bool f
   return phase_times(c, f, t_host0);
 }
 
-// Plain path (one bucket set per window): reduction, the window sums to the host, Horner over the windows.
-static int32_t msm_back_plain(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s) {
-  using namespace host;
-  const MsmPlan& P = f.P; const SortPhase& sp = f.sp; const uint32_t cpw = f.cpw, nchunks = f.nchunks;
-  char* V = c->vbuf.as<char>(); char* Vout = V + (size_t)nchunks * 192; char* h_win = (char*)c->h_pinned + 64;
-  HXYZZ total = HXYZZ::infinity();
-  hipLaunchKernelGGL(k_bucket_chunks_plain, dim3((nchunks + 255) / 256), dim3(256), 0, s, c->partial.as<char>(), sp.hist, sp.scan_local, sp.scan_blk, P.B, P.S, nchunks, V);
-  for (uint32_t L = cpw; L > 1; L = (L + 1) >> 1) {
-    uint32_t pairs = (L - ((L + 1) >> 1)) * P.W;
-    hipLaunchKernelGGL(k_seg_tree_pass, dim3((2 * pairs + 255) / 256), dim3(256), 0, s, V, cpw, P.W, L);
+// G1 on the plain back end (msm_reduce.h): 32-bit XYZZ partial sums, a lane per chunk
+struct G1Plain {
+  using PT = Pt32; using HF = host::HFq; static constexpr bool TIMED = true;
+  static host::HXYZZ read(const char* p) { return host::lazy_point(p); }
+  static void launch_chunks(Ctx* c, const Front& f, hipStream_t s, char* V, char*) {
+    hipLaunchKernelGGL(k_bucket_chunks_plain, dim3((f.nchunks + 255) / 256), dim3(256), 0, s, c->partial.as<char>(), f.sp.hist, f.sp.scan_local, f.sp.scan_blk, f.P.B, f.P.S, f.nchunks, V);
   }
-  hipLaunchKernelGGL(k_gather_windows, dim3((P.W * 12 + 255) / 256), dim3(256), 0, s, V, cpw, P.W, Vout);
-  HIPCHK(hipMemcpyAsync(h_win, Vout, (size_t)P.W * 192, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipEventRecord(c->ev[3], s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  const auto t_host0 = std::chrono::steady_clock::now();
-  // host tail: total = sum_w 2^(c*w) * S_w  (Horner from the top window), then affine normalisation
-  for (int w = (int)P.W - 1; w >= 0; --w) {
-    for (int d = 0; d < win_width((int)P.c, w); ++d) total = hdouble(total);          // window w spans win_width bits (balanced windows)
-    total = hadd(total, lazy_point(h_win + (size_t)w * 192));
-  }
-  hstore_jacobian_normalized(out_jac18, total);
-  return phase_times(c, f, t_host0);
-}
+};
 
 int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bool fire_tail, const FrontChain& older) {
-  if (!f.masked) return msm_back_plain(c, out_jac18, f, s);
+  if (!f.masked) return msm_back_plain<G1Plain>(c, out_jac18, f, s);
   const int32_t rc = msm_reduce_queue(c, f, s, older); return rc ? rc : msm_collect(c, out_jac18, f, s, fire_tail, TailWait::stream);
 }
 

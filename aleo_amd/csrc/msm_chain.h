@@ -1,6 +1,7 @@
 // msm_chain.h — the steps of ONE G1 launch chain (msm.hip) as msm_request.hip schedules them.
 #pragma once
 #include "msm_common.h"
+#include <chrono>
 
 namespace aleo_mi355x {
 #pragma GCC visibility push(hidden)      // seams between the library's own units stay out of its dynamic symbol table
@@ -15,12 +16,14 @@ struct FrontChain { FrontView v[3]; uint32_t n = 0; };
 //   msm_front_accum   the accumulation kernel (optionally behind an event, optionally seeded with the bucket sums of earlier chains)
 //   msm_front_finish  the slice metadata arrives (pinned buffer), the slice trees follow: bucket b's sum is then the first slice of b
 //   msm_reduce_queue / msm_collect   table path: the bucket reduction queued, ev[3] behind it / the wait for it, host tail, phase times
-//   msm_back          the two back to back, or the plain path's reduction and host tail
+//   msm_back          the two back to back, or the plain path's reduction and host tail (msm_reduce.h msm_back_plain, which G2 runs too)
 struct Front {
   MsmPlan P{}; SortPhase sp; SliceMeta sm;
   uint32_t K = 0, cpw = 0, nchunks = 0, lgN = 0, tseg = 0, fseg = 0, nseg = 0, setw = 0; size_t vpoints = 0;
   uint32_t out_pts = 0;      // result points per set the host tail reads: lgN + 1 from the sum trees (prog), lgN + 4 from the masked trees
   bool pre = false, masked = false, prog = false, aside = false, empty = false, lean = false; const char* bases = nullptr;      // lean: MsmJob::lean of a single-chain request (no phase-timing events)
+  // plain path: the lane-pair slice-tree kernel over the group's partial sums (msm_reduce.h k_tree_pass<PT, 2>) — how the group reaches msm_front_finish
+  void (*plain_tree)(char*, const uint32_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, const uint2*, const uint2*, uint32_t, const uint32_t*, uint32_t, uint32_t) = nullptr;
 };
 // Work queued on borrowed contexts must have finished before their locks are released, whatever way the function is left (an early HIPCHK return, an
 // exception on its way to the C ABI's catch): the guard synchronises the listed streams in its destructor unless the normal path — which ends
@@ -40,5 +43,8 @@ int32_t msm_reduce_queue(Ctx* c, Front& f, hipStream_t s, const FrontChain& olde
 enum class TailWait { stream, event };      // without a hook the host waits for the whole stream, or for ev[3] alone (other chains' work may be queued behind it; this chain's is all in front)
 int32_t msm_collect(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bool fire_tail, TailWait wait);
 int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bool fire_tail, const FrontChain& older);
+// phase times of a G1 chain into Ctx::last_msm / g_last_msm: HIP events on the launch stream up to the result's arrival (ev[3], already complete: the host has
+// waited for it), the host tail by the host clock — no further event round trip on the critical path of a small MSM
+int32_t phase_times(Ctx* c, const Front& f, std::chrono::steady_clock::time_point t_host0);
 #pragma GCC visibility pop
 }  // namespace aleo_mi355x

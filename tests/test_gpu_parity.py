@@ -1350,6 +1350,23 @@ def test_g2_lane_pair_arithmetic_matches_the_one_lane_code():
     assert aleo_amd.lib().aleo_mi355x_selftest_g2pair(None, 8, 4, f) == 2
 
 
+def test_msm_g2_both_slice_lists_in_one_tree_launch():
+    """A G2 request whose slice trees need BOTH lists of the scan in the merged launch of k_tree_pass (G2 used to launch them separately).
+    n = 600 bases (i + 1) * G2; the first 200 scalars are 1, the other 400 uniform.  make_plan(600): lg = 9, c = 5, so 51 windows of 2^(c-1) = 16 buckets
+    and about 51 * 400 + 200 = 20 600 pairs (a scalar 1 has one non-zero digit).  pick_rule: fewer than 2^18 pairs, so fill = 4; the mean bucket holds
+    ~25 points, by_mean = 64 >= 2 * fill, hence single = split = 4: every bucket above 4 points is cut into slices of at most 4.  Bucket 1 of window 0
+    holds the 200 ones (and ~25 more): at least 50 slices, more than 16 — the super-heavy list.  The uniform scalars leave ~25 points in every other
+    bucket: ~7 slices, at most 16 — the common list, bounded per level by the measured max_common."""
+    n = 600
+    B = _g2_multiples(n)
+    S = util.uniform_scalars(n, 16980); S[:200] = 0; S[:200, 0] = 1
+    got = M.msm_g2(B, S)
+    assert c.g2_jac_to_int_point(got) == p.g2_mul(p.G2_GENERATOR, synth.weighted_scalar_sum(S, 1))      # structured identity in big integers
+    assert c.g2_jac_to_int_point(got) == c.g2_jac_to_int_point(c.msm_g2(B, S))                          # the oracle's standard::msm
+    with M.PinnedG2Bases(B) as pg:
+        assert (pg.msm(S) == got).all()                                                                 # the same request over a pinned set
+
+
 def test_msm_g2_2_16_structured_identity():
     n = 1 << 16
     B = _g2_multiples(n); S = util.uniform_scalars(n, 16999)
