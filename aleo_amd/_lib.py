@@ -43,6 +43,7 @@ EXPORTS = [
     'aleo_mi355x_found_commitments',
     'aleo_mi355x_accounts_derive', 'aleo_mi355x_accounts_derive_host', 'aleo_mi355x_accounts_search', 'aleo_mi355x_accounts_search_host', 'aleo_mi355x_min_accounts',
     'aleo_mi355x_private_key_from_seed', 'aleo_mi355x_private_key_seed', 'aleo_mi355x_seed_from_bytes', 'aleo_mi355x_view_key_to_string',
+    'aleo_mi355x_private_key_encrypt', 'aleo_mi355x_private_key_decrypt', 'aleo_mi355x_private_keys_open', 'aleo_mi355x_private_keys_open_host', 'aleo_mi355x_min_key_ciphertexts',
 ]
 
 
@@ -235,6 +236,11 @@ def lib():
         'aleo_mi355x_private_key_seed': ([vp, ctypes.c_char_p], i32),
         'aleo_mi355x_seed_from_bytes': ([vp, vp], i32),
         'aleo_mi355x_view_key_to_string': ([vp, sz, vp], i32),
+        'aleo_mi355x_private_key_encrypt': ([vp, sz, ctypes.c_char_p, vp, sz, vp], i32),
+        'aleo_mi355x_private_key_decrypt': ([vp, sz, ctypes.c_char_p, vp, sz], i32),
+        'aleo_mi355x_private_keys_open': ([vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp], i32),
+        'aleo_mi355x_private_keys_open_host': ([vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp], i32),
+        'aleo_mi355x_min_key_ciphertexts': ([], sz),
         'aleo_mi355x_found_free': ([vp], None),
         **{'aleo_mi355x_found_' + name: ([vp], sz) for name in ('count', 'fields', 'unparsed', 'first_unparsed', 'owned')},
         **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits', 'serials', 'commitments')},

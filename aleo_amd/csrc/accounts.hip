@@ -7,7 +7,7 @@
 // The kernels (one account per lane: account_lane.h), their table (account_host.hpp: the signature table's words and the rate-2 constants, built on the host at
 // first use and resident per device), the same bytes on the host (records_bits.hpp / account_host.hpp serial::account_from_seed — what small batches take, and the
 // definition), the routing threshold, and the host-only calls: the strings and the reduction of 32 bytes to a seed.
-#include "entry.h"
+#include "accounts.h"
 #include "records_bits.hpp"
 #include "account_host.hpp"
 #include <algorithm>
@@ -16,20 +16,6 @@
 namespace aleo_mi355x {
 
 // ---- the kernels ------------------------------------------------------------------------------------------------------------------------------------
-static constexpr uint32_t ACC_BLOCK = 64;                    // one wave: a lane holds its whole account in registers, and small batches spread over the CUs
-static constexpr size_t ACC_CHUNK = (size_t)1 << 20;         // accounts or candidates per launch
-static constexpr uint32_t ACC_NONE = 0xffffffffu;            // an output the caller did not ask for
-
-// A chunk's arrays lie in one device buffer, at these byte offsets (each below 2^32: ACC_CHUNK rows of at most 63 bytes), and the offsets themselves at its start:
-// one base pointer, and the words a lane needs only at its end are read there and then instead of being held in scalar registers through the lane's phases, which
-// have none to spare.  sk, view, addr, str: ACC_NONE where the output is not wanted.
-struct AccChunk { uint32_t seeds, flags, sk, view, addr, str, n, pad; };
-
-__device__ __forceinline__ void store_words8(char* p, const uint32_t (&w)[8]) {      // 32 bytes at p (16-byte aligned), by two 16-byte stores
-  uint4* q = (uint4*)p;
-  q[0] = make_uint4(w[0], w[1], w[2], w[3]); q[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-
 // Account i of the chunk: its seed the 32 bytes at seeds + 32 i; rows of 32 bytes at sk, view, addr, of 63 characters at str, one flag byte at flags.
 __global__ void __launch_bounds__(ACC_BLOCK) k_accounts_derive(char* base, uint32_t n, const uint32_t* K) {
   const uint32_t i = blockIdx.x * ACC_BLOCK + threadIdx.x;
@@ -80,6 +66,10 @@ static int32_t account_table(int device, const uint32_t** out) {
   return resident_table(device, ResidentTable::ACCOUNT, []() -> const std::vector<uint32_t>& { return acct::account_tables().words; }, out);
 }
 
+void launch_accounts_derive(hipStream_t s, char* base, size_t m, const uint32_t* dK) {
+  hipLaunchKernelGGL(k_accounts_derive, dim3((uint32_t)((m + ACC_BLOCK - 1) / ACC_BLOCK)), dim3(ACC_BLOCK), 0, s, base, (uint32_t)m, dK);
+}
+
 // ---- derive -------------------------------------------------------------------------------------------------------------------------------------------
 // Chunk by chunk: the seeds go up, one launch runs, the rows asked for come down.
 static int32_t derive_on_device(const uint8_t* seeds, size_t n, uint8_t* sk, uint8_t* view, uint8_t* addr, char* str, uint8_t* flags) {
@@ -100,7 +90,7 @@ static int32_t derive_on_device(const uint8_t* seeds, size_t n, uint8_t* sk, uin
       HIPCHK(hipMemcpyAsync(b + o_seed, seeds + lo * 32, m * 32, hipMemcpyHostToDevice, s));
       head = AccChunk{(uint32_t)o_seed, (uint32_t)o_fl, (uint32_t)o_sk, (uint32_t)o_view, (uint32_t)o_addr, (uint32_t)o_str, (uint32_t)m, 0u};
       HIPCHK(hipMemcpyAsync(b + o_head, &head, sizeof head, hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_accounts_derive, dim3((uint32_t)((m + ACC_BLOCK - 1) / ACC_BLOCK)), dim3(ACC_BLOCK), 0, s, b, (uint32_t)m, dK);
+      launch_accounts_derive(s, b, m, dK);
       HIPCHK(hipGetLastError());
       if (sk) HIPCHK(hipMemcpyAsync(sk + lo * 32, b + o_sk, m * 32, hipMemcpyDeviceToHost, s));
       if (view) HIPCHK(hipMemcpyAsync(view + lo * 32, b + o_view, m * 32, hipMemcpyDeviceToHost, s));

@@ -46,7 +46,7 @@ template <class F> int32_t on_slot(F&& body) {
 }
 // The word table of a lane, resident on a device: uploaded once per (device, kind) from words() under a lock, never freed, and handed out only after the copy
 // has completed.  Every flow of the records and signature units gets its table here and nowhere else; each of the others begins with the records constants.
-enum class ResidentTable { RECORDS, SERIAL, COMMIT, SIGNATURE, ACCOUNT };      // records_lane.h RK_*, records_serial_lane.h SK_*, records_commit_lane.h CK_*, signature_lane.h SG_*, account_lane.h AC_*
+enum class ResidentTable { RECORDS, SERIAL, COMMIT, SIGNATURE, ACCOUNT, KEY_CIPHERTEXT };      // records_lane.h RK_*, records_serial_lane.h SK_*, records_commit_lane.h CK_*, signature_lane.h SG_*, account_lane.h AC_*, key_ciphertext_lane.h KC_*
 int32_t resident_table(int device, ResidentTable kind, const std::vector<uint32_t>& (*words)(), const uint32_t** out);
 // bases.hip
 int32_t find_bases(Device* d, uint64_t handle, std::shared_ptr<PinnedOwner>* keep, PinnedBases* snap);

@@ -23,12 +23,14 @@ static constexpr uint32_t SPAN_BLOCK = 256, SPAN_LDS_BYTES = 64 * 1024;      // 
 // 16-byte loads, every lane of a wave reading its neighbours' lines, and string i lies at stage + (off[i] - *lo_out); a lane's own byte loads from global memory
 // touch 64 cache lines per instruction of a wave (measured: DESIGN §11).  A longer span — 256 strings of more than 255 characters on average — gets false and is
 // read from global memory.  Every lane of the block calls it (a barrier follows the copy); text: readable up to the next multiple of 16 past its last character.
+// BLOCK, LDS_BYTES: the same for a block of another size (key_ciphertexts.hip: one wave).
+template <uint32_t BLOCK = SPAN_BLOCK, uint32_t LDS_BYTES = SPAN_LDS_BYTES>
 __device__ __forceinline__ bool stage_span(uint4* stage, const char* __restrict__ text, const uint32_t* __restrict__ off, uint32_t b0, uint32_t n, uint32_t* lo_out) {
-  const uint32_t b1 = b0 + SPAN_BLOCK < n ? b0 + SPAN_BLOCK : n;
+  const uint32_t b1 = b0 + BLOCK < n ? b0 + BLOCK : n;
   const uint32_t lo = off[b0] & ~15u, hi = off[b1];            // uniform: the block's span, from a 16-byte boundary
   *lo_out = lo;
-  if (hi - lo > SPAN_LDS_BYTES) return false;
-  for (uint32_t t = threadIdx.x; lo + 16 * t < hi; t += SPAN_BLOCK) stage[t] = *(const uint4*)(text + lo + 16 * (size_t)t);
+  if (hi - lo > LDS_BYTES) return false;
+  for (uint32_t t = threadIdx.x; lo + 16 * t < hi; t += BLOCK) stage[t] = *(const uint4*)(text + lo + 16 * (size_t)t);
   __syncthreads();
   return true;
 }

@@ -540,6 +540,19 @@ class Account:
         from . import account
         return account.account_from_seed(seed)
 
+    @classmethod
+    def from_ciphertext(cls, ciphertext: str, secret) -> 'Account':
+        """PrivateKey.fromPrivateKeyCiphertext (wasm/src/account/private_key.rs:124-130): the account of the key a "ciphertext1…" string holds under a secret;
+        raises as aleo_amd.key_ciphertext.decrypt does."""
+        from . import key_ciphertext
+        return cls.from_private_key(key_ciphertext.decrypt(ciphertext, secret))
+
+    def to_ciphertext(self, secret, nonce=None) -> str:
+        """PrivateKey.toCiphertext (wasm/src/account/private_key.rs:113-118): this account's private key encrypted under a secret (aleo_amd.key_ciphertext.encrypt)."""
+        from . import key_ciphertext
+        if self.private_key is None: raise ValueError('this account holds no private key')
+        return key_ciphertext.encrypt(self.private_key, secret, nonce)
+
     @property
     def view_key_string(self) -> str:
         v = int.from_bytes(_VIEW_KEY_PREFIX + self.view_key, 'big'); out = ''

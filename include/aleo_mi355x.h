@@ -868,6 +868,42 @@ int32_t aleo_mi355x_private_key_seed(void* seed32, const char* private_key);
 int32_t aleo_mi355x_seed_from_bytes(void* seed32, const void* bytes32);
 int32_t aleo_mi355x_view_key_to_string(char* out, size_t cap, const void* view_key32);
 
+/* ---- private key ciphertexts: a private key encrypted under a secret, decrypted one at a time and opened in batches ------------------------------------------------
+ * The reference's PrivateKeyCiphertext (wasm/src/account/private_key_ciphertext.rs:39-73 encryptPrivateKey, decryptToPrivateKey; wasm/src/account/private_key.rs:102-130
+ * newEncrypted, toCiphertext, fromPrivateKeyCiphertext; the algorithm: rust/src/account/encryptor.rs:26-67) over snarkVM 0.14.5's Plaintext and Ciphertext
+ * [UPSTREAM-RECALL]: the step between the "ciphertext1…" string a front end holds with a caller's password and accounts_derive.  Pinned by data the reference holds
+ * (private_key_ciphertext.rs:115-128; tests/golden/reference_account.json "ciphertext_kat"): decryption, and encryption under the nonce that ciphertext holds, byte for
+ * byte.  UNPINNED: a secret of more than 31 bytes (its bytes, little-endian, mod r; the reference's has 10), trailing payload bytes (refused), bit 252 of a decrypted
+ * field (ignored).  REFUSED though upstream would accept it: a ciphertext whose plaintext holds the members `key` and `nonce` in a valid Plaintext shape other than the
+ * one Encryptor::encrypt_field writes (csrc/key_ciphertext_lane.h).  A secret is any byte string, the empty one included.
+ *   private_key_encrypt   host code, a function of its arguments: the 174 characters "ciphertext1…" and their terminator (cap at least 175) of an "APrivateKey1…"
+ *                  string under `secret` and the nonce nonce32, a canonical little-endian field element the caller draws uniformly (upstream: Uniform::rand).
+ *                  ERR_BAD_ARG: a key private_key_seed refuses, a nonce not below r, a smaller buffer.
+ *   private_key_decrypt   host code: the "APrivateKey1…" string (cap: 60 bytes hold it).  ERR_BAD_ARG for what is no ciphertext string, ERR_NOT_OWNER where it does not
+ *                  decrypt under this secret (record_decrypt's status where the reference's decryption fails).
+ *   private_keys_open   n (ciphertext, secret) pairs: the ciphertexts as concatenated text with n + 1 offsets (as records_scan_strings takes its strings), the secrets
+ *                  as concatenated bytes with n + 1 offsets.  Out: seeds32 (the 32 bytes an "APrivateKey1…" string holds), the rows of accounts_derive (sk_sig32,
+ *                  view_key32, address_x32, address63) and flags: 0 opened; 1 a ciphertext that does not decrypt under this secret (one of a field count other than
+ *                  3 included); 3 no ciphertext string (a character, the checksum, the prefix, the payload's length, a field element not below r, more than 2^20
+ *                  characters).  Rows of a flagged pair are zero.  Every output may be NULL; n = 0 is fine; offsets that do not start at 0 or that decrease are
+ *                  ERR_BAD_ARG.  n below min_key_ciphertexts runs the host code inside the call and needs no device; else per 2^20 pairs (ALEO_MI355X_ACCOUNTS_CHUNK
+ *                  caps it lower) one launch of k_key_ciphertexts_open, one pair per lane, and, where an account row is asked for, one of k_accounts_derive behind
+ *                  it over the seeds where they lie: seeds come down only into seeds32.  The copies are inside the call.  Thread-safe (one slot per call).
+ *   private_keys_open_host   the same bytes, computed by the calling thread; touches no device.  The definition.
+ *   min_key_ciphertexts   the batch size from which private_keys_open takes the GPU: 64, the smallest power of two at which the GPU call beats the host loop on one
+ *                  thread in both of two timings, with the seeds alone and with the account outputs, the larger of the two (profiles/key_ciphertexts.txt: the seeds
+ *                  alone cost the call 1.61-1.73 ms for any batch up to 2^12 and the host 46-48 us a pair: 1.47 ms at 2^5, 0.91x and 0.91x, 3.00 ms at 2^6, 1.86x and
+ *                  1.86x; with every account output the call takes 3.8-4.4 ms and the host 221 us a pair: 3.55 ms at 2^4, 0.81x and 0.81x, 7.08 ms at 2^5, 1.62x
+ *                  and 1.61x); ALEO_MI355X_MIN_KEY_CIPHERTEXTS overrides it, read per call (a bad value: the default).
+ * No aleo_mi355x_last_error message of these calls holds a secret, a seed or a key. */
+int32_t aleo_mi355x_private_key_encrypt(char* out, size_t cap, const char* private_key, const void* secret, size_t secret_len, const void* nonce32);
+int32_t aleo_mi355x_private_key_decrypt(char* out, size_t cap, const char* ciphertext, const void* secret, size_t secret_len);
+int32_t aleo_mi355x_private_keys_open(const char* text, const uint64_t* offsets, const void* secrets, const uint64_t* secret_offsets, size_t n, void* seeds32, void* sk_sig32,
+                                      void* view_key32, void* address_x32, char* address63, uint8_t* flags);
+int32_t aleo_mi355x_private_keys_open_host(const char* text, const uint64_t* offsets, const void* secrets, const uint64_t* secret_offsets, size_t n, void* seeds32, void* sk_sig32,
+                                           void* view_key32, void* address_x32, char* address63, uint8_t* flags);
+size_t aleo_mi355x_min_key_ciphertexts(void);
+
 const char* aleo_mi355x_strerror(int32_t status);
 const char* aleo_mi355x_last_error(void);   /* thread-local detail string of the last failure */
 const char* aleo_mi355x_version(void);

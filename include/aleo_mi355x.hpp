@@ -811,6 +811,9 @@ struct PrivateAccount {
     return aleo_mi355x::sign(private_key, message, len, seed32);
   }
   bool verify(const void* message, size_t len, const Signature& signature) const { return aleo_mi355x::verify(signature, address, message, len); }
+  // PrivateKey.fromPrivateKeyCiphertext / toCiphertext: account_from_ciphertext and account_to_ciphertext below (private key ciphertexts)
+  static inline Result<PrivateAccount> from_ciphertext(const std::string& ciphertext, const std::string& secret);
+  inline Result<std::string> to_ciphertext(const std::string& secret, const uint8_t* nonce32) const;
 };
 inline Result<PrivateAccount> account_from_private_key(const std::string& private_key) {
   PrivateAccount a; a.private_key = private_key;
@@ -869,6 +872,59 @@ inline Result<PrivateAccount> account_from_seed(const uint8_t* bytes32) {
   if (!r.is_ok()) return {std::nullopt, r.error};
   return {(*r.value)[0], Error{0}};
 }
+// ---- private key ciphertexts (aleo_mi355x_private_key_encrypt, _decrypt, _private_keys_open): wasm/src/account/private_key_ciphertext.rs:39-73 -------------------------
+// PrivateKeyCiphertext.encryptPrivateKey: the "ciphertext1…" string of an "APrivateKey1…" string under a secret (any bytes).  nonce32: a canonical field element the
+// caller draws uniformly (aleo_mi355x_fr_random under 32 fresh bytes): a repeated nonce repeats the string.
+inline Result<std::string> encrypt_private_key(const std::string& private_key, const std::string& secret, const uint8_t* nonce32) {
+  char out[176];
+  int32_t rc = aleo_mi355x_private_key_encrypt(out, sizeof out, private_key.c_str(), secret.data(), secret.size(), nonce32);
+  if (rc) return {std::nullopt, Error{rc}};
+  return {std::string(out), Error{0}};
+}
+// PrivateKeyCiphertext.decryptToPrivateKey: ALEO_MI355X_ERR_NOT_OWNER where the ciphertext does not decrypt under this secret, ERR_BAD_ARG for what is no ciphertext
+inline Result<std::string> decrypt_private_key(const std::string& ciphertext, const std::string& secret) {
+  char out[64];
+  int32_t rc = aleo_mi355x_private_key_decrypt(out, sizeof out, ciphertext.c_str(), secret.data(), secret.size());
+  if (rc) return {std::nullopt, Error{rc}};
+  return {std::string(out), Error{0}};
+}
+// n (ciphertext, secret) pairs opened in one call (host: on the calling thread): accounts[i] with its private key string where flags[i] is 0; flags[i] 1 where the
+// ciphertext does not decrypt under its secret, 3 where it is no ciphertext string — accounts[i] is then empty (no private key, zero rows).
+struct OpenedKeys { std::vector<PrivateAccount> accounts; std::vector<uint8_t> flags; };
+inline Result<OpenedKeys> open_private_keys(const std::vector<std::string>& ciphertexts, const std::vector<std::string>& secrets, bool host = false) {
+  if (ciphertexts.size() != secrets.size()) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+  const size_t n = ciphertexts.size();
+  std::string text, sec; std::vector<uint64_t> off(n + 1, 0), soff(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) { text += ciphertexts[i]; sec += secrets[i]; off[i + 1] = text.size(); soff[i + 1] = sec.size(); }
+  std::vector<uint8_t> seeds(32 * n), sk(32 * n), vk(32 * n), ax(32 * n);
+  OpenedKeys out; out.accounts.resize(n); out.flags.assign(n, 0);
+  int32_t rc = (host ? aleo_mi355x_private_keys_open_host : aleo_mi355x_private_keys_open)(text.data(), off.data(), sec.data(), soff.data(), n, seeds.data(), sk.data(), vk.data(), ax.data(),
+                                                                                          nullptr, out.flags.data());
+  if (rc) return {std::nullopt, Error{rc}};
+  for (size_t i = 0; i < n; ++i) {
+    PrivateAccount& a = out.accounts[i];
+    std::memcpy(a.sk_sig, sk.data() + 32 * i, 32); std::memcpy(a.view_key.scalar, vk.data() + 32 * i, 32); std::memcpy(a.address.x, ax.data() + 32 * i, 32);
+    if (out.flags[i]) continue;
+    KeySeed seed; std::memcpy(seed.data(), seeds.data() + 32 * i, 32);
+    auto key = private_key_from_seed(seed);
+    if (!key.is_ok()) return {std::nullopt, key.error};
+    a.private_key = *key.value;
+  }
+  return {std::move(out), Error{0}};
+}
+// PrivateKey.fromPrivateKeyCiphertext and PrivateKey.toCiphertext (wasm/src/account/private_key.rs:113-130) for a PrivateAccount
+inline Result<PrivateAccount> account_from_ciphertext(const std::string& ciphertext, const std::string& secret) {
+  auto key = decrypt_private_key(ciphertext, secret);
+  if (!key.is_ok()) return {std::nullopt, key.error};
+  return account_from_private_key(*key.value);
+}
+inline Result<std::string> account_to_ciphertext(const PrivateAccount& account, const std::string& secret, const uint8_t* nonce32) {
+  if (account.private_key.empty()) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+  return encrypt_private_key(account.private_key, secret, nonce32);
+}
+inline Result<PrivateAccount> PrivateAccount::from_ciphertext(const std::string& ciphertext, const std::string& secret) { return account_from_ciphertext(ciphertext, secret); }
+inline Result<std::string> PrivateAccount::to_ciphertext(const std::string& secret, const uint8_t* nonce32) const { return account_to_ciphertext(*this, secret, nonce32); }
+
 // The first max_hits candidates of [first, first + count) under a 32-byte master seed whose address begins with "aleo1" + prefix (0 to 12 characters of the
 // bech32 alphabet), as accounts with their private key strings; index: their positions; next: where to resume.  Candidate i's private-key seed is element i of the
 // ChaCha20 stream under the master seed, which regenerates every key found: keep it secret.
