@@ -39,6 +39,7 @@ EXPORTS = [
     'aleo_mi355x_records_commitments_found', 'aleo_mi355x_records_commitments_found_host', 'aleo_mi355x_min_commitments',
     'aleo_mi355x_signature_sign', 'aleo_mi355x_signature_to_string', 'aleo_mi355x_signature_from_string', 'aleo_mi355x_signatures_verify',
     'aleo_mi355x_signatures_verify_host', 'aleo_mi355x_min_signatures',
+    'aleo_mi355x_signatures_sign', 'aleo_mi355x_signatures_sign_host', 'aleo_mi355x_min_sign',
     'aleo_mi355x_records_unspent_named', 'aleo_mi355x_records_unspent_named_host', 'aleo_mi355x_records_unspent_named_many', 'aleo_mi355x_records_unspent_named_many_host',
     'aleo_mi355x_found_commitments',
     'aleo_mi355x_accounts_derive', 'aleo_mi355x_accounts_derive_host', 'aleo_mi355x_accounts_search', 'aleo_mi355x_accounts_search_host', 'aleo_mi355x_min_accounts',
@@ -223,6 +224,9 @@ def lib():
         'aleo_mi355x_signatures_verify': ([vp, vp, vp, sz, vp, vp, sz], i32),
         'aleo_mi355x_signatures_verify_host': ([vp, vp, vp, sz, vp, vp, sz], i32),
         'aleo_mi355x_min_signatures': ([], sz),
+        'aleo_mi355x_signatures_sign': ([vp, vp, vp, sz, vp, vp, vp, sz], i32),
+        'aleo_mi355x_signatures_sign_host': ([vp, vp, vp, sz, vp, vp, vp, sz], i32),
+        'aleo_mi355x_min_sign': ([], sz),
         'aleo_mi355x_records_unspent_named': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, vp, sz], i32),
         'aleo_mi355x_records_unspent_named_host': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, vp, sz], i32),
         'aleo_mi355x_records_unspent_named_many': ([ctypes.POINTER(vp), vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, vp, sz, vp, sz], i32),

@@ -138,6 +138,16 @@ static uint8_t derive_one_host(const uint8_t* seed32, uint8_t* sk_sig32, uint8_t
   return (uint8_t)ACC_OK;
 }
 
+// what signing needs of the account of a seed below r (signature_host.hpp SignerKeys): derived once per key, whatever the number of signatures under it
+static sig::SignerKeys signer_keys_of_seed(const uint8_t* seed32) {
+  uint64_t sk[4], rs[4], prf[4];
+  serial::account_scalars_of_seed(seed32, sk, rs, prf);
+  sig::SignerKeys a;
+  std::memcpy(a.sk_sig, sk, 32); sig::x_of_mul_g(a.pk_x, sk); sig::x_of_mul_g(a.pr_x, rs);
+  serial::account_from_seed(seed32, nullptr, nullptr, a.address_x);
+  return a;
+}
+
 // ---- the address string: bech32m (BIP-350) under "aleo", written out here and not shared with the lane ------------------------------------------------------------
 static const char* const B32 = "qpzry9x8gf2tvdw0s3jn54khce6mua7l";
 static uint32_t bech32_polymod(const uint8_t* v, size_t n) {

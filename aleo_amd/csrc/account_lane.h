@@ -115,8 +115,10 @@ struct AccountWords { uint32_t sk_sig[8], view_key[8], address[8]; };      // ca
 // One account.  seedw: the seed's 32 bytes as little-endian words.  Returns the flag.
 // phase(): called between the lane's phases, as signature_verify_lane's: the kernel stores a provisional flag byte there, a store the table's loads may not be
 // moved across, so that no phase's constants are fetched ahead and carried through another phase in scalar registers the kernel does not have.
-template <class Phase>
-__device__ __forceinline__ uint32_t account_lane(const uint32_t (&seedw)[8], const uint32_t* K, AccountWords& out, Phase&& phase) {
+// sink(pkx, prx): handed x(pk_sig) and x(pr_sig), Montgomery form, where the lane has them (a refused lane's are those of the seed 0: the caller masks) — the
+// signing flow's key rows take them (signatures.hip k_signer_keys); the account kernels pass none.
+template <class Phase, class Sink>
+__device__ __forceinline__ uint32_t account_lane(const uint32_t (&seedw)[8], const uint32_t* K, AccountWords& out, Phase&& phase, Sink&& sink) {
   F29 seed = f29_from_words(seedw);
   const bool bad = !f29_below_r(seed);
 #pragma unroll
@@ -156,6 +158,7 @@ __device__ __forceinline__ uint32_t account_lane(const uint32_t (&seedw)[8], con
     const F29 inv = f29_pow(den, K + RK_EXP_INV, RK_INV_BITS);
     if (turn == 2) { ax = f29_mul(p.X, inv); continue; }
     const F29 pkx = f29_mul(pkX, f29_mul(inv, p.Z)), prx = f29_mul(p.X, f29_mul(inv, pkZ));
+    sink(pkx, prx);
     F29 st[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) st[i] = rk_const(K, SG_S4 + i);
@@ -175,6 +178,11 @@ __device__ __forceinline__ uint32_t account_lane(const uint32_t (&seedw)[8], con
 #pragma unroll
   for (int i = 0; i < 8; ++i) { out.sk_sig[i] = sk[i] & keep; out.view_key[i] = view[i] & keep; out.address[i] &= keep; }
   return keep ? ACC_OK : ACC_BAD_SEED;
+}
+
+template <class Phase>
+__device__ __forceinline__ uint32_t account_lane(const uint32_t (&seedw)[8], const uint32_t* K, AccountWords& out, Phase&& phase) {
+  return account_lane(seedw, K, out, phase, [](const F29&, const F29&) {});
 }
 
 // Candidate `index` of a search under a master seed: its private key's seed is element `index` of the ChaCha20 stream (chacha.h: uniform over Fr by rejection, a

@@ -197,18 +197,11 @@ static void sign_with_nonce(uint8_t* out128, const SignerKeys& a, const uint64_t
   scalar_mul(t, ch, a.sk_sig); scalar_sub(rs, nonce, t);
   std::memcpy(out128, ch, 32); std::memcpy(out128 + 32, rs, 32); std::memcpy(out128 + 64, a.pk_x, 32); std::memcpy(out128 + 96, a.pr_x, 32);
 }
-// The nonce of a seed: the ChaCha20 stream under the seed in blocks of 32 bytes (two to a ChaCha block, counter 0, 1, ...), the low 251 bits of each; the first
-// below l (rejection: uniform).
+// The nonce of a seed: signature_lane.h sg_nonce_of_seed, the one definition the signing lane runs too
 static void nonce_of_seed(uint64_t* out4, const uint8_t* seed32) {
-  uint32_t key[8]; std::memcpy(key, seed32, 32);
-  for (uint64_t counter = 0;; ++counter) {
-    uint32_t blk[16]; chacha20_block(blk, key, counter, 0);
-    for (int h = 0; h < 2; ++h) {
-      uint64_t v[4]; std::memcpy(v, blk + 8 * h, 32);
-      v[3] &= (1ull << (251 - 192)) - 1;
-      if (scalar_below_order(v)) { std::memcpy(out4, v, 32); return; }
-    }
-  }
+  uint32_t key[8], w[8]; std::memcpy(key, seed32, 32);
+  sg_nonce_of_seed(w, key);
+  std::memcpy(out4, w, 32);
 }
 
 }}  // namespace aleo_mi355x::sig

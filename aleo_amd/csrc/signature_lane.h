@@ -30,6 +30,7 @@
 // permutation, straight into the sponge: there is no per-lane buffer and no limit but the cap.
 #pragma once
 #include "records_serial_lane.h"
+#include "chacha.h"
 
 namespace aleo_mi355x {
 
@@ -156,6 +157,56 @@ __device__ __forceinline__ void sg_hash_words(const F29& h, uint32_t (&w)[8]) { 
   w[7] &= (1u << (SIG_SCALAR_BITS - 224)) - 1u;
 }
 
+// The challenge of a signature: hash_to_scalar_psd8 over [AleoPoseidon8, 4 + m, 0 x 6 | g_r.x, pk_sig.x, pr_sig.x, address.x | the message's m fields], eight to
+// a permutation, the first block included.  head(k), k = 0 .. 3: the four elements before the message, Montgomery form, asked for once each when block 1 is
+// built — the verifying and the signing lane (signature_sign_lane.h) both call this.
+template <class Head, class Byte, class Phase>
+__device__ __forceinline__ void sg_challenge(uint32_t (&out)[8], Head&& head, uint32_t len, uint32_t m, Byte&& byte, const uint32_t* K, Phase&& phase) {
+  F29 st[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) st[i] = f29_zero();
+  const uint32_t blocks = (12u + m + 7u) / 8u;
+  for (uint32_t b = 0; b < blocks; ++b) {
+    phase();
+    if (b == 0) {
+      F29 count = f29_zero(); count.v[0] = 4u + m;
+      st[1] = rk_const(K, SG_DOM8); st[2] = f29_mul(count, rk_const(K, RK_R2));
+    } else {
+      uint32_t j = 8u * b - 12u;                                                  // the field that st[1] takes; the four elements before field 0 in block 1
+      if (b == 1) {
+        st[1] = f29_add(st[1], head(0));
+        st[2] = f29_add(st[2], head(1)); st[3] = f29_add(st[3], head(2)); st[4] = f29_add(st[4], head(3));
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if ((b > 1 || i >= 4) && j + (uint32_t)i < m) {
+          uint32_t w[8];
+          sg_message_field(j + (uint32_t)i, len, byte, w);
+          st[1 + i] = f29_add(st[1 + i], f29_mul(f29_from_words(w), rk_const(K, RK_R2)));
+        }
+      }
+    }
+    psd_permute(st, K);
+  }
+  sg_hash_words(st[1], out);
+}
+
+// The nonce of a seed, on the host and in the signing lane alike: the ChaCha20 stream under the seed (counter 0, 1, ..., nonce word 0), two candidates of 32 bytes
+// to a block, the low 251 bits of each; the first below l (rejection: uniform; l / 2^251 = 0.583 of the candidates pass, and the loop ends with probability 1 as
+// chacha_fr's does).
+__host__ __device__ inline void sg_nonce_of_seed(uint32_t (&out)[8], const uint32_t (&seedw)[8]) {
+  const uint32_t order[8] = {0xc33fd9ffu, 0xb95aee9au, 0xc43c8afeu, 0x5293a3afu, 0x970dec00u, 0x982d1347u, 0xa68b2955u, 0x04aad957u};      // SIG_ORDER, for both compilers
+  for (uint64_t counter = 0;; ++counter) {
+    uint32_t blk[16]; chacha20_block(blk, seedw, counter, 0);
+    for (int h = 0; h < 2; ++h) {
+      uint32_t* c = blk + 8 * h; c[7] &= 0x07ffffffu;     // low 251 bits
+      bool lt = false;
+      for (int i = 7; i >= 0; --i) { if (c[i] != order[i]) { lt = c[i] < order[i]; break; } }
+      if (lt) { for (int i = 0; i < 8; ++i) out[i] = c[i]; return; }
+    }
+  }
+}
+
 // One signature.  load(k, w): the canonical words of the signature's part k = 0 .. 3 (challenge, response, pk_sig.x, pr_sig.x) and, k = 4, of the address x;
 // len, byte: the message.  Returns the flag.
 // phase(): called between the lane's phases.  The kernel stores a provisional flag byte there, a store the table's loads may not be moved across: without it the
@@ -231,35 +282,8 @@ __device__ __forceinline__ uint32_t signature_verify_lane(Load&& load, uint32_t 
     if (turn == 0) grx = f29_mul(p.X, f29_pow(p.Z, K + RK_EXP_INV, RK_INV_BITS));  // Z is never 0 (the law is complete)
     else address_ok = f29_same_limbs(f29_canonical(p.X), f29_canonical(f29_mul(p.Z, mont(4, RK_R2))));
   }
-  // the challenge: [AleoPoseidon8, 4 + m, 0 x 6 | g_r.x, pk_sig.x, pr_sig.x, address.x | the message's fields], eight to a permutation
-  F29 st[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) st[i] = f29_zero();
-  const uint32_t blocks = (12u + m + 7u) / 8u;
-  for (uint32_t b = 0; b < blocks; ++b) {
-    phase();
-    if (b == 0) {
-      F29 count = f29_zero(); count.v[0] = 4u + m;
-      st[1] = rk_const(K, SG_DOM8); st[2] = f29_mul(count, rk_const(K, RK_R2));
-    } else {
-      uint32_t j = 8u * b - 12u;                                                  // the field that st[1] takes; the four elements before field 0 in block 1
-      if (b == 1) {
-        st[1] = f29_add(st[1], grx);
-        st[2] = f29_add(st[2], mont(2, RK_R2)); st[3] = f29_add(st[3], mont(3, RK_R2)); st[4] = f29_add(st[4], mont(4, RK_R2));
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        if ((b > 1 || i >= 4) && j + (uint32_t)i < m) {
-          uint32_t w[8];
-          sg_message_field(j + (uint32_t)i, len, byte, w);
-          st[1 + i] = f29_add(st[1 + i], f29_mul(f29_from_words(w), rk_const(K, RK_R2)));
-        }
-      }
-    }
-    psd_permute(st, K);
-  }
   uint32_t got[8];
-  sg_hash_words(st[1], got);
+  sg_challenge(got, [&](uint32_t k) { return k == 0 ? grx : mont(1 + k, RK_R2); }, len, m, byte, K, phase);
   uint32_t diff = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) diff |= got[i] ^ cw[i];

@@ -5,7 +5,7 @@
 //
 // The kernel (one signature per lane: signature_lane.h), its table (signature_host.hpp: 139 KB with the scan's constants, built on the host at first use and
 // resident per device for the life of the process), the same flags on the host (signature_host.hpp verify_one_host — what small batches take, and the
-// definition), the routing threshold, and the host-only calls: signing and the string.
+// definition), the routing threshold, and the host-only calls: signing one message and the string.  (Signing in batches, on the device: signatures_sign.hip.)
 #include "entry.h"
 #include "records_bits.hpp"
 #include "signature_host.hpp"
@@ -90,11 +90,9 @@ static int32_t signatures_verify(uint8_t* flags, const void* sigs128, const void
 static int32_t signature_sign(void* out128, const char* private_key, const void* message, size_t len, const void* seed32) {
   if (!out128 || !seed32 || (len && !message)) return bad_arg("signature_sign: null buffer");
   if (len > SIG_MAX_BYTES) return bad_arg("signature_sign: the message exceeds the maximum of 4161 fields");
-  uint64_t sk[4], rs[4], prf[4];
-  if (int32_t rc = serial::account_scalars(private_key, sk, rs, prf)) return rc;
-  sig::SignerKeys a;
-  std::memcpy(a.sk_sig, sk, 32); sig::x_of_mul_g(a.pk_x, sk); sig::x_of_mul_g(a.pr_x, rs);
-  if (int32_t rc = serial::account_from_private_key(private_key, nullptr, nullptr, a.address_x)) return rc;
+  uint8_t key_seed[32];
+  if (int32_t rc = serial::private_key_seed(key_seed, private_key)) return rc;
+  const sig::SignerKeys a = acct::signer_keys_of_seed(key_seed);
   uint64_t nonce[4]; sig::nonce_of_seed(nonce, (const uint8_t*)seed32);
   sig::sign_with_nonce((uint8_t*)out128, a, nonce, (const uint8_t*)message, len);
   return ALEO_MI355X_OK;

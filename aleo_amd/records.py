@@ -568,6 +568,12 @@ class Account:
         if self.private_key is None: raise ValueError('this account holds no private key')
         return signature.sign(self.private_key, message, seed)
 
+    def sign_many(self, messages, seeds=None, host: bool = False):
+        """Account.sign over many messages in one call: aleo_amd.signature.sign_many under this account's private key — (n x 128 rows, flags)."""
+        from . import signature
+        if self.private_key is None: raise ValueError('this account holds no private key')
+        return signature.sign_many(self.private_key, messages, seeds, host)
+
     def verify(self, message, signature) -> bool:
         """Account.verify (sdk/src/account.ts:211-213): does the signature (a Signature or a "sign1…" string) verify under this account's address?"""
         from . import signature as sg

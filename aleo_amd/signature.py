@@ -1,7 +1,8 @@
 """Account signatures: the mirror of the reference's Signature.sign / verify / to_string (wasm/src/account/signature.rs:37-48), Address.verify
 (wasm/src/account/address.rs:69-71), PrivateKey.sign (wasm/src/account/private_key.rs:244-248) and Account.sign / verify (sdk/src/account.ts:195,211-213) —
 and, for a front end that answers for many accounts at once, verify_many: n signatures under one or n addresses over n messages in one call
-(aleo_mi355x_signatures_verify: csrc/signatures.hip, one signature per GPU lane; small batches and host=True run csrc/signature_host.hpp on the calling thread).
+(aleo_mi355x_signatures_verify: csrc/signatures.hip, one signature per GPU lane; small batches and host=True run csrc/signature_host.hpp on the calling thread),
+and sign_many: n messages signed under one key or under a key each in one call (aleo_mi355x_signatures_sign: csrc/signatures_sign.hip, likewise).
 A signature is 128 bytes, challenge | response | pk_sig.x | pr_sig.x, and a "sign1…" string (bech32m)."""
 from __future__ import annotations
 import ctypes, os
@@ -55,6 +56,33 @@ def sign(private_key: str, message, seed: bytes = None) -> Signature:
     m = _message(message); out = np.zeros(128, dtype=np.uint8)
     check(lib().aleo_mi355x_signature_sign(_p(out), private_key.encode(), ctypes.cast(ctypes.c_char_p(m), ctypes.c_void_p), len(m), ctypes.cast(ctypes.c_char_p(seed), ctypes.c_void_p)), 'signature_sign')
     return Signature(out.tobytes())
+
+
+def _key_seed_rows(private_keys) -> np.ndarray:
+    """n x 32: the seeds of one "APrivateKey1…" string, of a list of them, or an array of seed rows as it stands."""
+    from .account import private_key_seed
+    if isinstance(private_keys, np.ndarray): return np.ascontiguousarray(private_keys, dtype=np.uint8).reshape(-1, 32)
+    keys = [private_keys] if isinstance(private_keys, str) else list(private_keys)
+    return np.frombuffer(b''.join(private_key_seed(k) for k in keys), dtype=np.uint8).reshape(-1, 32).copy()
+
+
+def sign_many(private_keys, messages, seeds=None, host: bool = False):
+    """(rows, flags): row i (of an n x 128 array) is sign(key i, message i, seed i).bytes, flags[i] 0; or zeros with flags[i] 3 where the key's seed is no field
+    element or the message is longer than MAX_MESSAGE_BYTES.  private_keys: one "APrivateKey1…" string (one key for all messages), a list of n of them, or an
+    n x 32 array of their seeds (a 1 x 32 array: one key for all).  seeds: n x 32 bytes (an array, or the bytes joined), one nonce seed per signature;
+    os.urandom(32 * n) when None.  Two equal seeds in one call are refused: a seed must NEVER be used for two messages."""
+    msgs = [_message(m) for m in messages]; n = len(msgs)
+    keys = _key_seed_rows(private_keys)
+    if keys.shape[0] not in (1, n): raise ValueError('one private key, or one per message')
+    stride = 32 if keys.shape[0] == n and not isinstance(private_keys, str) and n != 1 else 0
+    if seeds is None: seeds = os.urandom(32 * n)
+    sd = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1) if isinstance(seeds, np.ndarray) else np.frombuffer(bytes(seeds), dtype=np.uint8)
+    if sd.size != 32 * n: raise ValueError('one seed of 32 bytes per message')
+    offsets = np.zeros(n + 1, dtype=np.uint64); offsets[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+    text = b''.join(msgs); rows = np.zeros((n, 128), dtype=np.uint8); flags = np.zeros(n, dtype=np.uint8)
+    L = lib(); call = L.aleo_mi355x_signatures_sign_host if host else L.aleo_mi355x_signatures_sign
+    check(call(_p(rows), _p(flags), _p(keys), stride, ctypes.cast(ctypes.c_char_p(text), ctypes.c_void_p), _p(offsets), _p(sd), n), 'signatures_sign')
+    return rows, flags
 
 
 def _signature_rows(signatures) -> np.ndarray:

@@ -830,6 +830,37 @@ int32_t aleo_mi355x_signatures_verify(uint8_t* flags, const void* sigs128, const
 int32_t aleo_mi355x_signatures_verify_host(uint8_t* flags, const void* sigs128, const void* addresses_x32, size_t address_stride, const void* messages, const uint64_t* offsets, size_t n);
 size_t aleo_mi355x_min_signatures(void);
 
+/* ---- account signatures in batches: one key signing many messages, or many keys signing one message each ----------------------------------------------------------
+ * Signature::sign (wasm/src/account/signature.rs:37-44, wasm/src/account/private_key.rs:92-96, sdk/src/account.ts:195) for n messages in one call.  Row i of the
+ * result is byte for byte what signature_sign returns for (key i, message i, nonce seed i): nonce = the first number below the group order in the ChaCha20 stream
+ * under the seed, g_r = nonce G, challenge = hash_to_scalar_psd8([g_r.x, pk_sig.x, pr_sig.x, address.x, m ...]), response = nonce - challenge sk_sig mod l, the
+ * row challenge | response | pk_sig.x | pr_sig.x.  [UPSTREAM-RECALL], and UNPINNED exactly where the block above says so: the order of the preimage, the packing,
+ * the layout and the cap are inherited from it unchanged.
+ * Neither path is hardened against side channels: the table lookups are indexed by secret digits (of the nonce; of the key in the derivation), as accounts_derive's are.
+ *   signatures_sign   sigs128: n rows of 128 bytes.  key_seeds32: rows of the 32 bytes an "APrivateKey1…" string holds (private_key_seed), as accounts_derive takes
+ *                  them, key_stride apart: 0, one key for all (derived once, on the host); 32, one key per signature (derived on the device by a launch of its
+ *                  own on the same stream; equal keys in such a batch are derived again, each).  messages / offsets: concatenated bytes with n + 1 offsets, as
+ *                  signatures_verify takes them.  nonce_seeds32: n rows of 32 bytes, always one per signature.  flags[i]: 0 signed; 3 the key seed is no canonical
+ *                  field element or the message is over the cap of 131071 bytes — row i is then zeros (the value accounts_derive and signatures_verify give
+ *                  to such inputs).  Refused (ALEO_MI355X_ERR_BAD_ARG): null buffers with n > 0, another stride, offsets that do not start at 0 or decrease, and
+ *                  TWO EQUAL ROWS IN nonce_seeds32 — NEVER REUSE A SEED: inside one call the library enforces it, on the host, before anything is uploaded,
+ *                  also where the two rows sign under different keys; last_error names the two indices.  n = 0 is fine.  Batches below min_sign run the host
+ *                  code inside the call and need no device; else launches of at most 2^20 signatures and 2^30 message bytes (ALEO_MI355X_SIGN_CHUNK caps the
+ *                  signatures lower), one signature per lane, the copies inside the call.  Thread-safe (one slot per call).
+ *   signatures_sign_host   the same bytes, computed by the calling thread; touches no device.  It is the definition of the result.
+ *   min_sign       the batch size from which signatures_sign takes the GPU: 64, the smallest power of two at which the GPU call beats the host path on one thread in both
+ *                  of two timings, in the mode that crosses later (profiles/signatures_sign.txt.  One key: a call costs 2.4-2.7 ms for any batch up to 2^12; the
+ *                  host path 1.61 / 1.61 ms at 2^5, 0.65x and 0.65x, and 2.93 / 2.93 ms at 2^6, 1.23x and 1.22x.  A key each, whose host path derives a key per
+ *                  row: a call costs 4.3-4.8 ms; the host path 5.61 / 5.61 ms at 2^4, 1.16x and 1.16x.  The parent's road, a loop of signature_sign on one
+ *                  thread, is behind the call from 2^4 on in both modes: 5.05 ms and 5.63 ms there, 1.88x and 1.16x); ALEO_MI355X_MIN_SIGN overrides it, read
+ *                  per call (a bad value: the default).
+ *                  The check for equal seeds costs 15 ms at 2^20 seeds, inside a call of 61-66 ms (one key) or 99 ms (a key each). */
+int32_t aleo_mi355x_signatures_sign(void* sigs128, uint8_t* flags, const void* key_seeds32, size_t key_stride, const void* messages, const uint64_t* offsets,
+                                    const void* nonce_seeds32, size_t n);
+int32_t aleo_mi355x_signatures_sign_host(void* sigs128, uint8_t* flags, const void* key_seeds32, size_t key_stride, const void* messages, const uint64_t* offsets,
+                                         const void* nonce_seeds32, size_t n);
+size_t aleo_mi355x_min_sign(void);
+
 /* ---- accounts in batches: keys and addresses of many seeds in one call, and the search for an address with a chosen prefix ---------------------------------------
  * The first step of every record and signature call above: an account's sk_sig, view key and address, from the 32-byte seed of its private key — the reference's
  * account module (wasm/src/account/private_key.rs:38-86 PrivateKey::new, from_seed_unchecked, to_view_key, to_address; sdk/src/account.ts:82) — snarkVM 0.14.5

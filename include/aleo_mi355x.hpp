@@ -784,6 +784,23 @@ inline Result<Signature> sign(const std::string& private_key, const void* messag
   if (rc) return {std::nullopt, Error{rc}};
   return {g, Error{0}};
 }
+// Many signatures in one call (aleo_mi355x_signatures_sign): signatures[i] is sign(key i, message i, seed i) and flags[i] 0 — or zeros and 3 where the message is
+// over the cap.  private_keys: one "APrivateKey1…" string for all messages, or one per message; seeds32: one row of 32 bytes per message, no two equal (the
+// call refuses them: never use a seed for two messages).  Batches of aleo_mi355x_min_sign() and more run on the GPU, one signature per lane.
+struct SignedBatch { std::vector<Signature> signatures; std::vector<uint8_t> flags; };
+inline Result<SignedBatch> sign_many(const std::vector<std::string>& private_keys, const std::vector<std::string>& messages, const uint8_t* seeds32, bool host = false) {
+  const size_t n = messages.size();
+  if (private_keys.size() != n && private_keys.size() != 1) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+  std::vector<uint8_t> keys(32 * private_keys.size()); std::vector<uint64_t> off(n + 1, 0); std::string text;
+  for (size_t i = 0; i < private_keys.size(); ++i) if (int32_t rc = aleo_mi355x_private_key_seed(keys.data() + 32 * i, private_keys[i].c_str())) return {std::nullopt, Error{rc}};
+  for (size_t i = 0; i < n; ++i) { text += messages[i]; off[i + 1] = text.size(); }
+  SignedBatch out; out.signatures.resize(n); out.flags.assign(n, 0);
+  static_assert(sizeof(Signature) == 128, "rows of 128 bytes");
+  const size_t stride = private_keys.size() == n && n != 1 ? 32 : 0;
+  int32_t rc = (host ? aleo_mi355x_signatures_sign_host : aleo_mi355x_signatures_sign)(out.signatures.data(), out.flags.data(), keys.data(), stride, text.data(), off.data(), seeds32, n);
+  if (rc) return {std::nullopt, Error{rc}};
+  return {std::move(out), Error{0}};
+}
 // flags[i]: 0 signature i verifies under its address over message i, 1 it does not, 3 it is no signature.  addresses: one for all, or one per signature.
 // Batches of aleo_mi355x_min_signatures() and more run on the GPU, one signature per lane.
 inline Result<std::vector<uint8_t>> verify_many(const std::vector<Signature>& signatures, const std::vector<Address>& addresses, const std::vector<std::string>& messages, bool host = false) {
@@ -809,6 +826,10 @@ struct PrivateAccount {
   Result<Signature> sign(const void* message, size_t len, const uint8_t* seed32) const {
     if (private_key.empty()) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
     return aleo_mi355x::sign(private_key, message, len, seed32);
+  }
+  Result<SignedBatch> sign_many(const std::vector<std::string>& messages, const uint8_t* seeds32, bool host = false) const {
+    if (private_key.empty()) return {std::nullopt, Error{ALEO_MI355X_ERR_BAD_ARG}};
+    return aleo_mi355x::sign_many({private_key}, messages, seeds32, host);
   }
   bool verify(const void* message, size_t len, const Signature& signature) const { return aleo_mi355x::verify(signature, address, message, len); }
   // PrivateKey.fromPrivateKeyCiphertext / toCiphertext: account_from_ciphertext and account_to_ciphertext below (private key ciphertexts)
