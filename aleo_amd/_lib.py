@@ -3,6 +3,7 @@ is missing or a call fails, an exception is raised (the Rust caller would fall b
 package never does, so a silent fallback cannot hide behind a green test)."""
 from __future__ import annotations
 import ctypes, os
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ALEO_MI355X_LIB: another build of the same library (the probe builds of tools/ntt_phase_probe.sh, an A/B build) — never a fallback: it must exist and export every symbol
@@ -262,6 +263,15 @@ def check(status: int, what: str):
             f'{what}: {L.aleo_mi355x_strerror(status).decode()} [{L.aleo_mi355x_last_error().decode()}]')
         e.status = status
         raise e
+
+
+# what the bindings pass to a void pointer: an array (None: NULL), bytes; and byte strings laid one after another with their n + 1 offsets
+def _p(a): return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+def _vp(b: bytes): return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
+def _blob(items):
+    off = np.zeros(len(items) + 1, dtype=np.uint64)
+    if items: off[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64)
+    return b''.join(items), off
 
 
 def seed32(seed=None):

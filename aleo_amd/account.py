@@ -7,16 +7,12 @@ little-endian field element); records.Account is what the calls return."""
 from __future__ import annotations
 import ctypes, os
 import numpy as np
-from ._lib import lib, check
+from ._lib import lib, check, _p, _vp
 from .records import Account
 
 DERIVED, BAD_SEED = 0, 3
 PREFIX_CHARSET = 'qpzry9x8gf2tvdw0s3jn54khce6mua7l'
 MAX_PREFIX = 12
-
-
-def _p(a): return a.ctypes.data_as(ctypes.c_void_p)
-def _vp(b: bytes): return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
 
 
 def _seed_rows(seeds) -> np.ndarray:

@@ -9,7 +9,6 @@
 // definition), the routing threshold, and the host-only calls: the strings and the reduction of 32 bytes to a seed.
 #include "accounts.h"
 #include "records_bits.hpp"
-#include "account_host.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -62,7 +61,7 @@ __global__ void __launch_bounds__(ACC_BLOCK) k_accounts_search(char* base, Seed3
   }
 }
 
-static int32_t account_table(int device, const uint32_t** out) {
+int32_t account_table(int device, const uint32_t** out) {
   return resident_table(device, ResidentTable::ACCOUNT, []() -> const std::vector<uint32_t>& { return acct::account_tables().words; }, out);
 }
 
@@ -72,7 +71,7 @@ void launch_accounts_derive(hipStream_t s, char* base, size_t m, const uint32_t*
 
 // ---- derive -------------------------------------------------------------------------------------------------------------------------------------------
 // Chunk by chunk: the seeds go up, one launch runs, the rows asked for come down.
-static int32_t derive_on_device(const uint8_t* seeds, size_t n, uint8_t* sk, uint8_t* view, uint8_t* addr, char* str, uint8_t* flags) {
+static int32_t derive_on_device(const uint8_t* seeds, size_t n, const AccOut& out, uint8_t* flags) {
   const size_t cap = env_cap("ALEO_MI355X_ACCOUNTS_CHUNK", ACC_CHUNK);
   AccChunk head;                                               // declared outside the slot: it outlives the copy that reads it
   return on_slot([&](Ctx* c) -> int32_t {
@@ -83,19 +82,15 @@ static int32_t derive_on_device(const uint8_t* seeds, size_t n, uint8_t* sk, uin
       const size_t m = std::min(cap, n - lo);
       Carve cv;
       const size_t o_head = cv.part(sizeof(AccChunk)), o_seed = cv.part(m * 32), o_fl = cv.part(m);
-      const size_t o_sk = sk ? cv.part(m * 32) : ACC_NONE, o_view = view ? cv.part(m * 32) : ACC_NONE, o_addr = addr ? cv.part(m * 32) : ACC_NONE;
-      const size_t o_str = str ? cv.part(m * ACC_ADDRESS_CHARS) : ACC_NONE;
+      head = AccChunk{(uint32_t)o_seed, (uint32_t)o_fl, ACC_NONE, ACC_NONE, ACC_NONE, ACC_NONE, (uint32_t)m, 0u};
+      out.carve(cv, head, m);
       if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
       char* b = c->scalars_stage.as<char>();
       HIPCHK(hipMemcpyAsync(b + o_seed, seeds + lo * 32, m * 32, hipMemcpyHostToDevice, s));
-      head = AccChunk{(uint32_t)o_seed, (uint32_t)o_fl, (uint32_t)o_sk, (uint32_t)o_view, (uint32_t)o_addr, (uint32_t)o_str, (uint32_t)m, 0u};
       HIPCHK(hipMemcpyAsync(b + o_head, &head, sizeof head, hipMemcpyHostToDevice, s));
       launch_accounts_derive(s, b, m, dK);
       HIPCHK(hipGetLastError());
-      if (sk) HIPCHK(hipMemcpyAsync(sk + lo * 32, b + o_sk, m * 32, hipMemcpyDeviceToHost, s));
-      if (view) HIPCHK(hipMemcpyAsync(view + lo * 32, b + o_view, m * 32, hipMemcpyDeviceToHost, s));
-      if (addr) HIPCHK(hipMemcpyAsync(addr + lo * 32, b + o_addr, m * 32, hipMemcpyDeviceToHost, s));
-      if (str) HIPCHK(hipMemcpyAsync(str + lo * ACC_ADDRESS_CHARS, b + o_str, m * ACC_ADDRESS_CHARS, hipMemcpyDeviceToHost, s));
+      if (int32_t rc = out.download(s, b, head, lo, m)) return rc;
       if (flags) HIPCHK(hipMemcpyAsync(flags + lo, b + o_fl, m, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffer
       lo += m;
@@ -108,15 +103,9 @@ static int32_t accounts_derive(const void* seeds32, size_t n, void* sk_sig32, vo
   if (!n) return ALEO_MI355X_OK;
   if (!seeds32) return bad_arg("accounts_derive: null seeds");
   const uint8_t* seeds = (const uint8_t*)seeds32;
-  uint8_t* sk = (uint8_t*)sk_sig32; uint8_t* view = (uint8_t*)view_key32; uint8_t* addr = (uint8_t*)address_x32;
-  if (may_route && n >= aleo_mi355x_min_accounts()) return derive_on_device(seeds, n, sk, view, addr, address63, flags);
-  for (size_t i = 0; i < n; ++i) {
-    uint8_t ax[32];
-    const uint8_t flag = acct::derive_one_host(seeds + 32 * i, sk ? sk + 32 * i : nullptr, view ? view + 32 * i : nullptr, ax);
-    if (addr) std::memcpy(addr + 32 * i, ax, 32);
-    if (address63) { if (flag) std::memset(address63 + ACC_ADDRESS_CHARS * i, 0, ACC_ADDRESS_CHARS); else acct::address_string(address63 + ACC_ADDRESS_CHARS * i, ax); }
-    if (flags) flags[i] = flag;
-  }
+  const AccOut out{(uint8_t*)sk_sig32, (uint8_t*)view_key32, (uint8_t*)address_x32, address63};
+  if (may_route && n >= aleo_mi355x_min_accounts()) return derive_on_device(seeds, n, out, flags);
+  for (size_t i = 0; i < n; ++i) { const uint8_t flag = out.row_on_host(i, seeds + 32 * i, 0); if (flags) flags[i] = flag; }
   return ALEO_MI355X_OK;
 }
 
@@ -176,12 +165,6 @@ static int32_t accounts_search(const void* master32, uint64_t first, uint64_t co
   }
   *n_hits = hits.size();
   *next = hits.size() == max_hits ? hits.back() + 1 : first + count;
-  return ALEO_MI355X_OK;
-}
-
-static int32_t string_out(char* out, size_t cap, const std::string& s, const char* too_small) {
-  if (s.size() + 1 > cap) return bad_arg(too_small);
-  std::memcpy(out, s.c_str(), s.size() + 1);
   return ALEO_MI355X_OK;
 }
 

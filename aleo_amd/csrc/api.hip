@@ -74,6 +74,16 @@ template <int N> void inverse_selftest(uint32_t count, uint64_t seed, uint32_t* 
 }
 }  // namespace
 
+int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offsets, size_t n) {
+  if (!n) return ALEO_MI355X_OK;
+  if (!offsets) { g_last_error = std::string(who) + ": null buffer"; return ALEO_MI355X_ERR_BAD_ARG; }
+  if (offsets[0] != 0) { g_last_error = std::string(who) + ": offsets[0] is not 0"; return ALEO_MI355X_ERR_BAD_ARG; }
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) { g_last_error = std::string(who) + ": offsets decrease"; return ALEO_MI355X_ERR_BAD_ARG; }
+  if (offsets[n] && !text) { g_last_error = std::string(who) + ": null buffer"; return ALEO_MI355X_ERR_BAD_ARG; }
+  return ALEO_MI355X_OK;
+}
+
 // ---- one prover round's commitments in one call -------------------------------------------------------------------
 int32_t batch_args_ok(const void* out, const void* const* ptrs, const size_t* lens, size_t k) {
   if (k == 0) return ALEO_MI355X_OK;

@@ -10,7 +10,7 @@
 // two normalised values is a valid multiplicand; a padded difference a + 19 r - b wants b normalised and below 18 r.  Whatever is used as a multiplier
 // or as a subtrahend is therefore "tidied" first (normalised, then brought below 3 r): ~45 simple instructions against the 206 of a product.
 #pragma once
-#ifndef ALEO_F29_PROVIDED      // tests/cpp/records_lane_emul.cpp supplies the same field on the host, with every bound above checked
+#ifndef ALEO_F29_PROVIDED      // tests/cpp/checked_f29.h supplies the same field on the host, with every bound above checked
 #include "fr29.h"
 #endif
 

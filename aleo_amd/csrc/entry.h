@@ -57,5 +57,7 @@ int32_t one_shot_bases(Ctx* c, const void* bases, size_t stride, size_t n, std::
 int32_t one_shot_bases_g2(Ctx* c, const void* bases, size_t stride, size_t n, const void** d_xy, const uint8_t** d_inf);
 // api.hip
 int32_t batch_args_ok(const void* out, const void* const* ptrs, const size_t* lens, size_t k);
+// n byte strings one after another in `text`, string i at text[offsets[i] .. offsets[i + 1]): what every call over such a blob refuses before it looks at a string
+int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offsets, size_t n);
 
 }  // namespace aleo_mi355x

@@ -60,24 +60,16 @@ static int32_t key_ciphertext_table(int device, const uint32_t** out) {
   return resident_table(device, ResidentTable::KEY_CIPHERTEXT, []() -> const std::vector<uint32_t>& { return kct::key_ciphertext_tables().words; }, out);
 }
 
-struct OpenOut { uint8_t* seeds; uint8_t* sk; uint8_t* view; uint8_t* addr; char* str; uint8_t* flags; bool accounts() const { return sk || view || addr || str; } };
+struct OpenOut { uint8_t* seeds; AccOut acc; uint8_t* flags; };
 
 // ---- the host path --------------------------------------------------------------------------------------------------------------------------------------------------
 static int32_t open_on_host(const char* text, const uint64_t* offsets, const uint8_t* secrets, const uint64_t* secret_offsets, size_t n, const OpenOut& o) {
   for (size_t i = 0; i < n; ++i) {
-    uint8_t seed[32], ax[32];
+    uint8_t seed[32];
     const uint8_t flag = kct::open_one_host(seed, text + offsets[i], offsets[i + 1] - offsets[i], secrets + secret_offsets[i], (size_t)(secret_offsets[i + 1] - secret_offsets[i]));
     if (o.seeds) std::memcpy(o.seeds + 32 * i, seed, 32);
     if (o.flags) o.flags[i] = flag;
-    if (!o.accounts()) continue;
-    if (flag) {
-      for (uint8_t* p : {o.sk, o.view, o.addr}) if (p) std::memset(p + 32 * i, 0, 32);
-      if (o.str) std::memset(o.str + ACC_ADDRESS_CHARS * i, 0, ACC_ADDRESS_CHARS);
-      continue;
-    }
-    (void)acct::derive_one_host(seed, o.sk ? o.sk + 32 * i : nullptr, o.view ? o.view + 32 * i : nullptr, ax);      // a seed that was opened is below r
-    if (o.addr) std::memcpy(o.addr + 32 * i, ax, 32);
-    if (o.str) acct::address_string(o.str + ACC_ADDRESS_CHARS * i, ax);
+    if (o.acc.any()) (void)o.acc.row_on_host(i, seed, flag);      // a seed that was opened is below r: the flag stays the open's
   }
   return ALEO_MI355X_OK;
 }
@@ -90,7 +82,7 @@ static int32_t open_on_device(const char* text, const uint64_t* offsets, const u
   src.cut_chunks(n, env_cap("ALEO_MI355X_ACCOUNTS_CHUNK", ACC_CHUNK));
   std::vector<uint32_t> trel, srel; std::vector<uint8_t> sblob, open_flags, derive_flags;
   KcChunk head;
-  const bool accounts = o.accounts();
+  const bool accounts = o.acc.any();
   return on_slot([&](Ctx* c) -> int32_t {
     const uint32_t* dK;
     if (int32_t rc = key_ciphertext_table(c->device, &dK)) return rc;
@@ -111,8 +103,8 @@ static int32_t open_on_device(const char* text, const uint64_t* offsets, const u
       }
       Carve cv;
       const size_t o_head = cv.part(sizeof(KcChunk)), o_seed = cv.part(m * 32), o_fl = cv.part(m), o_open = cv.part(m);
-      const size_t o_sk = o.sk ? cv.part(m * 32) : ACC_NONE, o_view = o.view ? cv.part(m * 32) : ACC_NONE, o_addr = o.addr ? cv.part(m * 32) : ACC_NONE;
-      const size_t o_str = o.str ? cv.part(m * ACC_ADDRESS_CHARS) : ACC_NONE;
+      head.acc = AccChunk{(uint32_t)o_seed, (uint32_t)o_fl, ACC_NONE, ACC_NONE, ACC_NONE, ACC_NONE, (uint32_t)m, 0u};
+      o.acc.carve(cv, head.acc, m);
       const size_t o_toff = cv.part((m + 1) * 4), o_soff = cv.part((m + 1) * 4), o_text = cv.part(pos + 16), o_sec = cv.part(sblob.size() + 16);
       if (cv.total > 0xffffffffull) { g_last_error = "private_keys_open: a chunk's buffer passes 4 GiB"; return ALEO_MI355X_ERR_BAD_ARG; }
       if (int32_t rc = c->scalars_stage.reserve(cv.total)) return rc;
@@ -134,8 +126,7 @@ static int32_t open_on_device(const char* text, const uint64_t* offsets, const u
       if (!sblob.empty()) HIPCHK(hipMemcpyAsync(b + o_sec, sblob.data(), sblob.size(), hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(b + o_toff, trel.data(), (m + 1) * 4, hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(b + o_soff, srel.data(), (m + 1) * 4, hipMemcpyHostToDevice, s));
-      head = KcChunk{AccChunk{(uint32_t)o_seed, (uint32_t)o_fl, (uint32_t)o_sk, (uint32_t)o_view, (uint32_t)o_addr, (uint32_t)o_str, (uint32_t)m, 0u},
-                     (uint32_t)o_open, (uint32_t)o_toff, (uint32_t)o_soff, (uint32_t)o_text, (uint32_t)o_sec, {0u, 0u, 0u}};
+      head = KcChunk{head.acc, (uint32_t)o_open, (uint32_t)o_toff, (uint32_t)o_soff, (uint32_t)o_text, (uint32_t)o_sec, {0u, 0u, 0u}};
       HIPCHK(hipMemcpyAsync(b + o_head, &head, sizeof head, hipMemcpyHostToDevice, s));
       hipLaunchKernelGGL(k_key_ciphertexts_open, dim3((uint32_t)((m + KC_BLOCK - 1) / KC_BLOCK)), dim3(KC_BLOCK), 0, s, b, (uint32_t)m, dK);
       HIPCHK(hipGetLastError());
@@ -143,10 +134,7 @@ static int32_t open_on_device(const char* text, const uint64_t* offsets, const u
       open_flags.resize(m);
       HIPCHK(hipMemcpyAsync(open_flags.data(), b + o_open, m, hipMemcpyDeviceToHost, s));
       if (o.seeds) HIPCHK(hipMemcpyAsync(o.seeds + at * 32, b + o_seed, m * 32, hipMemcpyDeviceToHost, s));
-      if (o.sk) HIPCHK(hipMemcpyAsync(o.sk + at * 32, b + o_sk, m * 32, hipMemcpyDeviceToHost, s));
-      if (o.view) HIPCHK(hipMemcpyAsync(o.view + at * 32, b + o_view, m * 32, hipMemcpyDeviceToHost, s));
-      if (o.addr) HIPCHK(hipMemcpyAsync(o.addr + at * 32, b + o_addr, m * 32, hipMemcpyDeviceToHost, s));
-      if (o.str) HIPCHK(hipMemcpyAsync(o.str + at * ACC_ADDRESS_CHARS, b + o_str, m * ACC_ADDRESS_CHARS, hipMemcpyDeviceToHost, s));
+      if (int32_t rc = o.acc.download(s, b, head.acc, at, m)) return rc;
       if (accounts) { derive_flags.resize(m); HIPCHK(hipMemcpyAsync(derive_flags.data(), b + o_fl, m, hipMemcpyDeviceToHost, s)); }
       HIPCHK(hipStreamSynchronize(s));                           // the next chunk reuses the buffer and the staging vectors
       for (size_t i = 0; i < m; ++i) {
@@ -164,7 +152,7 @@ static int32_t private_keys_open(const char* text, const uint64_t* offsets, cons
   if (!n) return ALEO_MI355X_OK;
   if (int32_t rc = strings_args_ok("private_keys_open", text, offsets, n)) return rc;
   if (int32_t rc = strings_args_ok("private_keys_open", (const char*)secrets, secret_offsets, n)) return rc;
-  const OpenOut o{(uint8_t*)seeds32, (uint8_t*)sk_sig32, (uint8_t*)view_key32, (uint8_t*)address_x32, address63, flags};
+  const OpenOut o{(uint8_t*)seeds32, AccOut{(uint8_t*)sk_sig32, (uint8_t*)view_key32, (uint8_t*)address_x32, address63}, flags};
   if (may_route && n >= aleo_mi355x_min_key_ciphertexts()) return open_on_device(text, offsets, (const uint8_t*)secrets, secret_offsets, n, o);
   return open_on_host(text, offsets, (const uint8_t*)secrets, secret_offsets, n, o);
 }
@@ -199,9 +187,7 @@ int32_t aleo_mi355x_private_key_encrypt(char* out, size_t cap, const char* priva
     if (serial::private_key_seed_or_why(seed, private_key)) return bad_arg("private_key_encrypt: not an Aleo private key");
     uint64_t nonce[4]; std::memcpy(nonce, nonce32, 32);
     if (host::HFr::geq_p(nonce)) return bad_arg("private_key_encrypt: the nonce is not a canonical field element");
-    const std::string s = kct::encrypt_host(seed, (const uint8_t*)secret, secret_len, (const uint8_t*)nonce32);
-    std::memcpy(out, s.c_str(), s.size() + 1);
-    return (int32_t)ALEO_MI355X_OK;
+    return string_out(out, cap, kct::encrypt_host(seed, (const uint8_t*)secret, secret_len, (const uint8_t*)nonce32), "private_key_encrypt: output buffer too small");
   });
 }
 int32_t aleo_mi355x_private_key_decrypt(char* out, size_t cap, const char* ciphertext, const void* secret, size_t secret_len) {
@@ -211,10 +197,7 @@ int32_t aleo_mi355x_private_key_decrypt(char* out, size_t cap, const char* ciphe
     const uint8_t flag = kct::open_one_host(seed, ciphertext, std::strlen(ciphertext), (const uint8_t*)secret, secret_len);
     if (flag == KC_NO_CIPHERTEXT) return bad_arg("private_key_decrypt: not a private key ciphertext string");
     if (flag) { g_last_error = "private_key_decrypt: the ciphertext does not decrypt under this secret"; return (int32_t)ALEO_MI355X_ERR_NOT_OWNER; }
-    const std::string s = serial::private_key_string(seed);
-    if (s.size() + 1 > cap) return bad_arg("private_key_decrypt: output buffer too small");
-    std::memcpy(out, s.c_str(), s.size() + 1);
-    return (int32_t)ALEO_MI355X_OK;
+    return string_out(out, cap, serial::private_key_string(seed), "private_key_decrypt: output buffer too small");
   });
 }
 

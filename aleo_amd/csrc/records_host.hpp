@@ -1,7 +1,7 @@
 // records_host.hpp — the host side of the record ownership scan (records.hip): the constants of a scan, the builder of the word tables the lanes read
 // (WordTable: the scan's own, and those of the serial-number, commitment and signature lanes on top of it), the recoding of the scalar, and the whole test
 // on the CPU from host_field.hpp and poseidon.hpp.  Plain C++ (no HIP): records.hip builds the library's entry points on it, and
-// tests/cpp/records_lane_emul.cpp runs the device lane's code (records_lane.h) against it on the host.
+// tests/cpp/records_lane_emul.cpp runs the device lane's code (records_lane.h) against it on the host (tests/cpp/checked_f29.h includes it over the checked field).
 #pragma once
 #include "records_lane.h"
 #include "poseidon.hpp"

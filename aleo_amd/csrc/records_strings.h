@@ -54,9 +54,6 @@ struct StringSource {
   void parts(char* scratch, uint32_t** off, int8_t** kinds, char** text) const;
 };
 
-// records_strings.hip: what both paths of a call over strings refuse before they look at one
-int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offsets, size_t n);
-
 // records_many.hip
 int32_t many_keys(ManyKeys& k, const void* view_keys32, const void* address_xs32, size_t n_keys);
 // the records come as rows (owner_c0, nonce_x) or, when `strings` is given, from it; takes a slot for itself (entry.h on_slot)

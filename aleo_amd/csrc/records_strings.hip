@@ -23,17 +23,6 @@ static constexpr uint32_t PARSE_BLOCK = SPAN_BLOCK;
 static constexpr size_t PARSE_CHUNK_RECORDS = (size_t)1 << 20;
 static constexpr size_t STRINGS_CHUNK_CHARS = (size_t)256 << 20;
 
-// what both paths refuse before they look at a string
-int32_t strings_args_ok(const char* who, const char* text, const uint64_t* offsets, size_t n) {
-  if (!n) return ALEO_MI355X_OK;
-  if (!offsets) { g_last_error = std::string(who) + ": null buffer"; return ALEO_MI355X_ERR_BAD_ARG; }
-  if (offsets[0] != 0) { g_last_error = std::string(who) + ": offsets[0] is not 0"; return ALEO_MI355X_ERR_BAD_ARG; }
-  for (size_t i = 0; i < n; ++i)
-    if (offsets[i + 1] < offsets[i]) { g_last_error = std::string(who) + ": offsets decrease"; return ALEO_MI355X_ERR_BAD_ARG; }
-  if (offsets[n] && !text) { g_last_error = std::string(who) + ": null buffer"; return ALEO_MI355X_ERR_BAD_ARG; }
-  return ALEO_MI355X_OK;
-}
-
 // ---- the host path ----------------------------------------------------------------------------------------------------------------------------------
 static int32_t parse_one_host(uint8_t* owner32, uint8_t* nonce32, const char* text, const uint64_t* offsets, size_t i) {
   const uint64_t span = offsets[i + 1] - offsets[i];

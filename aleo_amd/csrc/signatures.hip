@@ -6,7 +6,7 @@
 // The kernel (one signature per lane: signature_lane.h), its table (signature_host.hpp: 139 KB with the scan's constants, built on the host at first use and
 // resident per device for the life of the process), the same flags on the host (signature_host.hpp verify_one_host — what small batches take, and the
 // definition), the routing threshold, and the host-only calls: signing one message and the string.  (Signing in batches, on the device: signatures_sign.hip.)
-#include "entry.h"
+#include "signatures.h"
 #include "records_bits.hpp"
 #include "signature_host.hpp"
 #include <cstdlib>
@@ -14,9 +14,7 @@
 namespace aleo_mi355x {
 
 // ---- the kernel -----------------------------------------------------------------------------------------------------------------------------------
-static constexpr uint32_t SIG_BLOCK = 64;                    // one wave: a lane holds its whole signature in registers, and small batches spread over the CUs
 static constexpr size_t SIG_CHUNK = (size_t)1 << 20;         // signatures per launch
-static constexpr size_t SIG_CHUNK_BYTES = (size_t)1 << 30;   // message bytes per launch
 
 // A chunk's arrays lie in one device buffer, at these byte offsets (each below 2^32: SIG_CHUNK signatures and SIG_CHUNK_BYTES of messages): one base pointer
 // and five words in scalar registers instead of five pointers.
@@ -45,13 +43,7 @@ static int32_t verify_on_device(uint8_t* flags, const uint8_t* sigs, const uint8
     if (int32_t rc = resident_table(c->device, ResidentTable::SIGNATURE, []() -> const std::vector<uint32_t>& { return sig::sig_tables().words; }, &dK)) return rc;
     hipStream_t s = c->stream;
     for (size_t lo = 0; lo < n;) {
-      off.assign(1, 0); text.clear();
-      size_t hi = lo;
-      for (; hi < n && hi - lo < cap && text.size() < SIG_CHUNK_BYTES; ++hi) {
-        const uint64_t len = offsets[hi + 1] - offsets[hi];
-        if (len <= SIG_MAX_BYTES) text.insert(text.end(), messages + offsets[hi], messages + offsets[hi + 1]);
-        off.push_back((uint32_t)text.size());
-      }
+      const size_t hi = cut_messages(text, off, messages, offsets, lo, n, cap, [&](size_t i) { return offsets[i + 1] - offsets[i] <= SIG_MAX_BYTES; });
       const size_t m = hi - lo, rows = address_stride ? m : 1;
       Carve cv;
       const size_t o_sig = cv.part(m * 128), o_addr = cv.part(rows * 32), o_text = cv.part(text.size()), o_off = cv.part((m + 1) * 4), o_fl = cv.part(m);
@@ -77,10 +69,7 @@ static int32_t signatures_verify(uint8_t* flags, const void* sigs128, const void
   if (!n) return ALEO_MI355X_OK;
   if (!flags || !sigs128 || !addresses_x32) return bad_arg("signatures_verify: null buffer");
   if (address_stride != 0 && address_stride != 32) return bad_arg("signatures_verify: the address stride is 0 (one address) or 32 (one per signature)");
-  if (!offsets) return bad_arg("signatures_verify: null buffer");
-  if (offsets[0] != 0) return bad_arg("signatures_verify: offsets[0] is not 0");
-  for (size_t i = 0; i < n; ++i) if (offsets[i + 1] < offsets[i]) return bad_arg("signatures_verify: offsets decrease");
-  if (offsets[n] && !messages) return bad_arg("signatures_verify: null buffer");
+  if (int32_t rc = strings_args_ok("signatures_verify", (const char*)messages, offsets, n)) return rc;
   const uint8_t* sg = (const uint8_t*)sigs128; const uint8_t* ad = (const uint8_t*)addresses_x32; const uint8_t* ms = (const uint8_t*)messages;
   if (may_route && n >= aleo_mi355x_min_signatures()) return verify_on_device(flags, sg, ad, address_stride, ms, offsets, n);
   for (size_t i = 0; i < n; ++i) flags[i] = sig::verify_one_host(sg + 128 * i, ad + address_stride * i, ms + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));

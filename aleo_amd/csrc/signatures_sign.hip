@@ -7,6 +7,7 @@
 // with the signature lane's words), the same bytes on the host (signature_host.hpp sign_with_nonce under nonce_of_seed — what small batches take, and the
 // definition), the check that no nonce seed comes twice, and the routing threshold.
 #include "accounts.h"
+#include "signatures.h"
 #include "records_bits.hpp"
 #include "signature_host.hpp"
 #include "signature_sign_lane.h"
@@ -15,9 +16,7 @@
 
 namespace aleo_mi355x {
 
-static constexpr uint32_t SIG_BLOCK = 64;                    // one wave, as k_signatures_verify: a lane holds its whole signature in registers
 static constexpr size_t SIGN_CHUNK = (size_t)1 << 20;        // signatures per launch
-static constexpr size_t SIG_CHUNK_BYTES = (size_t)1 << 30;   // message bytes per launch
 
 // ---- the signing kernels ---------------------------------------------------------------------------------------------------------------------------------
 // A signing chunk's arrays, as SigChunk: the flags (up: 0, or 3 where the host refuses the row; down: the same), the rows of 128 bytes, the key rows (sk_sig |
@@ -93,15 +92,10 @@ static int32_t sign_on_device(uint8_t* sigs, uint8_t* flags, const uint8_t* key_
   std::vector<uint32_t> off; std::vector<uint8_t> text;
   return on_slot([&](Ctx* c) -> int32_t {
     const uint32_t* dK;
-    if (int32_t rc = resident_table(c->device, ResidentTable::ACCOUNT, []() -> const std::vector<uint32_t>& { return acct::account_tables().words; }, &dK)) return rc;
+    if (int32_t rc = account_table(c->device, &dK)) return rc;
     hipStream_t s = c->stream;
     for (size_t lo = 0; lo < n;) {
-      off.assign(1, 0); text.clear();
-      size_t hi = lo;
-      for (; hi < n && hi - lo < cap && text.size() < SIG_CHUNK_BYTES; ++hi) {
-        if (!flags[hi]) text.insert(text.end(), messages + offsets[hi], messages + offsets[hi + 1]);
-        off.push_back((uint32_t)text.size());
-      }
+      const size_t hi = cut_messages(text, off, messages, offsets, lo, n, cap, [&](size_t i) { return !flags[i]; });
       const size_t m = hi - lo;
       Carve cv;
       const size_t o_sig = cv.part(m * 128), o_keys = cv.part(key_stride ? m * 128 : 128), o_kseed = cv.part(key_stride ? m * 32 : 0), o_seed = cv.part(m * 32);
@@ -136,9 +130,7 @@ static int32_t signatures_sign(void* sigs128, uint8_t* flags, const void* key_se
   if (!sigs128 || !flags || !key_seeds32 || !nonce_seeds32 || !offsets) return bad_arg("signatures_sign: null buffer");
   if (key_stride != 0 && key_stride != 32) return bad_arg("signatures_sign: the key stride is 0 (one key) or 32 (one per signature)");
   if (n > 0xfffffffeull) return bad_arg("signatures_sign: too many signatures for one call");
-  if (offsets[0] != 0) return bad_arg("signatures_sign: offsets[0] is not 0");
-  for (size_t i = 0; i < n; ++i) if (offsets[i + 1] < offsets[i]) return bad_arg("signatures_sign: offsets decrease");
-  if (offsets[n] && !messages) return bad_arg("signatures_sign: null buffer");
+  if (int32_t rc = strings_args_ok("signatures_sign", (const char*)messages, offsets, n)) return rc;
   uint8_t* out = (uint8_t*)sigs128; const uint8_t* ks = (const uint8_t*)key_seeds32; const uint8_t* ms = (const uint8_t*)messages; const uint8_t* ns = (const uint8_t*)nonce_seeds32;
   size_t a = 0, b = 0;
   if (equal_seed_rows(ns, n, &a, &b)) {

@@ -7,7 +7,7 @@ behind it; small batches and host=True run the host path on the calling thread, 
 from __future__ import annotations
 import ctypes, os
 import numpy as np
-from ._lib import lib, check
+from ._lib import lib, check, _p, _vp, _blob
 from .records import Account
 from .account import private_key_from_seed
 
@@ -15,8 +15,6 @@ OPENED, NOT_DECRYPTED, NO_CIPHERTEXT = 0, 1, 3
 CHARS = 174
 
 
-def _p(a): return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-def _vp(b: bytes): return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
 def _secret(s) -> bytes: return s.encode() if isinstance(s, str) else bytes(s)
 
 
@@ -44,13 +42,6 @@ def decrypt(ciphertext: str, secret) -> str:
     sec = _secret(secret); out = ctypes.create_string_buffer(64)
     check(lib().aleo_mi355x_private_key_decrypt(out, len(out), ciphertext.encode(), _vp(sec), len(sec)), 'private_key_decrypt')
     return out.value.decode()
-
-
-def _blob(items):
-    """(bytes, n + 1 offsets) of byte strings laid one after another."""
-    off = np.zeros(len(items) + 1, dtype=np.uint64)
-    if items: off[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64)
-    return b''.join(items), off
 
 
 def open_many(ciphertexts, secrets, strings: bool = False, host: bool = False):

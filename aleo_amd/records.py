@@ -20,15 +20,12 @@ aleo_mi355x_found_serial_numbers: csrc/records_serial.hip), with record_commitme
 from __future__ import annotations
 import ctypes, weakref
 import numpy as np
-from ._lib import lib, check, AleoMi355xError, NotOwner      # noqa: F401
+from ._lib import lib, check, _p, AleoMi355xError, NotOwner      # noqa: F401
 from . import wire
 
 _B58 = '123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz'
 _VIEW_KEY_PREFIX = bytes([14, 138, 223, 204, 247, 224, 122])      # "AViewKey1"
 OWNER_PUBLIC, OWNER_PRIVATE = 0, 1
-
-
-def _p(a): return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def view_key_bytes(view_key) -> bytes:

@@ -7,14 +7,13 @@ A signature is 128 bytes, challenge | response | pk_sig.x | pr_sig.x, and a "sig
 from __future__ import annotations
 import ctypes, os
 import numpy as np
-from ._lib import lib, check
+from ._lib import lib, check, _p, _blob
 from .records import address_x_bytes
 
 VERIFIES, DOES_NOT_VERIFY, NOT_A_SIGNATURE = 0, 1, 3
 MAX_MESSAGE_BYTES = 131071                                       # 4161 fields of 252 bits
 
 
-def _p(a): return a.ctypes.data_as(ctypes.c_void_p)
 def _message(m) -> bytes: return m.encode() if isinstance(m, str) else bytes(m)
 
 
@@ -78,8 +77,7 @@ def sign_many(private_keys, messages, seeds=None, host: bool = False):
     if seeds is None: seeds = os.urandom(32 * n)
     sd = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1) if isinstance(seeds, np.ndarray) else np.frombuffer(bytes(seeds), dtype=np.uint8)
     if sd.size != 32 * n: raise ValueError('one seed of 32 bytes per message')
-    offsets = np.zeros(n + 1, dtype=np.uint64); offsets[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
-    text = b''.join(msgs); rows = np.zeros((n, 128), dtype=np.uint8); flags = np.zeros(n, dtype=np.uint8)
+    text, offsets = _blob(msgs); rows = np.zeros((n, 128), dtype=np.uint8); flags = np.zeros(n, dtype=np.uint8)
     L = lib(); call = L.aleo_mi355x_signatures_sign_host if host else L.aleo_mi355x_signatures_sign
     check(call(_p(rows), _p(flags), _p(keys), stride, ctypes.cast(ctypes.c_char_p(text), ctypes.c_void_p), _p(offsets), _p(sd), n), 'signatures_sign')
     return rows, flags
@@ -102,8 +100,7 @@ def verify_many(signatures, addresses, messages, host: bool = False) -> np.ndarr
     stride = 32 if addr.shape[0] == n and n != 1 else 0
     msgs = [_message(m) for m in messages]
     if len(msgs) != n: raise ValueError('one message per signature')
-    offsets = np.zeros(n + 1, dtype=np.uint64); offsets[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
-    text = b''.join(msgs); flags = np.zeros(n, dtype=np.uint8)
+    text, offsets = _blob(msgs); flags = np.zeros(n, dtype=np.uint8)
     L = lib(); call = L.aleo_mi355x_signatures_verify_host if host else L.aleo_mi355x_signatures_verify
     check(call(_p(flags), _p(sigs), _p(addr), stride, ctypes.cast(ctypes.c_char_p(text), ctypes.c_void_p), _p(offsets), n), 'signatures_verify')
     return flags

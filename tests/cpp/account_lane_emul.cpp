@@ -3,28 +3,22 @@
 // library builds it.  A search candidate is given as (master seed, index): the lane's own draw of its seed (account_candidate_seed) is checked against the seed the
 // test computed, and the head of its address's symbol stream (what the search kernel compares with the prefix) against the address's first bytes.
 //
-// The checked 29-bit-limb field is the one of records_lane_emul.cpp, taken as it stands (that file is included with its main renamed): every operand rule of
+// The checked 29-bit-limb field is the one of checked_f29.h: every operand rule of
 // fr29.h is a check there, so a bound the lane breaks shows as a count.  The lane must never put a character outside its row of 63.  Plain C++ for the host
 // compiler, built once plain and once with the address and undefined-behaviour sanitizers and run as a program of its own (tests/test_accounts.py):
 //   g++ -std=c++17 -O2 -fno-strict-aliasing -mbmi2 -madx [-fsanitize=address,undefined] -I aleo_amd/csrc tests/cpp/account_lane_emul.cpp
 //   account_lane_emul <case file>
 // The file: u32 count, then per account: u8 kind (0 a seed, 1 a candidate), [kind 1: the 32 bytes of the master seed, u64 index], the 32 bytes of the seed, u8 the
 // flag wanted, 32 bytes each of sk_sig, view key and address x, the 63 characters of the address (zeros with flag 3).
-#define __host__
-#define main records_lane_emul_main
-#include "records_lane_emul.cpp"
-#undef main
+#include "checked_f29.h"
 #include "account_host.hpp"
 #include <vector>
 
-static bool get(std::FILE* f, void* p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
 
 int main(int argc, char** argv) {
-  if (argc != 2) { std::fprintf(stderr, "usage: %s <case file>\n", argv[0]); return 2; }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) { std::perror(argv[1]); return 2; }
   uint32_t count = 0;
-  if (!get(f, &count, 4)) return 2;
+  std::FILE* f = open_cases(argc, argv, &count);
+  if (!f) return 2;
   const acct::AccountTables& T = acct::account_tables();
   unsigned long flags[4] = {0, 0, 0, 0}, bad = 0, past = 0, candidates = 0;
   for (uint32_t i = 0; i < count; ++i) {

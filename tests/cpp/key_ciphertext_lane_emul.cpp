@@ -2,7 +2,7 @@
 // returned (aleo_mi355x_private_keys_open_host) and against key_ciphertext_host.hpp's open_one_host compiled into this program, with the table built by
 // key_ciphertext_host.hpp as the library builds it and the secret handed over as the kernel gets it (kct::device_secret: a long one reduced by the host).
 //
-// The checked 29-bit-limb field is the one of records_lane_emul.cpp, taken as it stands (that file is included with its main renamed): every operand rule of
+// The checked 29-bit-limb field is the one of checked_f29.h: every operand rule of
 // fr29.h is a check there, so a bound the lane breaks shows as a count.  Every character and every secret byte the lane asks for is checked against the length
 // of what it was given, and both are held in buffers of exactly that length.  Plain C++ for the host compiler, built once plain and once with the address and
 // undefined-behaviour sanitizers and run as a program of its own (tests/test_key_ciphertexts.py):
@@ -10,21 +10,15 @@
 //   key_ciphertext_lane_emul <case file>
 // The file: u32 count, then per pair: u32 length and the characters of the string, u32 length and the bytes of the secret, u8 the flag wanted, the 32 bytes of
 // the seed wanted (zeros with a flag).
-#define __host__
-#define main records_lane_emul_main
-#include "records_lane_emul.cpp"
-#undef main
+#include "checked_f29.h"
 #include "key_ciphertext_host.hpp"
 #include <vector>
 
-static bool get(std::FILE* f, void* p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
 
 int main(int argc, char** argv) {
-  if (argc != 2) { std::fprintf(stderr, "usage: %s <case file>\n", argv[0]); return 2; }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) { std::perror(argv[1]); return 2; }
   uint32_t count = 0;
-  if (!get(f, &count, 4)) return 2;
+  std::FILE* f = open_cases(argc, argv, &count);
+  if (!f) return 2;
   const kct::KeyCiphertextTables& T = kct::key_ciphertext_tables();
   unsigned long flags[4] = {0, 0, 0, 0}, bad = 0, past = 0;
   for (uint32_t i = 0; i < count; ++i) {

@@ -2,7 +2,7 @@
 // (aleo_mi355x_records_commitments_found_host: records_bits.hpp's record_bits and serial_host.hpp's BHP1024, the code of aleo_mi355x_record_commitment), with the
 // table and the call's starting point built by commit_host.hpp as the library builds them.
 //
-// The checked 29-bit-limb field is the one of records_lane_emul.cpp, taken as it stands (that file is included with its main renamed): every operand rule of
+// The checked 29-bit-limb field is the one of checked_f29.h: every operand rule of
 // fr29.h is a check there, so a bound the lane breaks in its table additions or where an iteration's digest is fed back shows as a count.  A lane must never ask
 // for a character past its string's end or for a field past its record's.  Plain C++ for the host compiler, built once plain and once with the address and
 // undefined-behaviour sanitizers and run as a program of its own (tests/test_records_commit.py):
@@ -10,21 +10,16 @@
 //   records_commit_lane_emul <case file>
 // The file: u32 length and bytes of the program id, the same of the record name, u32 count, then per record: u32 length and the characters, i32 owner variant,
 // u32 number of plain fields and their 32 bytes each, u8 the flag wanted (0 computed, 4 refused, 8 routed to the host: the lane must say so) and the 32-byte row.
-#define __host__
-#define main records_lane_emul_main
-#include "records_lane_emul.cpp"
-#undef main
+#include "checked_f29.h"
 #include "commit_host.hpp"
 #include <string>
 #include <vector>
 
-static bool get(std::FILE* f, void* p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
 static bool get_string(std::FILE* f, std::string& s) { uint32_t n; if (!get(f, &n, 4) || n > (1u << 22)) return false; s.assign(n, 0); return get(f, &s[0], n); }
 
 int main(int argc, char** argv) {
-  if (argc != 2) { std::fprintf(stderr, "usage: %s <case file>\n", argv[0]); return 2; }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) { std::perror(argv[1]); return 2; }
+  std::FILE* f = open_cases(argc, argv);
+  if (!f) return 2;
   std::string program_id, record_name;
   uint32_t count = 0;
   if (!get_string(f, program_id) || !get_string(f, record_name) || !get(f, &count, 4)) return 2;

@@ -1,12 +1,10 @@
 // The record decryption's device lane (aleo_amd/csrc/records_decrypt_lane.h) run on the HOST, against what the library's host path computes:
 // plain_i = c_i - hash_many_psd8([encryption domain, rvk], m)_i through host::poseidon_hash_many_fr<8> (poseidon.hpp).
 //
-// The checked 29-bit-limb field is the one of records_lane_emul.cpp, taken as it stands (that file is included with its main renamed): every operand rule of
+// The checked 29-bit-limb field is the one of checked_f29.h: every operand rule of
 // fr29.h is a check there, so a bound the lane breaks — the state it carries from one permutation into the next, the subtrahend of the last step — shows as a count.
 //   hipcc -x c++ -std=c++17 -O2 -mbmi2 -madx -I aleo_amd/csrc tests/cpp/records_decrypt_lane_emul.cpp   (tests/test_records_decrypt.py builds and runs it).
-#define main records_lane_emul_main
-#include "records_lane_emul.cpp"
-#undef main
+#include "checked_f29.h"
 #include "records_decrypt_lane.h"
 #include <vector>
 

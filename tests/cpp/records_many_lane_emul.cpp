@@ -1,11 +1,9 @@
 // The grouped record scan's device lane (aleo_amd/csrc/records_many_lane.h) run on the HOST, against the library's host path key by key.
 //
-// The checked 29-bit-limb field is the one of records_lane_emul.cpp, taken as it stands (that file is included with its main renamed): every operand rule of
+// The checked 29-bit-limb field is the one of checked_f29.h: every operand rule of
 // fr29.h is a check there, so a bound the grouped lane breaks — its accumulators start at the neutral point, its inversion multiplies W denominators — shows as a count.
 //   hipcc -x c++ -std=c++17 -O2 -mbmi2 -madx -I aleo_amd/csrc tests/cpp/records_many_lane_emul.cpp   (tests/test_records_many.py builds and runs it).
-#define main records_lane_emul_main
-#include "records_lane_emul.cpp"
-#undef main
+#include "checked_f29.h"
 #include "records_many_lane.h"
 
 static unsigned long g_bad = 0, g_owned = 0, g_malformed = 0, g_pairs = 0;

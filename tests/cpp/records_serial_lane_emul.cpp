@@ -1,15 +1,13 @@
 // The serial-number kernel's device lane (aleo_amd/csrc/records_serial_lane.h) run on the HOST, against the library's host path (serial_host.hpp), and that
 // path against the same computation written from the definitions without the tables (serial_one_plain).
 //
-// The checked 29-bit-limb field is the one of records_lane_emul.cpp, taken as it stands (that file is included with its main renamed): every operand rule of
+// The checked 29-bit-limb field is the one of checked_f29.h: every operand rule of
 // fr29.h is a check there, so a bound the lane breaks — in the width-3 permutation, Elligator2's sums and differences, the table additions — shows as a count.
 // Plain C++ for the host compiler, built with the address and undefined-behaviour sanitizers and run as a program of its own (tests/test_records_serial.py):
 //   g++ -std=c++17 -O2 -mbmi2 -madx -fsanitize=address,undefined -I aleo_amd/csrc tests/cpp/records_serial_lane_emul.cpp
 // argv[1] (optional): a file of 32-byte commitments to use instead of the built-in ones; argv[2]: where to write the host path's rows for the first key (flag byte
 // and 32 bytes each), so that the test compares them with what the library's C ABI returns for the same commitments.
-#define main records_lane_emul_main
-#include "records_lane_emul.cpp"
-#undef main
+#include "checked_f29.h"
 #include "serial_host.hpp"
 #include <vector>
 

@@ -3,27 +3,21 @@
 // as the library builds it.  The lane picks the point of an x-coordinate with one exponentiation where the host path multiplies by the group order: every case
 // that reaches a point checks the one against the other.
 //
-// The checked 29-bit-limb field is the one of records_lane_emul.cpp, taken as it stands (that file is included with its main renamed): every operand rule of
+// The checked 29-bit-limb field is the one of checked_f29.h: every operand rule of
 // fr29.h is a check there, so a bound the lane breaks shows as a count.  A lane must never ask for a byte past its message's end.  Plain C++ for the host
 // compiler, built once plain and once with the address and undefined-behaviour sanitizers and run as a program of its own (tests/test_signatures.py):
 //   g++ -std=c++17 -O2 -fno-strict-aliasing -mbmi2 -madx [-fsanitize=address,undefined] -I aleo_amd/csrc tests/cpp/signature_lane_emul.cpp
 //   signature_lane_emul <case file>
 // The file: u32 count, then per signature: its 128 bytes, the 32 bytes of the address x, u32 length and the bytes of the message, u8 the flag wanted.
-#define __host__
-#define main records_lane_emul_main
-#include "records_lane_emul.cpp"
-#undef main
+#include "checked_f29.h"
 #include "signature_host.hpp"
 #include <vector>
 
-static bool get(std::FILE* f, void* p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
 
 int main(int argc, char** argv) {
-  if (argc != 2) { std::fprintf(stderr, "usage: %s <case file>\n", argv[0]); return 2; }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) { std::perror(argv[1]); return 2; }
   uint32_t count = 0;
-  if (!get(f, &count, 4)) return 2;
+  std::FILE* f = open_cases(argc, argv, &count);
+  if (!f) return 2;
   const sig::SigTables& T = sig::sig_tables();
   unsigned long flags[4] = {0, 0, 0, 0}, bad = 0, past = 0, permutations = 0;
   for (uint32_t i = 0; i < count; ++i) {

@@ -4,7 +4,7 @@
 // library's host path returned (aleo_mi355x_signatures_sign_host) and against signature_host.hpp's sign_with_nonce compiled into this program, with the table
 // built by account_host.hpp as the library builds it.
 //
-// The checked 29-bit-limb field is the one of records_lane_emul.cpp, taken as it stands (that file is included with its main renamed): every operand rule of
+// The checked 29-bit-limb field is the one of checked_f29.h: every operand rule of
 // fr29.h is a check there, so a bound a lane breaks shows as a count.  A lane must never ask for a byte past its message's end, and stores each part of its row
 // once.  Plain C++ for the host compiler, built once plain and once with the address and undefined-behaviour sanitizers and run as a program of its own
 // (tests/test_signatures_sign.py):
@@ -12,20 +12,15 @@
 //   signature_sign_lane_emul <case file>
 // The file: u32 count, then per product: 32 bytes each of k, c, s and of k - c s mod l; u32 count, then per signature: the 32 bytes of the key's seed, the 32 of the
 // nonce seed, u32 length and the bytes of the message, u8 the flag wanted, the 128 bytes wanted.
-#define __host__
-#define main records_lane_emul_main
-#include "records_lane_emul.cpp"
-#undef main
+#include "checked_f29.h"
 #include "account_host.hpp"
 #include "signature_sign_lane.h"
 #include <vector>
 
-static bool get(std::FILE* f, void* p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
 
 int main(int argc, char** argv) {
-  if (argc != 2) { std::fprintf(stderr, "usage: %s <case file>\n", argv[0]); return 2; }
-  std::FILE* f = std::fopen(argv[1], "rb");
-  if (!f) { std::perror(argv[1]); return 2; }
+  std::FILE* f = open_cases(argc, argv);
+  if (!f) return 2;
   unsigned long bad = 0, past = 0, flags[4] = {0, 0, 0, 0};
   uint32_t products = 0, count = 0;
   if (!get(f, &products, 4)) return 2;

@@ -6,7 +6,7 @@ restatement in Python integers (tests/serial_ref.py, pinned stage by stage), at 
 restatement built here from oracle.varuna_ref.random_fr, that derivation and a bech32 symbol split; the strings; the threshold; the code object.  The host path,
 byte for byte, checks the device lane: emulated on the CPU, plain and under the sanitizers, here, and on the GPU in the second half (ALEO_MI355X_MIN_ACCOUNTS=0).
 No test reads the reference tree."""
-import ctypes, functools, json, os, random, struct, subprocess, sys, threading
+import ctypes, functools, json, os, random, struct, subprocess, sys
 import numpy as np
 import pytest
 import aleo_amd
@@ -14,14 +14,11 @@ from aleo_amd import account as acct, records, wire
 from oracle import poseidon as ps
 from oracle import varuna_ref as V
 import serial_ref as S
+import batch_support as bs
+from batch_support import HERE, ROOT, HIPCC, le32, num, _p, _vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, 'aleo_amd', 'csrc')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ACC = json.load(open(os.path.join(HERE, 'golden', 'reference_account.json')))['accounts']
 SEED = json.load(open(os.path.join(HERE, 'golden', 'reference_seed.json')))
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']      # host code only: a program of its own, never a GPU build
 R, L = ps.R, ps.ED_SUBGROUP_ORDER
 CHARSET = 'qpzry9x8gf2tvdw0s3jn54khce6mua7l'
 MASTER = bytes((7 * i + 3) & 0xff for i in range(32))
@@ -29,15 +26,7 @@ FAR = (1 << 32) - 100                                                           
 RANGES = {0: 256, FAR: 200}                                                          # first -> count
 
 
-def le32(v: int) -> bytes: return v.to_bytes(32, 'little')
-def num(b: bytes) -> int: return int.from_bytes(b, 'little')
-
-
 # ---- through the C ABI ----------------------------------------------------------------------------------------------------------------------------------
-def _vp(b: bytes): return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
-def _p(a): return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-
-
 def derive_raw(seeds, host=True, want=('sk', 'vk', 'ax', 'str', 'flags')):
     """aleo_mi355x_accounts_derive[_host] on raw seeds: (status, {name: bytes}); the outputs not in `want` are passed as NULL."""
     n = len(seeds)
@@ -201,13 +190,12 @@ def lane_rows():
 def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path, sanitized):
     """tests/cpp/account_lane_emul.cpp: account_lane.h compiled for the CPU over the checked restatement of fr29.h, once plain and once with the address and
     undefined-behaviour sanitizers compiled into that program, run as a program of its own.  (-fno-strict-aliasing: as for signature_lane_emul.)"""
-    exe, data = os.path.join(str(tmp_path), 'account_lane_emul'), os.path.join(str(tmp_path), 'cases.bin')
-    subprocess.check_call(['g++', '-std=c++17', '-O1' if sanitized else '-O2', '-fno-strict-aliasing', '-mbmi2', '-madx'] + (SANITIZE if sanitized else []) + ['-I', CSRC, os.path.join(HERE, 'cpp', 'account_lane_emul.cpp'), '-o', exe])
+    data = os.path.join(str(tmp_path), 'cases.bin')
     rows = lane_rows()
     with open(data, 'wb') as f:
         f.write(struct.pack('<I', len(rows)))
         for kind, head, s, want in rows: f.write(bytes([kind]) + head + s + want)
-    r = subprocess.run([exe, data], capture_output=True, text=True, timeout=900)
+    r = bs.run_lane_emul(tmp_path, 'account_lane_emul', [data], sanitized=sanitized)
     print(r.stdout)
     assert r.returncode == 0 and '%d accounts' % len(rows) in r.stdout and '%d of them candidates' % sum(RANGES.values()) in r.stdout, r.stdout + r.stderr
     assert ' 0 mismatches, 0 reads past an end, 0 limb-rule violations' in r.stdout, r.stdout + r.stderr
@@ -293,11 +281,7 @@ DEFAULT_MIN_ACCOUNTS = 16
 
 
 def test_routing_threshold_and_its_environment_override():
-    code = 'import aleo_amd; print(int(aleo_amd.lib().aleo_mi355x_min_accounts()))'
-    def run(extra):
-        env = dict(os.environ, PYTHONPATH=ROOT); env.pop('ALEO_MI355X_MIN_ACCOUNTS', None); env.update(extra)
-        return int(subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, check=True).stdout)
-    assert run({}) == DEFAULT_MIN_ACCOUNTS and run({'ALEO_MI355X_MIN_ACCOUNTS': '5'}) == 5 and run({'ALEO_MI355X_MIN_ACCOUNTS': 'x'}) == DEFAULT_MIN_ACCOUNTS
+    assert bs.threshold_reads('min_accounts', 'ALEO_MI355X_MIN_ACCOUNTS') == (DEFAULT_MIN_ACCOUNTS, 5, DEFAULT_MIN_ACCOUNTS)
     # below the threshold the calls compute on the host: no device is needed for them
     env = dict(os.environ, PYTHONPATH=ROOT, ALEO_MI355X_MIN_ACCOUNTS='1000000', HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES='')
     code = ('from aleo_amd import account as a; k = %r; print(a.accounts_from_private_keys([k, k])[1].address, a.search(bytes(32), "", 5, 9, max_hits=2)[1])' % ACC[0]['private_key'])
@@ -306,20 +290,13 @@ def test_routing_threshold_and_its_environment_override():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_account_kernels_code_object_is_gfx950_and_has_no_scratch_and_no_spills():
-    import code_object as co
-    asm, blocks = co.compile_unit('accounts')
-    assert len(blocks) == 2                                                                      # these two and no other
-    for kernel in ('k_accounts_derive', 'k_accounts_search'):
-        b = co.block_of(blocks, kernel)
-        print(co.registers(kernel, b))
-        assert co.field(b, 'private_segment_fixed_size') == 0 and co.field(b, 'vgpr_spill_count') == 0 and co.field(b, 'sgpr_spill_count') == 0, kernel
+    kernels = ('k_accounts_derive', 'k_accounts_search')
+    assert bs.scratch_and_spills('accounts', kernels) == (2, {k: (0, 0, 0) for k in kernels})      # these two and no other
 
 
 def run_cpp_mirror(tmp_path, env, n):
     """tests/cpp/accounts_test.cpp: derive_accounts, accounts_from_private_keys, account_from_seed, search_accounts and the strings of include/aleo_mi355x.hpp."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'accounts_test')
-    r = subprocess.run([exe, ACC[0]['private_key'], ACC[0]['address'], str(n)], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'accounts_test', [ACC[0]['private_key'], ACC[0]['address'], n], env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 
@@ -392,13 +369,7 @@ def test_gpu_search_equals_the_host_search(on_kernel, first, chunk):
 def test_gpu_two_threads_at_once_get_the_host_path_s_bytes(on_kernel):
     seeds = mixed_seeds(130, seed=8)
     want = [derive_raw(seeds, host=True), search_raw(FAR, 300, 'q', 4, host=True)]
-    got = [None, None]
-    def work(i):
-        for _ in range(3): got[i] = derive_raw(seeds, host=False) if i == 0 else search_raw(FAR, 300, 'q', 4, host=False)
-    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
-    for t in threads: t.start()
-    for t in threads: t.join()
-    assert got == want
+    assert bs.two_threads(lambda i: derive_raw(seeds, host=False) if i == 0 else search_raw(FAR, 300, 'q', 4, host=False)) == want
 
 
 @pytest.mark.gpu

@@ -6,7 +6,7 @@ ciphertext — encrypted byte for byte.  Then encryption against the restatement
 decryption, at the edges of the secret's length, of the seed and of the nonce; the batched opening on the host path over one batch that holds every case; the
 threshold; the code object.  The host path, byte for byte, checks the device lane: emulated on the CPU, plain and under the sanitizers, here, and on the GPU in the
 second half (ALEO_MI355X_MIN_KEY_CIPHERTEXTS=0).  No test reads the reference tree."""
-import ctypes, functools, json, os, random, struct, subprocess, sys, threading
+import ctypes, functools, json, os, random, struct, subprocess, sys
 import numpy as np
 import pytest
 import aleo_amd
@@ -14,31 +14,22 @@ from aleo_amd import account as acct, key_ciphertext as kc, records
 from oracle import poseidon as ps
 from oracle import pyref as P
 import key_ciphertext_ref as ref
+import batch_support as bs
+from batch_support import HERE, ROOT, HIPCC, le32, num, _p, _vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, 'aleo_amd', 'csrc')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 GOLD = json.load(open(os.path.join(HERE, 'golden', 'reference_account.json')))
 ACC, KAT = GOLD['accounts'], GOLD['ciphertext_kat']
 RECORD = json.load(open(os.path.join(HERE, 'golden', 'reference_records.json')))['records']['owner']
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']      # host code only: a program of its own, never a GPU build
 R = ps.R
 SECRET_LENGTHS = (0, 1, 31, 32, 33, 62, 63, 100)
 OUTPUTS = ('seeds', 'sk', 'vk', 'ax', 'str', 'flags')
 NULL_SUBSETS = (('vk', 'ax', 'flags'), ('str',), ('sk', 'flags'), (), ('seeds',), ('seeds', 'flags'), ('flags',))      # test_accounts' subsets, and the seeds alone
 
 
-def le32(v: int) -> bytes: return v.to_bytes(32, 'little')
-def num(b: bytes) -> int: return int.from_bytes(b, 'little')
 def raw(s) -> bytes: return s.encode() if isinstance(s, str) else bytes(s)
 
 
 # ---- through the C ABI ----------------------------------------------------------------------------------------------------------------------------------
-def _vp(b: bytes): return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
-def _p(a): return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-
-
 def blob(items):
     off = np.zeros(len(items) + 1, np.uint64)
     if items: off[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64)
@@ -286,15 +277,14 @@ def test_open_accepts_no_pair_and_refuses_bad_arguments():
 def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path, sanitized):
     """tests/cpp/key_ciphertext_lane_emul.cpp: key_ciphertext_lane.h compiled for the CPU over the checked restatement of fr29.h, once plain and once with the
     address and undefined-behaviour sanitizers compiled into that program, run as a program of its own.  (-fno-strict-aliasing: as for account_lane_emul.)"""
-    exe, data = os.path.join(str(tmp_path), 'key_ciphertext_lane_emul'), os.path.join(str(tmp_path), 'cases.bin')
-    subprocess.check_call(['g++', '-std=c++17', '-O1' if sanitized else '-O2', '-fno-strict-aliasing', '-mbmi2', '-madx'] + (SANITIZE if sanitized else []) + ['-I', CSRC, os.path.join(HERE, 'cpp', 'key_ciphertext_lane_emul.cpp'), '-o', exe])
+    data = os.path.join(str(tmp_path), 'cases.bin')
     pairs = [(c, s) for c, s, _, _ in edge_batch()] + list(mixed_pairs(65))
     rc, out = open_raw(pairs, want=('seeds', 'flags'))
     assert rc == 0
     with open(data, 'wb') as f:
         f.write(struct.pack('<I', len(pairs)))
         for i, (c, s) in enumerate(pairs): f.write(struct.pack('<I', len(raw(c))) + raw(c) + struct.pack('<I', len(s)) + s + out['flags'][i:i + 1] + out['seeds'][32 * i:32 * i + 32])
-    r = subprocess.run([exe, data], capture_output=True, text=True, timeout=900)
+    r = bs.run_lane_emul(tmp_path, 'key_ciphertext_lane_emul', [data], sanitized=sanitized)
     print(r.stdout)
     assert r.returncode == 0 and '%d pairs' % len(pairs) in r.stdout, r.stdout + r.stderr
     assert ' 0 mismatches, 0 reads past an end, 0 limb-rule violations' in r.stdout, r.stdout + r.stderr
@@ -306,11 +296,7 @@ DEFAULT_MIN_KEY_CIPHERTEXTS = 64
 
 
 def test_routing_threshold_and_its_environment_override():
-    code = 'import aleo_amd; print(int(aleo_amd.lib().aleo_mi355x_min_key_ciphertexts()))'
-    def run(extra):
-        env = dict(os.environ, PYTHONPATH=ROOT); env.pop('ALEO_MI355X_MIN_KEY_CIPHERTEXTS', None); env.update(extra)
-        return int(subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, check=True).stdout)
-    assert run({}) == DEFAULT_MIN_KEY_CIPHERTEXTS and run({'ALEO_MI355X_MIN_KEY_CIPHERTEXTS': '5'}) == 5 and run({'ALEO_MI355X_MIN_KEY_CIPHERTEXTS': 'x'}) == DEFAULT_MIN_KEY_CIPHERTEXTS
+    assert bs.threshold_reads('min_key_ciphertexts', 'ALEO_MI355X_MIN_KEY_CIPHERTEXTS') == (DEFAULT_MIN_KEY_CIPHERTEXTS, 5, DEFAULT_MIN_KEY_CIPHERTEXTS)
     # below the threshold the call computes on the host: no device is needed for it
     env = dict(os.environ, PYTHONPATH=ROOT, ALEO_MI355X_MIN_KEY_CIPHERTEXTS='1000000', HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES='')
     code = 'from aleo_amd import key_ciphertext as k; c = %r; print([a and a.private_key for a in k.accounts_from_ciphertexts([(c, "mypassword"), (c, "x")])])' % KAT['ciphertext']
@@ -320,20 +306,14 @@ def test_routing_threshold_and_its_environment_override():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_key_ciphertext_kernel_code_object_is_gfx950_and_has_no_scratch_and_no_spills():
     import code_object as co
-    asm, blocks = co.compile_unit('key_ciphertexts')
-    assert len(blocks) == 1                                                                      # this one and no other: the account kernel is accounts.hip's
-    b = co.block_of(blocks, 'k_key_ciphertexts_open')
-    print(co.registers('k_key_ciphertexts_open', b))
-    assert co.field(b, 'private_segment_fixed_size') == 0 and co.field(b, 'vgpr_spill_count') == 0 and co.field(b, 'sgpr_spill_count') == 0
+    assert bs.scratch_and_spills('key_ciphertexts', ['k_key_ciphertexts_open']) == (1, {'k_key_ciphertexts_open': (0, 0, 0)})      # this one and no other: the account kernel is accounts.hip's
     asm, blocks = co.compile_unit('accounts')
     assert len(blocks) == 2 and all(len([b for b in blocks if k in b]) == 1 for k in ('k_accounts_derive', 'k_accounts_search'))
 
 
 def run_cpp_mirror(tmp_path, env, n):
     """tests/cpp/key_ciphertexts_test.cpp: encrypt_private_key, decrypt_private_key, open_private_keys and the two PrivateAccount methods of include/aleo_mi355x.hpp."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'key_ciphertexts_test')
-    r = subprocess.run([exe, KAT['private_key'], KAT['secret'], KAT['ciphertext'], KAT['bad_ciphertext'], str(n)], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'key_ciphertexts_test', [KAT['private_key'], KAT['secret'], KAT['ciphertext'], KAT['bad_ciphertext'], n], env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 
@@ -400,13 +380,7 @@ def test_gpu_two_threads_at_once_get_the_host_path_s_bytes(on_kernel):
         L_ = aleo_amd.lib(); call = L_.aleo_mi355x_accounts_derive_host if host else L_.aleo_mi355x_accounts_derive
         return call(_vp(b''.join(seeds)), n, _p(out[0]), _p(out[1]), _p(out[2]), None, _p(flags)), [o.tobytes() for o in out], flags.tobytes()
     want = [open_raw(pairs, host=True), derive(True)]
-    got = [None, None]
-    def work(i):
-        for _ in range(3): got[i] = open_raw(pairs, host=False) if i == 0 else derive(False)
-    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
-    for t in threads: t.start()
-    for t in threads: t.join()
-    assert got == want
+    assert bs.two_threads(lambda i: open_raw(pairs, host=False) if i == 0 else derive(False)) == want
 
 
 @pytest.mark.gpu

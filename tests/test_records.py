@@ -7,19 +7,18 @@ tests/golden/gen_reference_records.py) and against the rule written out with ora
 
 and, for an on-curve x without a prime-order point, the same with k = the odd one of {view_key, view_key + l} on either root.
 The first half needs no GPU (parser, host path, threshold, the kernel's code object and its lane code emulated on the host); the second half runs the kernel."""
-import ctypes, json, os, random, re, subprocess, sys, tempfile, threading
+import ctypes, json, os, random, re, subprocess, sys, tempfile
 import numpy as np
 import pytest
 import aleo_amd
 from aleo_amd import records, wire
 from oracle import poseidon as ps, pyref as P
+import batch_support as bs
+from batch_support import ROOT, HIPCC, le32
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'reference_records.json')))
 R, L_ORDER = P.FR_MODULUS, ps.ED_SUBGROUP_ORDER
 ENC_DOMAIN = ps.domain_separator('AleoSymmetricEncryption0')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-CSRC = os.path.join(ROOT, 'aleo_amd', 'csrc')
 
 
 def account_generator():
@@ -27,7 +26,6 @@ def account_generator():
     return ps.ed_mul(ps.address_point(REF['addresses']['owner']), pow(ps.view_key_scalar(REF['view_keys']['owner']), -1, L_ORDER))
 
 
-def le32(v): return int(v).to_bytes(32, 'little')
 def rows(vals): return np.frombuffer(b''.join(le32(v) for v in vals), dtype=np.uint8).reshape(-1, 32).copy() if len(vals) else np.zeros((0, 32), dtype=np.uint8)
 def randomizer(rvk): return ps.hash_many_psd8([ENC_DOMAIN, rvk], 1)[0]
 
@@ -181,14 +179,8 @@ def test_host_path_equals_the_rule_written_with_the_oracle_on_256_synthetic_reco
 
 # ---- 5: the threshold -------------------------------------------------------------------------------------------------------------------------------
 def test_routing_threshold_and_its_environment_override():
-    code = 'import aleo_amd; print(int(aleo_amd.lib().aleo_mi355x_min_records()))'
-    def run(extra):
-        env = dict(os.environ, PYTHONPATH=ROOT); env.pop('ALEO_MI355X_MIN_RECORDS', None); env.update(extra)
-        return subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300).stdout.split()
-    default = run({})
-    assert len(default) == 1 and 1 <= int(default[0]) <= 1 << 22
-    assert run({'ALEO_MI355X_MIN_RECORDS': '65536'}) == ['65536'] and run({'ALEO_MI355X_MIN_RECORDS': '0'}) == ['0']
-    assert run({'ALEO_MI355X_MIN_RECORDS': 'nonsense'}) == default
+    default, large, zero, nonsense = bs.threshold_reads('min_records', 'ALEO_MI355X_MIN_RECORDS', ('65536', '0', 'nonsense'))
+    assert 1 <= default <= 1 << 22 and (large, zero, nonsense) == (65536, 0, default)
     # below the threshold the call computes on the host: no device is needed for it
     env = dict(os.environ, PYTHONPATH=ROOT, ALEO_MI355X_MIN_RECORDS='1000000', HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES='')
     code = ('import numpy as np, json; from aleo_amd import records; R = json.load(open(%r)); r = records.RecordCiphertext.from_string(R["records"]["owner"]); '
@@ -213,9 +205,7 @@ def test_scan_kernel_code_object_is_gfx950_and_has_no_scratch():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path):
     """tests/cpp/records_lane_emul.cpp: records_lane.h compiled for the CPU over a restatement of fr29.h that checks every limb bound."""
-    exe = os.path.join(str(tmp_path), 'records_lane_emul')
-    subprocess.check_call([HIPCC, '-x', 'c++', '-std=c++17', '-O2', '-mbmi2', '-madx', '-I', CSRC, os.path.join(ROOT, 'tests', 'cpp', 'records_lane_emul.cpp'), '-o', exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    r = bs.run_lane_emul(tmp_path, 'records_lane_emul', flags=(), hipcc=True)
     assert r.returncode == 0 and ' 0 mismatches, 0 limb-rule violations' in r.stdout, r.stdout + r.stderr
 
 
@@ -290,12 +280,7 @@ def test_kernel_small_behaviours(on_kernel):
     hf, hr = records.scan(C0, NX, vk, ax, host=True)
     assert flags.tobytes() == hf.tobytes() and rvk.tobytes() == hr.tobytes() and (flags == 1).any()
     # two threads, different batches and keys at once: each gets the bytes it gets alone
-    got = [None, None]
-    def work(i):
-        for _ in range(3): got[i] = records.scan(*sets[i][:4])
-    th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
-    for t in th: t.start()
-    for t in th: t.join()
+    got = bs.two_threads(lambda i: records.scan(*sets[i][:4]))
     for i in range(2): assert got[i][0].tobytes() == sets[i][4][0].tobytes() and got[i][1].tobytes() == sets[i][4][1].tobytes()
     # another view key on the same records right after: neither stale digits nor a stale state
     again = records.scan(C0, NX, sets[1][2], ax); want = records.scan(C0, NX, sets[1][2], ax, host=True)

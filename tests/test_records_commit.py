@@ -12,20 +12,17 @@ import aleo_amd
 from aleo_amd import records
 from oracle import poseidon as ps
 import serial_ref as S
-from test_records import ENC_DOMAIN, R, L_ORDER, le32
+from test_records import ENC_DOMAIN, R, L_ORDER
 from test_records_strings import encode, payload_of
 from test_records_decrypt import Built, TWO_LEVELS, account, string_of_fields, plaintext_bytes
 from test_records_found import private_entry
+import batch_support as bs
+from batch_support import HERE, ROOT, HIPCC, le32
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, 'aleo_amd', 'csrc')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ACC = json.load(open(os.path.join(HERE, 'golden', 'reference_account.json')))
 REC = json.load(open(os.path.join(HERE, 'golden', 'reference_records.json')))
 SER = json.load(open(os.path.join(HERE, 'golden', 'reference_serial.json')))
 TX, SN = SER['transaction_output'], SER['serial_number']
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']      # host code only: a program of its own, never a GPU build
 PER = 1044                                                                           # message bits per BHP1024 iteration
 # 8 (|program name| + 4 + |record name|) = 0, 2, 1 (mod 3): the stream behind the pre-summed names starts with 0, 2 and 1 bits in hand
 NAMES = [('credits.aleo', 'credits'), ('credit_s.aleo', 'credits'), ('credit_s.aleo', 'credit_s')]
@@ -198,8 +195,7 @@ def write_lane_cases(path, names):
 def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path, sanitized):
     """tests/cpp/records_commit_lane_emul.cpp: records_commit_lane.h compiled for the CPU over the checked restatement of fr29.h, a program of its own, once plain and
     once with the address and undefined-behaviour sanitizers, on every shape under the three name pairs; the rows it is held against are the library's host path's."""
-    exe = os.path.join(str(tmp_path), 'records_commit_lane_emul')
-    subprocess.check_call(['g++', '-std=c++17', '-O1' if sanitized else '-O2', '-mbmi2', '-madx'] + (SANITIZE if sanitized else []) + ['-I', CSRC, os.path.join(HERE, 'cpp', 'records_commit_lane_emul.cpp'), '-o', exe])
+    exe = bs.build_lane_emul(tmp_path, 'records_commit_lane_emul', sanitized=sanitized, flags=())
     for names in NAMES:
         path = os.path.join(str(tmp_path), 'cases.bin'); n, computed = write_lane_cases(path, names)
         r = subprocess.run([exe, path], capture_output=True, text=True, timeout=600)
@@ -257,33 +253,22 @@ def test_refusals_and_edges():
 
 
 def test_routing_threshold_and_its_environment_override():
-    code = 'import aleo_amd; print(int(aleo_amd.lib().aleo_mi355x_min_commitments()))'
-    def run(extra):
-        env = dict(os.environ, PYTHONPATH=ROOT); env.pop('ALEO_MI355X_MIN_COMMITMENTS', None); env.update(extra)
-        return int(subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, check=True).stdout)
-    assert run({}) == 32 and run({'ALEO_MI355X_MIN_COMMITMENTS': '5'}) == 5 and run({'ALEO_MI355X_MIN_COMMITMENTS': 'x'}) == 32
+    assert bs.threshold_reads('min_commitments', 'ALEO_MI355X_MIN_COMMITMENTS') == (32, 5, 32)
 
 
 # ---- 5: the code object -------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_commit_kernel_code_object_is_gfx950_and_has_no_scratch():
-    import code_object as co
-    asm, blocks = co.compile_unit('records_commit')
-    assert len(blocks) == 1 and 'k_records_commit' in blocks[0]                                  # this one and no other
-    print(co.registers('k_records_commit', blocks[0]))
-    assert co.field(blocks[0], 'private_segment_fixed_size') == 0 and co.field(blocks[0], 'vgpr_spill_count') == 0 and co.field(blocks[0], 'sgpr_spill_count') == 0
+    assert bs.scratch_and_spills('records_commit', ['k_records_commit']) == (1, {'k_records_commit': (0, 0, 0)})      # this one and no other
 
 
 # ---- 6: the C++ mirror ----------------------------------------------------------------------------------------------------------------------------------
 def run_cpp_mirror(tmp_path, env):
     """tests/cpp/records_commit_test.cpp: found_commitments, unspent_named and unspent_named_many of include/aleo_mi355x.hpp on the reference's record, 70 copies among foreign ones."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'records_commit_test')
     strings = [REC['records']['owner'], REC['records']['sdk_foreign']] * 70
     plain = S.record_decrypt_fields(REC['records']['owner'], ps.view_key_scalar(REC['view_keys']['owner']))
     cm = S.record_commitment(REC['records']['owner'], plain, SN['program_id'], SN['record_name'])
-    r = subprocess.run([exe, SN['private_key'], REC['view_keys']['owner'], REC['addresses']['owner'], SN['program_id'], SN['record_name'], le32(cm).hex(), le32(field(SN['expected'])).hex()] + strings,
-                       capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'records_commit_test', [SN['private_key'], REC['view_keys']['owner'], REC['addresses']['owner'], SN['program_id'], SN['record_name'], le32(cm).hex(), le32(field(SN['expected'])).hex()] + strings, env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 

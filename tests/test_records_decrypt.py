@@ -13,7 +13,9 @@ import pytest
 import aleo_amd
 from aleo_amd import records, wire
 from oracle import poseidon as ps, pyref as P
-from test_records import REF, R, L_ORDER, ENC_DOMAIN, HIPCC, CSRC, ROOT, account_generator, le32, rows
+import batch_support as bs
+from batch_support import ROOT, HIPCC, CSRC, le32
+from test_records import REF, R, L_ORDER, ENC_DOMAIN, account_generator, rows
 
 NOT_OWNER, BAD_ARG = 7, 2
 SUFFIX = {2: 'field', 3: 'group', 14: 'scalar', **{4 + i: 'i%d' % (8 << i) for i in range(5)}, **{9 + i: 'u%d' % (8 << i) for i in range(5)}}
@@ -304,10 +306,8 @@ def test_small_behaviours(monkeypatch):
 # ---- 4, 5: the lane's code on the host, and the kernel's code object ------------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path):
-    """tests/cpp/records_decrypt_lane_emul.cpp: records_decrypt_lane.h compiled for the CPU over the field of records_lane_emul.cpp, which checks every limb bound."""
-    exe = os.path.join(str(tmp_path), 'records_decrypt_lane_emul')
-    subprocess.check_call([HIPCC, '-x', 'c++', '-std=c++17', '-O2', '-mbmi2', '-madx', '-I', CSRC, os.path.join(ROOT, 'tests', 'cpp', 'records_decrypt_lane_emul.cpp'), '-o', exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    """tests/cpp/records_decrypt_lane_emul.cpp: records_decrypt_lane.h compiled for the CPU over the field of checked_f29.h, which checks every limb bound."""
+    r = bs.run_lane_emul(tmp_path, 'records_decrypt_lane_emul', flags=(), hipcc=True)
     assert r.returncode == 0 and ' 0 mismatches, 0 limb-rule violations' in r.stdout, r.stdout + r.stderr
 
 

@@ -10,7 +10,9 @@ import pytest
 import aleo_amd
 from aleo_amd import records, wire
 from oracle import poseidon as ps
-from test_records import REF, ROOT, R, L_ORDER, HIPCC, CSRC, le32, account_generator, synthetic_records
+import batch_support as bs
+from batch_support import ROOT, HIPCC, CSRC, le32
+from test_records import REF, R, L_ORDER, account_generator, synthetic_records
 from test_records_strings import MAX_CHARS, encode, payload_of, reference_sized
 from test_records_decrypt import Built, TWO_LEVELS, account, string_of_fields
 
@@ -249,10 +251,8 @@ def test_python_mirrors_on_the_host_path(on_host):
 
 def run_cpp_mirror(tmp_path, env):
     """tests/cpp/records_found_test.cpp: decrypt_strings and balance of include/aleo_mi355x.hpp on the reference's strings."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'records_found_test')
     strings = [REF['records']['owner'], REF['records']['sdk_foreign'], REF['records']['sdk']] * 25 + ['garbage']
-    r = subprocess.run([exe, REF['view_keys']['owner'], REF['addresses']['owner'], REF['plaintexts']['owner'], '1500000000000000'] + strings, capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'records_found_test', [REF['view_keys']['owner'], REF['addresses']['owner'], REF['plaintexts']['owner'], '1500000000000000'] + strings, env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 

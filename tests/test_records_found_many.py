@@ -10,7 +10,9 @@ import pytest
 import aleo_amd
 from aleo_amd import records, wire
 from oracle import poseidon as ps
-from test_records import REF, R, L_ORDER, le32, account_generator
+import batch_support as bs
+from batch_support import le32
+from test_records import REF, R, L_ORDER, account_generator
 from test_records_strings import encode, payload_of
 from test_records_decrypt import Built, account, string_of_fields
 from test_records_found import shuffled_cases, pools, pattern, same_found, differences, good_strings, off_curve_nonce, private_entry, on_host, on_kernel      # noqa: F401 (the last two: fixtures)
@@ -232,11 +234,9 @@ def test_python_mirrors_on_the_host_path(on_host):
 def run_cpp_mirror(tmp_path, env):
     """tests/cpp/records_found_many_test.cpp: decrypt_strings_many and balances of include/aleo_mi355x.hpp on the reference's strings, for the reference's two
     accounts and the first of them once more."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'records_found_many_test')
     strings = [REF['records']['owner'], REF['records']['sdk_foreign'], REF['records']['sdk']] * 25 + ['garbage']
     keys = [REF['view_keys']['owner'], REF['addresses']['owner'], REF['view_keys']['sdk'], REF['addresses']['sdk'], REF['view_keys']['owner'], REF['addresses']['owner']]
-    r = subprocess.run([exe, '3'] + keys + strings, capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'records_found_many_test', ['3'] + keys + strings, env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 

@@ -4,13 +4,15 @@ csrc/records_many.hip, records_many_lane.h).  The contract is one sentence — r
 alone — so every check below is an equality of bytes: against the host path, against K single scans of the kernel, and on a sample against the Python rule.
 The first half needs no GPU (host path, refusals, reference vectors, the lane emulated on the host, the code object, routing); the second half runs the kernels
 at every width: ALEO_MI355X_SCAN_KEYS_PER_LANE forces the keys one lane takes, unset leaves it to the library's rule."""
-import ctypes, json, os, random, re, subprocess, sys, tempfile, threading
+import ctypes, json, os, random, re, subprocess, sys, tempfile
 import numpy as np
 import pytest
 import aleo_amd
 from aleo_amd import records, wire
 from oracle import poseidon as ps
-from test_records import REF, ROOT, R, L_ORDER, HIPCC, CSRC, le32, rows, randomizer, account_generator, reference_cases, synthetic_records, big_batch, oracle_rule
+import batch_support as bs
+from batch_support import ROOT, HIPCC, CSRC, le32
+from test_records import REF, R, L_ORDER, rows, randomizer, account_generator, reference_cases, synthetic_records, big_batch, oracle_rule
 
 WIDTHS = (1, 2, 4, 8)
 REF_JSON = os.path.join(ROOT, 'tests', 'golden', 'reference_records.json')
@@ -91,10 +93,8 @@ def test_one_call_answers_every_is_owner_assertion_of_the_reference():
 # ---- 3: the lane on the host ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_grouped_lane_emulated_on_the_host_matches_the_host_path(tmp_path):
-    """tests/cpp/records_many_lane_emul.cpp: records_many_lane.h at W = 2, 4, 8 over the checked field of records_lane_emul.cpp, key by key against scan_one_host."""
-    exe = os.path.join(str(tmp_path), 'records_many_lane_emul')
-    subprocess.check_call([HIPCC, '-x', 'c++', '-std=c++17', '-O2', '-mbmi2', '-madx', '-I', CSRC, os.path.join(ROOT, 'tests', 'cpp', 'records_many_lane_emul.cpp'), '-o', exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    """tests/cpp/records_many_lane_emul.cpp: records_many_lane.h at W = 2, 4, 8 over the checked field of checked_f29.h, key by key against scan_one_host."""
+    r = bs.run_lane_emul(tmp_path, 'records_many_lane_emul', flags=(), hipcc=True)
     assert r.returncode == 0 and ' 0 mismatches, 0 limb-rule violations' in r.stdout, r.stdout + r.stderr
     pairs, owned, malformed = (int(re.search(r'(\d+) %s' % w, r.stdout).group(1)) for w in ('pairs', 'owned', 'malformed'))
     assert pairs >= 3 * 3 * 40 and owned and malformed
@@ -244,12 +244,7 @@ def test_nothing_stale_and_nothing_shared(on_kernel, nine_keys, small_set, base_
     sets = [(C0, NX, keys[:5], addrs[:5]), (B0, BX, keys[2:9], addrs[2:9])]
     alone = [records.scan_many(*s) for s in sets]
     assert same(alone[0], (hf[:5], hr[:5])) and same(alone[1], records.scan_many(*sets[1], host=True))
-    got = [None, None]
-    def work(i):
-        for _ in range(3): got[i] = records.scan_many(*sets[i])
-    th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
-    for t in th: t.start()
-    for t in th: t.join()
+    got = bs.two_threads(lambda i: records.scan_many(*sets[i]))
     for i in range(2): assert same(got[i], alone[i]), i
     # the grouped scan and the plain one in turn on one slot: neither leaves the other a stale table, state or result
     for _ in range(2):

@@ -12,21 +12,17 @@ import aleo_amd
 from aleo_amd import records
 from oracle import poseidon as ps, pyref as P
 import serial_ref as S
+import batch_support as bs
+from batch_support import HERE, ROOT, HIPCC, le32
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, 'aleo_amd', 'csrc')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ACC = json.load(open(os.path.join(HERE, 'golden', 'reference_account.json')))
 REC = json.load(open(os.path.join(HERE, 'golden', 'reference_records.json')))
 SER = json.load(open(os.path.join(HERE, 'golden', 'reference_serial.json')))
 R, L_ORDER = P.FR_MODULUS, ps.ED_SUBGROUP_ORDER
 TX, SN = SER['transaction_output'], SER['serial_number']
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']      # host code only: a program of its own, never a GPU build
 
 
 def field(s: str) -> int: assert s.endswith('field'); return int(s[:-5])
-def le32(v: int) -> bytes: return int(v).to_bytes(32, 'little')
 def rows(vals) -> np.ndarray: return np.frombuffer(b''.join(le32(v) for v in vals), dtype=np.uint8).reshape(-1, 32).copy() if len(vals) else np.zeros((0, 32), dtype=np.uint8)
 def ints(a) -> list: return [int.from_bytes(r.tobytes(), 'little') for r in a]
 
@@ -191,12 +187,7 @@ def test_a_key_that_is_not_below_the_subgroup_order_refuses_the_call_and_an_empt
 
 
 def test_routing_threshold_and_its_environment_override():
-    code = 'import aleo_amd; print(int(aleo_amd.lib().aleo_mi355x_min_serials()))'
-    def run(extra):
-        env = dict(os.environ, PYTHONPATH=ROOT, **extra)
-        if 'ALEO_MI355X_MIN_SERIALS' not in extra: env.pop('ALEO_MI355X_MIN_SERIALS', None)
-        return subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300).stdout.split()
-    assert run({}) == ['64'] and run({'ALEO_MI355X_MIN_SERIALS': '1'}) == ['1'] and run({'ALEO_MI355X_MIN_SERIALS': 'nonsense'}) == ['64']
+    assert bs.threshold_reads('min_serials', 'ALEO_MI355X_MIN_SERIALS') == (64, 5, 64)
 
 
 # ---- 5: the device lane, emulated on the host under the sanitizers ------------------------------------------------------------------------------------------------
@@ -204,8 +195,8 @@ def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path):
     """tests/cpp/records_serial_lane_emul.cpp: records_serial_lane.h compiled for the CPU (plain C++, the host compiler, as tools/asan_records_found.sh builds its
     program) over the checked restatement of fr29.h, with the address and undefined-behaviour sanitizers, and run as a program of its own on the 64 commitments of
     part 3 (the reference's sk_sig first among its keys); what its host path writes is what the library returns."""
-    exe, cms, out, key = (os.path.join(str(tmp_path), name) for name in ('records_serial_lane_emul', 'commitments.bin', 'host_rows.bin', 'key.bin'))
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-mbmi2', '-madx'] + SANITIZE + ['-I', CSRC, os.path.join(HERE, 'cpp', 'records_serial_lane_emul.cpp'), '-o', exe])
+    cms, out, key = (os.path.join(str(tmp_path), name) for name in ('commitments.bin', 'host_rows.bin', 'key.bin'))
+    exe = bs.build_lane_emul(tmp_path, 'records_serial_lane_emul', sanitized=True, flags=())
     open(cms, 'wb').write(rows(commitments_64()).tobytes()); open(key, 'wb').write(le32(reference_sk_sig()))
     r = subprocess.run([exe, cms, out, key], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and ' 0 mismatches, 0 table mismatches, 0 limb-rule violations' in r.stdout and '256 commitments' in r.stdout, r.stdout + r.stderr
@@ -219,11 +210,7 @@ def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_serial_kernel_code_object_is_gfx950_and_has_no_scratch():
-    import code_object as co
-    asm, blocks = co.compile_unit('records_serial')
-    meta = co.block_of(blocks, 'k_records_serial')
-    print(co.registers('k_records_serial', meta))
-    assert co.field(meta, 'private_segment_fixed_size') == 0 and co.field(meta, 'vgpr_spill_count') == 0
+    assert bs.scratch_and_spills('records_serial', ['k_records_serial'])[1]['k_records_serial'][:2] == (0, 0)      # no private segment, no VGPR spills
 
 
 # ---- on the GPU ------------------------------------------------------------------------------------------------------------------------------------------------

@@ -11,7 +11,9 @@ import pytest
 import aleo_amd
 from aleo_amd import records, wire
 from oracle import poseidon as ps
-from test_records import REF, ROOT, R, L_ORDER, HIPCC, CSRC, le32, account_generator, reference_cases, synthetic_records
+import batch_support as bs
+from batch_support import ROOT, HIPCC, CSRC, le32
+from test_records import REF, R, L_ORDER, account_generator, reference_cases, synthetic_records
 
 ALPHABET = 'qpzry9x8gf2tvdw0s3jn54khce6mua7l'
 GOOD = REF['records']['owner']
@@ -357,10 +359,8 @@ def test_device_lane_code_run_on_the_host_equals_the_one_record_parser(tmp_path)
 
 def run_cpp_mirror(tmp_path, env):
     """tests/cpp/records_strings_test.cpp: the RecordBatch overloads of include/aleo_mi355x.hpp on the reference's strings and on built records."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'records_strings_test')
     strings = [REF['records']['owner'], REF['records']['sdk_foreign'], REF['records']['sdk']] * 25
-    r = subprocess.run([exe, REF['view_keys']['owner'], REF['addresses']['owner'], REF['plaintexts']['owner']] + strings, capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'records_strings_test', [REF['view_keys']['owner'], REF['addresses']['owner'], REF['plaintexts']['owner']] + strings, env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 

@@ -12,7 +12,9 @@ import aleo_amd
 from aleo_amd import records
 from test_records_found import same_found, differences
 from test_records_found_many import MAIN, Wanted, key_bytes, keys_for, laid_out, layouts, mixed, pool_of
-from test_records_serial import REC, SN, R, L_ORDER, SANITIZE, CSRC, HIPCC, field, le32, rows, ints, reference_commitment, reference_sk_sig
+import batch_support as bs
+from batch_support import SANITIZE, CSRC, HIPCC, le32
+from test_records_serial import REC, SN, R, L_ORDER, field, rows, ints, reference_commitment, reference_sk_sig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -221,10 +223,8 @@ def test_cpp_mirror_on_the_host_path(tmp_path):
 
 def run_cpp_mirror(tmp_path, env):
     """tests/cpp/records_unspent_test.cpp: unspent_strings and unspent_strings_many of include/aleo_mi355x.hpp on the reference's record, 70 copies among foreign ones."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'records_unspent_test')
     strings = [REC['records']['owner'], REC['records']['sdk_foreign']] * 70
-    r = subprocess.run([exe, SN['private_key'], REC['view_keys']['owner'], REC['addresses']['owner'], le32(reference_commitment()).hex(), le32(field(SN['expected'])).hex()] + strings, capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'records_unspent_test', [SN['private_key'], REC['view_keys']['owner'], REC['addresses']['owner'], le32(reference_commitment()).hex(), le32(field(SN['expected'])).hex()] + strings, env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 

@@ -6,30 +6,23 @@ restatement of signing and verification in Python integers below (affine twisted
 recovered from the first reference account as view_key^-1 address, the nonce's ChaCha20 written here) — in both directions; the reference's own assertion follows
 on its three accounts; then the flags, the edges of the arithmetic and the strings.  The host path, flag for flag, checks the device lane: emulated on the CPU,
 plain and under the sanitizers, here, and on the GPU in the second half (ALEO_MI355X_MIN_SIGNATURES=0).  No test reads the reference tree."""
-import ctypes, functools, json, os, random, re, struct, subprocess, sys, threading
+import ctypes, functools, json, os, random, re, struct, subprocess, sys
 import numpy as np
 import pytest
 import aleo_amd
 from aleo_amd import records, signature as sg
 from oracle import poseidon as ps
 from oracle import pyref as P
+import batch_support as bs
+from batch_support import HERE, ROOT, CSRC, HIPCC, SANITIZE, le32, num, _vp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, 'aleo_amd', 'csrc')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ACC = json.load(open(os.path.join(HERE, 'golden', 'reference_account.json')))['accounts']
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']      # host code only: a program of its own, never a GPU build
 R, L, D = ps.R, ps.ED_SUBGROUP_ORDER, ps.ED_D
 MAX_FIELDS = 128 * 1024 * 8 // 252                                                  # 4161
 CAP_BYTES = MAX_FIELDS * 252 // 8                                                   # 131071: the longest message of at most that many fields
 
 
 # ---- the restatement --------------------------------------------------------------------------------------------------------------------------------
-def le32(v: int) -> bytes: return v.to_bytes(32, 'little')
-def num(b: bytes) -> int: return int.from_bytes(b, 'little')
-
-
 def add(p, q):
     """-x^2 + y^2 = 1 + d x^2 y^2, affine: complete, since -1 is a square and d is not."""
     (x1, y1), (x2, y2) = p, q
@@ -123,9 +116,6 @@ def nonce_of_seed(seed: bytes) -> int:
 
 
 # ---- through the C ABI ----------------------------------------------------------------------------------------------------------------------------------
-def _vp(b: bytes): return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
-
-
 def verify_raw(sigs, addrs, messages, host=True, stride=None, offsets=None):
     """aleo_mi355x_signatures_verify[_host] on raw rows: (status, flags)."""
     n = len(sigs); sb = b''.join(sigs); ab = b''.join(addrs); text = b''.join(messages)
@@ -339,10 +329,9 @@ def test_device_lane_code_emulated_on_the_host_matches_the_host_path(tmp_path, s
     """tests/cpp/signature_lane_emul.cpp: signature_lane.h compiled for the CPU over the checked restatement of fr29.h, once plain and once with the address and
     undefined-behaviour sanitizers compiled into that program, run as a program of its own on every case above.  (-fno-strict-aliasing: host_field.hpp reads
     its uint64_t limbs through unsigned long long pointers for the carry-chain intrinsics, which g++ at -O2 may reorder; the library is built by clang.)"""
-    exe, data = os.path.join(str(tmp_path), 'signature_lane_emul'), os.path.join(str(tmp_path), 'cases.bin')
-    subprocess.check_call(['g++', '-std=c++17', '-O1' if sanitized else '-O2', '-fno-strict-aliasing', '-mbmi2', '-madx'] + (SANITIZE if sanitized else []) + ['-I', CSRC, os.path.join(HERE, 'cpp', 'signature_lane_emul.cpp'), '-o', exe])
+    data = os.path.join(str(tmp_path), 'cases.bin')
     rows = lane_rows(); case_file(data, rows)
-    r = subprocess.run([exe, data], capture_output=True, text=True, timeout=900)
+    r = bs.run_lane_emul(tmp_path, 'signature_lane_emul', [data], sanitized=sanitized)
     print(r.stdout)
     assert r.returncode == 0 and '%d signatures' % len(rows) in r.stdout and ' 0 mismatches, 0 reads past an end, 0 limb-rule violations' in r.stdout, r.stdout + r.stderr
 
@@ -352,11 +341,7 @@ DEFAULT_MIN_SIGNATURES = 32
 
 
 def test_routing_threshold_and_its_environment_override():
-    code = 'import aleo_amd; print(int(aleo_amd.lib().aleo_mi355x_min_signatures()))'
-    def run(extra):
-        env = dict(os.environ, PYTHONPATH=ROOT); env.pop('ALEO_MI355X_MIN_SIGNATURES', None); env.update(extra)
-        return int(subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, check=True).stdout)
-    assert run({}) == DEFAULT_MIN_SIGNATURES and run({'ALEO_MI355X_MIN_SIGNATURES': '5'}) == 5 and run({'ALEO_MI355X_MIN_SIGNATURES': 'x'}) == DEFAULT_MIN_SIGNATURES
+    assert bs.threshold_reads('min_signatures', 'ALEO_MI355X_MIN_SIGNATURES') == (DEFAULT_MIN_SIGNATURES, 5, DEFAULT_MIN_SIGNATURES)
     # below the threshold the call computes on the host: no device is needed for it
     env = dict(os.environ, PYTHONPATH=ROOT, ALEO_MI355X_MIN_SIGNATURES='1000000', HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES='')
     code = ('from aleo_amd import signature as sg; k = %r; s = sg.sign(k, b"m", bytes(32)); from aleo_amd import records; '
@@ -366,18 +351,12 @@ def test_routing_threshold_and_its_environment_override():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_signature_kernel_code_object_is_gfx950_and_has_no_scratch():
-    import code_object as co
-    asm, blocks = co.compile_unit('signatures')
-    assert len(blocks) == 1 and 'k_signatures_verify' in blocks[0]                               # this one and no other
-    print(co.registers('k_signatures_verify', blocks[0]))
-    assert co.field(blocks[0], 'private_segment_fixed_size') == 0 and co.field(blocks[0], 'vgpr_spill_count') == 0 and co.field(blocks[0], 'sgpr_spill_count') == 0
+    assert bs.scratch_and_spills('signatures', ['k_signatures_verify']) == (1, {'k_signatures_verify': (0, 0, 0)})      # this one and no other
 
 
 def run_cpp_mirror(tmp_path, env, n):
     """tests/cpp/signature_test.cpp: Signature, sign, verify, verify_many and the account's methods of include/aleo_mi355x.hpp."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'signature_test')
-    r = subprocess.run([exe, ACC[0]['private_key'], ACC[0]['address'], str(n)], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'signature_test', [ACC[0]['private_key'], ACC[0]['address'], n], env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 
@@ -458,13 +437,7 @@ def test_gpu_both_sides_of_the_threshold_and_chunked_launches_return_the_same_by
 def test_gpu_two_threads_at_once_get_the_host_path_s_bytes(on_kernel):
     batches = [mixed_batch(130, True, seed=7), mixed_batch(90, False, seed=8)]
     want = [verify_raw(*b, host=True) for b in batches]
-    got = [None, None]
-    def work(i):
-        for _ in range(3): got[i] = verify_raw(*batches[i], host=False)
-    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
-    for t in threads: t.start()
-    for t in threads: t.join()
-    assert got == want
+    assert bs.two_threads(lambda i: verify_raw(*batches[i], host=False)) == want
 
 
 @pytest.mark.gpu

@@ -5,17 +5,17 @@ Row i of a batch is defined as what the one-signature call returns for (key i, m
 the restatement of signing in Python integers (tests/test_signatures.py, imported as it stands: ref_sign under its own ChaCha20 nonce_of_seed), every row is
 verified, and the device lanes — the product modulo the group order first, alone, against Python integers — are emulated on the CPU, plain and under the
 sanitizers, on the same cases.  The second half runs the kernels (ALEO_MI355X_MIN_SIGN=1) against the host path.  No test reads the reference tree."""
-import ctypes, functools, os, random, struct, subprocess, sys, threading
+import ctypes, functools, os, random, struct, subprocess, sys
 import numpy as np
 import pytest
 import aleo_amd
 from aleo_amd import records, signature as sg
 from oracle import poseidon as ps
 import test_signatures as ts
+import batch_support as bs
+from batch_support import ROOT, HIPCC, le32, num
 
-HERE, ROOT, CSRC, HIPCC, ACC = ts.HERE, ts.ROOT, ts.CSRC, ts.HIPCC, ts.ACC
-R, L = ts.R, ts.L
-le32, num = ts.le32, ts.num
+ACC, R, L = ts.ACC, ts.R, ts.L
 CAP = ts.CAP_BYTES
 LENGTHS = ts.CHUNK_EDGE_BYTES + ts.BLOCK_EDGE_BYTES              # the field boundaries, then the sponge-block boundaries: the signing preimage has verify's four leading elements
 BAD_KEY = le32(R)                                                # the smallest seed that is no canonical field element
@@ -252,10 +252,9 @@ def test_device_lane_code_emulated_on_the_host_matches_python_integers_and_the_h
     """tests/cpp/signature_sign_lane_emul.cpp: signature_sign_lane.h and account_lane.h with its sink compiled for the CPU over the checked restatement of fr29.h,
     once plain and once with the address and undefined-behaviour sanitizers compiled into that program, run as a program of its own on the products and on every
     case above.  (-fno-strict-aliasing: as tests/test_signatures.py says.)"""
-    exe, data = os.path.join(str(tmp_path), 'signature_sign_lane_emul'), os.path.join(str(tmp_path), 'cases.bin')
-    subprocess.check_call(['g++', '-std=c++17', '-O1' if sanitized else '-O2', '-fno-strict-aliasing', '-mbmi2', '-madx'] + (ts.SANITIZE if sanitized else []) + ['-I', CSRC, os.path.join(HERE, 'cpp', 'signature_sign_lane_emul.cpp'), '-o', exe])
+    data = os.path.join(str(tmp_path), 'cases.bin')
     products, count = case_file(data)
-    r = subprocess.run([exe, data], capture_output=True, text=True, timeout=900)
+    r = bs.run_lane_emul(tmp_path, 'signature_sign_lane_emul', [data], sanitized=sanitized)
     print(r.stdout)
     assert r.returncode == 0 and '%d products, %d signatures, %d signed, 3 refused, 0 mismatches, 0 reads past an end, 0 limb-rule violations' % (products, count, count - 3) in r.stdout, r.stdout + r.stderr
 
@@ -265,11 +264,7 @@ DEFAULT_MIN_SIGN = 64
 
 
 def test_routing_threshold_and_its_environment_override():
-    code = 'import aleo_amd; print(int(aleo_amd.lib().aleo_mi355x_min_sign()))'
-    def run(extra):
-        env = dict(os.environ, PYTHONPATH=ROOT); env.pop('ALEO_MI355X_MIN_SIGN', None); env.update(extra)
-        return int(subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, check=True).stdout)
-    assert run({}) == DEFAULT_MIN_SIGN and run({'ALEO_MI355X_MIN_SIGN': '5'}) == 5 and run({'ALEO_MI355X_MIN_SIGN': 'x'}) == DEFAULT_MIN_SIGN
+    assert bs.threshold_reads('min_sign', 'ALEO_MI355X_MIN_SIGN') == (DEFAULT_MIN_SIGN, 5, DEFAULT_MIN_SIGN)
     # below the threshold the call computes on the host: no device is needed for it
     env = dict(os.environ, PYTHONPATH=ROOT, ALEO_MI355X_MIN_SIGN='1000000', HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES='')
     code = ('from aleo_amd import signature as sg, records; k = %r; rows, flags = sg.sign_many(k, [b"m", b"n"], bytes(range(64))); '
@@ -279,20 +274,13 @@ def test_routing_threshold_and_its_environment_override():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_signing_kernels_code_object_is_gfx950_and_has_no_scratch_and_no_spills():
-    import code_object as co
-    asm, blocks = co.compile_unit('signatures_sign')
-    assert len(blocks) == 2                                      # these two and no other
-    for kernel in ('k_signatures_sign', 'k_signer_keys'):
-        b = co.block_of(blocks, kernel)
-        print(co.registers(kernel, b))
-        assert co.field(b, 'private_segment_fixed_size') == 0 and co.field(b, 'vgpr_spill_count') == 0 and co.field(b, 'sgpr_spill_count') == 0, kernel
+    kernels = ('k_signatures_sign', 'k_signer_keys')
+    assert bs.scratch_and_spills('signatures_sign', kernels) == (2, {k: (0, 0, 0) for k in kernels})      # these two and no other
 
 
 def run_cpp_mirror(tmp_path, env, n):
     """tests/cpp/signatures_sign_test.cpp: sign_many and PrivateAccount::sign_many of include/aleo_mi355x.hpp."""
-    from test_abi import build_cpp_host_mirror
-    exe = build_cpp_host_mirror(tmp_path, 'signatures_sign_test')
-    r = subprocess.run([exe, ACC[0]['private_key'], ACC[1]['private_key'], ACC[0]['address'], str(n)], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+    r = bs.run_cpp_mirror(tmp_path, 'signatures_sign_test', [ACC[0]['private_key'], ACC[1]['private_key'], ACC[0]['address'], n], env)
     assert r.returncode == 0 and 'ALL OK' in r.stdout, r.stdout + r.stderr
 
 
@@ -365,13 +353,7 @@ def test_gpu_the_rows_verify_on_the_gpu(on_kernel):
 @pytest.mark.gpu
 def test_gpu_two_threads_at_once_get_the_host_path_s_bytes(on_kernel):
     want = [host_rows(130, True, 1), host_rows(90, False, 2)]
-    got = [None, None]
-    def work(i):
-        for _ in range(3): got[i] = device_rows(130, True, 1) if i == 0 else device_rows(90, False, 2)
-    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
-    for t in threads: t.start()
-    for t in threads: t.join()
-    assert got == want
+    assert bs.two_threads(lambda i: device_rows(130, True, 1) if i == 0 else device_rows(90, False, 2)) == want
 
 
 @pytest.mark.gpu
