@@ -651,6 +651,37 @@ int32_t aleo_mi355x_selftest_g2pair(const void* affine192, uint32_t n_points, ui
   return guarded([&] { if (!affine192 || !failures2 || n_points < 3 || !n_pairs || n_pairs > (1u << 20)) return ALEO_MI355X_ERR_BAD_ARG; Slot sl; if (sl.rc) return sl.rc; return selftest_g2pair(sl.c, affine192, n_points, n_pairs, failures2); });
 }
 
+// One host function of frops.h that has no entry point of its own, as the prover calls it (test hook: the header lists what each step takes).
+int32_t aleo_mi355x_selftest_fr_step(uint32_t step, const void* const* ptrs, const size_t* sizes, const void* consts_mont) {
+  return guarded([&] {
+    if (!ptrs || !sizes || step > 6) return bad_arg("selftest_fr_step: null array or unknown step");
+    // the pointers a launch of the step dereferences: the first `need` (step 3: dst and up to 8 sources; step 4: both tables, then four per range that is not empty)
+    const size_t count = sizes[0];
+    const size_t need = step == 0 ? 2 : step == 1 ? 4 : step == 2 ? 2 : step == 3 ? 1 + (count < 8 ? count : 8) : step == 4 ? 2 : 3;
+    for (size_t i = 0; i < need; ++i) if (!ptrs[i]) return bad_arg("selftest_fr_step: null pointer");
+    if (step == 4) for (size_t m = 0; m < count && m < 3; ++m) for (size_t i = 0; i < 4; ++i) if (sizes[1 + m] && !ptrs[2 + 4 * m + i]) return bad_arg("selftest_fr_step: null pointer in a range");
+    if (step == 2 && !consts_mont) return bad_arg("selftest_fr_step: scale_rows without constants");
+    Slot sl; if (sl.rc) return sl.rc;
+    Ctx* c = sl.c; hipStream_t s = c->stream; int32_t rc = ALEO_MI355X_OK;
+    switch (step) {
+      case 0: rc = fr_add_tiled(c, (void*)ptrs[0], sizes[0], ptrs[1], sizes[1], s); break;
+      case 1: rc = fr_sub_mul(c, (void*)ptrs[0], ptrs[1], ptrs[2], ptrs[3], sizes[0], s); break;
+      case 2: rc = fr_scale_rows(c, (void*)ptrs[0], ptrs[1], sizes[0], sizes[1], consts_mont, s); break;
+      case 3: rc = fr_pick(c, (void*)ptrs[0], ptrs + 1, count, s); break;
+      case 4: {
+        void* dst[3] = {}; const void* scale[3] = {}; const void* idx1[3] = {}; const void* idx2[3] = {}; size_t n[3] = {};
+        for (size_t m = 0; m < count && m < 3; ++m) { dst[m] = (void*)ptrs[2 + 4 * m]; scale[m] = ptrs[3 + 4 * m]; idx1[m] = ptrs[4 + 4 * m]; idx2[m] = ptrs[5 + 4 * m]; n[m] = sizes[1 + m]; }
+        rc = fr_gather_mul3(c, dst, n, scale, ptrs[0], idx1, ptrs[1], idx2, count > 3 ? 4u : (uint32_t)count, s); break;
+      }
+      case 5: rc = fr_scatter_to_mont(c, (void*)ptrs[0], ptrs[1], ptrs[2], sizes[0], (void*)ptrs[3], s); break;
+      default: rc = fr_split_quotient(c, (void*)ptrs[0], (void*)ptrs[1], ptrs[2], ptrs[3], sizes[0], (void*)ptrs[4], s); break;
+    }
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    return ALEO_MI355X_OK;
+  });
+}
+
 int32_t aleo_mi355x_last_msm_timing(double* out_ms, int32_t cap) {
   return guarded([&] {
     if (!out_ms || cap <= 0) return 0;

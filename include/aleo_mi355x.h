@@ -511,6 +511,19 @@ int32_t aleo_mi355x_selftest_g2pair(const void* affine192, uint32_t n_points, ui
  * (optional, 4 doubles): divsteps / Fermat for Fq, divsteps / Fermat for Fr. */
 int32_t aleo_mi355x_selftest_host_inverse(uint32_t count, uint64_t seed, uint32_t* failures, double* ns_per_inverse);
 
+/* Test hook: the Fr vector kernels that only the native prover launches (csrc/frops.h), one host function per call, on the serving slot's stream, complete on
+ * return.  ptrs: device pointers (a pointer named "or NULL" may be absent); sizes: element counts; consts_mont: 32-byte Montgomery constants on the host.
+ *   step 0  fr_add_tiled        ptrs = dst, src                        sizes = n, n_src                      dst[i] += src[i mod n_src]
+ *   step 1  fr_sub_mul          ptrs = dst, a, b, m                    sizes = n                             dst = (a - b) m
+ *   step 2  fr_scale_rows       ptrs = dst, src                        sizes = n, rows      consts = rows    dst[r][i] = k_r src[i]
+ *   step 3  fr_pick             ptrs = dst, src_0 .. src_{count-1}     sizes = count                         dst[j] = *src_j
+ *   step 4  fr_gather_mul3      ptrs = table1, table2, then (dst, scale, idx1, idx2) per range      sizes = count, n_0 .. n_{count-1}
+ *   step 5  fr_scatter_to_mont  ptrs = dst, src, pos, flag or NULL     sizes = n                             dst[pos[v]] = to_mont(src[v]); *flag |= 1 if a src[v] >= r
+ *   step 6  fr_split_quotient   ptrs = hq, rq, q, mask or NULL, host_sum or NULL    sizes = n                hq = [p1 + p2 | p2], rq = p0 + p1 + p2 (host_sum = rq[0])
+ * What a host function refuses (a block size that does not divide n, 5 rows, 9 picks, 0 or 4 ranges) comes back as its status.  ALEO_MI355X_ERR_BAD_ARG for an
+ * unknown step, a null array, or a null pointer the step needs. */
+int32_t aleo_mi355x_selftest_fr_step(uint32_t step, const void* const* ptrs, const size_t* sizes, const void* consts_mont);
+
 /* Per-call instrumentation of the calling thread's most recent MSM: milliseconds per phase
  * [0] total, [1] digit/sort, [2] bucket accumulation incl. slice tree, [3] bucket reduction, [4] host tail,
  * [5] the bucket-accumulation kernel alone (the dominant kernel bench.py prices against the roofline): mean duration of its launches,
