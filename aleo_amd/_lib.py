@@ -46,6 +46,8 @@ EXPORTS = [
     'aleo_mi355x_accounts_derive', 'aleo_mi355x_accounts_derive_host', 'aleo_mi355x_accounts_search', 'aleo_mi355x_accounts_search_host', 'aleo_mi355x_min_accounts',
     'aleo_mi355x_private_key_from_seed', 'aleo_mi355x_private_key_seed', 'aleo_mi355x_seed_from_bytes', 'aleo_mi355x_view_key_to_string',
     'aleo_mi355x_private_key_encrypt', 'aleo_mi355x_private_key_decrypt', 'aleo_mi355x_private_keys_open', 'aleo_mi355x_private_keys_open_host', 'aleo_mi355x_min_key_ciphertexts',
+    'aleo_mi355x_record_plaintext_parse', 'aleo_mi355x_plaintext_commitment', 'aleo_mi355x_plaintexts_commitments', 'aleo_mi355x_plaintexts_commitments_host',
+    'aleo_mi355x_plaintexts_serial_numbers', 'aleo_mi355x_plaintexts_serial_numbers_host', 'aleo_mi355x_min_plaintexts', 'aleo_mi355x_plaintexts_last_routed',
 ]
 
 
@@ -247,6 +249,14 @@ def lib():
         'aleo_mi355x_private_keys_open': ([vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp], i32),
         'aleo_mi355x_private_keys_open_host': ([vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp], i32),
         'aleo_mi355x_min_key_ciphertexts': ([], sz),
+        'aleo_mi355x_record_plaintext_parse': ([ctypes.c_char_p, ctypes.POINTER(i32), vp, vp, ctypes.POINTER(u64)], i32),
+        'aleo_mi355x_plaintext_commitment': ([vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p], i32),
+        'aleo_mi355x_plaintexts_commitments': ([vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p], i32),
+        'aleo_mi355x_plaintexts_commitments_host': ([vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p], i32),
+        'aleo_mi355x_plaintexts_serial_numbers': ([vp, vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, sz], i32),
+        'aleo_mi355x_plaintexts_serial_numbers_host': ([vp, vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, sz], i32),
+        'aleo_mi355x_min_plaintexts': ([], sz),
+        'aleo_mi355x_plaintexts_last_routed': ([], sz),
         'aleo_mi355x_found_free': ([vp], None),
         **{'aleo_mi355x_found_' + name: ([vp], sz) for name in ('count', 'fields', 'unparsed', 'first_unparsed', 'owned')},
         **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits', 'serials', 'commitments')},

@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(COMMIT_BLOCK) k_records_commit(char* __restric
   flags[j] = (uint8_t)flag;
 }
 
-static int32_t commit_tables_on_device(int device, const uint32_t** out) {
+int32_t commit_tables_on_device(int device, const uint32_t** out) {
   return resident_table(device, ResidentTable::COMMIT, []() -> const std::vector<uint32_t>& { return serial::commit_tables().words; }, out);
 }
 

@@ -11,8 +11,9 @@
 //             chunk 84 + k mod 348 of iteration k / 348, whatever the length, and an extra iteration costs one inversion.
 //
 // Two walks over the entries, as the u32 length precedes the data: commit_measure sums the lengths and refuses, commit_next hands out the message in order as
-// items of at most 256 bits, which records_commit_lane feeds straight into 3-bit chunks — there is no bit buffer.  ONE place adds a chunk's table entry, so the
-// eight products of an addition are in the code once (and once more where an iteration's digest is fed back).
+// items of at most 256 bits, which commit_hash feeds straight into 3-bit chunks — there is no bit buffer.  ONE place adds a chunk's table entry, so the
+// eight products of an addition are in the code once (and once more where an iteration's digest is fed back): commit_hash takes its items from a source
+// next(w, nbits), which is commit_next here and the walk over a plaintext string in plaintexts_lane.h.
 // The start.  The domain (chunks 0 .. 61), the zero chunks 74 .. 83 of the length's upper bits and the whole chunks of the three names (from chunk 84 on) are
 // the same for every record of a call: the host sums them (commit_host.hpp commit_args; 110 chunks for credits.aleo / credits) and passes the point and the
 // names' leftover 0-2 bits by value.  The lane adds chunks 62 .. 73 — the domain's last two bits and the length's low 34 — and goes on behind the names.
@@ -154,35 +155,23 @@ __device__ __forceinline__ Ed29Cached ck_entry(const uint32_t* __restrict__ K, u
   return c;
 }
 
-// One owned record whose found status is 0.  ch(i): character i of its string, of `len`; kind: its owner variant; load(k, w): its decrypted field k of n_fields,
-// canonical little-endian words, randomizer order.  Returns the flag; `emit` is handed the canonical limbs of the commitment when the flag is 0.
-template <class LoadChar, class LoadField, class Emit>
-__device__ __forceinline__ uint32_t records_commit_lane(LoadChar&& ch, uint32_t len, int32_t kind, uint32_t n_fields, LoadField&& load, const uint32_t* __restrict__ K,
-                                                        const CommitArgs& A, Emit&& emit) {
-  constexpr RsSymbols T = rs_symbols();
-  auto sym = [&](uint32_t k) { return RS_PREFIX_CHARS + k < len ? (uint32_t)T.of[(uint8_t)ch(RS_PREFIX_CHARS + k) & 127u] & 31u : 0u; };      // never past the string
-  auto field = [&](uint32_t k, uint32_t (&w)[8]) {
-    if (k < n_fields) load(k, w);
-    else { w[0] = w[1] = w[2] = w[3] = w[4] = w[5] = w[6] = w[7] = 0; }             // cannot happen: commit_measure counted them
-  };
-  uint32_t data_bits;
-  const uint32_t flag = commit_measure(sym, kind, n_fields, field, data_bits);
-  if (flag != COMMIT_OK) return flag;
-  const uint32_t message_bits = A.name_bits + 254u + 32u + data_bits + 253u;
-
+// The hash of a message of `message_bits` bits behind the call's names, whose items next(w, nbits) hands out in order (each at most 256 bits, little-endian in w,
+// anything above nbits; false: the message has ended): the start point, chunks 62 .. 73, the 3-bit chunks, the feed-back of an iteration's digest.  Returns the
+// canonical limbs of the digest's x.  The two item sources are commit_next above (a record string and its decrypted fields) and plaintexts_lane.h's (a plaintext string).
+template <class Next>
+__device__ __forceinline__ F29 commit_hash(Next&& next, uint32_t message_bits, const uint32_t* __restrict__ K, const CommitArgs& A) {
   Ed29 p;
 #pragma unroll
   for (int i = 0; i < 9; ++i) { p.X.v[i] = A.start[i]; p.Y.v[i] = A.start[9 + i]; p.T.v[i] = A.start[18 + i]; }
   p.Z = rk_const(K, RK_ONE);
   uint32_t c = CM_DOMAIN_CHUNKS, nb = 0;                       // the chunk to come; the bits waiting for a whole one
   uint64_t acc = 0;
-  CommitWalk W{}; W.stage = CW_OWNER;
   uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nbits;
   bool head = true, more = true;
   while (more) {
     if (head) { w[0] = A.head | (message_bits << 2); w[1] = message_bits >> 30; nbits = 3 * CM_LENGTH_CHUNKS; }      // chunks 62 .. 73
     else {
-      more = commit_next(W, sym, kind, field, data_bits, w, nbits);
+      more = next(w, nbits);
       if (!more) { w[0] = 0; nbits = nb ? 3u - nb : 0u; }      // the last chunk's padding
     }
     for (uint32_t left = nbits; left;) {                       // word by word from the bottom of w, which moves down: no lane indexes its registers
@@ -204,7 +193,25 @@ __device__ __forceinline__ uint32_t records_commit_lane(LoadChar&& ch, uint32_t 
     }
     if (head) { head = false; c = A.first_chunk; acc = A.lead; nb = A.lead_n; }      // behind the names
   }
-  emit(f29_canonical(f29_mul(p.X, f29_pow(p.Z, K + RK_EXP_INV, RK_INV_BITS))));
+  return f29_canonical(f29_mul(p.X, f29_pow(p.Z, K + RK_EXP_INV, RK_INV_BITS)));
+}
+
+// One owned record whose found status is 0.  ch(i): character i of its string, of `len`; kind: its owner variant; load(k, w): its decrypted field k of n_fields,
+// canonical little-endian words, randomizer order.  Returns the flag; `emit` is handed the canonical limbs of the commitment when the flag is 0.
+template <class LoadChar, class LoadField, class Emit>
+__device__ __forceinline__ uint32_t records_commit_lane(LoadChar&& ch, uint32_t len, int32_t kind, uint32_t n_fields, LoadField&& load, const uint32_t* __restrict__ K,
+                                                        const CommitArgs& A, Emit&& emit) {
+  constexpr RsSymbols T = rs_symbols();
+  auto sym = [&](uint32_t k) { return RS_PREFIX_CHARS + k < len ? (uint32_t)T.of[(uint8_t)ch(RS_PREFIX_CHARS + k) & 127u] & 31u : 0u; };      // never past the string
+  auto field = [&](uint32_t k, uint32_t (&w)[8]) {
+    if (k < n_fields) load(k, w);
+    else { w[0] = w[1] = w[2] = w[3] = w[4] = w[5] = w[6] = w[7] = 0; }             // cannot happen: commit_measure counted them
+  };
+  uint32_t data_bits;
+  const uint32_t flag = commit_measure(sym, kind, n_fields, field, data_bits);
+  if (flag != COMMIT_OK) return flag;
+  CommitWalk W{}; W.stage = CW_OWNER;
+  emit(commit_hash([&](uint32_t (&w)[8], uint32_t& nbits) { return commit_next(W, sym, kind, field, data_bits, w, nbits); }, A.name_bits + 254u + 32u + data_bits + 253u, K, A));
   return COMMIT_OK;
 }
 

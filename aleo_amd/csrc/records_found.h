@@ -83,6 +83,12 @@ inline SerialArgs serial_args_of(const ScanArgs& a) {
 // k_records_serial over every segment, key j's digits at dkeys[j] in device memory: launches of at most ALEO_MI355X_SERIAL_CHUNK lanes (read per call), which may span key boundaries
 int32_t launch_records_serial(hipStream_t s, char* dsn, uint8_t* dflags, const char* dcm, const uint32_t* dK, const SerialArgs* dkeys, const UnspentSegs& seg);
 
+// records_unspent.hip: the open-addressing table (records_spent_lane.h) over the n_spent rows of a spent set on the device: the table's `cap` slots are zeroed,
+// then k_spent_insert runs, one row per lane
+int32_t launch_spent_insert(hipStream_t s, uint32_t* table, uint32_t cap, const uint32_t* rows, size_t n_spent);
+
+// records_commit.hip: the commitment lane's table on this device (entry.h resident_table)
+int32_t commit_tables_on_device(int device, const uint32_t** out);
 // records_commit.hip: what a call's (program id, record name) comes to — refused with the reference's two texts — and the commitments of owned records
 struct CommitCall { std::vector<uint8_t> name_bits; CommitArgs args; };
 int32_t commit_call(CommitCall& cc, const char* program_id, const char* record_name);

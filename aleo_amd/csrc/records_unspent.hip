@@ -39,6 +39,13 @@ __global__ void __launch_bounds__(FOUND_BLOCK) k_spent_insert(uint32_t* __restri
   spent_insert(cap, i, rows[(size_t)i * 8], [&](uint32_t slot, uint32_t expected, uint32_t desired) { return atomicCAS(&table[slot], expected, desired); });
 }
 
+int32_t launch_spent_insert(hipStream_t s, uint32_t* table, uint32_t cap, const uint32_t* rows, size_t n_spent) {
+  HIPCHK(hipMemsetAsync(table, 0, (size_t)cap * 4, s));
+  hipLaunchKernelGGL(k_spent_insert, dim3((uint32_t)((n_spent + FOUND_BLOCK - 1) / FOUND_BLOCK)), dim3(FOUND_BLOCK), 0, s, table, cap, rows, (uint32_t)n_spent);
+  HIPCHK(hipGetLastError());
+  return ALEO_MI355X_OK;
+}
+
 // cnt / pos: the exclusive sums of the kept field counts and of the keep bits WITHIN the block; blk: [fields | kept][block], the block totals.  cap 0: no set.
 // cm_flags (unspent_named; else null): the flags of the commitments the call computed itself.
 __global__ void __launch_bounds__(FOUND_BLOCK) k_unspent_keep(uint32_t* __restrict__ cnt, uint32_t* __restrict__ pos, uint8_t* __restrict__ keep, uint32_t* __restrict__ blk,
@@ -120,10 +127,7 @@ struct UnspentStage : FoundStage {
     if (!n_spent) return ALEO_MI355X_OK;
     dspent = (const uint32_t*)(base + o_rows); dtable = (const uint32_t*)(base + o_table);
     HIPCHK(hipMemcpyAsync(base + o_rows, spent, n_spent * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(base + o_table, 0, (size_t)cap * 4, s));
-    hipLaunchKernelGGL(k_spent_insert, dim3((uint32_t)((n_spent + FOUND_BLOCK - 1) / FOUND_BLOCK)), dim3(FOUND_BLOCK), 0, s, (uint32_t*)(base + o_table), cap, dspent, (uint32_t)n_spent);
-    HIPCHK(hipGetLastError());
-    return ALEO_MI355X_OK;
+    return launch_spent_insert(s, (uint32_t*)(base + o_table), cap, dspent, n_spent);
   }
 
   // the owned records' indices come down now: the host gathers their commitments while the decryption runs

@@ -16,7 +16,10 @@ decrypt_strings_many, balances and decrypt_owned_many (aleo_mi355x_records_decry
 over the same strings: one upload and parse, one grouped scan, one gather and decryption of every owned (account, record) pair.
 What the reference needs before it can use an owned record — its serial number, to ask the chain whether it is spent (rust/src/api/blocking.rs:277-278;
 RecordPlaintext.serialNumberString of the wasm) — is serial_numbers, found_serial_numbers and unspent here (aleo_mi355x_records_serial_numbers,
-aleo_mi355x_found_serial_numbers: csrc/records_serial.hip), with record_commitment, record_checksum and Account.from_private_key on the host beside them."""
+aleo_mi355x_found_serial_numbers: csrc/records_serial.hip), with record_commitment, record_checksum and Account.from_private_key on the host beside them.
+Callers that hold record PLAINTEXT strings — what every write call of the reference takes, what findUnspentRecords hands back and a wallet stores — pass those:
+RecordPlaintext.from_string reads one, serial_number_string works on any plaintext, and plaintext_commitments, plaintext_serial_numbers and plaintexts_unspent
+take a batch of them through one call (aleo_mi355x_plaintexts_commitments, aleo_mi355x_plaintexts_serial_numbers: csrc/plaintexts.hip)."""
 from __future__ import annotations
 import ctypes, weakref
 import numpy as np
@@ -239,6 +242,14 @@ class RecordPlaintext:
     def __eq__(self, other): return isinstance(other, RecordPlaintext) and other.string == self.string
     def __hash__(self): return hash(self.string)
 
+    @classmethod
+    def from_string(cls, s: str) -> 'RecordPlaintext':
+        """RecordPlaintext.fromString (wasm/src/record/record_plaintext.rs:45-50): the string read by the library (aleo_mi355x_record_plaintext_parse, which also
+        asks that the owner, the nonce and group values are x-coordinates of points of the subgroup).  Raises AleoMi355xError with a text that begins with the
+        reference's "The record plaintext string provided was invalid"."""
+        if lib().aleo_mi355x_record_plaintext_parse(str(s).encode(), None, None, None, None): raise AleoMi355xError(lib().aleo_mi355x_last_error().decode())
+        return cls(str(s))
+
     def microcredits(self) -> int:
         """The value of a u64 entry named microcredits, else 0 (RecordPlaintext.microcredits of the wasm)."""
         v = self.entries.get('microcredits')
@@ -248,13 +259,17 @@ class RecordPlaintext:
 
     def serial_number_string(self, private_key, program_id: str, record_name: str) -> str:
         """RecordPlaintext.serialNumberString(privateKey, programId, recordName): "<decimal>field" (wasm/src/record/record_plaintext.rs:64-82).  The commitment is
-        taken over the record's bits, which this mirror reads from the "record1…" string and the decrypted fields the plaintext was made from (a plaintext that
-        RecordCiphertext.decrypt / plaintext or decrypt_owned returned carries them), not from the rendered text.  private_key: an "APrivateKey1…" string or an
+        taken over the record's bits: of a plaintext that RecordCiphertext.decrypt / plaintext or decrypt_owned returned, from the "record1…" string and the
+        decrypted fields it carries; of any other (RecordPlaintext.from_string), from the text itself (aleo_mi355x_plaintexts_serial_numbers_host).  private_key: an "APrivateKey1…" string or an
         Account.  Raises AleoMi355xError with the reference's messages: "Invalid ProgramID specified", "Invalid Identifier specified for record", "Serial number
         derivation failed"."""
-        if self.ciphertext is None: raise AleoMi355xError('serial_number_string: this plaintext was not made from a record ciphertext')
-        fields = self._plain_fields() if callable(self._plain_fields) else self._plain_fields
         account = private_key if isinstance(private_key, Account) else Account.from_private_key(private_key)
+        if self.ciphertext is None:                                 # from the text alone (RecordPlaintext.from_string): aleo_mi355x_plaintexts_serial_numbers_host
+            sn, _, _, flags = plaintext_serial_numbers([self.string], program_id, record_name, account, host=True)
+            if flags[0] == 3: raise AleoMi355xError(_PLAINTEXT_INVALID)
+            if flags[0]: raise AleoMi355xError('Serial number derivation failed')
+            return '%dfield' % int.from_bytes(sn[0].tobytes(), 'little')
+        fields = self._plain_fields() if callable(self._plain_fields) else self._plain_fields
         sn, flags = serial_numbers(record_commitment(self.ciphertext, fields, program_id, record_name), account.sk_sig, host=True)
         if flags[0]: raise AleoMi355xError('Serial number derivation failed')
         return '%dfield' % int.from_bytes(sn[0].tobytes(), 'little')
@@ -262,7 +277,7 @@ class RecordPlaintext:
 
 def _parse_plaintext(s: str, at: int):
     """One value of a plaintext string from position `at`: ('{' name: value, ... '}') -> dict, anything else -> the literal's text.  Returns (value, next position)."""
-    while s[at] in ' \n': at += 1
+    while s[at] in ' \t\r\n': at += 1
     if s[at] != '{':
         start = at; quoted = False
         while at < len(s) and (quoted or s[at] not in ',\n}'):
@@ -271,7 +286,7 @@ def _parse_plaintext(s: str, at: int):
         return s[start:at].strip(), at
     out = {}; at += 1
     while True:
-        while s[at] in ' \n,': at += 1
+        while s[at] in ' \t\r\n,': at += 1
         if s[at] == '}': return out, at + 1
         colon = s.index(':', at)
         name = s[at:colon].strip()
@@ -577,10 +592,13 @@ class Account:
         return (signature if isinstance(signature, sg.Signature) else sg.Signature.from_string(signature)).verify(self.address_x, message)
 
 
+_PLAINTEXT_INVALID = 'The record plaintext string provided was invalid'      # RecordPlaintext.fromString's refusal (wasm/src/record/record_plaintext.rs:178)
+
+
 def _raise_reference_message():
     """The two refusals whose text the reference's tests read are raised with that text alone."""
     L = lib(); msg = L.aleo_mi355x_last_error().decode()
-    if msg in ('Invalid ProgramID specified', 'Invalid Identifier specified for record'):
+    if msg in ('Invalid ProgramID specified', 'Invalid Identifier specified for record', _PLAINTEXT_INVALID):
         e = AleoMi355xError(msg); e.status = 2
         raise e
 
@@ -726,3 +744,60 @@ def unspent_named_many(batch, program_id: str, record_name: str, accounts, spent
 def unspent_named(batch, program_id: str, record_name: str, account, spent=(), host: bool = False) -> FoundRecords:
     """unspent_named_many for one account (an Account or a private key string): aleo_mi355x_records_unspent_named."""
     return unspent_named_many(batch, program_id, record_name, [account], spent, host=host)[0]
+
+
+# ---- record plaintext strings: commitments, serial numbers and the spent check from the text alone (csrc/plaintexts.hip) ---------------------------------------
+def _plaintext_batch(strings) -> RecordBatch:
+    """The blob of a RecordBatch (text plus offsets, as it stands) or of a sequence of strings and RecordPlaintext objects."""
+    if isinstance(strings, RecordBatch): return strings
+    return RecordBatch.from_strings([str(s) for s in strings])
+
+
+def plaintext_commitment(plaintext, program_id: str, record_name: str) -> bytes:
+    """to_commitment(program_id, record_name) of the record a plaintext string says (32 little-endian bytes), on the host (aleo_mi355x_plaintext_commitment).
+    Raises with the reference's three messages: a bad program id, a bad record name, a string that is no record plaintext."""
+    out = np.zeros(32, dtype=np.uint8)
+    rc = lib().aleo_mi355x_plaintext_commitment(_p(out), str(plaintext).encode(), program_id.encode(), record_name.encode())
+    if rc: _raise_reference_message()
+    check(rc, 'plaintext_commitment')
+    return out.tobytes()
+
+
+def plaintext_commitments(strings, program_id: str, record_name: str, host: bool = False):
+    """The commitments (uint8[n, 32]), microcredits (uint64[n]) and flags (uint8[n]: 0 computed; 3 not a record plaintext, its row zeros) of n plaintext strings
+    — a sequence of strings or RecordPlaintext objects, or a RecordBatch — in one call (aleo_mi355x_plaintexts_commitments / _host)."""
+    b = _plaintext_batch(strings); n = len(b)
+    cm = np.zeros((n, 32), dtype=np.uint8); mc = np.zeros(n, dtype=np.uint64); flags = np.zeros(n, dtype=np.uint8)
+    L = lib(); f = L.aleo_mi355x_plaintexts_commitments_host if host else L.aleo_mi355x_plaintexts_commitments
+    rc = f(_p(cm), _p(mc), _p(flags), _text_p(b), _p(b.offsets), n, program_id.encode(), record_name.encode())
+    if rc: _raise_reference_message()
+    check(rc, 'plaintexts_commitments')
+    return cm, mc, flags
+
+
+def plaintext_serial_numbers(strings, program_id: str, record_name: str, account, spent=(), host: bool = False):
+    """(serial numbers uint8[n, 32], commitments uint8[n, 32], microcredits uint64[n], flags uint8[n]) of n plaintext strings under one account (an Account, a
+    private key string or 32 bytes of sk_sig) and a set of spent serial numbers: flags 0 computed and not in the set, 1 computed and in the set, 2 the serial
+    number is refused, 3 not a record plaintext; a row that is not computed is zeros (aleo_mi355x_plaintexts_serial_numbers / _host)."""
+    b = _plaintext_batch(strings); n = len(b); sp = _rows32(spent)
+    if isinstance(account, str): account = Account.from_private_key(account)
+    sk = np.frombuffer(account.sk_sig if isinstance(account, Account) else view_key_bytes(account), dtype=np.uint8)
+    sn = np.zeros((n, 32), dtype=np.uint8); cm = np.zeros((n, 32), dtype=np.uint8); mc = np.zeros(n, dtype=np.uint64); flags = np.zeros(n, dtype=np.uint8)
+    L = lib(); f = L.aleo_mi355x_plaintexts_serial_numbers_host if host else L.aleo_mi355x_plaintexts_serial_numbers
+    rc = f(_p(sn), _p(cm), _p(mc), _p(flags), _text_p(b), _p(b.offsets), n, program_id.encode(), record_name.encode(), _p(sk), _p(sp) if sp.shape[0] else None, sp.shape[0])
+    if rc: _raise_reference_message()
+    check(rc, 'plaintexts_serial_numbers')
+    return sn, cm, mc, flags
+
+
+def plaintexts_unspent(strings, program_id: str, record_name: str, account, spent=(), host: bool = False):
+    """Which of the plaintexts a wallet holds are still unspent: (index uint32[c], serial numbers uint8[c, 32], microcredits uint64[c]) of the strings whose serial
+    number computes under the account and is not in `spent` — plaintext_serial_numbers' rows with flag 0."""
+    sn, _, mc, flags = plaintext_serial_numbers(strings, program_id, record_name, account, spent, host=host)
+    keep = np.flatnonzero(flags == 0)
+    return keep.astype(np.uint32), sn[keep], mc[keep]
+
+
+def plaintexts_last_routed() -> int:
+    """How many strings of this thread's last plaintext batch call the host code computed or refused (all of them below aleo_mi355x_min_plaintexts())."""
+    return int(lib().aleo_mi355x_plaintexts_last_routed())

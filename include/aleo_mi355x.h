@@ -804,6 +804,42 @@ int32_t aleo_mi355x_records_unspent_named_host(aleo_mi355x_found** out, const ch
 int32_t aleo_mi355x_records_unspent_named_many(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent);
 int32_t aleo_mi355x_records_unspent_named_many_host(aleo_mi355x_found** out, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sigs32, const void* view_keys32, const void* address_xs32, size_t n_keys, const void* spent32, size_t n_spent);
 const uint8_t* aleo_mi355x_found_commitments(const aleo_mi355x_found* found);
+/* Record PLAINTEXT strings — "{ owner: aleo1….private, microcredits: 5u64.private, _nonce: …group.public }" — read, committed and serial-numbered: what every
+ * write call of the reference takes its records as (fee_record / amount_record: wasm/src/programs/manager/transfer.rs:66-68), what findUnspentRecords hands back
+ * and a wallet stores, and what RecordPlaintext.fromString(..).serialNumberString(..) starts from (wasm/src/record/record_plaintext.rs:45-82, :131-140).  The calls
+ * above start from a record1… ciphertext and its decrypted fields; these start from the text.  The grammar, the bits a string comes to and every choice the
+ * reference cannot pin (UNPINNED: underscores in digits, leading zeros, signs, comments, the entry cap, reserved names) are csrc/plaintext_parse.hpp's header.
+ *   record_plaintext_parse   host: RecordPlaintext.fromString and microcredits().  owner_kind 0 public / 1 private, the owner's address x, the nonce's x, and the
+ *                  value of a top-level u64 entry named microcredits (else 0); every out pointer may be NULL.  This call alone also asks that the owner, the nonce
+ *                  and every `group` value are x-coordinates of points of the prime-order subgroup; the batch calls check canonical encoding (below the modulus)
+ *                  only, as record_plaintext's rendering does.  Refused with last_error beginning "The record plaintext string provided was invalid".
+ *   plaintext_commitment   host: to_commitment(program_id, record_name) of the record the string says, 32 B canonical little-endian.  last_error is exactly
+ *                  "Invalid ProgramID specified", "Invalid Identifier specified for record" or "The record plaintext string provided was invalid".
+ *   plaintexts_commitments   n strings (text / offsets as records_parse_many takes them): cm_out (n x 32 B), microcredits (n, may be NULL) and flags (n): 0 computed;
+ *                  3 not a record plaintext, the row zeros.  A bad string never fails the call.  One string per lane (csrc/plaintexts_lane.h) over the commitment
+ *                  lane's resident table; launches of at most 2^20 strings (ALEO_MI355X_PLAINTEXTS_CHUNK, read per call, lowers the cap: for tests).  The lane
+ *                  computes records whose entries are all numeric, boolean or address literals in the spelling record_plaintext prints, of at most 1024
+ *                  characters and 8 entries; structs, quoted strings, other spellings, longer strings and everything that looks malformed are computed or
+ *                  refused by the calling thread with the host code, inside the call.  Fewer than min_plaintexts strings run on the host.  Thread-safe.
+ *   plaintexts_serial_numbers   the same, then the serial number of every computed commitment under sk_sig32 (one key per call) into sn_out (n x 32 B), and the
+ *                  look-up of each in the n_spent rows of spent32 (may be NULL with n_spent 0).  cm_out may be NULL.  flags: 0 computed and not in the set; 1
+ *                  computed and in the set; 2 the serial number is refused (records_serial_numbers' flag; the row zeros); 3 not a record plaintext (both rows
+ *                  zeros).  One slot, one stream: k_plaintexts_commit, the routed rows patched, k_records_serial, k_spent_insert, the look-up, one download.
+ *   plaintexts_commitments_host, plaintexts_serial_numbers_host   the same bytes on the calling thread; touch no device.
+ *   min_plaintexts   the number of strings from which the two calls take the GPU: 32, the measured crossover against the host twin on one thread of a call that
+ *                  brings no spent set (profiles/records_plaintexts.txt: at 2^4 the GPU road takes 5.86 ms against 3.04 for serial numbers and 1.37 against 0.80 for
+ *                  commitments, at 2^5 5.89 against 6.09 and 1.38 against 1.58; with 2^16 spent rows, which the host twin sorts in every call, it wins from 2^3
+ *                  on); ALEO_MI355X_MIN_PLAINTEXTS overrides it, read per call.
+ *   plaintexts_last_routed   how many strings of the calling thread's last batch call the host code computed or refused: all n below the threshold, else the
+ *                  rows the lane routed. */
+int32_t aleo_mi355x_record_plaintext_parse(const char* plaintext, int32_t* owner_kind, void* owner_x32, void* nonce_x32, uint64_t* microcredits);
+int32_t aleo_mi355x_plaintext_commitment(void* out32, const char* plaintext, const char* program_id, const char* record_name);
+int32_t aleo_mi355x_plaintexts_commitments(void* cm_out, uint64_t* microcredits, uint8_t* flags, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name);
+int32_t aleo_mi355x_plaintexts_commitments_host(void* cm_out, uint64_t* microcredits, uint8_t* flags, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name);
+int32_t aleo_mi355x_plaintexts_serial_numbers(void* sn_out, void* cm_out, uint64_t* microcredits, uint8_t* flags, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sig32, const void* spent32, size_t n_spent);
+int32_t aleo_mi355x_plaintexts_serial_numbers_host(void* sn_out, void* cm_out, uint64_t* microcredits, uint8_t* flags, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sig32, const void* spent32, size_t n_spent);
+size_t aleo_mi355x_min_plaintexts(void);
+size_t aleo_mi355x_plaintexts_last_routed(void);
 
 /* ---- account signatures: sign, the sign1… string, and many verifications in one call ---------------------------------------------------------------------------
  * The two account calls of the reference besides derivation, ownership and decryption (wasm/src/account/signature.rs:37-48 Signature::sign / verify,

@@ -1056,4 +1056,47 @@ inline Result<FoundRecords> unspent_named(const RecordBatch& batch, const std::s
   return {std::move(found), Error{0}};
 }
 
+// ---- record plaintext strings (wasm/src/record/record_plaintext.rs:45-82; aleo_mi355x_plaintexts_serial_numbers) ---------------------------------------------------
+// A batch of RecordPlaintext strings (RecordBatch::from_strings takes any strings): per string the commitment under (program_id, record_name), the microcredits
+// and, from plaintext_serial_numbers, the serial number under the account's sk_sig.  flags: 0 computed (and not in the spent set); 1 computed and spent; 2 the
+// serial number is refused; 3 not a record plaintext.  A row that is not computed is zeros.
+struct PlaintextRows {
+  std::vector<uint8_t> serials, commitments, flags; std::vector<uint64_t> microcredits;
+  const uint8_t* serial(size_t i) const { return serials.data() + 32 * i; }
+  const uint8_t* commitment(size_t i) const { return commitments.data() + 32 * i; }
+  size_t size() const { return flags.size(); }
+};
+inline Result<PlaintextRows> plaintext_commitments(const RecordBatch& batch, const std::string& program_id, const std::string& record_name) {
+  const size_t n = batch.size();
+  PlaintextRows out{{}, std::vector<uint8_t>(32 * n), std::vector<uint8_t>(n), std::vector<uint64_t>(n)};
+  int32_t rc = aleo_mi355x_plaintexts_commitments(out.commitments.data(), out.microcredits.data(), out.flags.data(), batch.text(), batch.offsets(), n, program_id.c_str(), record_name.c_str());
+  if (rc) return {std::nullopt, Error{rc}};
+  return {std::move(out), Error{0}};
+}
+inline Result<PlaintextRows> plaintext_serial_numbers(const RecordBatch& batch, const std::string& program_id, const std::string& record_name, const uint8_t* sk_sig32,
+                                                      const uint8_t* spent32 = nullptr, size_t n_spent = 0) {
+  const size_t n = batch.size();
+  PlaintextRows out{std::vector<uint8_t>(32 * n), std::vector<uint8_t>(32 * n), std::vector<uint8_t>(n), std::vector<uint64_t>(n)};
+  int32_t rc = aleo_mi355x_plaintexts_serial_numbers(out.serials.data(), out.commitments.data(), out.microcredits.data(), out.flags.data(), batch.text(), batch.offsets(), n, program_id.c_str(),
+                                                     record_name.c_str(), sk_sig32, spent32, n_spent);
+  if (rc) return {std::nullopt, Error{rc}};
+  return {std::move(out), Error{0}};
+}
+// the indices of the strings whose serial number computes and is not spent: "which of the plaintexts I hold are still unspent?"
+inline Result<std::vector<size_t>> plaintexts_unspent(const RecordBatch& batch, const std::string& program_id, const std::string& record_name, const PrivateAccount& account,
+                                                      const uint8_t* spent32 = nullptr, size_t n_spent = 0) {
+  auto rows = plaintext_serial_numbers(batch, program_id, record_name, account.sk_sig, spent32, n_spent);
+  if (!rows.is_ok()) return {std::nullopt, rows.error};
+  std::vector<size_t> keep;
+  for (size_t i = 0; i < rows.value->size(); ++i) if (!rows.value->flags[i]) keep.push_back(i);
+  return {std::move(keep), Error{0}};
+}
+// RecordPlaintext.fromString(..).microcredits(): refused unless the string is a record plaintext whose owner, nonce and group values are points of the subgroup
+inline Result<uint64_t> plaintext_microcredits(const std::string& plaintext) {
+  uint64_t mc = 0;
+  int32_t rc = aleo_mi355x_record_plaintext_parse(plaintext.c_str(), nullptr, nullptr, nullptr, &mc);
+  if (rc) return {std::nullopt, Error{rc}};
+  return {mc, Error{0}};
+}
+
 }  // namespace aleo_mi355x
