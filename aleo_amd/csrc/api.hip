@@ -643,6 +643,15 @@ int32_t aleo_mi355x_selftest_f28_rows(const void* a224, const void* b224, uint32
     return selftest_f28_rows(sl.c, a224, b224, n_add, out_pair224, out_quad224, acc224, pt112, n_madd, out_acc224, ok_u8);
   });
 }
+int32_t aleo_mi355x_selftest_te28_rows(const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224, uint32_t* z_add_u32,
+                                       const void* acc224, const void* row168, const uint8_t* how_u8, uint32_t n_madd, void* out_acc224, uint8_t* z_madd_u8) {
+  return guarded([&] {
+    if (n_add > (1u << 20) || n_madd > (1u << 20)) return bad_arg("selftest_te28_rows: at most 2^20 rows of either kind");
+    if ((n_add && (!a224 || !b224 || !out_pair224 || !out_quad224 || !z_add_u32)) || (n_madd && (!acc224 || !row168 || !how_u8 || !out_acc224 || !z_madd_u8))) return bad_arg("selftest_te28_rows: bad argument");
+    Slot sl; if (sl.rc) return sl.rc;
+    return selftest_te28_rows(sl.c, a224, b224, n_add, out_pair224, out_quad224, z_add_u32, acc224, row168, how_u8, n_madd, out_acc224, z_madd_u8);
+  });
+}
 
 int32_t aleo_mi355x_selftest_slice_order(const uint32_t* hist, uint32_t n_buckets, uint32_t total_pairs, int32_t fused, uint32_t* violations) {
   return guarded([&] { if (!hist || !violations) return ALEO_MI355X_ERR_BAD_ARG; Slot sl; if (sl.rc) return sl.rc; return selftest_slice_order(sl.c, hist, n_buckets, total_pairs, fused != 0, violations); });

@@ -71,7 +71,9 @@ struct PinnedBases {
   // optional fixed-base tables (msm_precompute): up to three tiers so that every call size against one SRS gets a window width
   // that suits it — the full set at c = 20 / 17, its first 2^17 points at c = 16, its first 2^15 points at c = 13.
   // Rows: W x cover x 112 bytes, row w holds 2^(c w) * P_i in the 28-bit-limb form (fp28.h); serves min_n <= n <= cover.
-  struct PreTable { void* d = nullptr; int c = 0; size_t cover = 0, min_n = 0; };
+  // te: the whole-set tier in twisted Edwards form (te28.h): rows (y - x | y + x | 2d x y) of the Edwards image at a 192-byte stride, the chain's partial sums
+  // and everything behind them extended Edwards points — unless a base of the set has no finite image, which keeps the tier in the XYZZ form.
+  struct PreTable { void* d = nullptr; int c = 0; size_t cover = 0, min_n = 0; bool te = false; size_t row = ROW28; };
   PreTable tab[3];
   // optional table over ONE sub-range [range_off, range_off + range.cover) with a narrow window (aleo_mi355x_bases_precompute_range): MSMs whose
   // scalars are mostly 0 / 1 (a witness in evaluation form against the Lagrange-basis powers) put too few points into the wide windows' buckets
@@ -228,6 +230,9 @@ int32_t selftest_addquad(Ctx* c, uint32_t ops, uint64_t seed, uint32_t* failures
 // selftest_f28.hip: the formulas of fp28.h on rows of raw limbs from the host (pair and quad additions, mixed additions), raw limbs back
 int32_t selftest_f28_rows(Ctx* c, const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224,
                           const void* acc224, const void* pt112, uint32_t n_madd, void* out_acc224, uint8_t* ok_u8);
+// selftest_te28.hip: the same for the Edwards-form formulas of te28.h
+int32_t selftest_te28_rows(Ctx* c, const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224, uint32_t* z_add_u32,
+                           const void* acc224, const void* row168, const uint8_t* how_u8, uint32_t n_madd, void* out_acc224, uint8_t* z_madd_u8);
 // msm_sort.hip: the slice stage (bucket scan, top scan, slice ordering) on a host histogram, checked against a host recount
 int32_t selftest_slice_order(Ctx* c, const uint32_t* h_hist, uint32_t M, uint32_t pairs, bool fused, uint32_t* violations);
 // g1_setup.hip: synthetic base sets, the fixed-base tables, row formats

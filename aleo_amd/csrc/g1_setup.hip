@@ -2,6 +2,7 @@
 // msm_precompute_range) and the row formats (104-byte Affine rows, 96-byte rows, the 28-bit rows the accumulation kernel of msm.hip gathers).
 #include "ec.h"
 #include "fp28.h"
+#include "te28.h"
 #include "msm_common.h"
 
 namespace aleo_mi355x {
@@ -193,26 +194,98 @@ int32_t make_rows28(Ctx* c, PinnedBases* pb) {
   return ALEO_MI355X_OK;
 }
 
-static int32_t build_table(Ctx* c, const PinnedBases* pb, int pre_c, size_t n, PinnedBases::PreTable* out, size_t off = 0) {
+// Affine rows (x | y, 32-bit Montgomery; (0, 0) marks the identity) -> the Edwards rows of te28.h: (y' - x' | y' + x' | 2d x' y') of the image
+// x' = f (x + 1) / y, y' = (u - 1) / (u + 1), u = s (x + 1)  (tools/te28_model.py).  The two divisions of a row share ONE inverse, of y (u + 1), and the rows
+// of a lane share one inversion by the prefix-product scheme of k_gen_normalize.  The identity becomes the row (1, 1, 0).  A point without a finite image
+// (y = 0 or u = -1: neither is in G1) raises *no_image and gets the identity's row; the caller then drops the table.
+__device__ __forceinline__ Fq fq_of(const uint32_t (&k)[12]) { Fq r; for (int i = 0; i < 12; ++i) r.v[i] = k[i]; return r; }
+__device__ __noinline__ void te_denominator(const AffinePt* p, Fq* up1, Fq* den, bool* plain) {      // plain: an ordinary point (not the identity's marker, with an image)
+  const Fq one = Fq::one(), s = fq_of(TE_S_32);
+  Fq x1 = Fq::add(p->x, one), u;
+  fq_mul_ni(&u, &s, &x1);
+  *up1 = Fq::add(u, one);
+  fq_mul_ni(den, &p->y, up1);
+  *plain = !(p->x.is_zero_raw() && p->y.is_zero_raw()) && !den->is_zero_mod();
+}
+__global__ void __launch_bounds__(256) k_rows_te(const char* __restrict__ src96, uint32_t n, char* __restrict__ prefix, char* __restrict__ dst, uint32_t* __restrict__ no_image) {
+  uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  uint64_t i0 = (uint64_t)t * GEN_K; if (i0 >= n) return;
+  uint32_t cnt = (uint32_t)((n - i0) < GEN_K ? (n - i0) : GEN_K);
+  const Fq one = Fq::one();
+  Fq prod = one;
+  for (uint32_t j = 0; j < cnt; ++j) {
+    store_fp<Fq>(prefix + (i0 + j) * 48, prod);
+    const AffinePt p = load_affine(src96 + (i0 + j) * 96);
+    Fq up1, den; bool plain;
+    te_denominator(&p, &up1, &den, &plain);
+    if (plain) fq_mul_ni(&prod, &prod, &den);
+  }
+  fq_inverse_ni(&prod);
+  const F28 one28 = te28_const(TE_ONE_28), zero28 = f28_const(Limbs14{});
+  for (uint32_t jj = cnt; jj-- > 0;) {
+    const AffinePt p = load_affine(src96 + (i0 + jj) * 96);
+    Fq up1, den; bool plain;
+    te_denominator(&p, &up1, &den, &plain);
+    char* out = dst + (i0 + jj) * TE_ROW;
+    if (!plain) {
+      if (!(p.x.is_zero_raw() && p.y.is_zero_raw())) atomicOr(no_image, 1u);
+      store_te28_row(out, one28, one28, zero28);
+      continue;
+    }
+    const Fq pre = load_fp<Fq>(prefix + (i0 + jj) * 48), f = fq_of(TE_F_32), k = fq_of(TE_K_32);
+    Fq inv, iy, iu, xe, ye, r2;
+    fq_mul_ni(&inv, &prod, &pre);            // 1 / (y (u + 1))
+    fq_mul_ni(&prod, &prod, &den);
+    fq_mul_ni(&iy, &inv, &up1);              // 1 / y
+    fq_mul_ni(&iu, &inv, &p.y);              // 1 / (u + 1)
+    const Fq x1 = Fq::add(p.x, one), um1 = Fq::sub<2>(up1, Fq::dbl(one));      // x + 1; u - 1 = (u + 1) + 2q - 2
+    fq_mul_ni(&xe, &f, &x1); fq_mul_ni(&xe, &xe, &iy);
+    fq_mul_ni(&ye, &um1, &iu);
+    fq_mul_ni(&r2, &xe, &ye); fq_mul_ni(&r2, &r2, &k);
+    store_te28_row(out, f28_from_fq(Fq::sub<2>(ye, xe)), f28_from_fq(Fq::add(ye, xe)), f28_from_fq(r2));      // products are < 2q: sums and differences < 4q
+  }
+}
+
+// A table row 2^k * P that is the identity although P is not: P has even order, so it is no point of G1.  The rows are affine and cannot hold the identity (the
+// sort drops identity BASES by their flags, not rows), so a table over such a set would add the marker (0, 0) as if it were a point: the set gets no tables.
+__global__ void __launch_bounds__(256) k_rows_vanished(const char* __restrict__ row96, const uint8_t* __restrict__ inf, uint32_t n, uint32_t* __restrict__ vanished) {
+  uint32_t i = blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
+  const AffinePt p = load_affine(row96 + (size_t)i * 96);
+  if (p.x.is_zero_raw() && p.y.is_zero_raw() && !(inf && inf[i])) atomicOr(vanished, 1u);
+}
+
+// te: the rows in twisted Edwards form (k_rows_te).  A set with a base that has no Edwards image gets the XYZZ rows after all — and, like any set with a base of
+// even order whose multiples reach the identity inside the table, no table (out->d stays null, the status is OK: the set multiplies on the plain path).
+static int32_t build_table(Ctx* c, const PinnedBases* pb, int pre_c, size_t n, PinnedBases::PreTable* out, size_t off = 0, bool te = false) {
   const uint32_t W = (SCALAR_BITS + pre_c - 1) / pre_c;
   if (n * (size_t)W >= (1ull << 31)) { g_last_error = "bases_precompute: table index would exceed 31 bits"; return ALEO_MI355X_ERR_BAD_ARG; }
-  DevTmp tab, cur, prefix, row; int32_t rc;     // freed on every return path; tab is handed over at the end
-  if ((rc = tab.alloc(n * ROW28 * W))) return rc;                              // rows in the accumulation kernel's 28-bit format (fp28.h)
-  if ((rc = cur.alloc(n * 192)) || (rc = prefix.alloc(n * 48)) || (rc = row.alloc(n * 96))) return rc;
+  const size_t stride = te ? TE_ROW : ROW28;
+  DevTmp tab, cur, prefix, row, flag; int32_t rc;     // freed on every return path; tab is handed over at the end
+  if ((rc = tab.alloc(n * stride * W))) return rc;                             // rows in the accumulation kernel's 28-bit formats (fp28.h, te28.h)
+  if ((rc = cur.alloc(n * 192)) || (rc = prefix.alloc(n * 48)) || (rc = row.alloc(n * 96)) || (rc = flag.alloc(8))) return rc;
   hipStream_t s = c->stream;
   const uint32_t g = (uint32_t)((n + 255) / 256), lanes = (uint32_t)((n + GEN_K - 1) / GEN_K), gl = (lanes + 255) / 256;
   const char* xy = (const char*)pb->d_xy + off * 96;      // the table covers points [off, off + n) of the set
-  if (pb->d_xy28) HIPCHK(hipMemcpyAsync(tab.p, (const char*)pb->d_xy28 + off * ROW28, n * ROW28, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemsetAsync(flag.p, 0, 8, s));
+  const uint8_t* inf = pb->d_inf ? pb->d_inf + off : nullptr;
+  if (te) hipLaunchKernelGGL(k_rows_te, dim3(gl), dim3(256), 0, s, xy, (uint32_t)n, (char*)prefix.p, (char*)tab.p, (uint32_t*)flag.p);
+  else if (pb->d_xy28) HIPCHK(hipMemcpyAsync(tab.p, (const char*)pb->d_xy28 + off * ROW28, n * ROW28, hipMemcpyDeviceToDevice, s));
   else hipLaunchKernelGGL(k_rows_to28, dim3(g), dim3(256), 0, s, xy, (char*)tab.p, (uint32_t)n);
   hipLaunchKernelGGL(k_pre_init, dim3(g), dim3(256), 0, s, xy, (uint32_t)n, (char*)cur.p);
   for (uint32_t w = 1; w < W; ++w) {
     hipLaunchKernelGGL(k_pre_double, dim3(g), dim3(256), 0, s, (char*)cur.p, (uint32_t)n, win_width(pre_c, (int)w - 1));      // row w = 2^win_offset(w) * P
     hipLaunchKernelGGL(k_gen_normalize, dim3(gl), dim3(256), 0, s, (char*)cur.p, (uint32_t)n, (char*)prefix.p, (char*)row.p);
-    hipLaunchKernelGGL(k_rows_to28, dim3(g), dim3(256), 0, s, (const char*)row.p, (char*)tab.p + (size_t)w * n * ROW28, (uint32_t)n);
+    hipLaunchKernelGGL(k_rows_vanished, dim3(g), dim3(256), 0, s, (const char*)row.p, inf, (uint32_t)n, (uint32_t*)flag.p + 1);
+    if (te) hipLaunchKernelGGL(k_rows_te, dim3(gl), dim3(256), 0, s, (const char*)row.p, (uint32_t)n, (char*)prefix.p, (char*)tab.p + (size_t)w * n * stride, (uint32_t*)flag.p);
+    else hipLaunchKernelGGL(k_rows_to28, dim3(g), dim3(256), 0, s, (const char*)row.p, (char*)tab.p + (size_t)w * n * stride, (uint32_t)n);
   }
   HIPCHK(hipGetLastError());
+  uint32_t flags[2] = {0, 0};      // [0] a base without an Edwards image, [1] a row that vanished
+  HIPCHK(hipMemcpyAsync(flags, flag.p, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  out->d = tab.release(); out->c = pre_c; out->cover = n;
+  if (flags[1]) { *out = PinnedBases::PreTable(); return ALEO_MI355X_OK; }
+  if (te && flags[0]) { (void)hipFree(tab.release()); return build_table(c, pb, pre_c, n, out, off, false); }
+  out->d = tab.release(); out->c = pre_c; out->cover = n; out->te = te; out->row = stride;
   return ALEO_MI355X_OK;
 }
 
@@ -224,16 +297,16 @@ int32_t msm_precompute(Ctx* c, PinnedBases* pb) {
   if (pb->tabled || pb->n == 0) return ALEO_MI355X_OK;
   const size_t N = pb->n; int32_t rc = ALEO_MI355X_OK; int k = 0;
   auto lim = [&](size_t cap) { return N < cap ? N : cap; };
-  auto tier = [&](int cbits, size_t cover, size_t min_n) {
+  auto tier = [&](int cbits, size_t cover, size_t min_n, bool te = false) {
     if (rc) return;
-    if ((rc = build_table(c, pb, cbits, cover, &pb->tab[k])) == ALEO_MI355X_OK) pb->tab[k++].min_n = min_n;
+    if ((rc = build_table(c, pb, cbits, cover, &pb->tab[k], 0, te)) == ALEO_MI355X_OK && pb->tab[k].d) pb->tab[k++].min_n = min_n;      // (no table: a base of even order — see k_rows_vanished)
   };
   // Prefix tiers reach TIER_SLACK points past their power of two: a committer key is a power of two of powers FOLLOWED by a few hiding
   // powers, and commitments that touch those (every hiding one) would otherwise fall through to the next wider window (2x the buckets per
   // result: with 25 results in a chain, as many as a batch of 8 instances commits in its first round, most of the reduction time).
   constexpr size_t TIER_SLACK = 64;
   const size_t cover16 = lim(((size_t)1 << 17) + TIER_SLACK), cover13 = lim(((size_t)1 << 15) + TIER_SLACK);
-  if (N > cover16) tier(N >= (1u << 19) ? 20 : 17, N, cover16 + 1);      // up to cover16 points the c = 16 tier is faster (2^17: 0.90 vs 1.18 ms)
+  if (N > cover16) tier(N >= (1u << 19) ? 20 : 17, N, cover16 + 1, true);      // up to cover16 points the c = 16 tier is faster (2^17: 0.90 vs 1.18 ms); the whole-set tier alone is in Edwards form
   if (N >= (1u << 15)) tier(16, cover16, (size_t)1 << 15);
   if (N >= (1u << 10)) tier(13, cover13, (size_t)1 << 10);
   if (rc) {                                     // a later tier failed (out of memory): give back the ones already built
@@ -248,7 +321,7 @@ int32_t msm_precompute_range(Ctx* c, PinnedBases* pb, size_t off, size_t n, int 
   if (pb->range.d) { g_last_error = "bases_precompute_range: this set already has a range table"; return ALEO_MI355X_ERR_BAD_ARG; }
   if (!n || off + n > pb->n || (window_bits != 13 && window_bits != 16)) { g_last_error = "bases_precompute_range: bad range or window (13 or 16 bits)"; return ALEO_MI355X_ERR_BAD_ARG; }
   int32_t rc = build_table(c, pb, window_bits, n, &pb->range, off);
-  if (rc) return rc;
+  if (rc || !pb->range.d) return rc;      // (no table: a base of even order in the range — the calls take the other paths)
   pb->range.min_n = 0; pb->range_off = off;
   return ALEO_MI355X_OK;
 }

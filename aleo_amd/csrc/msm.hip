@@ -17,7 +17,9 @@
 //             window sums go to the host for the 2^c Horner chain (~250 dependent doublings are ~0.1 ms on a host core, ~4 ms on one GPU lane).
 // HBM layout: bases n x 96 B (x|y Montgomery, AoS so a gathered point is 1-2 cache lines), their 28-bit rows and the tables' W x n x 128 B; sorted stream n*W x 4 B; partial sums
 // #slices x 192 B (XYZZ) or 224 B (28-bit XYZZ).  Algorithmic bytes per point: 32 (scalar) + 96 (base).
-#include "msm_reduce.h"
+#include "msm_table.h"
+#include "msm_te.h"
+#include "te28_host.hpp"
 
 namespace aleo_mi355x {
 
@@ -41,10 +43,6 @@ __device__ __noinline__ void slice_slow_path28(const char* bases, const uint32_t
   *acc_out = acc; *inf_out = inf;
 }
 
-__device__ __forceinline__ const char* chain_sum(const FrontChain& ch, uint32_t g) {
-  for (uint32_t i = 0; i < ch.n; ++i) if (ch.v[i].hist[g]) return ch.v[i].partial + (size_t)scan_at(ch.v[i].scan_local, ch.v[i].scan_blk, g).y * 224u;
-  return nullptr;
-}
 
 template <bool OUT28, bool SEED = false>
 __global__ void __launch_bounds__(256) k_accum28(const char* __restrict__ bases, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ hist,
@@ -96,95 +94,24 @@ __global__ void __launch_bounds__(256) k_accum28(const char* __restrict__ bases,
   }
 }
 
-// Every kernel from here to the host tail is a chain of full XYZZ additions with little parallelism, so each addition
-// is shared by a lane pair (ec.h xyzz_add_pair: same work, half the latency).  "op" below = pair index = thread / 2.
-__device__ __forceinline__ void pair_fence() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
-template <bool F28> using PtFmt = std::conditional_t<F28, Pt28, Pt32>;      // the formats: msm_reduce.h
-template <uint32_t LANES, uint32_t BYTES> __device__ __forceinline__ void grp_copy(const char* src, char* dst) {      // BYTES / LANES per lane
-  const uint32_t o = (threadIdx.x & (LANES - 1)) * (BYTES / LANES);
-  const uint2* s2 = (const uint2*)(src + o); uint2* d2 = (uint2*)(dst + o);
-#pragma unroll
-  for (int i = 0; i < (int)(BYTES / LANES / 8); ++i) d2[i] = s2[i];
-}
-template <uint32_t LANES, uint32_t BYTES> __device__ __forceinline__ void grp_zero(char* dst) {
-  uint2* d2 = (uint2*)(dst + (threadIdx.x & (LANES - 1)) * (BYTES / LANES));
-#pragma unroll
-  for (int i = 0; i < (int)(BYTES / LANES / 8); ++i) d2[i] = make_uint2(0, 0);
-}
-// lanes per addition for a launch of `ops` independent additions: quads up to two waves per SIMD (2^17 lanes), pairs beyond.  Measured: k_seg_fold 90 -> 57 us,
-// k_tree_pass 15 -> 11 us, a 2^15-constraint proof 6.9 -> 6.6 ms; with the cut at 2^16 lanes the proof is at 6.8 ms.  (The 2^15-chunk kernel of the
-// widest window is the exception: 2^17 quad lanes take what 2^16 pair lanes take, 330 against 321 us — it keeps the pair form.)
-static constexpr uint32_t QUAD_MAX_LG = 17;  // lg of the most quad lanes a launch may have
-static constexpr uint32_t ASIDE_MAX = 8;  // super-heavy buckets whose slice trees may run beside the reduction (msm_run)
-static inline uint32_t grp_lanes(uint64_t ops) { return ops * 4 <= ((uint64_t)1 << QUAD_MAX_LG) ? 4u : 2u; }
-// One launch of `ops` independent additions on `lanes` lanes each: the quad (k4) or the pair (k2) instantiation of a kernel, blocks of 256 threads.
-template <class... KA, class... A>
-static void launch_grp(uint32_t lanes, void (*k4)(KA...), void (*k2)(KA...), uint64_t ops, hipStream_t s, A... args) {
-  hipLaunchKernelGGL(lanes == 4 ? k4 : k2, dim3((uint32_t)((lanes * ops + 255) / 256)), dim3(256), 0, s, args...);
-}
-// What is left of the common list's trees after the first level (at most 4 partial sums per bucket when no bucket had more than 8 slices) folded by ONE launch:
-// a lane quad per multi-slice bucket adds its partials 1.. into partial 0 one after the other.  Two or three dependent additions of ~7 us inside one launch
-// instead of two launches of one level each (~10 us of launch floor + its addition per level): the chains of real-circuit-sized proofs are made of such steps.
+// (the kernels below are msm_table.h's bodies for 28-bit XYZZ points; msm_te.hip holds the Edwards tier's)
 template <uint32_t LANES>
 __global__ void __launch_bounds__(256) k_tree_rest(char* __restrict__ partial, const uint32_t* __restrict__ list, uint32_t list_len, const uint2* __restrict__ scan_local,
                                                    const uint2* __restrict__ scan_blk, uint32_t M, const uint32_t* __restrict__ meta) {
-  constexpr uint32_t PB = Pt28::BYTES;
-  const uint32_t h = (blockIdx.x * 256 + threadIdx.x) >> lg_lanes(LANES);
-  if (h >= list_len) return;
-  const uint32_t g = list[h];
-  const uint32_t ft = scan_at(scan_local, scan_blk, g).y, fn = (g + 1 < M) ? scan_at(scan_local, scan_blk, g + 1).y : meta[0];
-  const uint32_t L1 = (fn - ft + 1) >> 1;                   // partial sums the first level left at ft .. ft + L1 - 1
-  char* pa = partial + (size_t)ft * PB;
-  for (uint32_t i = 1; i < L1; ++i) Pt28::add<LANES>(pa, pa + (size_t)i * PB, pa);
+  tree_rest_body<Pt28, LANES>(partial, list, list_len, scan_local, scan_blk, M, meta);
 }
 
-// The sums of slices 1.. of the super-heavy buckets (k_tree_pass with skip_b = 1 left them in slice 1) and the buckets' numbers, to the host.
 __global__ void k_gather_super(const char* __restrict__ partial, const uint32_t* __restrict__ list, uint32_t len, const uint2* __restrict__ scan_local,
                                const uint2* __restrict__ scan_blk, uint32_t* __restrict__ dst) {
-  constexpr uint32_t PW = Pt28::WORDS;
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x, h = t / (PW + 1), w = t % (PW + 1);
-  if (h >= len) return;
-  const uint32_t g = list[h];
-  dst[h * (PW + 1) + w] = w == PW ? g : ((const uint32_t*)(partial + (size_t)(scan_at(scan_local, scan_blk, g).y + 1) * Pt28::BYTES))[w];
+  gather_super_body(partial, list, len, scan_local, scan_blk, dst, nullptr);
 }
 
-// ---- bucket reduction -----------------------------------------------------------------------------
-// One lane QUAD per chunk of S consecutive buckets: running sums run_k = run_{k-1} + S_b (b descending) and acc += run_{k-1}
-// are independent once run_{k-1} exists, so two lane pairs work one step apart (S + 1 dependent additions instead of 2S):
-// sub-pair 0 extends the running sum (double-buffered in LDS), sub-pair 1 folds the previous one into acc.  Both make the
-// SAME addition call with per-lane pointers (a branch per sub-pair would serialise them inside the wave).
-// acc = sum_{b in chunk} (b - base + 1) * S_b and run = chunk total go to HBM (V, Vrun); the chunk weights are applied by
-// masked sums (fixed-base path).
-static constexpr uint32_t CHUNK_QUADS = 64;         // chunks per 256-thread block (LANES = 2: two lane pairs per chunk; 32 with LANES = 4: two lane quads)
+template <bool F28> using PtFmt = std::conditional_t<F28, Pt28, Pt32>;      // the formats: msm_reduce.h
 template <bool F28, uint32_t LANES = 2>
 __global__ void __launch_bounds__(256) k_bucket_chunks(const char* __restrict__ partial, const uint32_t* __restrict__ hist, const uint2* __restrict__ scan_local,
                                                        const uint2* __restrict__ scan_blk, uint32_t B, uint32_t S, uint32_t nchunks_total, char* __restrict__ V,
                                                        uint32_t v_set_stride, char* __restrict__ Vrun, FrontChain older) {
-  constexpr uint32_t PB = PtFmt<F28>::BYTES, PW = PtFmt<F28>::WORDS;
-  constexpr uint32_t CPB = 128 / LANES;                  // chunks per block: two groups of LANES lanes each
-  __shared__ __attribute__((aligned(16))) uint32_t lds[(3 * CPB + 1) * PW];
-  const uint32_t qd = threadIdx.x >> (lg_lanes(LANES) + 1), sp = (threadIdx.x >> lg_lanes(LANES)) & 1u, t = blockIdx.x * CPB + qd;
-  char* zero = (char*)(lds + 3 * CPB * PW);
-  if (threadIdx.x < LANES) grp_zero<LANES, PB>(zero);
-  __syncthreads();
-  if (t >= nchunks_total) return;
-  char* buf0 = (char*)(lds + (3 * qd) * PW); char* buf1 = buf0 + PB; char* acc = buf1 + PB;
-  grp_zero<LANES, PB>(sp ? acc : buf0); if (!sp) grp_zero<LANES, PB>(buf1);
-  pair_fence();
-  const uint32_t cpw = B / S, w = t / cpw, j = t % cpw, g0 = w * B + j * S;
-  // the address of the next bucket's sum (two dependent loads: histogram, scan) is fetched one step ahead of the addition that uses it
-  auto sum_of = [&](uint32_t g) -> const char* { if (hist[g]) return partial + (size_t)scan_at(scan_local, scan_blk, g).y * PB; const char* o = chain_sum(older, g); return o ? o : zero; };
-  const char* nxt = sp ? zero : sum_of(g0 + S - 1);
-  for (uint32_t k = 0; k <= S; ++k) {
-    char* rprev = (k & 1) ? buf0 : buf1; char* rnext = (k & 1) ? buf1 : buf0;      // run_k lives in buf[k & 1]; run_{-1} = 0
-    const char* add = k < S ? nxt : zero;
-    nxt = (!sp && k + 1 < S) ? sum_of(g0 + S - 2 - k) : zero;
-    const char* pa = sp ? acc : rprev; const char* pb = sp ? rprev : add; char* out = sp ? acc : rnext;
-    PtFmt<F28>::template add<LANES>(pa, pb, out);
-    pair_fence();
-  }
-  // after step S: buf[S & 1] holds run_{S-1} again (step S copied it forward), acc holds sum_k run_k
-  grp_copy<LANES, PB>(sp ? acc : ((S & 1) ? buf1 : buf0), sp ? V + ((size_t)w * v_set_stride + j) * PB : Vrun + (size_t)t * PB);
+  bucket_chunks_body<PtFmt<F28>, LANES>(partial, hist, scan_local, scan_blk, B, S, nchunks_total, V, v_set_stride, Vrun, older, 0u);
 }
 
 // Plain path (one window set per window): one lane per chunk, V = sum_{b in chunk} (b+1) * S_b with the chunk base applied
@@ -225,7 +152,6 @@ __global__ void __launch_bounds__(256) k_bucket_chunks_plain(const char* __restr
 // ins_l(x) = x with a 1 inserted at bit l.  The remaining levels are k_seg_pair_pass / k_seg_fold; the 2^l Horner runs
 // on the host.
 // (These kernels only run on the table path, whose points are 224-byte 28-bit XYZZ: PB below.)
-static constexpr uint32_t PB28 = 224, PW28 = 56;
 // Sets (batched calls): set q reads Vrun[q * 2^lgN ...] and writes its lgN sums behind its chunk sums, at
 // V[q * v_set_stride + 2^lgN ...] (v_set_stride = (lgN + 4) * 2^(lgN-2): the set's 4 + lgN segments are contiguous).
 template <uint32_t LANES>
@@ -240,7 +166,6 @@ __global__ void __launch_bounds__(256) k_masked_pairs(const char* __restrict__ V
 }
 // One block folds up to 256 consecutive points of one segment into a single point: 8 tree levels through two LDS
 // buffers, 128 lane pairs — the latency floor of the chain with no launch gaps.
-static constexpr uint32_t FOLD = 256;
 // (the block has FOLD / 2 lane groups: 256 threads as pairs, 512 as quads — the quad form halves the latency of each of the 8 levels)
 template <uint32_t LANES>
 __global__ void __launch_bounds__(128 * LANES) k_seg_fold(const char* __restrict__ in, uint32_t in_stride, uint32_t L, uint32_t nseg,
@@ -277,92 +202,22 @@ __global__ void __launch_bounds__(256) k_seg_pair_pass(const char* __restrict__ 
   char* dst = out + ((size_t)seg * out_stride + i) * PB28;
   if (2 * i + 1 < L) Pt28::add<LANES>(src, src + PB28, dst); else grp_copy<LANES, PB28>(src, dst);
 }
-// ---- the chunk weights by ONE sum tree (wide tables, round 3) -------------------------------------------------------------------------------------
-// sum_j j * run_j = sum_l 2^l T_l, T_l = the sum of run_j over the j with bit l set.  k_masked_pairs builds every T_l as its own tree over half of
-// the chunks: lg(N) / 2 additions per chunk.  But T_l is also the sum of the RIGHT children of level l of the plain sum tree over the chunks — so one
-// pairwise pass per level does it all: node'[i] = node[2i] + node[2i+1], the odd nodes node[2i+1] start the segment T_l, and every segment born
-// earlier (T_0 .. T_{l-1}, and A = the chunks' own weighted sums acc_j) is halved the same way.  After pass s every segment is N / 2^(s+1) long:
-// (s + 3) N / 2^(s+1) additions per pass, 3 N in all instead of (lg N + 4) N / 2 — which is what lets the chunks shrink (fewer dependent additions
-// in k_bucket_chunks) without the weights paying for it.  Layout of a set after pass s: [node | A | T_0 | ... | T_s], contiguous.
+// The chunk weights by ONE sum tree (msm_table.h prog_pass_body, prog_pass2_body, prog_final_body)
 template <uint32_t LANES>
 __global__ void __launch_bounds__(256) k_prog_pass(const char* __restrict__ node, uint32_t node_set_stride, const char* __restrict__ A, uint32_t a_set_stride,
                                                    const char* __restrict__ T, uint32_t t_set_stride, uint32_t nT, uint32_t L, uint32_t nsets,
                                                    char* __restrict__ out, uint32_t out_set_stride) {
-  const uint32_t half = L >> 1, per_set = (2 + nT) * half;
-  const uint32_t op = (blockIdx.x * 256 + threadIdx.x) >> lg_lanes(LANES);
-  if (op >= per_set * nsets) return;
-  const uint32_t q = op / per_set, r = op % per_set, g = r / half, i = r % half;
-  const char* src = g == 0 ? node + ((size_t)q * node_set_stride + 2 * i) * PB28
-                  : g == 1 ? A + ((size_t)q * a_set_stride + 2 * i) * PB28
-                           : T + ((size_t)q * t_set_stride + (size_t)(g - 2) * L + 2 * i) * PB28;
-  char* dst = out + ((size_t)q * out_set_stride + (size_t)g * half + i) * PB28;
-  Pt28::add<LANES>(src, src + PB28, dst);
-  if (g == 0) grp_copy<LANES, PB28>(src + PB28, out + ((size_t)q * out_set_stride + (size_t)(2 + nT) * half + i) * PB28);      // T_s is born: the right children of this level
+  prog_pass_body<Pt28, LANES>(node, node_set_stride, A, a_set_stride, T, t_set_stride, nT, L, nsets, out, out_set_stride, nullptr);
 }
-// TWO levels in one launch while the passes are latency-bound (lane quads): an octet of lanes per four consecutive points of a segment.  Step 1: quad 0 adds points
-// 0 + 1, quad 1 adds 2 + 3, into LDS; step 2: quad 0 adds the two halves (the point of the segment two levels up) while quad 1, on the node segment, adds points
-// 1 + 3 (T_nT, born at the first of the two levels, already halved by the second) and copies 2 + 3 out (T_(nT+1), born at the second).  Same sums as two k_prog_pass
-// launches — the grouping of the additions differs, the points they represent do not — for two dependent additions and ONE launch instead of two and two:
-// ~9 us less per pair of levels (a launch boundary costs about as much as a lane-quad addition).  Output layout as after two single passes:
-// [node | A | T_0 .. T_(nT-1) | T_nT | T_(nT+1)], every segment L / 4 long.
 __global__ void __launch_bounds__(256) k_prog_pass2(const char* __restrict__ node, uint32_t node_set_stride, const char* __restrict__ A, uint32_t a_set_stride,
                                                     const char* __restrict__ T, uint32_t t_set_stride, uint32_t nT, uint32_t L, uint32_t nsets,
                                                     char* __restrict__ out, uint32_t out_set_stride) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[(2 * 32 + 1) * PW28];
-  char* zero = (char*)(lds + 64 * PW28);
-  if (threadIdx.x < 4) grp_zero<4, PB28>(zero);
-  __syncthreads();
-  const uint32_t quarter = L >> 2, per_set = (2 + nT) * quarter;
-  const uint32_t oct = threadIdx.x >> 3, y = (threadIdx.x >> 2) & 1u, op = blockIdx.x * 32 + oct;
-  if (op >= per_set * nsets) return;
-  const uint32_t q = op / per_set, r = op % per_set, g = r / quarter, i = r % quarter;
-  const char* src = g == 0 ? node + ((size_t)q * node_set_stride + 4 * i) * PB28
-                  : g == 1 ? A + ((size_t)q * a_set_stride + 4 * i) * PB28
-                           : T + ((size_t)q * t_set_stride + (size_t)(g - 2) * L + 4 * i) * PB28;
-  char* slot = (char*)(lds + (2 * oct) * PW28);
-  Pt28::add<4>(src + (size_t)(2 * y) * PB28, src + (size_t)(2 * y + 1) * PB28, slot + y * PB28);
-  pair_fence();
-  char* base = out + (size_t)q * out_set_stride * PB28;
-  const bool born = y && g == 0;
-  const char* pa = y ? (born ? src + PB28 : zero) : slot;
-  const char* pb = y ? (born ? src + 3 * PB28 : zero) : slot + PB28;
-  char* dst = y ? (born ? base + ((size_t)(2 + nT) * quarter + i) * PB28 : zero) : base + ((size_t)g * quarter + i) * PB28;      // (an idle quad: 0 + 0 onto the zero point, nothing is written)
-  Pt28::add<4>(pa, pb, dst);
-  if (born) grp_copy<4, PB28>(slot + PB28, base + ((size_t)(3 + nT) * quarter + i) * PB28);
+  prog_pass2_body<Pt28>(node, node_set_stride, A, a_set_stride, T, t_set_stride, nT, L, nsets, out, out_set_stride, nullptr);
 }
-// The last levels, one block per result point: A and every T_l already born are plain folds of their (<= 256-point) segments; the weights of the
-// remaining lg L bits come from the node segment itself, T_(nT + b) = the sum of the nodes whose index has bit b set.  Output point o of set q:
-// 0 = A, 1 + l = T_l.
 template <uint32_t LANES>
 __global__ void __launch_bounds__(128 * LANES) k_prog_final(const char* __restrict__ in, uint32_t in_set_stride, uint32_t L, uint32_t nT, uint32_t lgL, uint32_t nsets,
                                                             char* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[2][(FOLD / 2) * PW28];
-  const uint32_t per_set = 1 + nT + lgL, q = blockIdx.x / per_set, o = blockIdx.x % per_set, pr = threadIdx.x >> lg_lanes(LANES);
-  if (q >= nsets) return;
-  const char* set = in + (size_t)q * in_set_stride * PB28;
-  {
-    char* dst = (char*)(lds[0] + pr * PW28);
-    if (o <= nT) {                                         // plain fold of segment 1 (A) or 2 + (o - 1) (T_{o-1})
-      const char* seg = set + (size_t)(o == 0 ? 1 : 1 + o) * L * PB28; const uint32_t e0 = 2 * pr;
-      if (e0 + 1 < L) Pt28::add<LANES>(seg + (size_t)e0 * PB28, seg + (size_t)(e0 + 1) * PB28, dst);
-      else if (e0 < L) grp_copy<LANES, PB28>(seg + (size_t)e0 * PB28, dst);
-      else grp_zero<LANES, PB28>(dst);
-    } else {                                               // bit b of the node index: the L / 2 nodes that have it set, in pairs
-      const uint32_t b = o - 1 - nT;
-      auto ins = [&](uint32_t x) { return ((x >> b) << (b + 1)) | (1u << b) | (x & ((1u << b) - 1u)); };
-      if (L >= 4 && 4 * pr + 3 < L) Pt28::add<LANES>(set + (size_t)ins(2 * pr) * PB28, set + (size_t)ins(2 * pr + 1) * PB28, dst);
-      else if (L == 2 && pr == 0) grp_copy<LANES, PB28>(set + PB28, dst);
-      else grp_zero<LANES, PB28>(dst);
-    }
-  }
-  uint32_t cur = 0;
-  for (uint32_t n = FOLD / 2; n > 1; n >>= 1) {
-    __syncthreads();
-    if (pr < (n >> 1)) Pt28::add<LANES>((const char*)(lds[cur] + (2 * pr) * PW28), (const char*)(lds[cur] + (2 * pr + 1) * PW28), (char*)(lds[cur ^ 1] + pr * PW28));
-    cur ^= 1;
-  }
-  __syncthreads();
-  if (pr == 0) grp_copy<LANES, PB28>((const char*)lds[cur], out + ((size_t)q * per_set + o) * PB28);
+  prog_final_body<Pt28, LANES>(in, in_set_stride, L, nT, lgL, nsets, out, nullptr, nullptr);
 }
 __global__ void k_gather_strided(const char* __restrict__ V, uint32_t stride, uint32_t count, char* __restrict__ out) {
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -398,11 +253,12 @@ int32_t msm_front_sort(Ctx* c, const PinnedBases& pb, const MsmJob& job, hipStre
     if (d_inf) d_inf += pb.range_off;
   } else T = msm_tier(pb, n);
   const bool pre = f.pre = T != nullptr;
+  f.te = pre && T->te;
   if (K > 1 && (!pre || K > (ranged ? msm_range_sets(pb) : msm_max_sets(pb, n)))) { g_last_error = "msm: internal: batch without a table tier (or too many sets)"; return ALEO_MI355X_ERR_BAD_ARG; }
   MsmPlan& P = f.P; P = make_plan(pre ? n : pts, pre ? T->c : 0);
   if (pre) { P.W = K; P.M = K * P.B; }                       // after the sort a set is "a window with its own buckets"
   if (!pre && !pb.d_xy28) { g_last_error = "msm: pinned set without 28-bit rows"; return ALEO_MI355X_ERR_HIP; }
-  f.bases = (const char*)(pre ? T->d : pb.d_xy28);          // 112-byte rows either way
+  f.bases = (const char*)(pre ? T->d : pb.d_xy28);          // 112-byte rows, or the Edwards tier's 168-byte ones (f.te)
   f.plain_tree = k_tree_pass<Pt32, 2>;
   const uint32_t cpw = f.cpw = P.B / P.S, nchunks = f.nchunks = cpw * P.W;
   uint32_t lgN = 0; while ((1u << lgN) < cpw) ++lgN;
@@ -419,7 +275,7 @@ int32_t msm_front_sort(Ctx* c, const PinnedBases& pb, const MsmJob& job, hipStre
   f.prog = masked && P.c >= SUM_TREE_MIN_C && cpw > FOLD;      // (a set of <= 256 chunks would go straight to the final fold: the masked form keeps those)
   f.out_pts = f.prog ? 1 + lgN : fseg;                        // sum tree: sum_j acc_j and the lgN weights T_l; masked trees: every one of the set's segments
   f.vpoints = masked ? (size_t)K * setw + nchunks + (nseg + 1) + (size_t)nseg * (tseg / 2 + tseg / 4 + 2) + 3 * (size_t)nchunks + 64 : (size_t)nchunks + P.W;      // + the two buffers of the sum-tree passes (3 cpw / 2 points per set each)
-  if ((rc = ensure_host_pinned(c, 64 + (size_t)(masked ? nseg : P.W) * 224 + ASIDE_MAX * 228))) return rc;      // before the sort phase: its read-back lands in this buffer
+  if ((rc = ensure_host_pinned(c, 64 + (size_t)(masked ? nseg : P.W) * 224 + ASIDE_MAX * 228 + 64 + (size_t)nseg * 4))) return rc;      // before the sort phase: its read-back lands in this buffer (behind the aside records: the Edwards tier's flag words)
   SortPhase& sp = f.sp;
   if ((rc = msm_sort_phase(c, segs, pts, job.mont, d_inf, (uint32_t)(pre ? T->cover : pb.n), P, pre, s, &sp, f.lean))) return rc;
   const uint32_t M = sp.M;
@@ -435,7 +291,8 @@ int32_t msm_front_accum(Ctx* c, hipStream_t s, Front& f, const FrontChain* seed,
   if (!f.lean) HIPCHK(hipEventRecord(c->ev[6], s));          // ev[6]..ev[5] bracket k_accum28 alone (bench.py's roofline kernel)
   const bool seeded = f.pre && seed && seed->n;
   auto* const kern = seeded ? k_accum28<true, true> : f.pre ? k_accum28<true, false> : k_accum28<false, false>;
-  hipLaunchKernelGGL(kern, dim3(sp.slice_blocks), dim3(256), 0, s, bases, sp.sorted, sp.hist, sp.scan_local, sp.scan_blk, sp.total_pairs, M, sp.meta, sp.order, sp.task_g, partial, seeded ? *seed : FrontChain{});
+  if (f.te) te_accum(seeded, s, bases, sp, partial, seeded ? *seed : FrontChain{});
+  else hipLaunchKernelGGL(kern, dim3(sp.slice_blocks), dim3(256), 0, s, bases, sp.sorted, sp.hist, sp.scan_local, sp.scan_blk, sp.total_pairs, M, sp.meta, sp.order, sp.task_g, partial, seeded ? *seed : FrontChain{});
   if (!f.lean) HIPCHK(hipEventRecord(c->ev[5], s));
   HIPCHK(hipGetLastError());
   return ALEO_MI355X_OK;
@@ -457,11 +314,13 @@ int32_t msm_front_finish(Ctx* c, hipStream_t s, Front& f, bool allow_aside) {
     HIPCHK(hipStreamWaitEvent(c->side, c->ev[5], 0));
     for (uint32_t pass = 0, L = sm.max_m - 1; L > 1; ++pass, L = (L + 1) >> 1) {
       const uint64_t ops = (uint64_t)sm.n_super * (L >> 1);
-      launch_grp(grp_lanes(ops), k_tree_pass<Pt28, 4>, k_tree_pass<Pt28, 2>, ops, c->side, partial, heavy, 0u, 0u, sp.super_list, sm.n_super, L >> 1, scan_local, scan_blk, M, meta, pass, 1u);
+      if (f.te) te_tree_pass(grp_lanes(ops), ops, c->side, partial, heavy, 0u, 0u, sp.super_list, sm.n_super, L >> 1, sp, pass, 1u);
+      else launch_grp(grp_lanes(ops), k_tree_pass<Pt28, 4>, k_tree_pass<Pt28, 2>, ops, c->side, partial, heavy, 0u, 0u, sp.super_list, sm.n_super, L >> 1, scan_local, scan_blk, M, meta, pass, 1u);
     }
     uint32_t* dst = nullptr;
     HIPCHK(hipHostGetDevicePointer((void**)&dst, h_aside, 0));
-    hipLaunchKernelGGL(k_gather_super, dim3((sm.n_super * 57 + 255) / 256), dim3(256), 0, c->side, partial, sp.super_list, sm.n_super, scan_local, scan_blk, dst);
+    if (f.te) te_gather_super(c->side, partial, sm.n_super, sp, dst);
+    else hipLaunchKernelGGL(k_gather_super, dim3((sm.n_super * 57 + 255) / 256), dim3(256), 0, c->side, partial, sp.super_list, sm.n_super, scan_local, scan_blk, dst);
     HIPCHK(hipEventRecord(c->ev[4], c->side));
   }
   // the levels behind the first in one launch (k_tree_rest) when only the common list is left and no bucket has more than 8 slices
@@ -469,7 +328,8 @@ int32_t msm_front_finish(Ctx* c, hipStream_t s, Front& f, bool allow_aside) {
   if (sm.NT) {
     for (uint32_t pass = 0, L = sm.max_m, Lcm = sm.max_common; L > 1; ++pass, L = (L + 1) >> 1, Lcm = (Lcm + 1) >> 1) {
       if (rest_ok && pass == 1) {
-        hipLaunchKernelGGL(k_tree_rest<4>, dim3((uint32_t)((4ull * sm.n_heavy + 255) / 256)), dim3(256), 0, s, partial, heavy, sm.n_heavy, scan_local, scan_blk, M, meta);
+        if (f.te) te_tree_rest(s, partial, heavy, sm.n_heavy, sp);
+        else hipLaunchKernelGGL(k_tree_rest<4>, dim3((uint32_t)((4ull * sm.n_heavy + 255) / 256)), dim3(256), 0, s, partial, heavy, sm.n_heavy, scan_local, scan_blk, M, meta);
         break;
       }
       const uint32_t Lc = sm.super_overflow ? L : Lcm;       // longest bucket of the common list at this level
@@ -480,7 +340,8 @@ int32_t msm_front_finish(Ctx* c, hipStream_t s, Front& f, bool allow_aside) {
       const uint64_t threads = lanes * ops;
       if (!threads) continue;
       if (threads >= (1ull << 32)) { (void)hipStreamSynchronize(s); g_last_error = "msm: slice tree too wide"; return ALEO_MI355X_ERR_HIP; }
-      launch_grp(lanes, k_tree_pass<Pt28, 4>, pre ? k_tree_pass<Pt28, 2> : f.plain_tree, ops, s, partial, heavy, len_a, pairs_a, sp.super_list, len_b, pairs_b, scan_local, scan_blk, M, meta, pass, 0u);
+      if (f.te) te_tree_pass(lanes, ops, s, partial, heavy, len_a, pairs_a, sp.super_list, len_b, pairs_b, sp, pass, 0u);
+      else launch_grp(lanes, k_tree_pass<Pt28, 4>, pre ? k_tree_pass<Pt28, 2> : f.plain_tree, ops, s, partial, heavy, len_a, pairs_a, sp.super_list, len_b, pairs_b, scan_local, scan_blk, M, meta, pass, 0u);
     }
   }
   if (!f.lean) HIPCHK(hipEventRecord(c->ev[2], s));
@@ -502,7 +363,9 @@ int32_t msm_reduce_queue(Ctx* c, Front& f, hipStream_t s, const FrontChain& olde
   // at 2^20; S = 8 / 32 / 4 with either form: 0.51-0.54 / 0.48-0.55 / 0.66-0.72 ms
   const uint32_t lanes = grp_lanes(2 * (uint64_t)nchunks), per_block = lanes == 4 ? 32u : CHUNK_QUADS;      // (its own geometry: two lane groups per chunk)
   auto* const chunks = lanes == 4 ? k_bucket_chunks<true, 4> : k_bucket_chunks<true, 2>;
-  hipLaunchKernelGGL(chunks, dim3((nchunks + per_block - 1) / per_block), dim3(256), 0, s, partial, hist, scan_local, scan_blk, P.B, P.S, nchunks, V, setw, Vrun, older);
+  if (f.te && !f.prog) { g_last_error = "msm: internal: Edwards tier without the sum-tree reduction"; return ALEO_MI355X_ERR_HIP; }      // (the whole-set tier's windows always take it)
+  if (f.te) te_bucket_chunks(lanes, s, partial, sp, P.B, P.S, nchunks, V, setw, Vrun, older);
+  else hipLaunchKernelGGL(chunks, dim3((nchunks + per_block - 1) / per_block), dim3(256), 0, s, partial, hist, scan_local, scan_blk, P.B, P.S, nchunks, V, setw, Vrun, older);
   if (f.prog) {
     char* G0 = Tout; char* G1 = G0 + (size_t)K * (3 * (cpw / 2)) * PB28;      // ping-pong: a set is at most 3 segments of cpw / 2 points after the first pass
     const char* node = Vrun; uint32_t node_ss = cpw; const char* A = V; uint32_t a_ss = setw; const char* T = Vrun; uint32_t t_ss = 0, nT = 0, L = cpw;
@@ -511,19 +374,22 @@ int32_t msm_reduce_queue(Ctx* c, Front& f, hipStream_t s, const FrontChain& olde
       const uint32_t half = L >> 1, out_ss = (3 + nT) * half; const uint64_t ops = (uint64_t)(2 + nT) * half * K;
       if ((L >> 2) >= FOLD && grp_lanes(ops) == 4) {      // two levels at once: L -> L / 4
         const uint32_t quarter = L >> 2, out2 = (4 + nT) * quarter; const uint64_t octs = (uint64_t)(2 + nT) * quarter * K;
-        hipLaunchKernelGGL(k_prog_pass2, dim3((uint32_t)((octs + 31) / 32)), dim3(256), 0, s, node, node_ss, A, a_ss, T, t_ss, nT, L, K, dstbuf, out2);
+        if (f.te) te_prog_pass2(octs, s, node, node_ss, A, a_ss, T, t_ss, nT, L, K, dstbuf, out2, sp);
+        else hipLaunchKernelGGL(k_prog_pass2, dim3((uint32_t)((octs + 31) / 32)), dim3(256), 0, s, node, node_ss, A, a_ss, T, t_ss, nT, L, K, dstbuf, out2);
         node = dstbuf; node_ss = out2; A = dstbuf + (size_t)quarter * PB28; a_ss = out2; T = dstbuf + (size_t)2 * quarter * PB28; t_ss = out2; nT += 2; L = quarter;
         dstbuf = dstbuf == G0 ? G1 : G0;
         continue;
       }
-      launch_grp(grp_lanes(ops), k_prog_pass<4>, k_prog_pass<2>, ops, s, node, node_ss, A, a_ss, T, t_ss, nT, L, K, dstbuf, out_ss);
+      if (f.te) te_prog_pass(grp_lanes(ops), ops, s, node, node_ss, A, a_ss, T, t_ss, nT, L, K, dstbuf, out_ss, sp);
+      else launch_grp(grp_lanes(ops), k_prog_pass<4>, k_prog_pass<2>, ops, s, node, node_ss, A, a_ss, T, t_ss, nT, L, K, dstbuf, out_ss);
       node = dstbuf; node_ss = out_ss; A = dstbuf + (size_t)half * PB28; a_ss = out_ss; T = dstbuf + (size_t)2 * half * PB28; t_ss = out_ss; ++nT; L = half;
       dstbuf = dstbuf == G0 ? G1 : G0;
     }
     uint32_t lgL = 0; while ((1u << lgL) < L) ++lgL;
     char* dst = nullptr;
     HIPCHK(hipHostGetDevicePointer((void**)&dst, h_win, 0));
-    hipLaunchKernelGGL(k_prog_final<4>, dim3(K * (1 + nT + lgL)), dim3(512), 0, s, node, node_ss, L, nT, lgL, K, dst);
+    if (f.te) te_prog_final(K * (1 + nT + lgL), s, node, node_ss, L, nT, lgL, K, dst, sp, (uint32_t*)(dst + (size_t)nseg * 224 + ASIDE_MAX * 228 + 64));      // (K (1 + lgN) <= nseg flag words behind the aside records)
+    else hipLaunchKernelGGL(k_prog_final<4>, dim3(K * (1 + nT + lgL)), dim3(512), 0, s, node, node_ss, L, nT, lgL, K, dst);
   } else {
     const uint64_t mops = (uint64_t)tseg * lgN * K;
     launch_grp(grp_lanes(mops), k_masked_pairs<4>, k_masked_pairs<2>, mops, s, Vrun, lgN, K, V, setw);
@@ -592,14 +458,23 @@ int32_t msm_collect(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bool f
   HT("msm: result arrived");
   const auto t_host0 = std::chrono::steady_clock::now();
   HXYZZ totals[MAX_SETS];
+  // Edwards tier: a Z3 == 0 anywhere in the chain (the words k_prog_final's blocks and the side stream left) or in a point the tail reads -> rerun without tables
+  std::atomic<bool> te_bad{false};
+  if (f.te) {
+    const uint32_t* fl = (const uint32_t*)(h_win + (size_t)f.nseg * 224 + ASIDE_MAX * 228 + 64);
+    bool any = aside && h_aside[(size_t)sm.n_super * 57];
+    for (uint32_t i = 0; i < K * out_pts; ++i) any = any || fl[i];
+    te_bad.store(any);
+  }
+  auto point = [&](const char* p) { if (!f.te) return lazy_point28(p); bool z = false; const HXYZZ r = te_point28(p, &z); if (z) te_bad.store(true); return r; };
   // one Horner chain per result (~15 us): from 3 results on they are spread over the library's parked helper threads (a lockstep round has 8 x k of them)
   auto horner = [&](size_t q) {
     const char* hw = h_win + q * out_pts * PB28;
     const uint32_t na = prog ? 1u : 4u;                  // points that hold sum_j acc_j: one (k_prog_final) or the four segment sums of the masked form
     HXYZZ total = HXYZZ::infinity();
-    for (int l = (int)lgN - 1; l >= 0; --l) { total = hdouble(total); total = hadd(total, lazy_point28(hw + (size_t)(na + l) * PB28)); }
+    for (int l = (int)lgN - 1; l >= 0; --l) { total = hdouble(total); total = hadd(total, point(hw + (size_t)(na + l) * PB28)); }
     for (uint32_t sft = P.S; sft > 1; sft >>= 1) total = hdouble(total);
-    for (uint32_t r = 0; r < na; ++r) total = hadd(total, lazy_point28(hw + (size_t)r * PB28));
+    for (uint32_t r = 0; r < na; ++r) total = hadd(total, point(hw + (size_t)r * PB28));
     totals[q] = total;
   };
   constexpr uint32_t TAIL_POOL = 3;                      // results from which the pool is used (2^15 proof: 5.68 / 5.65 / 5.74 ms with 8 / 3 / 2, profiles/r05_tailpool_min_ab.txt)
@@ -607,11 +482,12 @@ int32_t msm_collect(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bool f
   for (uint32_t h = 0; aside && h < sm.n_super; ++h) {             // (b + 1) * (slices 1.. of super-heavy bucket b), by double-and-add
     const uint32_t* rec = h_aside + (size_t)h * 57; const uint32_t g = rec[56], q = g / P.B, wgt = g % P.B + 1;
     if (q >= K) { g_last_error = "msm: internal: super-heavy bucket outside the sets"; return ALEO_MI355X_ERR_HIP; }
-    const HXYZZ T = lazy_point28((const char*)rec); HXYZZ acc = HXYZZ::infinity();
+    const HXYZZ T = point((const char*)rec); HXYZZ acc = HXYZZ::infinity();
     for (int bit = 31 - __builtin_clz(wgt); bit >= 0; --bit) { acc = hdouble(acc); if ((wgt >> bit) & 1u) acc = hadd(acc, T); }
     totals[q] = hadd(totals[q], acc);
   }
   HT("msm: horner done");
+  if (te_bad.load()) { (void)phase_times(c, f, t_host0); return MSM_RERUN_WITHOUT_TABLES; }
   hstore_jacobian_normalized_batch(out_jac18, totals, K);          // one shared inversion for the K results
   HT("msm: normalised");
   return phase_times(c, f, t_host0);

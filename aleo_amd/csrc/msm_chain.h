@@ -21,7 +21,8 @@ struct Front {
   MsmPlan P{}; SortPhase sp; SliceMeta sm;
   uint32_t K = 0, cpw = 0, nchunks = 0, lgN = 0, tseg = 0, fseg = 0, nseg = 0, setw = 0; size_t vpoints = 0;
   uint32_t out_pts = 0;      // result points per set the host tail reads: lgN + 1 from the sum trees (prog), lgN + 4 from the masked trees
-  bool pre = false, masked = false, prog = false, aside = false, empty = false, lean = false; const char* bases = nullptr;      // lean: MsmJob::lean of a single-chain request (no phase-timing events)
+  bool pre = false, masked = false, prog = false, aside = false, empty = false, lean = false, te = false; const char* bases = nullptr;      // te: the chain's tier is in Edwards form (msm_te.h)
+       // lean: MsmJob::lean of a single-chain request (no phase-timing events)
   // plain path: the lane-pair slice-tree kernel over the group's partial sums (msm_reduce.h k_tree_pass<PT, 2>) — how the group reaches msm_front_finish
   void (*plain_tree)(char*, const uint32_t*, uint32_t, uint32_t, const uint32_t*, uint32_t, uint32_t, const uint2*, const uint2*, uint32_t, const uint32_t*, uint32_t, uint32_t) = nullptr;
 };
@@ -40,6 +41,9 @@ int32_t msm_front_accum(Ctx* c, hipStream_t s, Front& f, const FrontChain* seed,
 int32_t msm_front_finish(Ctx* c, hipStream_t s, Front& f, bool allow_aside);
 // older: the earlier chunks of the same request (msm_run_chunked) — a bucket this chain did not touch keeps its sum there.
 int32_t msm_reduce_queue(Ctx* c, Front& f, hipStream_t s, const FrontChain& older);
+// What msm_collect (and so msm_back) returns when an addition of an Edwards-tier chain reported Z3 == 0 — bases outside the prime-order subgroup: the results are
+// not written and msm_request.hip reruns the request without the tables.  Never leaves the library.
+static constexpr int32_t MSM_RERUN_WITHOUT_TABLES = -1000;
 enum class TailWait { stream, event };      // without a hook the host waits for the whole stream, or for ev[3] alone (other chains' work may be queued behind it; this chain's is all in front)
 int32_t msm_collect(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bool fire_tail, TailWait wait);
 int32_t msm_back(Ctx* c, uint64_t* out_jac18, Front& f, hipStream_t s, bool fire_tail, const FrontChain& older);

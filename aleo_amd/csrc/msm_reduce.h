@@ -6,6 +6,7 @@
 #include "fp28.h"
 #include "host_field.hpp"
 #include "msm_chain.h"
+#include <type_traits>
 
 namespace aleo_mi355x {
 
@@ -16,13 +17,18 @@ namespace aleo_mi355x {
 // seven; msm.hip grp_lanes); G2's pair form (448 B) is g2.hip's PtG2.
 constexpr uint32_t lg_lanes(uint32_t lanes) { return lanes == 4 ? 2u : 1u; }
 struct Pt32 {
-  static constexpr uint32_t BYTES = 192, WORDS = BYTES / 4;
+  static constexpr uint32_t BYTES = 192, WORDS = BYTES / 4; static constexpr bool TE = false;
   template <uint32_t LANES> static __device__ __forceinline__ void add(const char* pa, const char* pb, char* out) { static_assert(LANES == 2, "quad additions work on 28-bit points"); xyzz_add_pair(pa, pb, out); }
 };
 struct Pt28 {
-  static constexpr uint32_t BYTES = 224, WORDS = BYTES / 4;
+  static constexpr uint32_t BYTES = 224, WORDS = BYTES / 4; static constexpr bool TE = false;
   template <uint32_t LANES> static __device__ __forceinline__ void add(const char* pa, const char* pb, char* out) { if constexpr (LANES == 4) xyzz28_add_quad(pa, pb, out); else xyzz28_add_pair(pa, pb, out); }
 };
+// A format whose addition reports Z3 == 0 (the extended Edwards points of msm_table.h: operands that differ by a point of even order) says so with TE = true;
+// the report goes into word TE_FLAG_WORD of the sort's metadata block, zeroed with it for every chain.
+static constexpr uint32_t TE_FLAG_WORD = 12;
+template <class PT, class = void> struct pt_reports : std::false_type {};
+template <class PT> struct pt_reports<PT, std::void_t<decltype(PT::TE)>> : std::bool_constant<PT::TE> {};
 
 // partial[ft + i] += partial[ft + i + half] inside every multi-slice bucket: one launch per level serves both lists of the scan —
 // the common one (buckets of <= 16 slices, `pairs_a` lane pairs each) and the super-heavy one (`pairs_b` each; skewed scalars).
@@ -47,7 +53,8 @@ __global__ void __launch_bounds__(256) k_tree_pass(char* __restrict__ partial, c
   uint32_t half = (L + 1) >> 1;
   if (i >= L - half) return;
   char* pa = partial + (size_t)(ft + i) * PB;
-  PT::template add<LANES>(pa, pa + (size_t)half * PB, pa);
+  if constexpr (pt_reports<PT>::value) { if (PT::template add<LANES>(pa, pa + (size_t)half * PB, pa)) ((uint32_t*)meta)[TE_FLAG_WORD] = 1u; }
+  else PT::template add<LANES>(pa, pa + (size_t)half * PB, pa);
 }
 // V[seg*seg_len + i] += V[seg*seg_len + i + half] for i < L - half, L = current length of every segment
 template <class PT>

@@ -17,7 +17,24 @@ static void identity_results(uint64_t* out_jac18, size_t k, const uint32_t* wher
 // beside an accumulation holding every wave slot cost more than the 0.3-1.0 ms of sort they move out of the way; holding a later chunk's sort until the
 // previous accumulation starts (as run_chains does for whole chains) makes it worse (2^20 3.07, 2^21 5.91, 2^22 9.83 ms against 2.83 / 5.04 / 9.32 whole:
 // tools/resident_ab.py).
+// A pinned set as the plain path sees it: the same points, no tables.  Where a chain on the Edwards tier reports Z3 == 0 (msm_chain.h MSM_RERUN_WITHOUT_TABLES: bases
+// outside the prime-order subgroup, which the tier's unified law does not cover) the request is computed again against this view — every result on the plain path,
+// whose XYZZ law handles any curve points.
+static PinnedBases without_tables(const PinnedBases& pb) {
+  PinnedBases plain = pb;
+  for (auto& t : plain.tab) t = PinnedBases::PreTable();
+  plain.range = PinnedBases::PreTable(); plain.range_off = 0; plain.tabled = false; plain.shards = 0;
+  return plain;
+}
+static int32_t msm_batch_tiers(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s);
+static int32_t msm_run_tiers(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s);
 int32_t msm_run(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s) {
+  const int32_t rc = msm_run_tiers(c, out_jac18, pb, job, s);
+  if (rc != MSM_RERUN_WITHOUT_TABLES) return rc;
+  MsmJob again = job; again.fire_tail = false; again.tier_n = 0;
+  return msm_batch_tiers(c, out_jac18, without_tables(pb), again, s);      // (one chain per result: the plain path holds one)
+}
+static int32_t msm_run_tiers(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s) {
   if (job.k == 0) return ALEO_MI355X_OK;
   Front f; int32_t rc;
   f.lean = job.lean;
@@ -214,7 +231,12 @@ int32_t msm_run1_split(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const
   const bool tiered = msm_tier(pb, n) != nullptr;
   HelperSet hs;
   if (host_src && may_merge && !sparse && tiered && n >= ((size_t)1 << MERGE_MIN_LG) && c->dev) { const int32_t rc = acquire_helpers(c->dev, n >= ((size_t)1 << CHUNKS3_MIN_LG) ? 2 : 1, hs); if (rc) return rc; }
-  if (!hs.ctx.empty()) return msm_run_chunked(c, hs, out_jac18, pb, n, mont, s, host_src);
+  if (!hs.ctx.empty()) {
+    const int32_t rc = msm_run_chunked(c, hs, out_jac18, pb, n, mont, s, host_src);
+    if (rc != MSM_RERUN_WITHOUT_TABLES) return rc;
+    hs = HelperSet();                                      // the borrowed contexts go back; the rerun uploads whole
+    return msm_run1_split(c, out_jac18, without_tables(pb), d_scalars, n, mont, s, sparse, host_src, false);
+  }
   if (host_src) {
     const int32_t rc = c->scalars_stage.reserve((n ? n : 1) * 32); if (rc) return rc;
     if (n) HIPCHK(hipMemcpyAsync(c->scalars_stage.p, host_src, n * 32, hipMemcpyHostToDevice, s));
@@ -248,6 +270,10 @@ static int32_t cut_chains(const MsmJob& job, const std::vector<uint32_t>& ids, c
 // (longest tier first) and every group goes through msm_run in chunks of msm_max_sets() results / MAX_SEGS segments; results no tier
 // serves (no table, or fewer than 2^10 bases reached) run one by one.
 int32_t msm_batch(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s) {
+  const int32_t rc = msm_batch_tiers(c, out_jac18, pb, job, s);
+  return rc == MSM_RERUN_WITHOUT_TABLES ? msm_batch_tiers(c, out_jac18, without_tables(pb), job, s) : rc;
+}
+static int32_t msm_batch_tiers(Ctx* c, uint64_t* out_jac18, const PinnedBases& pb, const MsmJob& job, hipStream_t s) {
   const uint32_t K = job.k;
   auto tier_of = [&](size_t n) { const PinnedBases::PreTable* t = msm_tier(pb, n); return t ? (int)(t - pb.tab) : -1; };
   std::vector<size_t> reach(K, 0), points(K, 0); std::vector<uint32_t> nsegs(K, 0);

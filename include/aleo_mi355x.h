@@ -119,7 +119,13 @@ int32_t aleo_mi355x_bases_from_scalars(const void* base_affine104, const void* s
  * of every degree against one SRS): the whole set at c = 20 (>= 2^19 points; 13 rows) or c = 17, its first 2^17 + 64 points at
  * c = 16, its first 2^15 + 64 points at c = 13 (the 64: a committer key is a power of two of powers followed by a few hiding powers).  MSMs over this handle then add one table entry per window into ONE shared bucket
  * set (13 instead of 16 additions per point at 2^20) and skip the Horner tail.  Same results, bit for bit after
- * normalisation.  About 0.15 s and 1.8 GB for a 2^20-point set. */
+ * normalisation.  The whole-set tier is kept in twisted Edwards form (rows y - x | y + x | 2d x y of the point's Edwards image, 168 bytes at a
+ * 192-byte stride: 7 field products per bucket addition instead of 10); the two prefix tiers keep x | y rows at a 128-byte stride.  Bytes per power
+ * of a 2^20-point set: 13 x 192 + the prefix tiers' share = 2832 (3.0 GB, about 0.20 s) against 2000 (2.1 GB, 0.15 s) with x | y rows throughout.
+ * Calls that use the tables REQUIRE bases in the prime-order subgroup, which is all a snarkVM G1Affine can hold: the Edwards tier's addition law has
+ * exceptions only between points that differ by one of even order.  A set that breaks this still never yields a wrong result: an exception is noticed
+ * on the device and the call computes the request again without tables; and a set with a base of even order whose multiples reach the identity inside a
+ * table (such as (-1, 0)) gets no tables at all — the call succeeds and its products run on the plain path. */
 int32_t aleo_mi355x_bases_precompute(uint64_t handle);
 /* What a pinned set holds in HBM: out[0] points, [1] bytes of the base rows (96-byte snarkVM rows + their 112-byte
  * 28-bit-limb copies), [2] bytes of the fixed-base tables, [3..5] window width c of each table tier (0 = none), [6] tiers.
@@ -493,6 +499,14 @@ int32_t aleo_mi355x_selftest_addquad(uint32_t ops, uint64_t seed, uint32_t* fail
  * ok_u8[i] = what the formula returned (0: the point is +-acc and acc is untouched).  Either count may be 0 (its pointers are then ignored); at most 2^20. */
 int32_t aleo_mi355x_selftest_f28_rows(const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224,
                                       const void* acc224, const void* pt112, uint32_t n_madd, void* out_acc224, uint8_t* ok_u8);
+/* The Edwards-form formulas of the whole-set table tier (te28.h) on rows the caller built, the same way.  A point is a 224-byte row X | Y | Z | T of 14 limbs each,
+ * every coordinate exact digits < 2q; the identity is the ordinary point (0 : Z : Z : 0).  Additions: a224[i] + b224[i] by one lane quad per row into
+ * out_quad224[i], lanes 0 and 1 of the quad run the lane-pair form into out_pair224[i]; z_add_u32[i] bit 0 / bit 1: the pair / quad form reported Z3 == 0
+ * (operands that differ by a point of even order: outside what the unified law covers).  Mixed additions: acc224[i] + the entry row168[i] (y - x | y + x | 2d x y of
+ * the Edwards image, canonical digits) by one lane per row; how_u8[i] bit 0: the entry is negated on the device first, bit 1: the entry starts a slice (acc224[i] is
+ * ignored); out_acc224[i] = the sum, z_madd_u8[i] = 1 if Z3 == 0 was reported.  Either count may be 0 (its pointers are then ignored); at most 2^20. */
+int32_t aleo_mi355x_selftest_te28_rows(const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224, uint32_t* z_add_u32,
+                                       const void* acc224, const void* row168, const uint8_t* how_u8, uint32_t n_madd, void* out_acc224, uint8_t* z_madd_u8);
 
 /* The slice stage of the MSM sort alone (bucket scan, top scan, slice ordering) on a histogram from the host: hist[g] = points of bucket g, n_buckets <= 2^20,
  * total_pairs = the pair count the slice rule is picked from (the sum of hist or more: less is refused); fused != 0 runs the top scan inside the ordering kernel, as the
