@@ -653,6 +653,16 @@ int32_t aleo_mi355x_selftest_te28_rows(const void* a224, const void* b224, uint3
   });
 }
 
+int32_t aleo_mi355x_selftest_g2p_rows(const void* a448, const void* b448, uint32_t n_add, void* out_add448, const void* d448, uint32_t n_dbl, void* out_dbl448,
+                                      const void* acc448, const void* ent224, const uint8_t* neg_u8, uint32_t n_madd, void* out_acc448, uint8_t* ok2_u8) {
+  return guarded([&] {
+    if (n_add > (1u << 20) || n_dbl > (1u << 20) || n_madd > (1u << 20)) return bad_arg("selftest_g2p_rows: at most 2^20 rows of each kind");
+    if ((n_add && (!a448 || !b448 || !out_add448)) || (n_dbl && (!d448 || !out_dbl448)) || (n_madd && (!acc448 || !ent224 || !neg_u8 || !out_acc448 || !ok2_u8))) return bad_arg("selftest_g2p_rows: bad argument");
+    Slot sl; if (sl.rc) return sl.rc;
+    return selftest_g2p_rows(sl.c, a448, b448, n_add, out_add448, d448, n_dbl, out_dbl448, acc448, ent224, neg_u8, n_madd, out_acc448, ok2_u8);
+  });
+}
+
 int32_t aleo_mi355x_selftest_slice_order(const uint32_t* hist, uint32_t n_buckets, uint32_t total_pairs, int32_t fused, uint32_t* violations) {
   return guarded([&] { if (!hist || !violations) return ALEO_MI355X_ERR_BAD_ARG; Slot sl; if (sl.rc) return sl.rc; return selftest_slice_order(sl.c, hist, n_buckets, total_pairs, fused != 0, violations); });
 }

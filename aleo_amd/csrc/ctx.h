@@ -233,6 +233,9 @@ int32_t selftest_f28_rows(Ctx* c, const void* a224, const void* b224, uint32_t n
 // selftest_te28.hip: the same for the Edwards-form formulas of te28.h
 int32_t selftest_te28_rows(Ctx* c, const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224, uint32_t* z_add_u32,
                            const void* acc224, const void* row168, const uint8_t* how_u8, uint32_t n_madd, void* out_acc224, uint8_t* z_madd_u8);
+// selftest_g2p.hip: the same for the G2 lane-pair formulas of g2p28.h (additions, doublings, mixed additions; 448-byte points)
+int32_t selftest_g2p_rows(Ctx* c, const void* a448, const void* b448, uint32_t n_add, void* out_add448, const void* d448, uint32_t n_dbl, void* out_dbl448,
+                          const void* acc448, const void* ent224, const uint8_t* neg_u8, uint32_t n_madd, void* out_acc448, uint8_t* ok2_u8);
 // msm_sort.hip: the slice stage (bucket scan, top scan, slice ordering) on a host histogram, checked against a host recount
 int32_t selftest_slice_order(Ctx* c, const uint32_t* h_hist, uint32_t M, uint32_t pairs, bool fused, uint32_t* violations);
 // g1_setup.hip: synthetic base sets, the fixed-base tables, row formats

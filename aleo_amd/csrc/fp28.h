@@ -15,8 +15,9 @@
 // needs b's limbs < S * 2^28 - S + (K*q)_i and b < K*q as a value; the result's limbs are < a_max + (S + 1) * 2^28.
 //
 // Two parts.  Everything that touches F28::v or a device builtin sits behind ALEO_F28_PROVIDED; the four point formulas below it use only those
-// names.  tests/cpp/fp28_bounds_emul.cpp defines the macro, supplies the same names on the host over limbs that carry their bounds along, and
-// includes this file: every "class Lk", "< k q" and column claim of the formulas is then checked mechanically (tests/test_fp28_bounds.py).
+// names.  tests/cpp/checked_f28.h defines the macro, supplies the same names on the host over limbs that carry their bounds along, and includes this
+// file for tests/cpp/fp28_bounds_emul.cpp: every "class Lk", "< k q" and column claim of the formulas is then checked mechanically
+// (tests/test_fp28_bounds.py).  te28.h and g2p28.h (the G2 lane-pair formulas) are written over the same names and checked the same way.
 #pragma once
 #ifndef ALEO_F28_PROVIDED
 #include <hip/hip_runtime.h>
@@ -202,7 +203,15 @@ template <int S0, int S1, int S2, int S3> __device__ __forceinline__ F28 f28_qpe
   for (int i = 0; i < 14; ++i) r.v[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)a.v[i], S0 | (S1 << 2) | (S2 << 4) | (S3 << 6), 0xF, 0xF, true);
   return r;
 }
-__device__ __forceinline__ uint32_t f28_lane() { return threadIdx.x; }      // the formulas mask it themselves (& 1, & 3): a helper that masks changes the quad kernels' registers
+// what the Fq2 lane-pair formulas of g2p28.h add: 5 v limb-wise (for an exact-digit v: limbs < 5 * 2^28), and a flag that holds in both lanes of a pair
+__device__ __forceinline__ F28 f28_times5(const F28& v) {
+  F28 t;
+#pragma unroll
+  for (int i = 0; i < 14; ++i) t.v[i] = 5u * v.v[i];
+  return t;
+}
+__device__ __forceinline__ bool f28_pair_and(bool v) { const bool o = (bool)__shfl_xor((int)v, 1); return v && o; }      // the exchange first, by BOTH lanes: `v && shfl(..)` would skip it on the lane whose v is false and leave its partner reading an inactive lane
+__device__ __forceinline__ uint32_t f28_lane() { return threadIdx.x; }     // the formulas mask it themselves (& 1, & 3): a helper that masks changes the quad kernels' registers
 // the flag of the pair's even lane / of lane 1 of the quad, in every lane of it
 __device__ __forceinline__ int f28_pair_flag_of_even(int z) { return __shfl(z, (int)(threadIdx.x & 63u & ~1u)); }
 __device__ __forceinline__ int f28_quad_flag_of_lane1(int z) { return __builtin_amdgcn_mov_dpp(z, 1 | (1 << 2) | (1 << 4) | (1 << 6), 0xF, 0xF, true); }

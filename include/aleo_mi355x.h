@@ -519,6 +519,16 @@ int32_t aleo_mi355x_selftest_slice_order(const uint32_t* hist, uint32_t n_bucket
  * chains over n_points affine G2 points (192-byte rows, host memory, >= 3 of them, all on the curve): sums, a sum with a shared operand, a doubling, the
  * same-point case of the addition.  failures2[0] = pairs that disagreed, failures2[1] = OR of the failing steps (1 a, 2 s, 4 u, 8 2u, 16 u + u). */
 int32_t aleo_mi355x_selftest_g2pair(const void* affine192, uint32_t n_points, uint32_t n_pairs, uint32_t* failures2);
+/* The lane-pair formulas themselves (csrc/g2p28.h) on rows the caller built, raw 28-bit limbs in and out (host memory; the device converts nothing), so that a
+ * test can place every component of every coordinate where the stored invariant allows it and compare with the group law in integers.  A point is a 448-byte row
+ * X.a | X.b | Y.a | Y.b | ZZ.a | ZZ.b | ZZZ.a | ZZZ.b of 14 limbs each (an Fq2 value a + b u): X exact digits < 12q, Y exact < 6q, ZZ / ZZZ exact < 2q per
+ * component; the identity is the all-zero row.  One lane pair per row.  Additions: out_add448[i] = a448[i] + b448[i] (g2p_add_any: any operand may be the
+ * identity, they may be equal or opposite).  Doublings: out_dbl448[i] = 2 d448[i] (g2p_double_any).  Mixed additions: acc448[i] + the entry ent224[i]
+ * (x.a | y.a | x.b | y.b, exact digits < 2q; canonical where neg_u8[i] != 0, which has the device negate it first as the accumulation kernel does) through
+ * g2p_madd_fast; out_acc448[i] = acc afterwards, ok2_u8[2 i] and ok2_u8[2 i + 1] = what the formula returned to the even and to the odd lane (0: the point is
+ * +-acc and acc is untouched).  Outputs are filled with 0xA5 before the kernels run.  A count may be 0 (its pointers are then ignored); at most 2^20 each. */
+int32_t aleo_mi355x_selftest_g2p_rows(const void* a448, const void* b448, uint32_t n_add, void* out_add448, const void* d448, uint32_t n_dbl, void* out_dbl448,
+                                      const void* acc448, const void* ent224, const uint8_t* neg_u8, uint32_t n_madd, void* out_acc448, uint8_t* ok2_u8);
 
 /* Host arithmetic (no device needed): the inversion the host tails use — Bernstein-Yang divsteps on 62-bit limbs (csrc/host_modinv.hpp) — against the Fermat
  * chain a^(p-2) on `count` pseudo-random elements of Fq and of Fr plus the edge values 0, 1, 2, p - 1, p - 2: *failures = results that differ; ns_per_inverse

@@ -1,7 +1,7 @@
 // The Edwards-form formulas of aleo_amd/csrc/te28.h (te28_madd in its two halves, te28_first, te28_row_negate_if, te28_add_pair, te28_add_quad) run on the HOST over values
 // and bounds together, against the affine group law on y^2 = x^3 + 1 in host_field.hpp's HFq carried through the map of tools/te28_model.py.
 //
-// The harness is fp28_bounds_emul.cpp's, taken whole (its main renamed): limbs that carry a bound each, a value bound in multiples of q and an
+// The harness is checked_f28.h, which fp28_bounds_emul.cpp uses too: limbs that carry a bound each, a value bound in multiples of q and an
 // exact-digits flag; primitives that compute what the device computes, propagate the bounds from the operation alone and check their preconditions
 // against the BOUNDS (limb, column, value rules), lanes as host threads in lockstep at every exchange, stores held back until every lane has returned.
 // What this file adds: load_te28 / store_te28 with the stored invariant of an Edwards point (every coordinate exact digits < 2q; a store that breaks
@@ -10,9 +10,8 @@
 // pair of points that differ by a 2-torsion point at infinity of the Edwards model, for which every form must report Z3 == 0.
 //   hipcc -x c++ -std=c++17 -O2 -mbmi2 -madx -pthread -I aleo_amd/csrc tests/cpp/te28_bounds_emul.cpp      (tests/test_te28_bounds.py builds and runs it,
 //   also with -fsanitize=address,undefined; -DTE28_HEADER='"path"' points it at a patched copy of te28.h: the negative controls)
-#define main fp28_bounds_emul_main
-#include "fp28_bounds_emul.cpp"
-#undef main
+#include "checked_f28.h"       // the bounds-carrying F28, the books, the lanes; includes fp28.h
+#include "g1_affine_ref.h"     // the reference
 
 #ifndef TE28_HEADER
 #define TE28_HEADER "te28.h"
@@ -139,7 +138,7 @@ static void te_add_case(const Aff& A, const HFq& za, const uint32_t ka[4], const
 }
 
 int main() {
-  t_grp = nullptr; t_lane = 0;
+  t_grp = nullptr; t_lane = 0; g_formula_header = "te28.h";
   const HFq one = HFq::one();
   std::vector<Aff> P; for (int i = 0; i < 4; ++i) P.push_back(rnd_g1_point());
   const Aff O = aff_inf();

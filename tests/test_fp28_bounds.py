@@ -1,7 +1,7 @@
 """The limb and value bounds of the 28-bit-limb point formulas (aleo_amd/csrc/fp28.h), checked mechanically on the host.
 
-tests/cpp/fp28_bounds_emul.cpp defines ALEO_F28_PROVIDED, supplies the primitives of the header's guarded block over limbs that carry their bounds
-along, and includes the header: the shipped source of xyzz28_madd_fast, xyzz28_double_both, xyzz28_add_pair and xyzz28_add_quad then runs on the
+tests/cpp/fp28_bounds_emul.cpp (on tests/cpp/checked_f28.h) defines ALEO_F28_PROVIDED, supplies the primitives of the header's guarded block over limbs
+that carry their bounds along, and includes the header: the shipped source of xyzz28_madd_fast, xyzz28_double_both, xyzz28_add_pair and xyzz28_add_quad then runs on the
 host, every "class Lk", "< k q" and column claim turned into a check against the bounds, every result compared with the affine group law in HFq.
 The negative controls patch a copy of the header and expect the checker to fire: a checker that never fires proves nothing.
 """

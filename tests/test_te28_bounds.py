@@ -1,6 +1,6 @@
 """The limb and value bounds of the Edwards-form point formulas (aleo_amd/csrc/te28.h), checked mechanically on the host.
 
-tests/cpp/te28_bounds_emul.cpp takes the harness of tests/cpp/fp28_bounds_emul.cpp whole (limbs that carry their bounds, a value bound in multiples of q,
+tests/cpp/te28_bounds_emul.cpp takes the harness that tests/cpp/fp28_bounds_emul.cpp uses, tests/cpp/checked_f28.h (limbs that carry their bounds, a value bound in multiples of q,
 an exact-digits flag, lanes as host threads), adds the stored invariant of an Edwards point and includes te28.h: the shipped source of te28_madd (in its two halves),
 te28_first, te28_row_negate_if, te28_add_pair and te28_add_quad then runs on the host, every "class Lk", "< k q" and column claim turned into a check
 against the bounds, every result compared with the affine group law carried through the map of tools/te28_model.py.  The negative controls patch a copy
