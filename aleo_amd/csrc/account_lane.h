@@ -121,8 +121,7 @@ template <class Phase, class Sink>
 __device__ __forceinline__ uint32_t account_lane(const uint32_t (&seedw)[8], const uint32_t* K, AccountWords& out, Phase&& phase, Sink&& sink) {
   F29 seed = f29_from_words(seedw);
   const bool bad = !f29_below_r(seed);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) seed.v[i] = bad ? 0u : seed.v[i];                   // a refused lane goes through the motions on zeros
+  seed = f29_zero_if(bad, seed);                                                  // a refused lane goes through the motions on zeros
   uint32_t keep = bad ? 0u : 0xffffffffu;                                         // what the results are masked with at the end: a word of the lane's own,
   ac_lane_word(keep);                                                             // not a mask held in two scalar registers through every phase
   const F29 sm = f29_mul(seed, rk_const(K, RK_R2));

@@ -663,6 +663,19 @@ int32_t aleo_mi355x_selftest_g2p_rows(const void* a448, const void* b448, uint32
   });
 }
 
+int32_t aleo_mi355x_selftest_ed29_rows(const void* mul_a36, const void* mul_b36, uint32_t n_mul, void* out_mul36, const void* tidy36, uint32_t n_tidy, void* out_tidy36,
+                                       const void* canon36, uint32_t n_canon, void* out_canon36, const void* p144, const void* q144, const uint8_t* neg_u8, const void* d2_36,
+                                       uint32_t n_add, void* out_add144, const void* dbl144, const uint8_t* want_t_u8, uint32_t n_dbl, void* out_dbl144) {
+  return guarded([&] {
+    if (n_mul > (1u << 20) || n_tidy > (1u << 20) || n_canon > (1u << 20) || n_add > (1u << 20) || n_dbl > (1u << 20)) return bad_arg("selftest_ed29_rows: at most 2^20 rows of each kind");
+    if ((n_mul && (!mul_a36 || !mul_b36 || !out_mul36)) || (n_tidy && (!tidy36 || !out_tidy36)) || (n_canon && (!canon36 || !out_canon36)) ||
+        (n_add && (!p144 || !q144 || !neg_u8 || !d2_36 || !out_add144)) || (n_dbl && (!dbl144 || !want_t_u8 || !out_dbl144))) return bad_arg("selftest_ed29_rows: bad argument");
+    Slot sl; if (sl.rc) return sl.rc;
+    return selftest_ed29_rows(sl.c, mul_a36, mul_b36, n_mul, out_mul36, tidy36, n_tidy, out_tidy36, canon36, n_canon, out_canon36, p144, q144, neg_u8, d2_36, n_add, out_add144,
+                              dbl144, want_t_u8, n_dbl, out_dbl144);
+  });
+}
+
 int32_t aleo_mi355x_selftest_slice_order(const uint32_t* hist, uint32_t n_buckets, uint32_t total_pairs, int32_t fused, uint32_t* violations) {
   return guarded([&] { if (!hist || !violations) return ALEO_MI355X_ERR_BAD_ARG; Slot sl; if (sl.rc) return sl.rc; return selftest_slice_order(sl.c, hist, n_buckets, total_pairs, fused != 0, violations); });
 }

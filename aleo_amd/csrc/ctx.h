@@ -236,6 +236,10 @@ int32_t selftest_te28_rows(Ctx* c, const void* a224, const void* b224, uint32_t 
 // selftest_g2p.hip: the same for the G2 lane-pair formulas of g2p28.h (additions, doublings, mixed additions; 448-byte points)
 int32_t selftest_g2p_rows(Ctx* c, const void* a448, const void* b448, uint32_t n_add, void* out_add448, const void* d448, uint32_t n_dbl, void* out_dbl448,
                           const void* acc448, const void* ent224, const uint8_t* neg_u8, uint32_t n_madd, void* out_acc448, uint8_t* ok2_u8);
+// selftest_ed29.hip: the 29-bit-limb product, f29_tidy, f29_canonical, ed29_add over ed29_cache and ed29_dbl of edwards29.h on rows of raw limbs from the host
+int32_t selftest_ed29_rows(Ctx* c, const void* mul_a36, const void* mul_b36, uint32_t n_mul, void* out_mul36, const void* tidy36, uint32_t n_tidy, void* out_tidy36,
+                           const void* canon36, uint32_t n_canon, void* out_canon36, const void* p144, const void* q144, const uint8_t* neg_u8, const void* d2_36,
+                           uint32_t n_add, void* out_add144, const void* dbl144, const uint8_t* want_t_u8, uint32_t n_dbl, void* out_dbl144);
 // msm_sort.hip: the slice stage (bucket scan, top scan, slice ordering) on a host histogram, checked against a host recount
 int32_t selftest_slice_order(Ctx* c, const uint32_t* h_hist, uint32_t M, uint32_t pairs, bool fused, uint32_t* violations);
 // g1_setup.hip: synthetic base sets, the fixed-base tables, row formats

@@ -9,25 +9,42 @@
 // Limb discipline (fr29.h): a product takes a lazy multiplicand (limbs < 2^31.4) and a normalised multiplier, and returns normalised limbs; a sum of
 // two normalised values is a valid multiplicand; a padded difference a + 19 r - b wants b normalised and below 18 r.  Whatever is used as a multiplier
 // or as a subtrahend is therefore "tidied" first (normalised, then brought below 3 r): ~45 simple instructions against the 206 of a product.
+//
+// The contracts below are what tests/cpp/checked_f29.h establishes when it runs this source over limbs that carry their bounds (tests/test_ed29_bounds.py, at the
+// edges of every class; the lane programs of tests/cpp on top of it), and what tests/test_gpu_ed29_extremes.py holds the kernels to on rows built at those edges:
+//   f29_tidy       any limbs whose carries fit 32 bits and a value below 445 r  ->  exact digits (limbs 0..7 below 2^29), below 3 r
+//   f29_canonical  a multiplicand (limbs below 2^31.4, value below 2^261 = 438.79 r)  ->  the digits of the canonical number, below r
+//   Ed29           every coordinate exact digits and below 3 r: a product (below 1.14 r from these formulas), a table constant (below r) or a tidied value (the
+//                  lanes store w, s and f29_neg_tidy(..) into points).  ed29_add and ed29_dbl accept that and return X, Y, Z, T below 1.1373 r: closed.
+//   Ed29Cached     ym, yp, z2, k exact digits and below 3 r (ed29_cache: three tidied values and a product below 1.01 r; a table entry: canonical numbers)
+// With operands at those edges the largest product column is 0.47 of 2^64, the tightest padded difference is e = s - h of ed29_dbl (h = A + B lazy: 21 units
+// of limb 0 to spare) and every subtrahend stays below 3 r of the 18 r the padding covers.
 #pragma once
 #ifndef ALEO_F29_PROVIDED      // tests/cpp/checked_f29.h supplies the same field on the host, with every bound above checked
 #include "fr29.h"
 #endif
 
+#ifndef ALEO_F29_LIMB_WRITES_PROVIDED      // ... and, where it says so, the five below as well
 namespace aleo_mi355x {
-
-__device__ __forceinline__ void f29_tidy(F29& a) { f29_normalise(a); f29_reduce_partial(a); }       // any lazy value below 445 r -> normalised, below 3 r
-__device__ __forceinline__ F29 f29_sqr(const F29& a) { return f29_mul(a, a); }                       // a normalised
+// Everything in the lanes that writes a limb other than through fr29.h: tests/cpp/checked_f29.h supplies these five with bounds, so the lanes' source runs on it unmodified
+// (a host field that supplies fr29.h's part alone takes them as they stand here).
+__device__ __forceinline__ F29 f29_limbs(const uint32_t* p, uint32_t at = 0) { F29 r;                // nine limbs as they lie in a table (from word `at`) or an argument block
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.v[i] = p[at + i];
+  return r; }
+__device__ __forceinline__ F29 f29_small(uint32_t k) { F29 r; r.v[0] = k;                             // the plain number k
+#pragma unroll
+  for (int i = 1; i < 9; ++i) r.v[i] = 0;
+  return r; }
+__device__ __forceinline__ F29 f29_zero_if(bool c, const F29& a) { F29 r;                             // a malformed lane goes through the motions on zeros
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.v[i] = c ? 0u : a.v[i];
+  return r; }
 __device__ __forceinline__ F29 f29_select(bool c, const F29& a, const F29& b) { F29 r;
 #pragma unroll
   for (int i = 0; i < 9; ++i) r.v[i] = c ? a.v[i] : b.v[i];
   return r; }
-// Montgomery form -> the canonical number (limbs of a value below r): one product by the plain 1 leaves a value <= r, one conditional subtraction the rest
-__device__ __forceinline__ F29 f29_canonical(const F29& a) {
-  F29 one; one.v[0] = 1;
-#pragma unroll
-  for (int i = 1; i < 9; ++i) one.v[i] = 0;
-  F29 r = f29_mul(a, one);
+__device__ __forceinline__ F29 f29_sub_r_if_ge(F29 r) {                                               // exact digits, at most r -> below r
   bool ge = true;
 #pragma unroll
   for (int i = 0; i < 9; ++i) ge = r.v[i] > FR29_P[i] || (r.v[i] == FR29_P[i] && ge);
@@ -35,6 +52,17 @@ __device__ __forceinline__ F29 f29_canonical(const F29& a) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) { const int32_t t = (int32_t)r.v[i] - (ge ? (int32_t)FR29_P[i] : 0) + br; r.v[i] = (uint32_t)t & M29; br = t >> 29; }
   return r;
+}
+}  // namespace aleo_mi355x
+#endif
+
+namespace aleo_mi355x {
+
+__device__ __forceinline__ void f29_tidy(F29& a) { f29_normalise(a); f29_reduce_partial(a); }       // any lazy value below 445 r -> exact digits, below 3 r
+__device__ __forceinline__ F29 f29_sqr(const F29& a) { return f29_mul(a, a); }                       // a normalised
+// Montgomery form -> the canonical number (limbs of a value below r): one product by the plain 1 leaves a value <= r, one conditional subtraction the rest
+__device__ __forceinline__ F29 f29_canonical(const F29& a) {
+  return f29_sub_r_if_ge(f29_mul(a, f29_small(1)));
 }
 __device__ __forceinline__ bool f29_same_limbs(const F29& a, const F29& b) { uint32_t o = 0;
 #pragma unroll
@@ -47,8 +75,8 @@ __device__ __forceinline__ bool f29_below_r(const F29& a) {                     
   return !ge;
 }
 
-struct Ed29 { F29 X, Y, Z, T; };                         // normalised coordinates (each the result of a product)
-struct Ed29Cached { F29 ym, yp, k, z2; };                // Y - X, Y + X, 2 d T, 2 Z of a fixed second operand, tidied
+struct Ed29 { F29 X, Y, Z, T; };                         // every coordinate exact digits, below 3 r (a product, a table constant or a tidied value)
+struct Ed29Cached { F29 ym, yp, k, z2; };                // Y - X, Y + X, 2 d T, 2 Z of a fixed second operand: exact digits, below 3 r (tidied; k a product)
 
 __device__ __forceinline__ Ed29Cached ed29_cache(const Ed29& p, const F29& d2) {
   Ed29Cached c;

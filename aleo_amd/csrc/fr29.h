@@ -7,7 +7,7 @@
 // leave room for values up to 445 r: a butterfly needs no conditional subtraction, the product brings everything back below 1.1 r.
 //
 // Classes.  "normalised": limbs 0..7 < 2^29 (the top limb holds what is left).  A product accepts a multiplicand with limbs < 2^31.4 and a
-// normalised multiplier; value bounds a < A r, b < B r give a normalised result < (A B / 445 + 1) r.
+// normalised multiplier; value bounds a < A r (A r <= 2^261 = 438.79 r), b < B r give a normalised result < (A B / 438 + 1) r.
 // The data in HBM stays what it is (8 x 32-bit words, Montgomery with R = 2^256): repacking the words into 29-bit limbs does not change the
 // number, and multiplying a number X by a table entry w * 2^261 under this product gives X * w — the TABLES carry the second Montgomery form.
 #pragma once

@@ -161,8 +161,7 @@ __device__ __forceinline__ Ed29Cached ck_entry(const uint32_t* __restrict__ K, u
 template <class Next>
 __device__ __forceinline__ F29 commit_hash(Next&& next, uint32_t message_bits, const uint32_t* __restrict__ K, const CommitArgs& A) {
   Ed29 p;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) { p.X.v[i] = A.start[i]; p.Y.v[i] = A.start[9 + i]; p.T.v[i] = A.start[18 + i]; }
+  p.X = f29_limbs(A.start); p.Y = f29_limbs(A.start + 9); p.T = f29_limbs(A.start + 18);
   p.Z = rk_const(K, RK_ONE);
   uint32_t c = CM_DOMAIN_CHUNKS, nb = 0;                       // the chunk to come; the bits waiting for a whole one
   uint64_t acc = 0;

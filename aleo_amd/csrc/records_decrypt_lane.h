@@ -24,8 +24,7 @@ __device__ __forceinline__ uint32_t records_decrypt_lane(const uint32_t (&rvkw)[
   F29 rv = f29_from_words(rvkw);
   bool bad = !f29_below_r(rv);
   for (uint32_t j = 0; j < m; ++j) { uint32_t w[8]; load(j, w); bad = bad || !f29_below_r(f29_from_words(w)); }
-#pragma unroll
-  for (int i = 0; i < 9; ++i) rv.v[i] = bad ? 0u : rv.v[i];
+  rv = f29_zero_if(bad, rv);
   const F29 r2 = rk_const(K, RK_R2);
   F29 st[9];
 #pragma unroll
@@ -37,13 +36,8 @@ __device__ __forceinline__ uint32_t records_decrypt_lane(const uint32_t (&rvkw)[
     for (uint32_t j = 0; j < 8; ++j)
       if (at + j < m) {
         uint32_t w[8]; load(at + j, w);
-        F29 c = f29_from_words(w);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) c.v[i] = bad ? 0u : c.v[i];
-        F29 out = f29_canonical(f29_sub_pad(f29_mul(c, r2), st[1 + j]));
-#pragma unroll
-        for (int i = 0; i < 9; ++i) out.v[i] = bad ? 0u : out.v[i];
-        emit(at + j, out);
+        const F29 c = f29_zero_if(bad, f29_from_words(w));
+        emit(at + j, f29_zero_if(bad, f29_canonical(f29_sub_pad(f29_mul(c, r2), st[1 + j]))));
       }
   }
   return bad ? 2u : 0u;

@@ -39,10 +39,7 @@ static constexpr int RK_SQRT_BITS = 205, RK_INV_BITS = 253, RK_TWO_ADICITY = 47;
 
 struct ScanArgs { uint32_t naf_pos[8], naf_neg[8], naf_len; uint32_t addr[9]; };      // digits of k (bit i of pos / neg: digit i is +1 / -1), canonical limbs of the address x
 
-__device__ __forceinline__ F29 rk_const(const uint32_t* __restrict__ K, uint32_t idx) { F29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = K[idx * 9 + i];
-  return r; }
+__device__ __forceinline__ F29 rk_const(const uint32_t* __restrict__ K, uint32_t idx) { return f29_limbs(K, idx * 9); }
 
 #ifdef __HIPCC__
 // the 32 bytes at p (16-byte aligned) as eight words, by two 16-byte loads: how the kernels hand a lane a field that lies in device memory
@@ -71,9 +68,7 @@ static constexpr int SQRT_CHUNK = 8;
 __device__ __forceinline__ F29 f29_sqrt_fixed(const F29& a, const uint32_t* __restrict__ K) {
   const F29 y = f29_pow(a, K + RK_EXP_SQRT, RK_SQRT_BITS);
   F29 x = f29_mul(y, a), b = f29_mul(x, y);
-  F29 one; one.v[0] = 1;
-#pragma unroll
-  for (int i = 1; i < 9; ++i) one.v[i] = 0;
+  const F29 one = f29_small(1);
   constexpr int HEIGHT = RK_TWO_ADICITY - 1;                      // 46
   for (int j0 = 0; j0 < HEIGHT; j0 += SQRT_CHUNK) {
     const int c = HEIGHT - j0 < SQRT_CHUNK ? HEIGHT - j0 : SQRT_CHUNK;
@@ -152,8 +147,7 @@ template <class Emit>
 __device__ __forceinline__ uint32_t records_scan_lane(const uint32_t (&c0w)[8], const uint32_t (&nxw)[8], const uint32_t* __restrict__ K, const ScanArgs& A, Emit&& emit) {
   F29 nx = f29_from_words(nxw);
   bool bad = !f29_below_r(f29_from_words(c0w)) || !f29_below_r(nx);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) nx.v[i] = bad ? 0u : nx.v[i];                        // a malformed lane goes through the motions on zeros
+  nx = f29_zero_if(bad, nx);                                                      // a malformed lane goes through the motions on zeros
   const F29 one = rk_const(K, RK_ONE);
   const F29 x = f29_mul(nx, rk_const(K, RK_R2));
   const F29 xx = f29_sqr(x);
@@ -169,20 +163,13 @@ __device__ __forceinline__ uint32_t records_scan_lane(const uint32_t (&c0w)[8], 
     if (pos || neg) ed29_add(p, pc, neg);
   }
   const F29 xq = f29_mul(p.X, f29_pow(p.Z, K + RK_EXP_INV, RK_INV_BITS));         // Z is never 0 (the law is complete)
-  {
-    F29 out = f29_canonical(xq);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) out.v[i] = bad ? 0u : out.v[i];
-    emit(out);
-  }
+  emit(f29_zero_if(bad, f29_canonical(xq)));
   F29 st[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) st[i] = rk_const(K, RK_S0 + i);
   st[2] = f29_add(st[2], xq);
   const F29 rnd = psd_permute_take1(st, K);
-  F29 c0 = f29_from_words(c0w), addr;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) { c0.v[i] = bad ? 0u : c0.v[i]; addr.v[i] = A.addr[i]; }
+  const F29 c0 = f29_zero_if(bad, f29_from_words(c0w)), addr = f29_limbs(A.addr);
   const bool owner = f29_same_limbs(f29_canonical(f29_sub_pad(f29_mul(c0, rk_const(K, RK_R2)), rnd)), addr);
   return bad ? 2u : (owner ? 1u : 0u);
 }

@@ -39,8 +39,7 @@ __device__ __forceinline__ void records_scan_lane_many(const uint32_t (&c0w)[8],
   // the record alone: exactly the head of records_scan_lane
   F29 nx = f29_from_words(nxw);
   bool bad = !f29_below_r(f29_from_words(c0w)) || !f29_below_r(nx);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) nx.v[i] = bad ? 0u : nx.v[i];
+  nx = f29_zero_if(bad, nx);
   const F29 one = rk_const(K, RK_ONE);
   Ed29 q;                                                                           // Q = 2^i P
   {
@@ -56,8 +55,7 @@ __device__ __forceinline__ void records_scan_lane_many(const uint32_t (&c0w)[8],
 #pragma unroll
   for (int j = 0; j < W; ++j) {
     acc[j].Y = one; acc[j].Z = one;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) acc[j].X.v[i] = acc[j].T.v[i] = 0;
+    acc[j].X = f29_small(0); acc[j].T = f29_small(0);
   }
   const F29 d2 = rk_const(K, RK_D2);
   bool any = naf_len_max != 0;                                                      // every k is odd: position 0 holds a digit of every live key
@@ -84,26 +82,16 @@ __device__ __forceinline__ void records_scan_lane_many(const uint32_t (&c0w)[8],
     park(0, f29_mul(acc[0].X, inv));
   }
   // per key: as the tail of records_scan_lane
-  F29 c0 = f29_from_words(c0w);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) c0.v[i] = bad ? 0u : c0.v[i];
-  c0 = f29_mul(c0, rk_const(K, RK_R2));
+  const F29 c0 = f29_mul(f29_zero_if(bad, f29_from_words(c0w)), rk_const(K, RK_R2));
   for (uint32_t j = 0; j < live; ++j) {
     const F29 xq = fetch(j);
-    {
-      F29 out = f29_canonical(xq);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) out.v[i] = bad ? 0u : out.v[i];
-      emit(j, out);
-    }
+    emit(j, f29_zero_if(bad, f29_canonical(xq)));
     F29 st[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) st[i] = rk_const(K, RK_S0 + i);
     st[2] = f29_add(st[2], xq);
     const F29 rnd = psd_permute_take1(st, K);
-    F29 addr;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) addr.v[i] = A[j].addr[i];
+    const F29 addr = f29_limbs(A[j].addr);
     const bool owner = f29_same_limbs(f29_canonical(f29_sub_pad(c0, rnd)), addr);
     done(j, bad ? 2u : (owner ? 1u : 0u));
   }

@@ -51,10 +51,7 @@ static constexpr int SK_LEG_BITS = 252, SK_FIRST_CHUNK = 168, SK_CHUNKS = 85, SK
 
 struct SerialArgs { uint32_t naf_pos[8], naf_neg[8], naf_len; };      // the digits of the odd one of {sk_sig, sk_sig + l}, as ScanArgs holds the view key's
 
-__device__ __forceinline__ F29 f29_zero() { F29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = 0;
-  return r; }
+__device__ __forceinline__ F29 f29_zero() { return f29_small(0); }
 __device__ __forceinline__ bool f29_is_zero_limbs(const F29& a) { uint32_t o = 0;
 #pragma unroll
   for (int i = 0; i < 9; ++i) o |= a.v[i];
@@ -105,9 +102,7 @@ __device__ __forceinline__ Ed29 ell29_tail(const Ell29& e, const F29& qinv, bool
   F29 v = f29_mul(qinv, rk_const(K, SK_NEGA)); f29_tidy(v);
   F29 gv = ell29_curve(v, K); f29_tidy(gv);
   const F29 leg = f29_canonical(f29_pow(gv, K + SK_EXP_LEG, SK_LEG_BITS));      // 1, r - 1 or 0, as a plain number
-  F29 one; one.v[0] = 1;
-#pragma unroll
-  for (int i = 1; i < 9; ++i) one.v[i] = 0;
+  const F29 one = f29_small(1);
   const bool qr = f29_same_limbs(leg, one);
   bad = bad || f29_is_zero_limbs(leg);                                          // v = 0 or e = 0
   F29 alt = f29_sub_pad(rk_const(K, SK_NEGA), v); f29_tidy(alt);                // -v - a
@@ -142,8 +137,7 @@ template <class Emit>
 __device__ __forceinline__ uint32_t records_serial_lane(const uint32_t (&cmw)[8], const uint32_t* __restrict__ K, const SerialArgs& A, Emit&& emit) {
   F29 cm = f29_from_words(cmw);
   bool bad = !f29_below_r(cm);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) cm.v[i] = bad ? 0u : cm.v[i];                       // a refused lane goes through the motions on zeros
+  cm = f29_zero_if(bad, cm);                                                      // a refused lane goes through the motions on zeros
   const F29 d2 = rk_const(K, RK_D2);
   // H
   F29 st[3];
@@ -193,10 +187,7 @@ __device__ __forceinline__ uint32_t records_serial_lane(const uint32_t (&cmw)[8]
     for (int b = 0; b < 4; ++b) if (4 * w + b < SK_NONCE_BITS) v |= (uint32_t)f29_bit(nonce, 4 * w + b) << b;
     ed29_add(p, sk_entry(K, SK_RND + 3 * (16 * w + v)), false);
   }
-  F29 out = f29_canonical(f29_mul(p.X, f29_pow(p.Z, K + RK_EXP_INV, RK_INV_BITS)));
-#pragma unroll
-  for (int i = 0; i < 9; ++i) out.v[i] = bad ? 0u : out.v[i];
-  emit(out);
+  emit(f29_zero_if(bad, f29_canonical(f29_mul(p.X, f29_pow(p.Z, K + RK_EXP_INV, RK_INV_BITS)))));
   return bad ? 2u : 0u;
 }
 

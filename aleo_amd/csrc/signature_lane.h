@@ -169,7 +169,7 @@ __device__ __forceinline__ void sg_challenge(uint32_t (&out)[8], Head&& head, ui
   for (uint32_t b = 0; b < blocks; ++b) {
     phase();
     if (b == 0) {
-      F29 count = f29_zero(); count.v[0] = 4u + m;
+      const F29 count = f29_small(4u + m);
       st[1] = rk_const(K, SG_DOM8); st[2] = f29_mul(count, rk_const(K, RK_R2));
     } else {
       uint32_t j = 8u * b - 12u;                                                  // the field that st[1] takes; the four elements before field 0 in block 1
@@ -220,10 +220,7 @@ __device__ __forceinline__ uint32_t signature_verify_lane(Load&& load, uint32_t 
   load(2, w8); bad |= !f29_below_r(f29_from_words(w8));
   load(3, w8); bad |= !f29_below_r(f29_from_words(w8));
   load(4, w8); bad |= !f29_below_r(f29_from_words(w8));
-  auto part = [&](uint32_t k) { uint32_t w[8]; load(k, w); F29 v = f29_from_words(w);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) v.v[i] = bad ? 0u : v.v[i];                       // a malformed lane goes through the motions on zeros
-    return v; };
+  auto part = [&](uint32_t k) { uint32_t w[8]; load(k, w); return f29_zero_if(bad, f29_from_words(w)); };      // a malformed lane goes through the motions on zeros
   if (bad) len = 0;
   const uint32_t m = (8u * len + SIG_FIELD_BITS - 1u) / SIG_FIELD_BITS;
   auto mont = [&](uint32_t k, uint32_t r2) { return f29_mul(part(k), rk_const(K, r2)); };      // part k in Montgomery form

@@ -508,6 +508,17 @@ int32_t aleo_mi355x_selftest_f28_rows(const void* a224, const void* b224, uint32
 int32_t aleo_mi355x_selftest_te28_rows(const void* a224, const void* b224, uint32_t n_add, void* out_pair224, void* out_quad224, uint32_t* z_add_u32,
                                        const void* acc224, const void* row168, const uint8_t* how_u8, uint32_t n_madd, void* out_acc224, uint8_t* z_madd_u8);
 
+/* The 29-bit-limb form of Fr (csrc/fr29.h: 9 limbs, Montgomery with R = 2^261) and the Edwards helpers on it (csrc/edwards29.h) on rows the caller built, raw
+ * limbs in and out (host memory; the device converts nothing), one lane per row, so that a test can place every limb at the edge of an operand class and compare
+ * with integers.  An element is 9 u32, a point 36 u32 (X | Y | Z | T; each coordinate exact digits below 3 r).  out_mul36[i] = f29_mul(mul_a36[i], mul_b36[i])
+ * (a: limbs below 2^31.4, value below 2^261; b: limbs 0..7 digits); out_tidy36[i] = f29_tidy(tidy36[i]) (any limbs whose carries fit, value below 445 r);
+ * out_canon36[i] = f29_canonical(canon36[i]) (a multiplicand); out_add144[i] = p144[i] + q144[i], or p144[i] - q144[i] where neg_u8[i] != 0, by ed29_add onto
+ * ed29_cache(q144[i], d2_36) with d2_36 the limbs of 2 d in Montgomery form; out_dbl144[i] = 2 dbl144[i] by ed29_dbl, which computes T only where want_t_u8[i] != 0
+ * (the T that came in is stored otherwise).  Outputs are filled with 0xA5 before the kernels run.  A count may be 0 (its pointers are then ignored); at most 2^20 each. */
+int32_t aleo_mi355x_selftest_ed29_rows(const void* mul_a36, const void* mul_b36, uint32_t n_mul, void* out_mul36, const void* tidy36, uint32_t n_tidy, void* out_tidy36,
+                                       const void* canon36, uint32_t n_canon, void* out_canon36, const void* p144, const void* q144, const uint8_t* neg_u8, const void* d2_36,
+                                       uint32_t n_add, void* out_add144, const void* dbl144, const uint8_t* want_t_u8, uint32_t n_dbl, void* out_dbl144);
+
 /* The slice stage of the MSM sort alone (bucket scan, top scan, slice ordering) on a histogram from the host: hist[g] = points of bucket g, n_buckets <= 2^20,
  * total_pairs = the pair count the slice rule is picked from (the sum of hist or more: less is refused); fused != 0 runs the top scan inside the ordering kernel, as the
  * chains of a proof do.  *violations = how often what the device left behind breaks one of: `order` is a permutation of the slice ids; slice lengths never increase along
