@@ -16,7 +16,7 @@ EXPORTS = [
     'aleo_mi355x_ntt_fr_device', 'aleo_mi355x_ntt_fr_batch_device', 'aleo_mi355x_ntt_fr_from_device', 'aleo_mi355x_fr_grid_scale_device', 'aleo_mi355x_kzg_commit', 'aleo_mi355x_kzg_commit_device', 'aleo_mi355x_kzg_commit_hiding',
     'aleo_mi355x_msm_g1_batch_device', 'aleo_mi355x_kzg_commit_batch_device', 'aleo_mi355x_kzg_commit_batch', 'aleo_mi355x_kzg_commit_segments', 'aleo_mi355x_kzg_commit_segments_device',
     'aleo_mi355x_fr_vec_op_device', 'aleo_mi355x_fr_batch_inverse_device', 'aleo_mi355x_fr_spmv_device', 'aleo_mi355x_fr_divide_by_linear_device', 'aleo_mi355x_kzg_open_device', 'aleo_mi355x_fq_mul',
-    'aleo_mi355x_fr_mul', 'aleo_mi355x_selftest_madd28', 'aleo_mi355x_selftest_addquad', 'aleo_mi355x_selftest_f28_rows', 'aleo_mi355x_selftest_te28_rows', 'aleo_mi355x_selftest_g2pair', 'aleo_mi355x_selftest_g2p_rows', 'aleo_mi355x_selftest_ed29_rows', 'aleo_mi355x_selftest_slice_order', 'aleo_mi355x_selftest_fr_step', 'aleo_mi355x_last_msm_timing', 'aleo_mi355x_strerror', 'aleo_mi355x_last_error',
+    'aleo_mi355x_fr_mul', 'aleo_mi355x_selftest_madd28', 'aleo_mi355x_selftest_addquad', 'aleo_mi355x_selftest_f28_rows', 'aleo_mi355x_selftest_te28_rows', 'aleo_mi355x_selftest_g2pair', 'aleo_mi355x_selftest_g2p_rows', 'aleo_mi355x_selftest_ed29_rows', 'aleo_mi355x_selftest_slice_order', 'aleo_mi355x_selftest_sort_pairs', 'aleo_mi355x_selftest_fr_step', 'aleo_mi355x_last_msm_timing', 'aleo_mi355x_strerror', 'aleo_mi355x_last_error',
     'aleo_mi355x_version',
     'aleo_mi355x_g1_compress', 'aleo_mi355x_g1_decompress', 'aleo_mi355x_fr_to_bytes', 'aleo_mi355x_fr_from_bytes',
     'aleo_mi355x_bech32m_encode', 'aleo_mi355x_bech32m_decode', 'aleo_mi355x_proof_to_bytes',
@@ -179,6 +179,7 @@ def lib():
         'aleo_mi355x_selftest_g2p_rows': ([vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp], i32),
         'aleo_mi355x_selftest_ed29_rows': ([vp, vp, u32, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp], i32),
         'aleo_mi355x_selftest_slice_order': ([vp, u32, u32, i32, ctypes.POINTER(u32)], i32),
+        'aleo_mi355x_selftest_sort_pairs': ([vp, vp, vp, vp, u32, i32, i32, i32, u32, u32, vp, u32, vp, vp, sz, ctypes.POINTER(u32)], i32),
         'aleo_mi355x_selftest_fr_step': ([u32, ctypes.POINTER(vp), ctypes.POINTER(sz), vp], i32),
         'aleo_mi355x_last_msm_timing': ([ctypes.POINTER(ctypes.c_double), i32], i32),
         'aleo_mi355x_strerror': ([i32], ctypes.c_char_p),

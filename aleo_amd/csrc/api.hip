@@ -679,6 +679,14 @@ int32_t aleo_mi355x_selftest_ed29_rows(const void* mul_a36, const void* mul_b36,
 int32_t aleo_mi355x_selftest_slice_order(const uint32_t* hist, uint32_t n_buckets, uint32_t total_pairs, int32_t fused, uint32_t* violations) {
   return guarded([&] { if (!hist || !violations) return ALEO_MI355X_ERR_BAD_ARG; Slot sl; if (sl.rc) return sl.rc; return selftest_slice_order(sl.c, hist, n_buckets, total_pairs, fused != 0, violations); });
 }
+int32_t aleo_mi355x_selftest_sort_pairs(const void* scalars, const uint32_t* seg_n, const uint32_t* seg_off, const uint8_t* seg_set, uint32_t nseg, int32_t c, int32_t pre, int32_t mont,
+                                        uint32_t k_sets, uint32_t row_stride, const uint8_t* inf_u8, uint32_t tile, uint32_t* hist_out, uint32_t* sorted_out, size_t sorted_cap, uint32_t* pairs_out) {
+  return guarded([&] {
+    if (!scalars || !seg_n || !seg_off || !seg_set || !hist_out || !sorted_out || !pairs_out || (pre != 0 && pre != 1) || (mont != 0 && mont != 1)) return bad_arg("selftest_sort_pairs: bad argument");
+    Slot sl; if (sl.rc) return sl.rc;
+    return selftest_sort_pairs(sl.c, scalars, seg_n, seg_off, seg_set, nseg, c, pre != 0, mont != 0, k_sets, row_stride, inf_u8, tile, hist_out, sorted_out, sorted_cap, pairs_out);
+  });
+}
 int32_t aleo_mi355x_selftest_g2pair(const void* affine192, uint32_t n_points, uint32_t n_pairs, uint32_t* failures2) {
   return guarded([&] { if (!affine192 || !failures2 || n_points < 3 || !n_pairs || n_pairs > (1u << 20)) return ALEO_MI355X_ERR_BAD_ARG; Slot sl; if (sl.rc) return sl.rc; return selftest_g2pair(sl.c, affine192, n_points, n_pairs, failures2); });
 }

@@ -242,6 +242,9 @@ int32_t selftest_ed29_rows(Ctx* c, const void* mul_a36, const void* mul_b36, uin
                            uint32_t n_add, void* out_add144, const void* dbl144, const uint8_t* want_t_u8, uint32_t n_dbl, void* out_dbl144);
 // msm_sort.hip: the slice stage (bucket scan, top scan, slice ordering) on a host histogram, checked against a host recount
 int32_t selftest_slice_order(Ctx* c, const uint32_t* h_hist, uint32_t M, uint32_t pairs, bool fused, uint32_t* violations);
+// msm_sort.hip: the sort itself (msm_sort_phase) on scalars, segments and infinity flags from the host; hist[], the index stream and the pair count copied back
+int32_t selftest_sort_pairs(Ctx* c, const void* h_scalars, const uint32_t* seg_n, const uint32_t* seg_off, const uint8_t* seg_set, uint32_t nseg, int cbits, bool pre, bool mont,
+                            uint32_t k_sets, uint32_t row_stride, const uint8_t* h_inf, uint32_t tile, uint32_t* hist_out, uint32_t* sorted_io, size_t sorted_cap, uint32_t* pairs_out);
 // g1_setup.hip: synthetic base sets, the fixed-base tables, row formats
 int32_t generate_multiples(Ctx* c, const void* base104, uint64_t first, size_t n, PinnedBases* out);
 int32_t generate_from_scalars(Ctx* c, const void* base104, const void* scalars32, size_t n, PinnedBases* out);

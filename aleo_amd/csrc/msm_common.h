@@ -81,8 +81,9 @@ struct SliceMeta { uint32_t NT = 0, max_m = 0, n_heavy = 0, n_super = 0, max_com
 // a set's buckets).  Records ev[0] before and ev[1] after the sort unless `lean` (phase timing off: every event record between two kernels is ~6 us of
 // idle GPU); the slice metadata comes back through the slot's pinned, device-mapped buffer (k_scan_top stores it, msm_wait_meta polls).
 // segs: ptr / n / off / set filled in by the caller; col0, ncol are computed here.  pts = sum of the segment lengths.
+// tile: 0, or the scalars per block of the level-1 passes (2048, 4096 or 8192) in place of the one picked from pts — the test hook selftest_sort_pairs alone passes it.
 int32_t msm_sort_phase(Ctx* c, SegArgs& segs, size_t pts, bool mont, const uint8_t* d_inf, uint32_t row_stride,
-                       const MsmPlan& P, bool pre, hipStream_t s, SortPhase* out, bool lean = false);
+                       const MsmPlan& P, bool pre, hipStream_t s, SortPhase* out, bool lean = false, uint32_t tile = 0);
 int32_t msm_wait_meta(Ctx* c, const SortPhase& sp, hipStream_t s, SliceMeta* m);
 
 }  // namespace aleo_mi355x

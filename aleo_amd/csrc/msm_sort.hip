@@ -586,6 +586,7 @@ template <bool MONT> static void launch_sort(int c, bool pre, const SortArgs& a,
   }
 #undef CASE
 }
+static bool sort_has_case(int c, bool pre) { return pre ? (c == 13 || c == 16 || c == 17 || c == 20) : (c >= 2 && c <= 16); }      // the widths launch_sort instantiates
 
 // lg of the slice count pick_rule() aims for when it cuts buckets to fill the chip (2^17 = 2 waves per SIMD: measured equal to 2^18 on uniform input, 4 % better on witness-like scalars)
 static constexpr uint32_t FILL_SHIFT = 17;
@@ -628,11 +629,11 @@ static int32_t launch_slice_stage(const SortPhase& sp, uint2* tile_tot, const ui
 }
 
 int32_t msm_sort_phase(Ctx* c, SegArgs& segs, size_t pts, bool mont, const uint8_t* d_inf, uint32_t row_stride,
-                       const MsmPlan& P, bool pre, hipStream_t s, SortPhase* out, bool lean) {
+                       const MsmPlan& P, bool pre, hipStream_t s, SortPhase* out, bool lean, uint32_t tile) {
   SortPhase& sp = *out; sp.P = P;
   // columns of the level-1 count matrix: the blocks of a set's segments side by side; every row is as wide as the widest set
   uint32_t width[MAX_SETS] = {}, nblk_x = 0;
-  segs.tile = pts >= ((size_t)1 << 22) ? 8192u : (pts >= ((size_t)1 << 21) ? 4096u : PART_TILE);
+  segs.tile = tile ? tile : pts >= ((size_t)1 << 22) ? 8192u : (pts >= ((size_t)1 << 21) ? 4096u : PART_TILE);      // (tile != 0: selftest_sort_pairs alone)
   for (uint32_t q = 0; q < segs.nseg; ++q) {
     const uint32_t nb = (segs.n[q] + segs.tile - 1) / segs.tile, st = pre ? segs.set[q] : 0;
     segs.col0[q] = width[st]; width[st] += nb; nblk_x = nb > nblk_x ? nb : nblk_x;
@@ -804,6 +805,55 @@ int32_t selftest_slice_order(Ctx* c, const uint32_t* h_hist, uint32_t M, uint32_
     }
   }
   *violations = bad;
+  return ALEO_MI355X_OK;
+}
+
+// Test hook (aleo_mi355x_selftest_sort_pairs): msm_sort_phase itself on scalars, segments and infinity flags from the host, and what it left behind — hist[], the index
+// stream, the level-1 scan's grand total — copied back for a test to compare with the digits of the scalars in integers.  Everything the kernels index is checked here first
+// (a width without an instance, a set the count matrix has no rows for, a flag or table index past row_stride are refused before anything is launched).
+int32_t selftest_sort_pairs(Ctx* c, const void* h_scalars, const uint32_t* seg_n, const uint32_t* seg_off, const uint8_t* seg_set, uint32_t nseg, int cbits, bool pre, bool mont,
+                            uint32_t k_sets, uint32_t row_stride, const uint8_t* h_inf, uint32_t tile, uint32_t* hist_out, uint32_t* sorted_io, size_t sorted_cap, uint32_t* pairs_out) {
+  auto refuse = [](const char* why) { g_last_error = std::string("selftest_sort_pairs: ") + why; return ALEO_MI355X_ERR_BAD_ARG; };
+  if (!sort_has_case(cbits, pre)) return refuse("no sort instance of this window width on this path");
+  if (!nseg || nseg > MAX_SEGS) return refuse("1 .. MAX_SEGS segments");
+  if (!k_sets || k_sets > sets_of_window(cbits) || (!pre && k_sets != 1)) return refuse("more sets than a chain of this width holds (the plain path: one)");
+  if (tile && tile != 2048 && tile != 4096 && tile != 8192) return refuse("tile is 0, 2048, 4096 or 8192");
+  const uint32_t W = (uint32_t)win_count(cbits);
+  size_t pts = 0;
+  for (uint32_t q = 0; q < nseg; ++q) {
+    if (!seg_n[q]) return refuse("empty segment");
+    if (seg_set[q] >= k_sets) return refuse("segment of a set the call does not have");
+    if ((uint64_t)seg_off[q] + seg_n[q] > row_stride) return refuse("a segment reaches past row_stride");
+    pts += seg_n[q];
+  }
+  if (pts > ((size_t)1 << 20)) return refuse("at most 2^20 scalars");
+  if ((uint64_t)W * row_stride >= (1ull << 31)) return refuse("windows * row_stride reaches bit 31 of an index");
+  const size_t pairs_max = pts * W;
+  if (sorted_cap < pairs_max) return refuse("sorted_io is shorter than scalars * windows");
+
+  MsmPlan P; P.c = (uint32_t)cbits; P.B = 1u << (cbits - 1); P.W = pre ? k_sets : W; P.M = P.W * P.B; P.S = P.B >= 8 ? 8 : P.B;
+  DevTmp d_scalars, d_inf; int32_t rc;
+  if ((rc = d_scalars.alloc(pts * 32))) return rc;
+  if (h_inf && (rc = d_inf.alloc(row_stride))) return rc;
+  if ((rc = c->sorted.reserve(pairs_max * 4))) return rc;      // (what msm_sort_phase reserves: it keeps this buffer)
+  hipStream_t s = c->stream;
+  HIPCHK(hipMemcpyAsync(d_scalars.p, h_scalars, pts * 32, hipMemcpyHostToDevice, s));
+  if (h_inf) HIPCHK(hipMemcpyAsync(d_inf.p, h_inf, row_stride, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->sorted.p, sorted_io, pairs_max * 4, hipMemcpyHostToDevice, s));      // the caller's fill: what the sort does not write comes back as it went in
+  SegArgs segs{}; size_t at = 0;
+  for (uint32_t q = 0; q < nseg; ++q) {
+    segs.ptr[q] = (const char*)d_scalars.p + at * 32; segs.n[q] = seg_n[q]; segs.off[q] = seg_off[q]; segs.set[q] = seg_set[q]; at += seg_n[q];
+  }
+  segs.nseg = nseg;
+  SortPhase sp;
+  rc = msm_sort_phase(c, segs, pts, mont, (const uint8_t*)d_inf.p, row_stride, P, pre, s, &sp, true, tile);
+  const hipError_t drained = hipStreamSynchronize(s);          // before d_scalars / d_inf go out of scope, whatever was queued
+  if (rc) return rc;
+  HIPCHK(drained);
+  if (sp.sorted != c->sorted.as<uint32_t>() || sp.M != P.M) { g_last_error = "selftest_sort_pairs: internal: workspace moved"; return ALEO_MI355X_ERR_HIP; }
+  HIPCHK(hipMemcpy(hist_out, sp.hist, (size_t)P.M * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(sorted_io, sp.sorted, pairs_max * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(pairs_out, sp.total_pairs, 4, hipMemcpyDeviceToHost));
   return ALEO_MI355X_OK;
 }
 

@@ -526,6 +526,19 @@ int32_t aleo_mi355x_selftest_ed29_rows(const void* mul_a36, const void* mul_b36,
  * sets) equal a host recount. */
 int32_t aleo_mi355x_selftest_slice_order(const uint32_t* hist, uint32_t n_buckets, uint32_t total_pairs, int32_t fused, uint32_t* violations);
 
+/* The scalar sort of the MSMs alone (signed balanced digits, both levels of the counting sort, as every G1 and G2 call runs them), on host memory, and what it left
+ * behind copied back.  scalars: the segments' scalars one after another, 32 bytes each (canonical, or Montgomery form where mont != 0); segment q has seg_n[q] >= 1
+ * scalars for the bases seg_off[q] .. of the set and adds into result seg_set[q]; nseg <= 64.  c = window width, pre != 0 the table path (every window of a set shares
+ * its 2^(c-1) buckets; the index of digit w of scalar i is w * row_stride + off + i), pre == 0 the plain path (bucket sets per window; the index is off + i; k_sets == 1,
+ * every seg_set 0).  inf_u8: NULL, or row_stride bytes: scalar i of segment q is skipped where inf_u8[off + i] != 0.  tile: 0 for the level-1 tile the sort picks itself,
+ * or 2048, 4096, 8192.  With W = ceil(254 / c):  hist_out[M], M = (pre ? k_sets : W) * 2^(c-1): hist_out[g] = indices in bucket g;  sorted_out[sorted_cap], sorted_cap >=
+ * (sum of seg_n) * W: uploaded as it comes (fill it with a value no index takes), sorted, and the first (sum of seg_n) * W words copied back: bucket g's indices (bit 31:
+ * negative digit) at [prefix(g), prefix(g) + hist_out[g]) in any order, the rest untouched;  *pairs_out = the pair count of the level-1 scan.
+ * ALEO_MI355X_ERR_BAD_ARG, and nothing launched: a (c, pre) without a sort instance (plain 2..16; table 13, 16, 17, 20), more sets than a chain of that width holds
+ * (32, 32, 16, 2), a set >= k_sets, an empty segment, off + n > row_stride, W * row_stride >= 2^31, more than 2^20 scalars, a short sorted_out. */
+int32_t aleo_mi355x_selftest_sort_pairs(const void* scalars, const uint32_t* seg_n, const uint32_t* seg_off, const uint8_t* seg_set, uint32_t nseg, int32_t c, int32_t pre, int32_t mont,
+                                        uint32_t k_sets, uint32_t row_stride, const uint8_t* inf_u8, uint32_t tile, uint32_t* hist_out, uint32_t* sorted_out, size_t sorted_cap, uint32_t* pairs_out);
+
 /* The lane-pair Fq2 arithmetic of the G2 path (g2.hip: components of an Fq2 value across two lanes, 28-bit limbs) against the one-lane 32-bit code on
  * chains over n_points affine G2 points (192-byte rows, host memory, >= 3 of them, all on the curve): sums, a sum with a shared operand, a doubling, the
  * same-point case of the addition.  failures2[0] = pairs that disagreed, failures2[1] = OR of the failing steps (1 a, 2 s, 4 u, 8 2u, 16 u + u). */
