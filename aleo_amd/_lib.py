@@ -48,6 +48,9 @@ EXPORTS = [
     'aleo_mi355x_private_key_encrypt', 'aleo_mi355x_private_key_decrypt', 'aleo_mi355x_private_keys_open', 'aleo_mi355x_private_keys_open_host', 'aleo_mi355x_min_key_ciphertexts',
     'aleo_mi355x_record_plaintext_parse', 'aleo_mi355x_plaintext_commitment', 'aleo_mi355x_plaintexts_commitments', 'aleo_mi355x_plaintexts_commitments_host',
     'aleo_mi355x_plaintexts_serial_numbers', 'aleo_mi355x_plaintexts_serial_numbers_host', 'aleo_mi355x_min_plaintexts', 'aleo_mi355x_plaintexts_last_routed',
+    'aleo_mi355x_record_encrypt', 'aleo_mi355x_record_encrypt_symmetric', 'aleo_mi355x_record_nonce', 'aleo_mi355x_records_encrypt', 'aleo_mi355x_records_encrypt_host',
+    'aleo_mi355x_encrypted_free', 'aleo_mi355x_encrypted_text', 'aleo_mi355x_encrypted_offsets', 'aleo_mi355x_encrypted_flags', 'aleo_mi355x_encrypted_rvk',
+    'aleo_mi355x_min_encrypt', 'aleo_mi355x_records_encrypt_last_routed',
 ]
 
 
@@ -261,6 +264,15 @@ def lib():
         'aleo_mi355x_plaintexts_serial_numbers_host': ([vp, vp, vp, vp, vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, vp, vp, sz], i32),
         'aleo_mi355x_min_plaintexts': ([], sz),
         'aleo_mi355x_plaintexts_last_routed': ([], sz),
+        'aleo_mi355x_record_encrypt': ([ctypes.c_char_p, vp, i32, ctypes.c_char_p, ctypes.POINTER(sz)], i32),
+        'aleo_mi355x_record_encrypt_symmetric': ([ctypes.c_char_p, vp, ctypes.c_char_p, ctypes.POINTER(sz)], i32),
+        'aleo_mi355x_record_nonce': ([vp, vp], i32),
+        'aleo_mi355x_records_encrypt': ([ctypes.POINTER(vp), vp, vp, sz, vp, i32], i32),
+        'aleo_mi355x_records_encrypt_host': ([ctypes.POINTER(vp), vp, vp, sz, vp, i32], i32),
+        'aleo_mi355x_encrypted_free': ([vp], None),
+        **{'aleo_mi355x_encrypted_' + name: ([vp], vp) for name in ('text', 'offsets', 'flags', 'rvk')},
+        'aleo_mi355x_min_encrypt': ([], sz),
+        'aleo_mi355x_records_encrypt_last_routed': ([], sz),
         'aleo_mi355x_found_free': ([vp], None),
         **{'aleo_mi355x_found_' + name: ([vp], sz) for name in ('count', 'fields', 'unparsed', 'first_unparsed', 'owned')},
         **{'aleo_mi355x_found_' + name: ([vp], vp) for name in ('index', 'kind', 'rvk', 'offsets', 'plain', 'status', 'microcredits', 'serials', 'commitments')},

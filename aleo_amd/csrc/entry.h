@@ -4,6 +4,7 @@
 #pragma once
 #include "ctx.h"
 #include <cstdlib>
+#include <cstring>
 
 namespace aleo_mi355x {
 
@@ -11,6 +12,15 @@ namespace aleo_mi355x {
 template <class F> int32_t guarded(F&& body, int32_t on_throw = ALEO_MI355X_ERR_HIP) { try { return body(); } catch (...) { return on_throw; } }
 
 inline int32_t bad_arg(const char* why) { g_last_error = why; return ALEO_MI355X_ERR_BAD_ARG; }      // a refused argument and the text that says which
+
+// A string through the (out, in/out length) convention of the C ABI: *out_len in = the capacity of out, out = the string's length without the terminating 0, which is
+// written as well; a buffer that is too short is BAD_ARG with the length in place
+inline int32_t put_string(const std::string& s, char* out, size_t* out_len, const char* who) {
+  const size_t cap = *out_len; *out_len = s.size();
+  if (!out || cap < s.size() + 1) { g_last_error = std::string(who) + ": the output buffer is too short (out_len holds the string's length; one more byte ends it)"; return ALEO_MI355X_ERR_BAD_ARG; }
+  std::memcpy(out, s.c_str(), s.size() + 1);
+  return ALEO_MI355X_OK;
+}
 
 // A size from the environment, read per call: `dflt` where the variable is unset, empty or no decimal number.
 inline size_t env_size(const char* name, size_t dflt) { const char* e = std::getenv(name); if (!e || !*e) return dflt; char* end = nullptr; const unsigned long long v = std::strtoull(e, &end, 10); return end && *end == 0 ? (size_t)v : dflt; }

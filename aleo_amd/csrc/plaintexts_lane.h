@@ -153,9 +153,11 @@ __host__ __device__ __forceinline__ bool pt_field(Ch&& c, uint32_t& at, PtField&
 struct PtMeasure { uint32_t first_at, entries, data_bits; uint64_t microcredits; };
 
 // The first walk over a string of `len` characters: everything the lane verifies.  Field 0 is the owner, fields 1 .. entries the entries, the last one the nonce.
+// visit(F, which): every field once it has passed its checks, in order — which PT_OWNER, PT_ENTRY or PT_NONCE (records_encrypt_lane.h sizes its output there).
 // false: route
-template <class Ch>
-__host__ __device__ __forceinline__ bool pt_measure(Ch&& c, uint32_t len, PtMeasure& M) {
+static constexpr uint32_t PT_OWNER = 0, PT_ENTRY = 1, PT_NONCE = 2;
+template <class Ch, class Visit>
+__host__ __device__ __forceinline__ bool pt_measure(Ch&& c, uint32_t len, PtMeasure& M, Visit&& visit) {
   if (len > PT_MAX_CHARS) return false;
   uint32_t at = 0, hashes[PT_MAX_ENTRIES];
 #pragma unroll
@@ -174,10 +176,12 @@ __host__ __device__ __forceinline__ bool pt_measure(Ch&& c, uint32_t len, PtMeas
     const bool is_owner = PT_IS(name, "owner"), is_nonce = PT_IS(name, "_nonce");
     if (k == 0) {
       if (!is_owner || F.type != 0 || F.vis == 0 || !pt_punct(c, at, ',')) return false;
+      visit(F, PT_OWNER);
       continue;
     }
     if (is_nonce) {
       if (F.type != 3 || F.vis != 1 || !pt_punct(c, at, '}')) return false;
+      visit(F, PT_NONCE);
       break;
     }
     if (is_owner || F.name_len > 31 || !pt_is_letter(c(F.name_at)) || M.entries == PT_MAX_ENTRIES || !pt_punct(c, at, ',')) return false;
@@ -190,10 +194,12 @@ __host__ __device__ __forceinline__ bool pt_measure(Ch&& c, uint32_t len, PtMeas
     if (name.lo == pt_pack("microcre", 0) && name.hi == pt_pack("microcre", 4) && name.n == 12 && PT_IS(tail, "dits") && F.type == 12) M.microcredits = (uint64_t)F.v[0] | (uint64_t)F.v[1] << 32;
     M.data_bits += 8u * F.name_len + 2u + 26u + pt_literal_bits(F.type);
     ++M.entries;
+    visit(F, PT_ENTRY);
   }
   pt_skip_ws(c, at);
   return at == len;
 }
+template <class Ch> __host__ __device__ __forceinline__ bool pt_measure(Ch&& c, uint32_t len, PtMeasure& M) { return pt_measure(c, len, M, [](const PtField&, uint32_t) {}); }
 
 // The second walk: the message behind the names, item by item, of a string pt_measure accepted
 struct PtWalk { uint32_t stage, at, k; PtField F; };

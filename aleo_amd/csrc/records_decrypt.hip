@@ -109,13 +109,6 @@ static int32_t decrypt_on_device(uint8_t* plain, uint8_t* flags, const uint8_t* 
 }
 
 // ---- one record, entirely on the host ---------------------------------------------------------------------------------------------------------------------
-static int32_t put_string(const std::string& s, char* out, size_t* out_len, const char* who) {
-  const size_t cap = *out_len; *out_len = s.size();
-  if (!out || cap < s.size() + 1) { g_last_error = std::string(who) + ": the output buffer is too short (out_len holds the string's length; one more byte ends it)"; return ALEO_MI355X_ERR_BAD_ARG; }
-  std::memcpy(out, s.c_str(), s.size() + 1);
-  return ALEO_MI355X_OK;
-}
-
 static int32_t record_decrypt_on_host(const char* record1, const void* view_key32, const void* address_x32, char* out, size_t* out_len) {
   if (!record1 || !address_x32 || !out_len) return bad_arg("record_decrypt: null argument");
   plaintext::Record r; if (int32_t rc = plaintext::parse(r, record1, "record_decrypt")) return rc;

@@ -19,7 +19,10 @@ RecordPlaintext.serialNumberString of the wasm) — is serial_numbers, found_ser
 aleo_mi355x_found_serial_numbers: csrc/records_serial.hip), with record_commitment, record_checksum and Account.from_private_key on the host beside them.
 Callers that hold record PLAINTEXT strings — what every write call of the reference takes, what findUnspentRecords hands back and a wallet stores — pass those:
 RecordPlaintext.from_string reads one, serial_number_string works on any plaintext, and plaintext_commitments, plaintext_serial_numbers and plaintexts_unspent
-take a batch of them through one call (aleo_mi355x_plaintexts_commitments, aleo_mi355x_plaintexts_serial_numbers: csrc/plaintexts.hip)."""
+take a batch of them through one call (aleo_mi355x_plaintexts_commitments, aleo_mi355x_plaintexts_serial_numbers: csrc/plaintexts.hip).
+The other direction — what every execute, transfer, split and join runs for each output record (rust/src/program/execute.rs:74,177, transfer.rs:99-106) — is
+RecordPlaintext.encrypt / encrypt_symmetric, record_nonce and, for a batch, encrypt_many (aleo_mi355x_record_encrypt, aleo_mi355x_records_encrypt:
+csrc/records_encrypt.hip): plaintext strings and randomizers in, a RecordBatch of "record1…" strings out that scan_strings and decrypt_strings take as it is."""
 from __future__ import annotations
 import ctypes, weakref
 import numpy as np
@@ -256,6 +259,18 @@ class RecordPlaintext:
         if not isinstance(v, str): return 0
         lit = v.rsplit('.', 1)[0]
         return int(lit[:-3]) if lit.endswith('u64') and lit[:-3].isdigit() else 0
+
+    def encrypt(self, randomizer, set_nonce: bool = False) -> RecordCiphertext:
+        """Record::encrypt(randomizer) on the host (aleo_mi355x_record_encrypt): the randomizer is a scalar below the subgroup order (an integer or 32 little-endian
+        bytes) and x(randomizer G) must be this string's _nonce — or, with set_nonce, replaces it."""
+        r = np.frombuffer(view_key_bytes(randomizer), dtype=np.uint8)
+        return RecordCiphertext.from_string(_string_out(lambda buf, ln: lib().aleo_mi355x_record_encrypt(self.string.encode(), _p(r), 1 if set_nonce else 0, buf, ln), 'record_encrypt'))
+
+    def encrypt_symmetric(self, rvk) -> RecordCiphertext:
+        """Record::encrypt_symmetric_unchecked(record view key) on the host (aleo_mi355x_record_encrypt_symmetric): rvk is the key's x (an integer or 32 bytes); the
+        nonce stays what the string says."""
+        k = np.frombuffer(address_x_bytes(rvk), dtype=np.uint8)
+        return RecordCiphertext.from_string(_string_out(lambda buf, ln: lib().aleo_mi355x_record_encrypt_symmetric(self.string.encode(), _p(k), buf, ln), 'record_encrypt_symmetric'))
 
     def serial_number_string(self, private_key, program_id: str, record_name: str) -> str:
         """RecordPlaintext.serialNumberString(privateKey, programId, recordName): "<decimal>field" (wasm/src/record/record_plaintext.rs:64-82).  The commitment is
@@ -801,3 +816,38 @@ def plaintexts_unspent(strings, program_id: str, record_name: str, account, spen
 def plaintexts_last_routed() -> int:
     """How many strings of this thread's last plaintext batch call the host code computed or refused (all of them below aleo_mi355x_min_plaintexts())."""
     return int(lib().aleo_mi355x_plaintexts_last_routed())
+
+
+# ---- encryption: plaintext strings and randomizers to record1… strings (csrc/records_encrypt.hip) ---------------------------------------------------------------
+def record_nonce(randomizer) -> int:
+    """x(randomizer G): the _nonce of a record encrypted under this randomizer (aleo_mi355x_record_nonce)."""
+    r = np.frombuffer(view_key_bytes(randomizer), dtype=np.uint8); out = np.zeros(32, dtype=np.uint8)
+    check(lib().aleo_mi355x_record_nonce(_p(out), _p(r)), 'record_nonce')
+    return int.from_bytes(out.tobytes(), 'little')
+
+
+def encrypt_many(strings, randomizers, set_nonce: bool = False, host: bool = False):
+    """n plaintext strings (a sequence of strings or RecordPlaintext objects, or a RecordBatch) under n randomizers (integers, 32-byte strings, or uint8[n, 32]) in one
+    call (aleo_mi355x_records_encrypt / _host): (RecordBatch of the record1… strings, flags uint8[n], rvk uint8[n, 32]).  flags: 0 encrypted; 1 x(r G) is not the
+    string's nonce (never with set_nonce); 2 the randomizer is not below the subgroup order or the owner is no point of the subgroup; 3 not a record plaintext.  A
+    row with a flag is the empty string and a zero rvk.  The batch goes into scan_strings / decrypt_strings as it stands.  Equal randomizers are not looked for."""
+    b = _plaintext_batch(strings); n = len(b)
+    if isinstance(randomizers, np.ndarray): r = np.ascontiguousarray(randomizers, dtype=np.uint8).reshape(-1, 32)
+    else: r = np.frombuffer(b''.join(view_key_bytes(v) for v in randomizers), dtype=np.uint8).reshape(-1, 32)
+    if r.shape[0] != n: raise ValueError('one randomizer per string')
+    L = lib(); out = ctypes.c_void_p()
+    f = L.aleo_mi355x_records_encrypt_host if host else L.aleo_mi355x_records_encrypt
+    check(f(ctypes.byref(out), _text_p(b), _p(b.offsets), n, _p(r) if n else None, 1 if set_nonce else 0), 'records_encrypt')
+    try:
+        offsets = np.frombuffer(ctypes.string_at(L.aleo_mi355x_encrypted_offsets(out), 8 * (n + 1)), dtype=np.uint64).copy()
+        total = int(offsets[-1])
+        text = ctypes.string_at(L.aleo_mi355x_encrypted_text(out), total) if total else b''
+        flags = np.frombuffer(ctypes.string_at(L.aleo_mi355x_encrypted_flags(out), n) if n else b'', dtype=np.uint8).copy()
+        rvk = np.frombuffer(ctypes.string_at(L.aleo_mi355x_encrypted_rvk(out), 32 * n) if n else b'', dtype=np.uint8).reshape(n, 32).copy()
+    finally: L.aleo_mi355x_encrypted_free(out)
+    return RecordBatch(text, offsets), flags, rvk
+
+
+def encrypt_last_routed() -> int:
+    """How many strings of this thread's last encrypt_many the host code encrypted or refused (all of them below aleo_mi355x_min_encrypt())."""
+    return int(lib().aleo_mi355x_records_encrypt_last_routed())

@@ -888,6 +888,62 @@ int32_t aleo_mi355x_plaintexts_serial_numbers(void* sn_out, void* cm_out, uint64
 int32_t aleo_mi355x_plaintexts_serial_numbers_host(void* sn_out, void* cm_out, uint64_t* microcredits, uint8_t* flags, const char* text, const uint64_t* offsets, size_t n, const char* program_id, const char* record_name, const void* sk_sig32, const void* spent32, size_t n_spent);
 size_t aleo_mi355x_min_plaintexts(void);
 size_t aleo_mi355x_plaintexts_last_routed(void);
+/* Record plaintexts ENCRYPTED to the record1… strings a transition publishes (csrc/records_encrypt.hip, csrc/record_encrypt_host.hpp): the other direction of everything
+ * above.  snarkVM 0.14.5 console/program/src/data/record/encrypt.rs, Record<N, Plaintext<N>>::encrypt(randomizer) / encrypt_symmetric_unchecked(record_view_key)
+ * [UPSTREAM-RECALL], which every execute, transfer, split and join of the reference runs for each output record (rust/src/program/execute.rs:74,177,
+ * rust/src/program/transfer.rs:99-106).  With r the randomizer, a scalar below the subgroup order l, G the account generator and Owner the point of the prime-order
+ * subgroup with the owner's x:  nonce = x(r G);  rvk = x(r Owner);  the private fields in randomizer order — the owner's x if the owner is private, then for every
+ * private entry its plaintext bits, a terminus 1 and zero padding, 252 bits to a field —;  c_i = plain_i + hash_many_psd8([domain "AleoSymmetricEncryption0", rvk], m)_i;
+ * the bytes exactly as record_parse, record_fields and record_plaintext read them; bech32m under "record".
+ * Pinned: the symmetric half.  The reference's own plaintext (tests/golden/reference_records.json, plaintexts.owner and .sdk) under x(view key . nonce) gives the
+ * reference's record1… string character for character.  [UPSTREAM-RECALL] and UNPINNED: the byte layout of public and constant entries (as under record_plaintext);
+ * and everything about `encrypt` that the randomizer-free known answer cannot reach — that the nonce is x(r G) with the account generator, that rvk is x(r Owner),
+ * that r = 0 is computed and not refused, that upstream refuses what flag 2 refuses.  The two rest on r A = view key . (r G) and are tested by the round trip through
+ * records_scan_strings and records_decrypt_strings.  Neither path is hardened against side channels, as elsewhere.  Equal randomizers are NOT looked for: two records
+ * encrypted under one randomizer share their nonce, and if they share the owner their record view key; giving every record its own is the caller's to see to.
+ *   record_encrypt   host, one record.  mode 0 is upstream's encrypt: the string's _nonce must be x(r G) (BAD_ARG otherwise).  mode ALEO_MI355X_ENCRYPT_SET_NONCE
+ *                  ignores the value of the string's nonce and writes x(r G): for a producer that has a template and a randomizer.  out / out_len: the contract
+ *                  of record_plaintext.  BAD_ARG with last_error beginning "The record plaintext string provided was invalid" for a string
+ *                  record_plaintext_parse's grammar refuses (or an entry whose body passes the 65535 bytes its length holds); BAD_ARG for a randomizer not below l
+ *                  and an owner whose x has no point in the prime-order subgroup.
+ *   record_encrypt_symmetric   host: the string under a record view key given as it is (32 B canonical, below r): no randomizer, no owner point, the nonce kept.
+ *                  This is the pinned half.
+ *   record_nonce   host: x(r G), 32 B canonical little-endian; BAD_ARG for r not below l.
+ *   records_encrypt   n plaintext strings (text / offsets as records_parse_many takes them) under n randomizers (n x 32 B), one mode for all.  *out is a result the
+ *                  library owns (the sizes are known only afterwards), read through the accessors, whose pointers are valid until encrypted_free:
+ *     encrypted_text      the record1… strings one after another, no separator
+ *     encrypted_offsets   uint64_t[n + 1]   string i is text[offsets[i] .. offsets[i + 1])
+ *     encrypted_flags     uint8_t[n]        first match wins: 3 not a record plaintext; 2 the randomizer is not below l, or the owner's x has no prime-order point;
+ *                                           1 mode 0 and x(r G) is not the string's nonce; 0 encrypted.  A row whose flag is not 0 has an empty string and a zero rvk
+ *     encrypted_rvk       uint8_t[n][32]    the record view key's x: what records_scan_strings returns for the owner
+ *                  A bad row never fails the call; it fails only for null buffers, an unknown mode, offsets that records_parse_many refuses, and a launch of more
+ *                  than 2^32 - 1 characters.  n = 0 gives an empty result.  On failure *out is null.  Below min_encrypt strings the call runs on the calling thread.
+ *                  Else per launch of at most 2^20 strings (ALEO_MI355X_ENCRYPT_CHUNK, read per call, lowers the cap: for tests; the bytes do not depend on it) two
+ *                  kernels, one string per lane each (csrc/records_encrypt_lane.h): the keys (the measure walk, r G from the resident table of G, the owner's point,
+ *                  r Owner), the project's two-level exclusive sum over the rows' lengths, one 32-byte read, the text (the second walk, the squeeze, a bech32m symbol
+ *                  writer).  The lanes compute the records plaintexts_commitments' lane computes (numeric, boolean and address literals in record_plaintext's
+ *                  spelling, any visibility, at most 1024 characters and 8 entries); every other row is encrypted or refused by the calling thread with the host
+ *                  code inside the call and spliced in.  Thread-safe (one slot per call).  Returns byte for byte what records_encrypt_host returns.
+ *   records_encrypt_host   the same bytes on the calling thread; touches no device.
+ *   min_encrypt    the number of strings from which records_encrypt takes the GPU: 32, the measured crossover against the host twin on one thread
+ *                  (profiles/records_encrypt.txt: at 2^4 the GPU road takes 4.15 ms against 2.41, 0.58x; at 2^5 4.13 against 4.80, 1.16x; the parent commit has no road
+ *                  from a plaintext to a ciphertext); ALEO_MI355X_MIN_ENCRYPT overrides it, read per call.
+ *   records_encrypt_last_routed   how many strings of the calling thread's last batch call the host code encrypted or refused: all n below the threshold, else the
+ *                  rows the lanes routed. */
+#define ALEO_MI355X_ENCRYPT_SET_NONCE 1
+typedef struct aleo_mi355x_encrypted aleo_mi355x_encrypted;
+int32_t aleo_mi355x_record_encrypt(const char* plaintext, const void* randomizer32, int32_t mode, char* out, size_t* out_len);
+int32_t aleo_mi355x_record_encrypt_symmetric(const char* plaintext, const void* rvk32, char* out, size_t* out_len);
+int32_t aleo_mi355x_record_nonce(void* out32, const void* randomizer32);
+int32_t aleo_mi355x_records_encrypt(aleo_mi355x_encrypted** out, const char* text, const uint64_t* offsets, size_t n, const void* randomizers32, int32_t mode);
+int32_t aleo_mi355x_records_encrypt_host(aleo_mi355x_encrypted** out, const char* text, const uint64_t* offsets, size_t n, const void* randomizers32, int32_t mode);
+void aleo_mi355x_encrypted_free(aleo_mi355x_encrypted* encrypted);
+const char* aleo_mi355x_encrypted_text(const aleo_mi355x_encrypted* encrypted);
+const uint64_t* aleo_mi355x_encrypted_offsets(const aleo_mi355x_encrypted* encrypted);
+const uint8_t* aleo_mi355x_encrypted_flags(const aleo_mi355x_encrypted* encrypted);
+const uint8_t* aleo_mi355x_encrypted_rvk(const aleo_mi355x_encrypted* encrypted);
+size_t aleo_mi355x_min_encrypt(void);
+size_t aleo_mi355x_records_encrypt_last_routed(void);
 
 /* ---- account signatures: sign, the sign1… string, and many verifications in one call ---------------------------------------------------------------------------
  * The two account calls of the reference besides derivation, ownership and decryption (wasm/src/account/signature.rs:37-48 Signature::sign / verify,

@@ -1099,4 +1099,33 @@ inline Result<uint64_t> plaintext_microcredits(const std::string& plaintext) {
   return {mc, Error{0}};
 }
 
+// ---- encryption: record plaintexts to record1… strings (rust/src/program/execute.rs:74,177, transfer.rs:99-106; aleo_mi355x_records_encrypt) --------------------------
+// Record::encrypt(randomizer) of one plaintext on the host: randomizer32 a scalar below the subgroup order, 32 little-endian bytes.  x(randomizer G) must be the
+// string's _nonce — or, with set_nonce, replaces it.
+inline Result<RecordCiphertext> encrypt_record(const RecordPlaintext& plaintext, const uint8_t* randomizer32, bool set_nonce = false) {
+  std::string buf(4096, '\0'); size_t len = buf.size();
+  const int32_t mode = set_nonce ? ALEO_MI355X_ENCRYPT_SET_NONCE : 0;
+  int32_t rc = aleo_mi355x_record_encrypt(plaintext.to_string().c_str(), randomizer32, mode, &buf[0], &len);
+  if (rc == ALEO_MI355X_ERR_BAD_ARG && len + 1 > buf.size()) { buf.assign(len + 1, '\0'); len = buf.size(); rc = aleo_mi355x_record_encrypt(plaintext.to_string().c_str(), randomizer32, mode, &buf[0], &len); }      // too short, not refused: a refusal leaves len as it was
+  if (rc) return {std::nullopt, Error{rc}};
+  buf.resize(len); return RecordCiphertext::from_string(buf);
+}
+// n plaintext strings under n randomizers (n x 32 bytes) in one call: the record1… strings as a RecordBatch that find_owned, decrypt_strings and the rest take as it
+// stands, flags (0 encrypted; 1 x(r G) is not the string's nonce; 2 the randomizer is not below the subgroup order or the owner is no point of the subgroup; 3 not
+// a record plaintext — the row's string is empty and its key zeros) and the record view keys' x, 32 bytes each.  Equal randomizers are not looked for.
+struct EncryptedRecords { RecordBatch batch; std::vector<uint8_t> flags, rvk; const uint8_t* record_view_key_x(size_t i) const { return rvk.data() + 32 * i; } };
+inline Result<EncryptedRecords> encrypt_records(const RecordBatch& plaintexts, const uint8_t* randomizers32, bool set_nonce = false, bool host = false) {
+  const size_t n = plaintexts.size();
+  aleo_mi355x_encrypted* e = nullptr;
+  int32_t rc = (host ? aleo_mi355x_records_encrypt_host : aleo_mi355x_records_encrypt)(&e, plaintexts.text(), plaintexts.offsets(), n, randomizers32, set_nonce ? ALEO_MI355X_ENCRYPT_SET_NONCE : 0);
+  if (rc) return {std::nullopt, Error{rc}};
+  EncryptedRecords out{RecordBatch(std::vector<std::string>{}), {}, {}};
+  const char* text = aleo_mi355x_encrypted_text(e); const uint64_t* off = aleo_mi355x_encrypted_offsets(e);
+  for (size_t i = 0; i < n; ++i) out.batch.push_back(std::string(text + off[i], (size_t)(off[i + 1] - off[i])));
+  out.flags.assign(aleo_mi355x_encrypted_flags(e), aleo_mi355x_encrypted_flags(e) + n);
+  out.rvk.assign(aleo_mi355x_encrypted_rvk(e), aleo_mi355x_encrypted_rvk(e) + 32 * n);
+  aleo_mi355x_encrypted_free(e);
+  return {std::move(out), Error{0}};
+}
+
 }  // namespace aleo_mi355x
